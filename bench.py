@@ -2,7 +2,7 @@
 """
 Benchmark of the regridding hot path on MI355X.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
     python bench.py --gpus N --steps K --warmup W          (launches itself under torch.distributed.run, one rank per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -27,6 +27,13 @@ target cells / max-over-ranks time.
 Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
 "roofline" for the dominant kernel (algorithmic bytes / hipEvent-timed duration)
 and, at N = 1, "cpu_baseline" (the CPU oracle -- a port of the reference path -- timed on the host).
+At N = 1 both are measured with --full only (null otherwise), as are the other figures of "config"
+and "other_configs": a plain run sets up, warms up, times the K steps and prints the headline.
+
+--dump-outputs DIR (N = 1): after the timed steps, the outputs of the last one -- the regridded field
+(regridded, float64[T]) and the weight matrix (weights float64[nnz], weights_indices, weights_indptr;
+CSR over the target rows) -- are written as DIR/<name>.npy, at most 64 MB in all (dump_outputs).  The
+inputs are generated from fixed seeds, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -42,6 +49,7 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec, /opt/skills/guides/MI355X_MICROARCH.md
 CPU_RUNS = 5  # timed runs of the CPU baseline (median), after one warm-up
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
 
 
 def log(*a):
@@ -188,6 +196,28 @@ def cpu_baseline(sxy, sf, txy, tf, data):
     }, out[0]
 
 
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write ``arrays`` (name -> 1-D array) as ``path/<name>.npy``: float arrays as float64, integer arrays as float32 when
+    every value is exact in it (|v| < 2**24), else float64.  If the whole exceeds ``limit`` bytes, each array keeps the same
+    fraction of its entries, at the positions ``np.sort(np.random.default_rng(0).choice(size, n, replace=False))`` -- a fixed
+    sample, so two runs on the same inputs write the same positions."""
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a).ravel()
+        exact32 = a.dtype.kind in "iu" and (a.size == 0 or int(np.abs(a).max()) < 2 ** 24)
+        out[name] = a.astype(np.float32 if exact32 else np.float64)
+    total = sum(a.nbytes for a in out.values())
+    room = limit - 1024 * len(out)  # (an .npy header is 128 bytes)
+    if total > room:
+        for name, a in out.items():
+            n = int(a.size * room / total)
+            out[name] = a[np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))]
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"[bench] outputs: {', '.join(f'{k} {v.shape[0]}' for k, v in out.items())} -> {path}")
+
+
 def make_step(E, ms, mt, d_src, d_out, state):
     """One step of the headline: nothing cached (both meshes lose their derived state), then the whole weight build and the
     mean apply of one variable, from HBM-resident raw arrays to an HBM-resident result."""
@@ -248,6 +278,45 @@ def run_single(args):
     ms_per_step = 1e3 * elapsed / args.steps
     csr = state["csr"]
     C, P = ms.last_candidates(), csr.nnz
+    if args.dump_outputs:
+        # what the caller of the timed entry point holds after the last timed step: the weight matrix and the regridded field
+        out_step = np.empty(T)
+        _lib.check(lib.xr_dev_download(out_step.ctypes.data_as(ctypes.c_void_p), d_out, 8 * T))
+        w_data, w_indices, w_indptr = csr.download()
+        dump_outputs(args.dump_outputs, {"regridded": out_step, "weights": w_data, "weights_indices": w_indices,
+                                         "weights_indptr": w_indptr})
+        del out_step, w_data, w_indices, w_indptr
+    result = {
+        "metric": "target cells regridded/s (OverlapRegridder 1M->1M tri, weights + mean apply)",
+        "value": T / (elapsed / args.steps),
+        "unit": "target cells/s",
+        "n_gpus": 1,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {
+            "workload": "BASELINE config 2: ~1M-triangle jittered-lattice Delaunay source -> ~1M-triangle target "
+            "(seed 1, rotated 30 deg, scaled 0.7), OverlapRegridder area-weighted mean, K=1",
+            "source_faces": S,
+            "target_faces": T,
+            "candidate_pairs": C,
+            "nnz": P,
+            "parallelism": "1 GPU",
+            "step_entry_point": "xr_overlap_apply_dev under xr_set_async: the raw C-ABI step on HBM-resident arrays (weights + "
+            "apply enqueued as one call); the reference-shaped classes (weights in the constructor, apply in regrid(), host "
+            "arrays in and out) are `api_ms`",
+        },
+        "roofline": None,
+        "cpu_baseline": None,
+    }
+    if not args.full:  # the headline only; the measurements below (and their extra runs of the step) are --full
+        print(json.dumps(result), flush=True)
+        return
 
     # weights-only and apply-only rates (reported in config, not the headline).  Apply only: every call synchronous (the
     # reference's contract: regrid() returns the result), after a few untimed calls -- the first synchronous apply of a
@@ -493,30 +562,7 @@ def run_single(args):
             "(rows > 32 entries are reduced cooperatively in a fixed tree order; all others bit-identical)")
         cpu["gpu_values_differing"] = n_diff
         cpu["gpu_max_rel_diff"] = max_rel
-    result = {
-        "metric": "target cells regridded/s (OverlapRegridder 1M->1M tri, weights + mean apply)",
-        "value": T / (elapsed / args.steps),
-        "unit": "target cells/s",
-        "n_gpus": 1,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {
-            "workload": "BASELINE config 2: ~1M-triangle jittered-lattice Delaunay source -> ~1M-triangle target "
-            "(seed 1, rotated 30 deg, scaled 0.7), OverlapRegridder area-weighted mean, K=1",
-            "source_faces": S,
-            "target_faces": T,
-            "candidate_pairs": C,
-            "nnz": P,
-            "parallelism": "1 GPU",
-            "step_entry_point": "xr_overlap_apply_dev under xr_set_async: the raw C-ABI step on HBM-resident arrays (weights + "
-            "apply enqueued as one call); the reference-shaped classes (weights in the constructor, apply in regrid(), host "
-            "arrays in and out) are `api_ms`",
+    result["config"].update({
             "apply_only_ms": apply_ms,
             "apply_only_cells_per_s": T / (apply_ms * 1e-3),
             "apply_only_back_to_back_ms": apply_async_ms,
@@ -539,10 +585,9 @@ def run_single(args):
             "regrid = apply + download.  (3.0-3.7 ms by run: the passes allocate ~150 MB of fresh numpy arrays "
             "whose first-touch page faults depend on the state of the process heap; a mallopt() that keeps released memory did not "
             "settle it)",
-        },
-        "roofline": roofline,
-        "cpu_baseline": cpu,
-    }
+    })
+    result["roofline"] = roofline
+    result["cpu_baseline"] = cpu
     if not args.no_extras:
         result["other_configs"] = other_configs(E, lib, _lib, csr, S, T, ms, sxy, sf, delaunay=not args.no_delaunay,
                                                  target_centroids=mt.centroids())
@@ -1454,9 +1499,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--points", type=int, default=500_000, help="lattice points per mesh and per GPU (faces ~ 2x)")
     ap.add_argument("--no-delaunay", action="store_true", help="lattice-split triangulation instead of qhull")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-extras", action="store_true", help="skip the informative extras (configs 3 and 5, structured pair)")
-    ap.add_argument("--step-only", action="store_true", help="skip the passes from host arrays (host_to_host_ms, api_ms): "
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the headline also measure everything else the line reports (apply-only, weights-only, "
+                    "host-array and public-API passes, per-kernel roofline, the CPU oracle baseline and its comparison, "
+                    "other_configs); without it the run times the step and prints the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: write what the last timed step computed (regridded field, weight matrix) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-extras", action="store_true", help="skip the informative extras (--full at N = 1: configs 3 and 5, "
+                    "structured pair; N > 1: the config-4 and config-5 workloads)")
+    ap.add_argument("--step-only", action="store_true", help="--full: skip the passes from host arrays (host_to_host_ms, api_ms): "
                     "every launch of the process then belongs to the step's loops (profiler runs)")
     ap.add_argument("--partition", default="balanced", choices=["balanced", "morton", "hash"],
                     help="source shards: Morton blocks of equal estimated work (default) / equal face counts, or id mod N")
@@ -1485,6 +1537,9 @@ def main():
     ap.add_argument("--compute-backend", default=None, help=argparse.SUPPRESS)  # test hook: module:attr of a backend class
     args = ap.parse_args()
     in_group = "WORLD_SIZE" in os.environ and "RANK" in os.environ
+    if args.dump_outputs and (args.project_shards > 1 or args.gpus > 1 or args.force_dist
+                              or (in_group and int(os.environ["WORLD_SIZE"]) > 1)):
+        ap.error("--dump-outputs writes the outputs of the one-GPU step only")
     if args.project_shards > 1:
         run_projection(args)
     elif (args.gpus > 1 or args.force_dist) and not in_group:

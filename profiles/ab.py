@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""A/B on ONE box: `python profiles/ab.py [--steps N] [--reps R] NAME=VALUE[,NAME=VALUE...] ...` runs bench.py --no-cpu --no-extras once per
+"""A/B on ONE box: `python profiles/ab.py [--steps N] [--reps R] NAME=VALUE[,NAME=VALUE...] ...` runs bench.py --full --no-cpu --no-extras once per
 variant ("base" = no variable set) -- interleaved, R rounds -- and prints step / kernel times per variant (median over rounds)."""
 import json
 import os
@@ -24,7 +24,7 @@ for _ in range(reps):
             for kv in v.split(","):
                 k, val = kv.split("=", 1)
                 env[k] = val
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu", "--no-extras", "--steps", str(steps), "--warmup", "20"],
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu", "--no-extras", "--steps", str(steps), "--warmup", "20"],
                              env=env, capture_output=True, text=True)
         try:
             res[v].append(json.loads(out.stdout.strip().splitlines()[-1]))

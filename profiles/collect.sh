@@ -1,7 +1,7 @@
 #!/bin/bash
 # Run ON THE GPU BOX (through gpurun) from the repository root:   bash profiles/collect.sh <tag> [bench args...]
 # Produces under gpurun_out/<tag>/ :
-#   kernel_stats.csv     rocprofv3 --kernel-trace --stats of `python bench.py --no-cpu --no-extras --steps 10`
+#   kernel_stats.csv     rocprofv3 --kernel-trace --stats of `python bench.py --full --no-cpu --no-extras --steps 10`
 #   bench_under_rocprof.json   the bench line of that run
 #   pmc_<set>/           one rocprofv3 --pmc pass per counter set (kernel-trace only; never combined with other traces)
 #   pmc_per_launch.json  per-kernel averages of all passes (profiles/pmc_summary.py)
@@ -13,7 +13,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $ROOT/bench.py --no-cpu --no-extras --step-only $*"
+BENCH="python $ROOT/bench.py --full --no-cpu --no-extras --step-only $*"
 timeout -k 5 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o bench -- $BENCH --steps 10 > "$OUT/bench_under_rocprof.json" 2> "$OUT/stats.log"
 cp "$(find "$OUT/stats" -name '*kernel_stats.csv' | head -1)" "$OUT/kernel_stats.csv" 2>/dev/null
 for SET in "FETCH_SIZE" "WRITE_SIZE" \

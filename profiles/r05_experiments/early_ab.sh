@@ -1,5 +1,5 @@
 timeout 900 python -m pytest tests/test_gpu_parity.py -x -q -m gpu 2>&1 | tail -3
-for e in 0 16; do echo == XR_BIG_EARLY=$e; XR_BIG_EARLY=$e timeout 300 python bench.py --no-cpu --step-only --no-extras 2>/dev/null | python -c "
+for e in 0 16; do echo == XR_BIG_EARLY=$e; XR_BIG_EARLY=$e timeout 300 python bench.py --full --no-cpu --step-only --no-extras 2>/dev/null | python -c "
 import sys,json
 b=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(b['ms_per_step'], b['config']['weights_only_ms'])"; done
 bash profiles/timeline.sh tl7 10 > /dev/null 2>&1

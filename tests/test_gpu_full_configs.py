@@ -18,7 +18,7 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import same_or_nan
+from conftest import canon, same_or_nan
 from test_gpu_parity import assert_apply_equal
 from xugrid_amd import meshgen
 
@@ -222,6 +222,51 @@ def test_bench_projection_of_eight_shards():
         # cent, seen once in a full-suite run -- so only their sanity is asserted, not their size)
         assert 1.0 <= out["imbalance_max_over_mean"] < 10.0
         assert out["projected_step_ms"] > 0 and 0 < out["projected_efficiency_1_to_W"] < 10.0
+
+
+def test_bench_plain_line_dump_outputs_and_full(hip, oracle, tmp_path):
+    """`bench.py --gpus 1` without --full times the step and prints the headline only (the steps asked for, no roofline, no
+    CPU leg); --dump-outputs writes the last timed step's weight matrix and regridded field, which are the CPU oracle's on
+    the same seeded meshes.  With --full the line carries the measurements that moved behind it."""
+    from xugrid_amd import engine as E
+
+    points, steps = 20_000, 7
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "2",
+           "--points", str(points)]
+    proc = subprocess.run(cmd + ["--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert proc.returncode == 0, proc.stdout[-3000:] + proc.stderr[-3000:]
+    line = json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith("{")][-1])
+    T = line["config"]["target_faces"]
+    assert line["steps"] == steps and line["ms_per_step"] > 0 and line["unit"] == "target cells/s" and line["dtype"] == "f64"
+    assert abs(line["value"] - T / (line["ms_per_step"] * 1e-3)) <= 1e-9 * line["value"]
+    assert line["roofline"] is None and line["cpu_baseline"] is None and "other_configs" not in line
+    assert "weights_only_ms" not in line["config"] and "api_ms" not in line["config"]
+
+    sxy, sf = meshgen.triangle_mesh(points, 0)
+    txy, tf = meshgen.triangle_mesh(points, 1, 30.0, 0.7)
+    assert tf.shape[0] == T
+    got = {n: np.load(os.path.join(tmp_path, n + ".npy")) for n in ("regridded", "weights", "weights_indices", "weights_indptr")}
+    assert got["regridded"].dtype == np.float64 and got["regridded"].shape == (T,)
+    data, indices, indptr = got["weights"], got["weights_indices"].astype(np.int64), got["weights_indptr"].astype(np.int64)
+    assert indptr.shape == (T + 1,) and indptr[-1] == data.size == line["config"]["nnz"]
+    q, s, a = canon(np.repeat(np.arange(T), np.diff(indptr)), indices, data)
+    oq, os_, oa = canon(*oracle.CellTree2d(sxy, sf).intersect_faces(txy, tf))
+    assert np.array_equal(q, oq) and np.array_equal(s, os_), "pair set differs from the oracle"
+    assert np.array_equal(a, oa), "overlap areas differ from the oracle"
+    field = meshgen.smooth_field(E.DeviceMesh(sxy, sf).centroids(), 0)  # (bench.py's source field)
+    exp = oracle.regrid_csr("mean", field[None, :], data, indices, indptr, T)[0]
+    short = np.diff(indptr) <= 32  # longer rows are reduced cooperatively (fixed tree order, ~1e-15)
+    assert np.array_equal(got["regridded"][short], exp[short], equal_nan=True)
+    assert np.allclose(got["regridded"], exp, rtol=1e-13, atol=0, equal_nan=True)
+
+    proc = subprocess.run(cmd + ["--full", "--no-extras"], env=env, capture_output=True, text=True, timeout=600)
+    assert proc.returncode == 0, proc.stdout[-3000:] + proc.stderr[-3000:]
+    full = json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith("{")][-1])
+    assert full["steps"] == steps and full["config"]["nnz"] == line["config"]["nnz"]
+    assert full["roofline"]["kernel"] and full["roofline"]["kernel_ms_per_step"]
+    assert full["cpu_baseline"]["value"] > 0 and full["cpu_baseline"]["gpu_values_differing"] <= int((~short).sum())
+    assert full["config"]["weights_only_ms"] > 0 and full["config"]["apply_only_ms"] > 0 and full["config"]["api_ms"] > 0
 
 
 def _check_scale_fields(line, exchange, world):
