@@ -236,6 +236,13 @@ def test_run_time_options_are_an_api_not_the_environment():
         engine.set_option("no_such_option", 1)
     with pytest.raises(ValueError):
         engine.get_option("XR_OVERLAP_FUSED")
+    # concluded A/B switches: retired with their losing paths, unknown names now
+    for retired in ("no_side", "side_fork", "mail_poll", "points_defer", "star_flag", "early_apply", "stats_sample",
+                    "force_query_sort", "ingest_device"):
+        with pytest.raises(ValueError):
+            engine.get_option(retired)
+        with pytest.raises(ValueError):
+            engine.set_option(retired, 0)
     # ONE getenv call site in the device library's sources
     calls = []
     for path in glob.glob(os.path.join(ROOT, "xugrid_amd", "csrc", "*.h*")):

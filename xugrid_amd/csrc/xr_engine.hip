@@ -54,17 +54,17 @@ struct OptionDef {
     const char *name;
     int64_t def;
 };
-const OptionDef k_option_defs[OPT_COUNT] = {
-    {"overlap_fused", 1}, {"queue_margin", 0}, {"clip_quad", 1}, {"dust", 1}, {"no_side", 0}, {"side_fork", 1}, {"debug", 0},
-    {"host_stamps", 0}, {"apply_plan", 1}, {"apply_contract", 0}, {"plan_merge", -1}, {"plan_dbg", 0}, {"apply_chunk_bytes", 0},
-    {"outer_apply", 0}, {"edge_big", 0}, {"edge_stage", 0}, {"edge_queue", 0}, {"edge_sort", 1}, {"mail_poll", 1},
-    {"points_defer", 1}, {"ingest_device", 0}, {"stats_sample", 1}, {"force_query_sort", 0}, {"early_apply", 1}, {"star_flag", 1},
+const OptionDef k_option_defs[] = {
+    {"overlap_fused", 1}, {"queue_margin", 0}, {"clip_quad", 1}, {"dust", 1}, {"debug", 0}, {"host_stamps", 0}, {"apply_plan", 1},
+    {"apply_contract", 0}, {"plan_merge", -1}, {"plan_dbg", 0}, {"apply_chunk_bytes", 0}, {"outer_apply", 0}, {"edge_big", 0},
+    {"edge_stage", 0}, {"edge_queue", 0}, {"edge_sort", 1},
 };
+static_assert(sizeof(k_option_defs) / sizeof(k_option_defs[0]) == OPT_COUNT, "one table row per enum Option");
 std::atomic<int64_t> g_options[OPT_COUNT];
 std::once_flag g_options_once;
 // words some options accepted as environment values before they were numbers
 int64_t option_word(const char *v) {
-    static const struct { const char *word; int64_t value; } words[] = {{"free", 1}, {"csr", 2}, {"device", 1}};
+    static const struct { const char *word; int64_t value; } words[] = {{"free", 1}, {"csr", 2}};
     for (const auto &w : words)
         if (!strcmp(v, w.word)) return w.value;
     char *end = nullptr;
@@ -382,7 +382,6 @@ static constexpr size_t STAGE_BYTES = (size_t)64 << 20;
 static constexpr size_t BIG_COPY_BYTES = (size_t)1 << 20; // copies of this size and more go through the pinned staging buffers
 static constexpr size_t SMALL_COPY_BYTES = BIG_COPY_BYTES;
 
-static bool mail_poll_enabled();
 static inline void cpu_relax();
 
 // ---- small copies without a stream synchronisation (round 5) -----------------------------------------------------------
@@ -391,8 +390,7 @@ static inline void cpu_relax();
 // regridder construction is little else).  On the engine's own main stream they now go the mailbox's way: a kernel copies
 // the bytes into a coherent pinned page and the LAST of its blocks stores a sequence number behind them, which the host
 // polls.  Uploads copy the host bytes into a pinned ring slot and enqueue the DMA without waiting for it (the slot is
-// reused after its event).  Anything else -- lanes, a caller's stream, the side stream, XR_MAIL_POLL=0 -- keeps the
-// synchronous path.
+// reused after its event).  Anything else -- lanes, a caller's stream, the side stream -- keeps the synchronous path.
 static constexpr size_t FAST_D2H_MAX = (size_t)1 << 20;  // bytes of the pinned read-back page
 static constexpr size_t FAST_H2D_SLOT = (size_t)1 << 18, FAST_H2D_SLOTS = 16; // (256 KB: the boundary lists of a Voronoi pre-step -- a pageable copy goes through a blit KERNEL, which waits for wave slots beside a kernel that fills the device)
 struct FastCopy {
@@ -423,7 +421,7 @@ k_copy_to_host(const uint32_t *__restrict__ src, uint32_t *dst, size_t n_words, 
 
 static bool fast_copy_allowed() {
     Engine &e = engine();
-    return mail_poll_enabled() && !t_lane && !t_stream_override && !e.on_side && e.stream == e.own_stream;
+    return !t_lane && !t_stream_override && !e.on_side && e.stream == e.own_stream;
 }
 static void fast_copy_init() {
     if (g_fast.page) return;
@@ -739,8 +737,6 @@ void mailbox_wait() {
     pool_release_deferred();
 }
 
-static bool mail_poll_enabled() { return option(OPT_MAIL_POLL) != 0; }
-
 static inline void cpu_relax() {
 #if defined(__x86_64__) || defined(__i386__)
     __builtin_ia32_pause();
@@ -755,7 +751,7 @@ int32_t mailbox_next_seq() {
 
 void mailbox_wait_seq(int32_t seq) {
     Engine &e = engine();
-    if (!mail_poll_enabled() || e.stream != e.own_stream) { // (a caller's stream: its events order things, keep the event path)
+    if (e.stream != e.own_stream) { // (a caller's stream: its events order things, keep the event path)
         mailbox_wait();
         XR_REQUIRE(e.mailbox[MAIL_SEQ_SLOT] == seq, XR_ERR_HIP, "mailbox sequence word missing after synchronisation");
         return;
@@ -775,7 +771,6 @@ void mailbox_wait_seq(int32_t seq) {
 }
 
 bool poll_pinned_f64(const volatile double *word, double expected) {
-    if (!mail_poll_enabled()) return false;
     const auto t0 = std::chrono::steady_clock::now();
     for (uint64_t spins = 0; *word != expected; spins++) {
         cpu_relax();
@@ -786,18 +781,15 @@ bool poll_pinned_f64(const volatile double *word, double expected) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// host stamps (XR_HOST_STAMPS=1)
+// host stamps (option host_stamps = 1)
 // ---------------------------------------------------------------------------------------------
 namespace {
 struct HostStamps {
-    bool on = option(OPT_HOST_STAMPS) != 0;
     std::chrono::steady_clock::time_point last[16];
-    bool seen[16] = {};
     double sum_us[16][16] = {}; // [from][to] accumulated interval from the latest stamp of `from` to a stamp of `to`
     long n[16][16] = {};
     int prev = -1;
-    ~HostStamps() {
-        if (!on) return;
+    ~HostStamps() { // (whatever was recorded while the option was on)
         for (int a = 0; a < 16; a++)
             for (int b = 0; b < 16; b++)
                 if (n[a][b] > 20) fprintf(stderr, "[host stamps] %d -> %d: %.2f us (n = %ld)\n", a, b, sum_us[a][b] / n[a][b], n[a][b]);
@@ -806,7 +798,7 @@ struct HostStamps {
 HostStamps g_stamps;
 } // namespace
 void host_stamp(int point) {
-    if (!g_stamps.on) return;
+    if (option(OPT_HOST_STAMPS) == 0) return;
     const auto now = std::chrono::steady_clock::now();
     if (g_stamps.prev >= 0) {
         const int a = g_stamps.prev;
@@ -861,9 +853,6 @@ ProfScope::~ProfScope() {
     g_pending.push_back({name, e0, e1});
 }
 
-// XR_NO_SIDE=1 (measurement hook): the "side" work runs in line on the main stream -- every kernel alone on the device
-static bool side_disabled() { return option(OPT_NO_SIDE) != 0; }
-
 static bool lane_side_ready(Lane *l) {
     if (l->side) return true;
     hipStream_t st = nullptr;
@@ -887,7 +876,6 @@ void assert_no_open_mark(const char *what) {
     XR_REQUIRE(!t_mark_open, XR_ERR_INVALID, "internal: %s between side_mark() and SideScope(at_mark): the side work would not see it", what);
 }
 bool side_mark() {
-    if (side_disabled()) return false;
     if (Lane *l = current_lane()) {
         if (!lane_side_ready(l)) return false;
         XR_HIP(hipEventRecord(l->fork_event, l->stream));
@@ -901,7 +889,6 @@ bool side_mark() {
 }
 SideScope::SideScope(bool at_mark) {
     if (at_mark) t_mark_open = false;
-    if (side_disabled()) return;
     if (Lane *l = current_lane()) {
         if (!lane_side_ready(l)) return;
         if (!at_mark) XR_HIP(hipEventRecord(l->fork_event, l->stream));
@@ -932,7 +919,7 @@ SideScope::~SideScope() {
 static bool g_fork2_pending = false; // (exclusive path only) the second side stream holds work the next side_join must wait for
 SideForkScope::SideForkScope() {
     Engine &e = engine();
-    if (option(OPT_SIDE_FORK) == 0 || current_lane() || !e.on_side || t_stream_override || !e.side2) return;
+    if (current_lane() || !e.on_side || t_stream_override || !e.side2) return;
     XR_HIP(hipEventRecord(e.fork2_event, e.side));
     XR_HIP(hipStreamWaitEvent(e.side2, e.fork2_event, 0));
     prev = t_stream_override;
@@ -953,7 +940,6 @@ SideForkScope::~SideForkScope() {
     g_fork2_pending = true;
 }
 void side_join() {
-    if (side_disabled()) return;
     if (Lane *l = current_lane()) {
         if (!l->side_active) return;
         XR_HIP(hipStreamWaitEvent(l->stream, l->join_event, 0));

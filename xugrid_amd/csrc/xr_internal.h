@@ -120,7 +120,7 @@ inline hipStream_t launch_stream();
 void mailbox_wait(); // everything enqueued so far has executed and its mailbox writes are visible
 // The same without an event: the publishing kernel stores `seq` in mailbox[MAIL_SEQ_SLOT] (system scope) BEHIND its other
 // mailbox words and the host polls that word -- no event record / barrier packet on the stream, no interrupt-driven wake-up
-// (an event costs ~5 us of stream time and ~10 us of host latency per wait; XR_MAIL_POLL=0 restores it).  Bounded: after
+// (an event costs ~5 us of stream time and ~10 us of host latency per wait).  Bounded: after
 // ~20 ms without the word the stream is synchronised and the word checked once more (a failed kernel raises the HIP error).
 static constexpr int MAIL_SEQ_SLOT = 1023;
 int32_t mailbox_next_seq();
@@ -304,15 +304,13 @@ bool side_mark(); // record the fork point now; false: no side stream here (Side
 // Run-time options: every switch a test or a measurement script flips.  The table (name, default, meaning) is in
 // xr_engine.hip; values are read ONCE from the environment (XR_<NAME IN CAPITALS>) when the library is first used -- the one
 // getenv call site of the library, no getenv on any call path or worker thread -- and changed afterwards only through
-// xr_set_option.  None of them changes a result.
+// xr_set_option.  None of them changes a result except apply_contract (opt-in, within (n + 2) ulp: DESIGN section 8).
 // ---------------------------------------------------------------------------------------------
 enum Option : int {
     OPT_OVERLAP_FUSED,     // 1: dense meshes of <= 4 nodes per face take the one-round-trip pipeline; 0: the general kernel chain
     OPT_QUEUE_MARGIN,      // > 0: capacity of the big faces' pair queue (tests force the regrow path with a tiny one)
     OPT_CLIP_QUAD,         // 1: quadrilateral targets x triangle source through k_clip_quad_tri (general chain); 0: k_clip_small
     OPT_DUST,              // 1: rounding dust confirmed by the reference's pre-clip tests; 0: the round-3 behaviour
-    OPT_NO_SIDE,           // 1: side-stream work in line on the main stream (every kernel alone on the device)
-    OPT_SIDE_FORK,         // 1: the big faces' bitmap rows on a second side stream beside the light ones
     OPT_DEBUG,             // bits: 1 one line per weight build, 2 apply-plan statistics, 4 Voronoi sizes (stderr)
     OPT_HOST_STAMPS,       // 1: wall-clock stamps along the host path of a weight build, averages at exit
     OPT_APPLY_PLAN,        // 1: K >= 8 variables through the planned kernels; 0: the direct kernel
@@ -325,14 +323,6 @@ enum Option : int {
     OPT_EDGE_STAGE,        // > 0: candidates a wave of 64 edges may stage (<= 1024; tests force the overflow into the wave-per-edge kernel)
     OPT_EDGE_QUEUE,        // > 0: candidate pairs the edge queue holds at first (tests force the regrow path with a tiny one)
     OPT_EDGE_SORT,         // 1: the edges are walked in the order of the grid tiles of their midpoints; 0: as they come
-    OPT_MAIL_POLL,         // 1: the host polls the mailbox's sequence word, small copies without a stream synchronisation
-    OPT_POINTS_DEFER,      // 1: xr_locate_flags_begin defers its kernels to the next call that has the device to spare
-    OPT_INGEST_DEVICE,     // 1 ("device"): connectivity validated and narrowed on the device instead of while it is staged
-    OPT_STATS_SAMPLE,      // 1: tree statistics from a sample of the faces (exact on demand); 0: always exact
-    OPT_FORCE_QUERY_SORT,  // 1: Morton query order even for coherent numberings
-    OPT_EARLY_APPLY,       // 1: the apply of xr_overlap_apply_dev enqueued in front of the size read-back
-    OPT_STAR_FLAG,         // 1: "inside the source grid" of a barycentric construction from the faces around the located Voronoi
-                           //    cell (k_star_flag), the grid walk only for the points they leave open; 0: the grid walk for all
     OPT_COUNT
 };
 int64_t option(Option o);

@@ -16,15 +16,16 @@ struct xr_points {
     int64_t n = 0;
     xr_mesh *source = nullptr;
     xr::PointsBuf pts; // (the query mesh's centroids are shared with the mesh, not copied)
+    // filled by the construction that consumes the handle, from the faces around each point's Voronoi cell (k_star_flag) --
+    // the handle only carries the points
     xr::DevBuf<uint8_t> inside;
-    // The kernels that fill the two buffers (centroids of the query, point location in the source grid) go to the engine's
-    // SIDE stream -- the high-priority stream the big faces of xr_overlap use, known to run beside the main one -- as soon as
-    // the handle is made; the construction that consumes the handle joins the side stream first.  They then run beside the
-    // latency-bound kernels of the Voronoi pre-step instead of in front of them.  (Versions that did not survive: a stream
-    // per handle -- creating and destroying a HIP stream costs 1-3 ms; one extra plain stream -- whether it really runs
-    // beside the engine's depends on how the runtime maps streams onto its few hardware queues: it did in a small script,
-    // not in bench.py; launching them on the main stream right before the host computes the boundary cells -- that host
-    // part turned out too short to hide anything, the gain had come from kernel-beside-kernel.)
+    // The kernels that fill `pts` (centroids of the query) go to the engine's SIDE stream -- the high-priority stream the big
+    // faces of xr_overlap use, known to run beside the main one --; the construction that consumes the handle waits for them
+    // first.  They then run beside the latency-bound kernels of the Voronoi pre-step instead of in front of them.  (Versions
+    // that did not survive: a stream per handle -- creating and destroying a HIP stream costs 1-3 ms; one extra plain stream
+    // -- whether it really runs beside the engine's depends on how the runtime maps streams onto its few hardware queues: it
+    // did in a small script, not in bench.py; launching them on the main stream right before the host computes the boundary
+    // cells -- that host part turned out too short to hide anything, the gain had come from kernel-beside-kernel.)
     xr_mesh *query = nullptr;
     double tol_source = 0.0;
     bool on_side = false; // launched on the side stream: join before use
@@ -34,9 +35,6 @@ struct xr_points {
     // locate pass only shared the vector ALUs with the pre-step's kernels, and the first of those that needs LDS waited for
     // it to drain), or the construction that consumes the handle (a cached tessellation: no pre-step in between)
     bool deferred = false;
-    // round 6: the flags are not computed here at all but by the construction that consumes the handle, from the faces around
-    // each point's Voronoi cell (k_star_flag); the handle then only carries the points
-    bool flags_pending = false;
 };
 
 
@@ -412,9 +410,8 @@ k_bary_cell_flag(const int32_t *__restrict__ faces_raw, int64_t n_cell, int m, i
     flag[c] = any;
 }
 
-// OPEN_ONLY: only the points whose flag is STAR_OPEN (left open by k_star_flag) are located; a block without one leaves at once
+// only the points whose flag is STAR_OPEN (left open by k_star_flag) are located; a block without one leaves at once
 static constexpr uint8_t STAR_OPEN = 2;
-template <bool OPEN_ONLY>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8)))
 k_locate_flag(const double *__restrict__ rec_fxy, const uint8_t *__restrict__ rec_len, const int32_t *__restrict__ rec_off, int m, GridParams g,
               const int32_t *__restrict__ cell_start, const float *__restrict__ rec_bb,
@@ -422,11 +419,8 @@ k_locate_flag(const double *__restrict__ rec_fxy, const uint8_t *__restrict__ re
               uint8_t *__restrict__ inside) {
     __shared__ LocateBig sh_big;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    bool valid = i < n;
-    if (OPEN_ONLY) {
-        valid = valid && inside[i] == STAR_OPEN;
-        if (!__syncthreads_or(valid)) return;
-    }
+    const bool valid = i < n && inside[i] == STAR_OPEN;
+    if (!__syncthreads_or(valid)) return;
     const P2 p = valid ? load_p2(pts, (int)i) : P2{0.0, 0.0};
     const int l_split = locate_prepare(sh_big, g, cell_start, rec_bb, n_tree, p, valid, tol);
     const int r = locate_point(rec_fxy, rec_len, rec_off, m, g, cell_start, rec_bb, rec_face, p, valid, tol, sh_big, l_split);
@@ -439,7 +433,7 @@ k_locate_flag(const double *__restrict__ rec_fxy, const uint8_t *__restrict__ re
 // cell lies in.  The point is tested against exactly those faces with the locate kernels' own test (xr_point_in_face.h, on the
 // face's counter-clockwise-normalised vertices as the tree holds them: the same directed edges, the same roundings): a hit means
 // locate_points finds A face, i.e. != -1, which is all the reference asks (:189).  No hit (a point in a concave exterior cell beyond
-// the hull, a degenerate star) leaves the flag OPEN and k_locate_flag<true> walks the grid for those points alone.  Per point ~6
+// the hull, a degenerate star) leaves the flag OPEN and k_locate_flag walks the grid for those points alone.  Per point ~6
 // triangle tests instead of a grid walk + ~18 box tests + the exact tests of the parked records: 1M faces / 4M points,
 // locate_flag 284 us (175 us of vector instructions, PMC) -> see DESIGN.
 // The faces' vertices come from the source mesh's own face-major block (fxy: counter-clockwise-normalised, caller's face order --
@@ -666,11 +660,6 @@ static void launch_points(xr_points *h) {
         XR_HIP(hipEventRecord(engine().aux_event, engine().side));
         h->pts_marked = true;
     }
-    if (h->flags_pending) return; // (the consumer fills `inside`: k_star_flag)
-    xr_mesh *source = h->source;
-    XR_LAUNCH("locate_flag", k_locate_flag<false>, dim3(div_up(h->n, 256)), dim3(256), 0, source->rec_fxy.get(),
-              source->rec_len.get(), source->record_off(), source->m, source->grid, source->cell_start.get(), source->rec_bb.get(),
-              source->rec_face.get(), source->n_face, h->pts.get(), h->n, h->tol_source, h->inside.get());
 }
 
 static std::vector<xr_points *> &pending_points() {
@@ -799,10 +788,12 @@ int xr_barycentric(xr_mesh *mesh, const double *points, int64_t n, double tolera
 // vertex v of the tessellation belongs to source face v for v < n_identity (the face centroids come first) and to
 // vertex_face[v - n_identity] beyond (projections: their face; substitute vertices: -1)
 
-// the source-side part of UnstructuredGrid2d.barycentric (unstructured.py:147, 188-190) -- the query points and
-// `grid.locate_points(points) == -1` -- enqueued WITHOUT a final wait: it needs nothing of the Voronoi tessellation
-static void locate_flags(xr_mesh *source, xr_mesh *query, const double *points, int64_t n, PointsBuf &pts,
-                         DevBuf<uint8_t> &inside, bool points_only = false) {
+// the source-side part of UnstructuredGrid2d.barycentric (unstructured.py:147, 188-190) that needs nothing of the Voronoi
+// tessellation: the query points, the source grid's index and the buffer of the `grid.locate_points(points) == -1` flags
+// (filled behind the barycentric kernel: k_star_flag + k_locate_flag) -- enqueued WITHOUT a final wait.
+// -> the source grid's default tolerance
+static double prepare_points(xr_mesh *source, xr_mesh *query, const double *points, int64_t n, PointsBuf &pts,
+                             DevBuf<uint8_t> &inside) {
     mesh_prepare(source, false);
     mesh_build_index(source);
     const double tol_source = resolve_tolerance(source, -1.0); // unstructured.py:189: default tolerance
@@ -813,10 +804,7 @@ static void locate_flags(xr_mesh *source, xr_mesh *query, const double *points, 
         pts.alloc((size_t)n * 2);
         h2d(pts.get(), points, sizeof(double) * 2 * (size_t)n);
     }
-    if (points_only) return; // (the flags come from k_star_flag)
-    XR_LAUNCH("locate_flag", k_locate_flag<false>, dim3(div_up(n, 256)), dim3(256), 0, source->rec_fxy.get(),
-              source->rec_len.get(), source->record_off(), source->m, source->grid, source->cell_start.get(), source->rec_bb.get(),
-              source->rec_face.get(), source->n_face, pts.get(), n, tol_source, inside.get());
+    return tol_source;
 }
 
 static void barycentric_csr(xr_mesh *voronoi, xr_mesh *source, xr_mesh *query, const double *points, int64_t n,
@@ -864,10 +852,7 @@ static void barycentric_csr(xr_mesh *voronoi, xr_mesh *source, xr_mesh *query, c
             PointsBuf own_pts;
             DevBuf<double> w((size_t)n * m);
             DevBuf<uint8_t> own_inside;
-            // the flags from the faces around each point's cell (k_star_flag, behind the barycentric kernel) unless the handle
-            // brings them (option "star_flag" = 0, or a handle made while it was)
-            const bool star = pre ? pre->flags_pending : option(OPT_STAR_FLAG) != 0;
-            if (!pre) locate_flags(source, query, points, n, own_pts, own_inside, star);
+            const double tol_source = pre ? pre->tol_source : prepare_points(source, query, points, n, own_pts, own_inside);
             bool join_later = false;
             if (pre && pre->on_side) { // (filled on the side stream)
                 if (pre->pts_marked) { // the points now, the flags in front of bary_fix_count
@@ -922,24 +907,22 @@ static void barycentric_csr(xr_mesh *voronoi, xr_mesh *source, xr_mesh *query, c
                 side_join();
                 pre->on_side = false;
             }
-            if (star) {
-                const double tol_source = pre ? pre->tol_source : resolve_tolerance(source, -1.0);
-                const int64_t *vface_tab = voronoi->bary_ids.get();
-                mesh_face_coords(source); // (its face-major vertex block in the caller's order: built once per mesh)
-                mesh_prepare(source, false); // (the index for the points the star leaves open: still there unless the mesh was
-                mesh_build_index(source);    // invalidated since the handle was made)
+            // the flags from the faces around each point's cell, behind the barycentric kernel
+            const int64_t *vface_tab = voronoi->bary_ids.get();
+            mesh_face_coords(source); // (its face-major vertex block in the caller's order: built once per mesh)
+            mesh_prepare(source, false); // (the index for the points the star leaves open: still there unless the mesh was
+            mesh_build_index(source);    // invalidated since the handle was made)
 #define XR_STAR(MSV)                                                                                                                 \
     XR_LAUNCH("star_flag", k_star_flag<MSV>, dim3(div_up(n, 256)), dim3(256), 0, face.get(), voronoi->faces_raw.get(), m, n_identity,  \
               vface_tab, nv - n_extra, source->fxy.get(), source->len.get(), source->caller_off(), source->m, pts.get(), n,           \
               tol_source, inside.get())
-                if (source->m == 3 && !source->ragged()) XR_STAR(3);
-                else if (source->m == 4 && !source->ragged()) XR_STAR(4);
-                else XR_STAR(0);
+            if (source->m == 3 && !source->ragged()) XR_STAR(3);
+            else if (source->m == 4 && !source->ragged()) XR_STAR(4);
+            else XR_STAR(0);
 #undef XR_STAR
-                XR_LAUNCH("locate_flag", k_locate_flag<true>, dim3(div_up(n, 256)), dim3(256), 0, source->rec_fxy.get(),
-                          source->rec_len.get(), source->record_off(), source->m, source->grid, source->cell_start.get(),
-                          source->rec_bb.get(), source->rec_face.get(), source->n_face, pts.get(), n, tol_source, inside.get());
-            }
+            XR_LAUNCH("locate_flag", k_locate_flag, dim3(div_up(n, 256)), dim3(256), 0, source->rec_fxy.get(),
+                      source->rec_len.get(), source->record_off(), source->m, source->grid, source->cell_start.get(),
+                      source->rec_bb.get(), source->rec_face.get(), source->n_face, pts.get(), n, tol_source, inside.get());
             if (reference_order)
                 XR_LAUNCH("bary_fix_count", k_bary_fix_count<int32_t>, dim3(div_up(n, 256)), dim3(256), 0, face.get(), w.get(), m,
                           voronoi->faces_raw.get(), voronoi->node_xy.get(), n2n, nv - n_extra, inside.get(), n, count.get(), n_pos.get());
@@ -1015,18 +998,8 @@ int xr_locate_flags_begin(xr_mesh *source, xr_mesh *query, const double *points,
                 h->pts.alloc((size_t)n * 2);
                 h2d(h->pts.get(), points, sizeof(double) * 2 * (size_t)n);
             }
-            h->flags_pending = option(OPT_STAR_FLAG) != 0;
-            const bool defer = option(OPT_POINTS_DEFER) != 0; // (A/B switch)
-            if (defer) {
-                h->deferred = true; // launched by flush_pending_points
-                pending_points().push_back(h);
-            } else {
-                {
-                    SideScope side; // (forks behind everything enqueued so far: the index of the source grid, the points)
-                    launch_points(h);
-                }
-                h->on_side = true;
-            }
+            h->deferred = true; // launched by flush_pending_points
+            pending_points().push_back(h);
         }
         else if (n > 0) { // (no source faces: every point is outside)
             h->inside.alloc((size_t)n);

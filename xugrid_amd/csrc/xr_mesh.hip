@@ -483,12 +483,11 @@ void mesh_prepare(xr_mesh *mesh, bool want_fxy, bool stats_on_side, bool allow_s
     if (mesh->prepared && (mesh->has_attrs || !want_fxy) && (!mesh->stats_sampled || allow_sampled)) return;
     const int64_t F = mesh->n_face;
     const int m = mesh->m;
-    const bool sampling_off = option(OPT_STATS_SAMPLE) == 0; // measurement switch
     // Polygon (ragged) meshes always keep len / bbox: the index build then reads one coalesced 32-byte box per face instead
     // of gathering the face's 6-20 vertices again in both of its passes (Voronoi tessellation of 1M triangles:
     // index_count 0.134 -> see DESIGN, index_scatter 0.067 ms).
     if (mesh->ragged()) want_fxy = true;
-    if (!want_fxy && allow_sampled && !sampling_off && F >= SAMPLE_MIN_FACES && !mesh->has_attrs) {
+    if (!want_fxy && allow_sampled && F >= SAMPLE_MIN_FACES && !mesh->has_attrs) {
         mesh->stats.alloc(8);
         const int64_t nb_all = (F + PREP_BLOCK - 1) / PREP_BLOCK;
         const int64_t nb = (nb_all + SAMPLE_STRIDE - 1) / SAMPLE_STRIDE;
@@ -814,10 +813,9 @@ void mesh_query_order(xr_mesh *mesh) {
     const int m = mesh->m;
     // coherent numbering (consecutive faces are, on average, within a few face extents of each
     // other -- typical for mesh generators, not for qhull output): keep the caller's order
-    const bool force_sort = option(OPT_FORCE_QUERY_SORT) != 0;
     const double mean_ext = F > 0 ? mesh->h_stats[4] / (double)F : 0.0;
     const double mean_jump = F > 0 ? mesh->h_stats[7] / ((double)F * 63.0 / 64.0) : 0.0;
-    mesh->query_identity = !force_sort && (F == 0 || mean_jump <= 4.0 * mean_ext);
+    mesh->query_identity = F == 0 || mean_jump <= 4.0 * mean_ext;
     if (mesh->query_identity) {
         mesh_face_coords(mesh); // the caller-order vertex blocks ARE the query-order ones (no-op if prepared with them)
         mesh->query_ready = true;
@@ -1059,13 +1057,10 @@ int xr_mesh_create(const double *node_xy, int64_t n_node, const void *faces, int
     // link rate).  The connectivity is NARROWED while it is copied: fill value -> -1, int64 -> int32 (half the bytes over
     // PCIe), validated (every face has at least three nodes, every node id is inside [0, n_node)); the first offending
     // face is reported.  Nothing waits for the last DMA: the arrays are consumed, later work is stream-ordered behind it.
-    // (XR_INGEST=device: raw upload + k_ingest_faces on the device, as until round 3 -- measurement switch.)
     const size_t cnt = (size_t)n_face * (size_t)n_max_node;
     // (Meshes of less than 1 MB take the device-side ingest: two plain copies and a kernel, no pinned staging buffers --
     // those are 2 x 64 MiB of pinned host memory, allocated on first use.)
-    const bool device_ingest_env = option(OPT_INGEST_DEVICE) != 0;
-    const bool device_ingest =
-        device_ingest_env || cnt * (size_t)faces_itemsize + sizeof(double) * 2 * (size_t)n_node < ((size_t)1 << 20);
+    const bool device_ingest = cnt * (size_t)faces_itemsize + sizeof(double) * 2 * (size_t)n_node < ((size_t)1 << 20);
     xr_mesh *mesh = new xr_mesh();
     try {
         mesh->n_node = n_node;

@@ -1870,7 +1870,7 @@ int xr_overlap_apply_dev(xr_mesh *tree, xr_mesh *query, int relative, int method
         EarlyApply early;
         early.fn = [&](const xr_csr *c) { csr_apply_dev(c, method, percentile, source_dev, source_dtype, K, out_dev); };
         // one variable and a streaming reducer: the apply is one launch that needs no size on the host
-        const bool can_early = option(OPT_EARLY_APPLY) != 0 && K == 1 && method != XR_MODE && method != XR_PERCENTILE;
+        const bool can_early = K == 1 && method != XR_MODE && method != XR_PERCENTILE;
         overlap(tree, query, relative != 0, csr, can_early ? &early : nullptr);
         host_stamp(8);
         if (!early.done && K > 0) csr_apply_dev(csr, method, percentile, source_dev, source_dtype, K, out_dev);
@@ -1899,7 +1899,7 @@ int xr_overlap_partial_dev(xr_mesh *tree, xr_mesh *query, int relative, int meth
     try {
         EarlyApply early;
         early.fn = [&](const xr_csr *c) { csr_partial_dev(c, method, source_dev, source_dtype, K, out_dev, rows_layout); };
-        const bool can_early = option(OPT_EARLY_APPLY) != 0 && K == 1; // (one variable: the wave-window kernel needs no size on the host)
+        const bool can_early = K == 1; // (one variable: the wave-window kernel needs no size on the host)
         overlap(tree, query, relative != 0, csr, can_early ? &early : nullptr);
         if (!early.done && K > 0) csr_partial_dev(csr, method, source_dev, source_dtype, K, out_dev, rows_layout);
         dev_call_done();
