@@ -457,6 +457,33 @@ int xr_finalize_partial_dev(int method, const double *planes_dev, int64_t K, int
 int xr_reduce_partial_rows_dev(int method, const double *rows_dev, const int64_t *indptr_dev, const int64_t *order_dev,
                                int64_t n_targets, int64_t K, double *out_dev);
 
+/* ---- filling NaN entries (xugrid UgridDataArrayAccessor.laplace_interpolate / interpolate_na) ------------------- */
+/* A symmetric adjacency on the device: CSR from the host (int64 indptr [n+1], indices [nnz] ascending per row), weights
+ * `data` [nnz] (NULL: none; the fill then runs with unit weights only) and connected-component labels [n] (NULL: computed
+ * on the device -- the smallest node id of each component, by minimum-label propagation to a fixed point). */
+typedef struct xr_graph xr_graph;
+int xr_graph_from_csr(const int64_t *indptr, const int64_t *indices, const double *data, int64_t n, int64_t nnz,
+                      const int64_t *labels, xr_graph **out);
+int xr_graph_info(const xr_graph *graph, int64_t *n, int64_t *nnz);
+/* any pointer may be NULL; indptr [n+1], indices [nnz], data [nnz], labels [n] */
+int xr_graph_download(const xr_graph *graph, int64_t *indptr, int64_t *indices, double *data, int64_t *labels);
+int xr_graph_destroy(xr_graph *graph);
+/* Laplace fill of K slices in_dev float64 [K, n] -> out_dev [K, n] (device pointers; in_dev is not modified): unpreconditioned
+ * CG on the diagonally scaled system of xugrid/ugrid/interpolate.py:286-329 with scipy's stopping rule (||r|| < max(atol,
+ * rtol ||b||) before every iteration, x0 = 0), all slices together; the host reads the slices' state every `chunk`
+ * iterations (<= 0: default).  Per slice: iterations_out [K] and status_out [K] = XR_FILL_*.  Slices without NaN are copied. */
+#define XR_FILL_CONVERGED 0
+#define XR_FILL_MAXITER 1   /* the last iterate after maxiter iterations */
+#define XR_FILL_BREAKDOWN 2 /* p.Ap <= 0 or not finite */
+#define XR_FILL_NODATA 3    /* the slice holds no value at all */
+int xr_graph_laplace_fill_dev(const xr_graph *graph, const double *in_dev, double *out_dev, int64_t K, int use_weights,
+                              double atol, double rtol, int64_t maxiter, int64_t chunk, int64_t *iterations_out,
+                              int *status_out);
+/* nearest fill: null entries of in_dev [K, n] take the value of the nearest non-null entry (points xy_dev float64 [n, 2],
+ * Euclidean distance strictly below max_distance (INFINITY: no limit), lowest index among equidistant ones); the rest stays
+ * NaN.  XR_ERR_INVALID "All values are NA." for a slice without any value. */
+int xr_nearest_fill_dev(const double *xy_dev, int64_t n, const double *in_dev, double *out_dev, int64_t K, double max_distance);
+
 /* ---- raw HBM helpers for hosts that do not bring their own allocator -------------------- */
 int xr_dev_alloc(int64_t bytes, void **ptr_out);
 int xr_dev_free(void *ptr);

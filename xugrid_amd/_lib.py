@@ -119,6 +119,12 @@ SIGNATURES = {
     "xr_partial_fill_identity_dev": (c_int, [c_int, vp, c_i64, c_i64]),
     "xr_finalize_partial_dev": (c_int, [c_int, vp, c_i64, c_i64, vp]),
     "xr_reduce_partial_rows_dev": (c_int, [c_int, vp, vp, vp, c_i64, c_i64, vp]),
+    "xr_graph_from_csr": (c_int, [vp, vp, vp, c_i64, c_i64, vp, p_vp]),
+    "xr_graph_info": (c_int, [vp, p_i64, p_i64]),
+    "xr_graph_download": (c_int, [vp, vp, vp, vp, vp]),
+    "xr_graph_destroy": (c_int, [vp]),
+    "xr_graph_laplace_fill_dev": (c_int, [vp, vp, vp, c_i64, c_int, c_f64, c_f64, c_i64, c_i64, vp, vp]),
+    "xr_nearest_fill_dev": (c_int, [vp, c_i64, vp, vp, c_i64, c_f64]),
     "xr_dev_alloc": (c_int, [c_i64, p_vp]),
     "xr_dev_free": (c_int, [vp]),
     "xr_dev_upload": (c_int, [vp, vp, c_i64]),

@@ -4,6 +4,8 @@ xugrid/ugrid/connectivity.py used by the regridders: polygon
 (:372-382), dense connectivity inversion (:325-333), unique edges (:419-457) and the raster
 bounds helper of xugrid/conversion.py:272-282.  Face areas and centroids are computed on the
 device (xugrid_amd/csrc/xr_mesh.hip), not here.
+Also the adjacency matrices of the fills (xugrid/ugrid/connectivity.py:487-531): face -> face through shared edges and
+node -> node along edges, both symmetric scipy CSR whose data is the id of the connecting edge.
 """
 import numpy as np
 from scipy import sparse
@@ -93,3 +95,24 @@ def edge_connectivity(face_node_connectivity):
     order = np.argsort(face_edges == FILL_VALUE, axis=1, kind="stable")
     face_edges = np.take_along_axis(face_edges, order, axis=1)
     return edges.astype(IntDType), face_edges
+
+
+def _symmetric_csr(a, b, edge, n):
+    """Entries (a, b) and (b, a) with data ``edge`` -> (n, n) CSR, sorted columns, duplicates summed (coo -> csr)."""
+    rows = np.concatenate([a, b])
+    cols = np.concatenate([b, a])
+    data = np.concatenate([edge, edge])
+    return sparse.coo_matrix((data, (rows, cols)), shape=(n, n)).tocsr()
+
+
+def face_face_connectivity(edge_face_connectivity, n_face):
+    """Faces that share an edge; data = the shared edge's id."""
+    inner = edge_face_connectivity[:, 1] != FILL_VALUE
+    edge = np.nonzero(inner)[0].astype(IntDType)
+    return _symmetric_csr(edge_face_connectivity[inner, 0], edge_face_connectivity[inner, 1], edge, n_face)
+
+
+def node_node_connectivity(edge_node_connectivity, n_node):
+    """Nodes joined by an edge; data = the edge's id."""
+    edge = np.arange(len(edge_node_connectivity), dtype=IntDType)
+    return _symmetric_csr(edge_node_connectivity[:, 0], edge_node_connectivity[:, 1], edge, n_node)

@@ -1,0 +1,667 @@
+// xr_fill.hip -- filling the NaN entries of mesh data on the device: the Laplace fill of
+// xugrid/ugrid/interpolate.py:207-330 (UgridDataArrayAccessor.laplace_interpolate) and the nearest fill of
+// UgridDataArrayAccessor.interpolate_na (method "nearest").
+//
+// Laplace: a symmetric adjacency (xr_graph: CSR, optional weights, connected-component labels) and a batched masked
+// conjugate gradient.  Slice k of the K data slices has its own unknown set U_k (NaN entries of components that hold at
+// least one value); the system is the reference's diagonally scaled one, A = S L[U,U] S, b = S (-L[U,K] data[K]) with
+// S = diag(1/sqrt(D)), solved by plain CG (no ILU0: DESIGN section 7) with scipy's stopping rule.  All K slices iterate
+// together, four launches per iteration (spmv + p.q partials, alpha, update + r.r partials, beta / stopping rule); every
+// dot product is a block partial combined in a fixed order, so results are bit-identical run to run and independent of K.
+// A slice that stops freezes; the host enqueues chunks of iterations and reads the K active words once per chunk.
+//
+// Nearest: one lane per null point searches a uniform grid of the valid points ring by ring (exact f64 squared distances,
+// lowest index among equidistant candidates).  Slices with the same NaN mask as slice 0 share one search.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "xr_objects.h"
+
+struct xr_graph {
+    int64_t n = 0, nnz = 0;
+    xr::DevBuf<int32_t> indptr;  // [n+1]
+    xr::DevBuf<int32_t> indices; // [nnz] ascending per row
+    xr::DevBuf<double> data;     // [nnz] weights (1.0 when the caller gave none)
+    xr::DevBuf<int32_t> labels;  // [n] connected component: the smallest node id of the component
+    bool has_data = false;
+};
+
+namespace xr {
+
+enum FillStatus : int { FILL_CONVERGED = 0, FILL_MAXITER = 1, FILL_BREAKDOWN = 2, FILL_NODATA = 3 };
+
+static constexpr int FB = 256; // threads per block of the row kernels (one row per thread)
+
+// ---- fixed-order block sum (wave64 butterfly, then the four wave sums in wave order)
+__device__ __forceinline__ double block_sum(double v, double *sh) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) sh[w] = v;
+    __syncthreads();
+    double t = 0.0;
+    for (int i = 0; i < (int)(blockDim.x >> 6); i++) t += sh[i];
+    __syncthreads();
+    return t;
+}
+
+// ---------------------------------------------------------------------------------------------
+// graph construction
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(FB) k_label_init(int32_t *__restrict__ lab, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
+    if (i < n) lab[i] = (int32_t)i;
+}
+
+// one round of minimum-label propagation over the rows, then a pointer jump.  Labels only decrease and every label is a
+// node id of the same component, so the fixed point -- the smallest id of each component -- does not depend on the order
+// in which lanes see each other's stores.  `changed` is written with a plain store (any lane that lowers a label).
+__global__ void __launch_bounds__(FB)
+k_label_round(const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices, int64_t n, int32_t *lab,
+              int32_t *__restrict__ changed) {
+    const int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
+    if (i >= n) return;
+    int32_t m = lab[i];
+    for (int e = indptr[i]; e < indptr[i + 1]; e++) m = min(m, lab[indices[e]]);
+    m = min(m, lab[m]);
+    if (m < lab[i]) {
+        lab[i] = m;
+        *changed = 1;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Laplace fill: set-up
+// ---------------------------------------------------------------------------------------------
+// comp_valid[k, label] = 1 for every component of slice k that holds a value; has_valid / has_null per slice
+__global__ void __launch_bounds__(FB)
+k_fill_mark(const double *__restrict__ in, const int32_t *__restrict__ lab, int64_t n, uint8_t *__restrict__ comp_valid,
+            uint8_t *__restrict__ has_valid, uint8_t *__restrict__ has_null) {
+    const int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
+    const int64_t k = blockIdx.y;
+    if (i >= n) return;
+    const double v = in[k * n + i];
+    if (v == v) {
+        comp_valid[k * n + lab[i]] = 1;
+        has_valid[k] = 1;
+    } else {
+        has_null[k] = 1;
+    }
+}
+
+// out = in; unknown flag; scale s = 1/sqrt(D); b = s * sum_{j known} w_ij in_j; x = 0, r = b, p = 0; partial b.b
+__global__ void __launch_bounds__(FB)
+k_fill_setup(const double *__restrict__ in, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+             const double *__restrict__ data, int use_weights, const int32_t *__restrict__ lab,
+             const uint8_t *__restrict__ comp_valid, int64_t n, double *__restrict__ out, uint8_t *__restrict__ unknown,
+             double *__restrict__ scale, double *__restrict__ x, double *__restrict__ r, double *__restrict__ p0,
+             double *__restrict__ p1, double *__restrict__ partial) {
+    __shared__ double sh[FB / 64];
+    const int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
+    const int64_t k = blockIdx.y;
+    double bb = 0.0;
+    if (i < n) {
+        const int64_t o = k * n + i;
+        const double v = in[o];
+        out[o] = v;
+        const bool u = v != v && comp_valid[k * n + lab[i]];
+        unknown[o] = u;
+        double b = 0.0, s = 0.0;
+        if (u) {
+            double D = 0.0;
+            for (int e = indptr[i]; e < indptr[i + 1]; e++) {
+                const double w = use_weights ? data[e] : 1.0;
+                D += w;
+                const double dj = in[k * n + indices[e]];
+                if (dj == dj) b += w * dj;
+            }
+            s = D > 0.0 ? 1.0 / sqrt(D) : 1.0; // (an unknown row always has a neighbour: its component holds a value)
+            b *= s;
+        }
+        scale[o] = s;
+        x[o] = 0.0;
+        r[o] = b;
+        p0[o] = 0.0;
+        p1[o] = 0.0;
+        bb = b * b;
+    }
+    const double t = block_sum(bb, sh);
+    if (threadIdx.x == 0) partial[k * gridDim.x + blockIdx.x] = t;
+}
+
+// per-slice state, one record per slice
+struct CgState {
+    double rho, alpha, beta, tol;
+    int64_t iter;
+    int32_t active, status;
+};
+
+__device__ __forceinline__ double sum_partials(const double *__restrict__ part, int nb, double *sh) {
+    double t = 0.0;
+    for (int b = threadIdx.x; b < nb; b += blockDim.x) t += part[b];
+    return block_sum(t, sh);
+}
+
+// one block per slice: the scipy 1.15 `cg` prologue (bnrm2, atol = max(atol, rtol * bnrm2), bnrm2 == 0 -> x = 0)
+__global__ void __launch_bounds__(FB)
+k_cg_start(const double *__restrict__ partial, int nb, const uint8_t *__restrict__ has_valid,
+           const uint8_t *__restrict__ has_null, double atol, double rtol, int64_t maxiter, CgState *__restrict__ st,
+           int32_t *__restrict__ active_out) {
+    __shared__ double sh[FB / 64];
+    const int64_t k = blockIdx.x;
+    const double rr = sum_partials(partial + k * nb, nb, sh);
+    if (threadIdx.x) return;
+    CgState s{};
+    s.rho = rr;
+    s.tol = fmax(atol, rtol * sqrt(rr));
+    s.iter = 0;
+    s.active = 0;
+    s.status = FILL_CONVERGED;
+    if (!has_valid[k]) s.status = FILL_NODATA;
+    else if (!has_null[k] || rr == 0.0 || maxiter <= 0) s.status = FILL_CONVERGED;
+    else if (!(sqrt(rr) < s.tol)) s.active = 1;
+    st[k] = s;
+    active_out[k] = s.active;
+}
+
+// q = A p_new with p_new = r + beta p_old computed on the fly for every gathered row (p_old is never rewritten here), and
+// the block partial of p_new . q
+__global__ void __launch_bounds__(FB)
+k_cg_spmv(const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices, const double *__restrict__ data,
+          int use_weights, int64_t n, const uint8_t *__restrict__ unknown, const double *__restrict__ scale,
+          const double *__restrict__ r, const double *__restrict__ p_old, double *__restrict__ p_new,
+          double *__restrict__ q, const CgState *__restrict__ st, double *__restrict__ partial) {
+    __shared__ double sh[FB / 64];
+    const int64_t k = blockIdx.y;
+    if (!st[k].active) return;
+    const double beta = st[k].beta;
+    const int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
+    double pq = 0.0;
+    if (i < n && unknown[k * n + i]) {
+        const int64_t o = k * n + i;
+        const double si = scale[o];
+        const double pi = r[o] + beta * p_old[o];
+        double D = 0.0, acc = 0.0;
+        for (int e = indptr[i]; e < indptr[i + 1]; e++) {
+            const double w = use_weights ? data[e] : 1.0;
+            D += w;
+            const int64_t oj = k * n + indices[e];
+            if (unknown[oj]) acc += w * scale[oj] * (r[oj] + beta * p_old[oj]);
+        }
+        const double qi = si * (D * si * pi - acc);
+        p_new[o] = pi;
+        q[o] = qi;
+        pq = pi * qi;
+    }
+    const double t = block_sum(pq, sh);
+    if (threadIdx.x == 0) partial[k * gridDim.x + blockIdx.x] = t;
+}
+
+__global__ void __launch_bounds__(FB)
+k_cg_alpha(const double *__restrict__ partial, int nb, CgState *__restrict__ st, int32_t *__restrict__ active_out) {
+    __shared__ double sh[FB / 64];
+    const int64_t k = blockIdx.x;
+    if (!st[k].active) return;
+    const double pq = sum_partials(partial + k * nb, nb, sh);
+    if (threadIdx.x) return;
+    if (!(pq > 0.0) || !isfinite(pq)) {
+        st[k].active = 0;
+        st[k].status = FILL_BREAKDOWN;
+        active_out[k] = 0;
+        return;
+    }
+    st[k].alpha = st[k].rho / pq;
+}
+
+__global__ void __launch_bounds__(FB)
+k_cg_update(int64_t n, const uint8_t *__restrict__ unknown, const double *__restrict__ p, const double *__restrict__ q,
+            double *__restrict__ x, double *__restrict__ r, const CgState *__restrict__ st, double *__restrict__ partial) {
+    __shared__ double sh[FB / 64];
+    const int64_t k = blockIdx.y;
+    if (!st[k].active) return;
+    const double alpha = st[k].alpha;
+    const int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
+    double rr = 0.0;
+    if (i < n && unknown[k * n + i]) {
+        const int64_t o = k * n + i;
+        x[o] += alpha * p[o];
+        const double ri = r[o] - alpha * q[o];
+        r[o] = ri;
+        rr = ri * ri;
+    }
+    const double t = block_sum(rr, sh);
+    if (threadIdx.x == 0) partial[k * gridDim.x + blockIdx.x] = t;
+}
+
+// the top of scipy's next loop pass: stop when ||r|| < tol -- unless this was the last allowed iteration (scipy then
+// leaves the loop without the test and reports maxiter)
+__global__ void __launch_bounds__(FB)
+k_cg_beta(const double *__restrict__ partial, int nb, int64_t maxiter, CgState *__restrict__ st,
+          int32_t *__restrict__ active_out) {
+    __shared__ double sh[FB / 64];
+    const int64_t k = blockIdx.x;
+    if (!st[k].active) return;
+    const double rr = sum_partials(partial + k * nb, nb, sh);
+    if (threadIdx.x) return;
+    CgState s = st[k];
+    s.iter += 1;
+    if (s.iter >= maxiter) {
+        s.active = 0;
+        s.status = FILL_MAXITER;
+    } else if (sqrt(rr) < s.tol) {
+        s.active = 0;
+        s.status = FILL_CONVERGED;
+    } else {
+        s.beta = rr / s.rho;
+        s.rho = rr;
+    }
+    st[k] = s;
+    active_out[k] = s.active;
+}
+
+__global__ void __launch_bounds__(FB)
+k_fill_finish(int64_t n, int64_t total, const uint8_t *__restrict__ unknown, const double *__restrict__ scale,
+              const double *__restrict__ x, double *__restrict__ out) {
+    const int64_t o = (int64_t)blockIdx.x * FB + threadIdx.x;
+    if (o < total && unknown[o]) out[o] = scale[o] * x[o];
+}
+
+__global__ void k_cg_report(const CgState *__restrict__ st, int64_t K, int64_t *__restrict__ iters, int32_t *__restrict__ status) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < K) {
+        iters[k] = st[k].iter;
+        status[k] = st[k].status;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// nearest fill
+// ---------------------------------------------------------------------------------------------
+// mismatch[k] = 1 if the NaN mask of slice k differs from slice 0's
+__global__ void __launch_bounds__(FB)
+k_nn_mask_cmp(const double *__restrict__ in, int64_t n, uint8_t *__restrict__ mismatch) {
+    const int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
+    const int64_t k = blockIdx.y + 1;
+    if (i >= n) return;
+    const double a = in[i], b = in[k * n + i];
+    if ((a != a) != (b != b)) mismatch[k] = 1;
+}
+
+// per block: valid count, null count and the bbox of the valid points -> partial[b * 6 ..]
+__global__ void __launch_bounds__(FB)
+k_nn_stats(const double *__restrict__ xy, const double *__restrict__ v, int64_t n, double *__restrict__ partial) {
+    __shared__ double sh[6][FB / 64];
+    const int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
+    double c = 0.0, cn = 0.0, x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
+    if (i < n) {
+        if (v[i] == v[i]) {
+            c = 1.0;
+            x0 = x1 = xy[2 * i];
+            y0 = y1 = xy[2 * i + 1];
+        } else {
+            cn = 1.0;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        c += __shfl_xor(c, o, 64);
+        cn += __shfl_xor(cn, o, 64);
+        x0 = fmin(x0, __shfl_xor(x0, o, 64));
+        x1 = fmax(x1, __shfl_xor(x1, o, 64));
+        y0 = fmin(y0, __shfl_xor(y0, o, 64));
+        y1 = fmax(y1, __shfl_xor(y1, o, 64));
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        sh[0][w] = c, sh[1][w] = cn, sh[2][w] = x0, sh[3][w] = x1, sh[4][w] = y0, sh[5][w] = y1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int u = 1; u < FB / 64; u++) {
+            sh[0][0] += sh[0][u], sh[1][0] += sh[1][u];
+            sh[2][0] = fmin(sh[2][0], sh[2][u]), sh[3][0] = fmax(sh[3][0], sh[3][u]);
+            sh[4][0] = fmin(sh[4][0], sh[4][u]), sh[5][0] = fmax(sh[5][0], sh[5][u]);
+        }
+        for (int u = 0; u < 6; u++) partial[(int64_t)blockIdx.x * 6 + u] = sh[u][0];
+    }
+}
+
+__global__ void __launch_bounds__(FB) k_nn_stats_final(const double *__restrict__ partial, int nb, double *__restrict__ out) {
+    if (threadIdx.x) return;
+    double a[6] = {0.0, 0.0, INFINITY, -INFINITY, INFINITY, -INFINITY};
+    for (int b = 0; b < nb; b++) {
+        const double *p = partial + (int64_t)b * 6;
+        a[0] += p[0], a[1] += p[1];
+        a[2] = fmin(a[2], p[2]), a[3] = fmax(a[3], p[3]), a[4] = fmin(a[4], p[4]), a[5] = fmax(a[5], p[5]);
+    }
+    for (int u = 0; u < 6; u++) out[u] = a[u];
+}
+
+struct NnGrid {
+    double x0, y0, inv_h, h;
+    int nx, ny;
+};
+
+__device__ __forceinline__ int nn_cell_x(const NnGrid &g, double x) {
+    const double t = (x - g.x0) * g.inv_h;
+    return t < 0.0 ? 0 : t >= (double)(g.nx - 1) ? g.nx - 1 : (int)t;
+}
+__device__ __forceinline__ int nn_cell_y(const NnGrid &g, double y) {
+    const double t = (y - g.y0) * g.inv_h;
+    return t < 0.0 ? 0 : t >= (double)(g.ny - 1) ? g.ny - 1 : (int)t;
+}
+
+__global__ void __launch_bounds__(FB)
+k_nn_count(const double *__restrict__ xy, const double *__restrict__ v, int64_t n, NnGrid g, int32_t *__restrict__ count) {
+    const int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
+    if (i >= n || v[i] != v[i]) return;
+    atomicAdd(&count[(int64_t)nn_cell_y(g, xy[2 * i + 1]) * g.nx + nn_cell_x(g, xy[2 * i])], 1);
+}
+
+__global__ void __launch_bounds__(FB)
+k_nn_scatter(const double *__restrict__ xy, const double *__restrict__ v, int64_t n, NnGrid g, const int32_t *__restrict__ start,
+             int32_t *__restrict__ cursor, int32_t *__restrict__ items) {
+    const int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
+    if (i >= n || v[i] != v[i]) return;
+    const int64_t c = (int64_t)nn_cell_y(g, xy[2 * i + 1]) * g.nx + nn_cell_x(g, xy[2 * i]);
+    items[start[c] + atomicAdd(&cursor[c], 1)] = (int32_t)i;
+}
+
+// one lane per null point: rings of cells around the point's cell.  After ring R every point within the block of cells
+// [cx - R, cx + R] x [cy - R, cy + R] has been seen; an unseen point is at least as far as the nearest side of that block.
+__global__ void __launch_bounds__(FB)
+k_nn_search(const double *__restrict__ xy, const double *__restrict__ v, int64_t n, NnGrid g, const int32_t *__restrict__ start,
+            const int32_t *__restrict__ items, double md2, double max_distance, int32_t *__restrict__ src) {
+    const int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
+    if (i >= n) return;
+    if (v[i] == v[i]) {
+        src[i] = (int32_t)i;
+        return;
+    }
+    const double px = xy[2 * i], py = xy[2 * i + 1];
+    const int cx = nn_cell_x(g, px), cy = nn_cell_y(g, py);
+    const int rmax = max(g.nx, g.ny);
+    double best = INFINITY;
+    int32_t bj = -1;
+    for (int R = 0; R <= rmax; R++) {
+        const int ylo = cy - R, yhi = cy + R, xlo = cx - R, xhi = cx + R;
+        for (int yy = max(ylo, 0); yy <= min(yhi, g.ny - 1); yy++) {
+            const bool edge_row = yy == ylo || yy == yhi;
+            // the ring's cells of this row: all of it on the two edge rows, its two ends elsewhere
+            for (int xx = edge_row ? max(xlo, 0) : xlo; xx <= min(xhi, g.nx - 1); xx = edge_row || xx == xhi ? xx + 1 : xhi) {
+                if (xx < 0) continue;
+                const int64_t c = (int64_t)yy * g.nx + xx;
+                for (int e = start[c]; e < start[c + 1]; e++) {
+                    const int32_t j = items[e];
+                    const double dx = xy[2 * (int64_t)j] - px, dy = xy[2 * (int64_t)j + 1] - py;
+                    const double d2 = dx * dx + dy * dy;
+                    if (d2 < md2 && (d2 < best || (d2 == best && j < bj))) {
+                        best = d2;
+                        bj = j;
+                    }
+                }
+            }
+        }
+        // distance from the point to the outside of the block seen so far
+        const double lx = px - (g.x0 + (double)(cx - R) * g.h), hx = g.x0 + (double)(cx + R + 1) * g.h - px;
+        const double ly = py - (g.y0 + (double)(cy - R) * g.h), hy = g.y0 + (double)(cy + R + 1) * g.h - py;
+        const double lb = fmax(0.0, fmin(fmin(lx, hx), fmin(ly, hy)));
+        if (lb * lb > best || lb >= max_distance) break;
+    }
+    src[i] = bj;
+}
+
+__global__ void __launch_bounds__(FB)
+k_nn_gather(const double *__restrict__ in, int64_t n, const int32_t *__restrict__ src, const int64_t *__restrict__ slices,
+            double *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
+    if (i >= n) return;
+    const int64_t k = slices[blockIdx.y];
+    const int32_t j = src[i];
+    out[k * n + i] = j >= 0 ? in[k * n + j] : NAN;
+}
+
+static void nearest_group(const double *xy, int64_t n, const double *in, double *out, const std::vector<int64_t> &slices,
+                          double max_distance) {
+    const int64_t k0 = slices[0];
+    const double *v = in + k0 * n;
+    const unsigned nb = div_up(n, FB);
+    DevBuf<double> partial((size_t)nb * 6), stats(6);
+    XR_LAUNCH("nn_stats", k_nn_stats, dim3(nb), dim3(FB), 0, xy, v, n, partial.get());
+    XR_LAUNCH("nn_stats_final", k_nn_stats_final, dim3(1), dim3(64), 0, partial.get(), (int)nb, stats.get());
+    double h[6];
+    d2h(h, stats.get(), sizeof(h));
+    const int64_t nv = (int64_t)h[0], nnull = (int64_t)h[1];
+    XR_REQUIRE(nv > 0, XR_ERR_INVALID, "All values are NA.");
+    NnGrid g{};
+    const double w = std::max(h[3] - h[2], 0.0), ht = std::max(h[5] - h[4], 0.0);
+    const double target = std::max<double>(1.0, (double)nv / 2.0); // ~2 valid points per cell
+    double cell = std::sqrt(std::max(w * ht, 0.0) / target);
+    if (!(cell > 0.0)) cell = std::max(std::max(w, ht) / target, 0.0);
+    if (!(cell > 0.0) || !std::isfinite(cell)) cell = 1.0;
+    int64_t nx = std::min<int64_t>((int64_t)(w / cell) + 1, 1 << 15), ny = std::min<int64_t>((int64_t)(ht / cell) + 1, 1 << 15);
+    while (nx * ny > 4 * nv + 16) { // (degenerate boxes)
+        cell *= 1.5;
+        nx = (int64_t)(w / cell) + 1;
+        ny = (int64_t)(ht / cell) + 1;
+    }
+    g.x0 = h[2], g.y0 = h[4], g.h = cell, g.inv_h = 1.0 / cell, g.nx = (int)nx, g.ny = (int)ny;
+    const int64_t nc = nx * ny;
+    DevBuf<int32_t> count_cursor(2 * (size_t)nc), start((size_t)nc + 1), items((size_t)nv), src((size_t)n);
+    fill_i32(count_cursor.get(), 0, 2 * nc);
+    if (nnull > 0) {
+        XR_LAUNCH("nn_count", k_nn_count, dim3(nb), dim3(FB), 0, xy, v, n, g, count_cursor.get());
+        exclusive_scan_i32(count_cursor.get(), start.get(), nc);
+        XR_LAUNCH("nn_scatter", k_nn_scatter, dim3(nb), dim3(FB), 0, xy, v, n, g, start.get(), count_cursor.get() + nc, items.get());
+        const double md2 = std::isinf(max_distance) ? INFINITY : max_distance * max_distance;
+        XR_LAUNCH("nn_search", k_nn_search, dim3(nb), dim3(FB), 0, xy, v, n, g, start.get(), items.get(), md2, max_distance,
+                  src.get());
+    } else {
+        XR_LAUNCH("nn_identity", k_label_init, dim3(nb), dim3(FB), 0, src.get(), n);
+    }
+    DevBuf<int64_t> sl(slices.size());
+    h2d(sl.get(), slices.data(), sizeof(int64_t) * slices.size());
+    for (size_t s0 = 0; s0 < slices.size(); s0 += 65535) {
+        const size_t cnt = std::min<size_t>(65535, slices.size() - s0);
+        XR_LAUNCH("nn_gather", k_nn_gather, dim3(nb, (unsigned)cnt), dim3(FB), 0, in, n, src.get(), sl.get() + s0, out);
+    }
+}
+
+static void laplace_fill(const xr_graph *g, const double *in_dev, double *out_dev, int64_t K, int use_weights, double atol,
+                         double rtol, int64_t maxiter, int64_t chunk, int64_t *iterations_out, int *status_out);
+static void nearest_fill(const double *xy_dev, int64_t n, const double *in_dev, double *out_dev, int64_t K, double max_distance);
+
+} // namespace xr
+
+using namespace xr;
+
+extern "C" {
+
+int xr_graph_from_csr(const int64_t *indptr, const int64_t *indices, const double *data, int64_t n, int64_t nnz,
+                      const int64_t *labels, xr_graph **out) {
+    XR_API_BEGIN
+    XR_REQUIRE(indptr && out && (indices || nnz == 0), XR_ERR_INVALID, "xr_graph_from_csr: NULL argument");
+    XR_REQUIRE(n >= 0 && nnz >= 0, XR_ERR_INVALID, "xr_graph_from_csr: negative size");
+    XR_REQUIRE(n < INT32_MAX && nnz < INT32_MAX, XR_ERR_LIMIT, "xr_graph_from_csr: more than 2^31 rows or entries");
+    XR_REQUIRE(indptr[0] == 0 && indptr[n] == nnz, XR_ERR_INVALID, "xr_graph_from_csr: indptr does not span the entries");
+    std::vector<int32_t> ip((size_t)n + 1), ix((size_t)nnz), lb;
+    for (int64_t i = 0; i <= n; i++) {
+        XR_REQUIRE(i == 0 || indptr[i] >= indptr[i - 1], XR_ERR_INVALID, "xr_graph_from_csr: indptr is not ascending");
+        ip[(size_t)i] = (int32_t)indptr[i];
+    }
+    for (int64_t e = 0; e < nnz; e++) {
+        XR_REQUIRE(indices[e] >= 0 && indices[e] < n, XR_ERR_INVALID, "xr_graph_from_csr: column index out of range");
+        ix[(size_t)e] = (int32_t)indices[e];
+    }
+    if (labels) {
+        lb.resize((size_t)n);
+        for (int64_t i = 0; i < n; i++) {
+            XR_REQUIRE(labels[i] >= 0 && labels[i] < n, XR_ERR_INVALID, "xr_graph_from_csr: component label out of range");
+            lb[(size_t)i] = (int32_t)labels[i];
+        }
+    }
+    std::unique_ptr<xr_graph> g(new xr_graph());
+    g->n = n, g->nnz = nnz, g->has_data = data != nullptr;
+    g->indptr.alloc((size_t)n + 1);
+    g->indices.alloc((size_t)nnz);
+    g->data.alloc((size_t)nnz);
+    g->labels.alloc((size_t)n);
+    h2d(g->indptr.get(), ip.data(), sizeof(int32_t) * ip.size());
+    if (nnz) h2d(g->indices.get(), ix.data(), sizeof(int32_t) * ix.size());
+    if (nnz) {
+        if (data) h2d(g->data.get(), data, sizeof(double) * (size_t)nnz);
+        else fill_f64(g->data.get(), 1.0, nnz);
+    }
+    if (labels) {
+        if (n) h2d(g->labels.get(), lb.data(), sizeof(int32_t) * lb.size());
+    } else if (n) {
+        DevBuf<int32_t> changed(1);
+        XR_LAUNCH("label_init", k_label_init, dim3(div_up(n, FB)), dim3(FB), 0, g->labels.get(), n);
+        for (;;) {
+            fill_i32(changed.get(), 0, 1);
+            XR_LAUNCH("label_round", k_label_round, dim3(div_up(n, FB)), dim3(FB), 0, g->indptr.get(), g->indices.get(), n,
+                      g->labels.get(), changed.get());
+            if (!read_scalar(changed.get())) break;
+        }
+    }
+    stream_sync();
+    *out = g.release();
+    XR_API_END
+}
+
+int xr_graph_info(const xr_graph *g, int64_t *n, int64_t *nnz) {
+    XR_API_BEGIN
+    XR_REQUIRE(g, XR_ERR_INVALID, "xr_graph_info: NULL handle");
+    if (n) *n = g->n;
+    if (nnz) *nnz = g->nnz;
+    XR_API_END
+}
+
+int xr_graph_download(const xr_graph *g, int64_t *indptr, int64_t *indices, double *data, int64_t *labels) {
+    XR_API_BEGIN
+    XR_REQUIRE(g, XR_ERR_INVALID, "xr_graph_download: NULL handle");
+    std::vector<int32_t> t((size_t)std::max(g->n + 1, g->nnz));
+    if (indptr) {
+        d2h(t.data(), g->indptr.get(), sizeof(int32_t) * (size_t)(g->n + 1));
+        for (int64_t i = 0; i <= g->n; i++) indptr[i] = t[(size_t)i];
+    }
+    if (indices && g->nnz) {
+        d2h(t.data(), g->indices.get(), sizeof(int32_t) * (size_t)g->nnz);
+        for (int64_t e = 0; e < g->nnz; e++) indices[e] = t[(size_t)e];
+    }
+    if (data && g->nnz) d2h(data, g->data.get(), sizeof(double) * (size_t)g->nnz);
+    if (labels && g->n) {
+        d2h(t.data(), g->labels.get(), sizeof(int32_t) * (size_t)g->n);
+        for (int64_t i = 0; i < g->n; i++) labels[i] = t[(size_t)i];
+    }
+    XR_API_END
+}
+
+int xr_graph_destroy(xr_graph *g) {
+    XR_API_BEGIN
+    if (g) {
+        release_point();
+        delete g;
+    }
+    XR_API_END
+}
+
+int xr_graph_laplace_fill_dev(const xr_graph *g, const double *in_dev, double *out_dev, int64_t K, int use_weights,
+                              double atol, double rtol, int64_t maxiter, int64_t chunk, int64_t *iterations_out,
+                              int *status_out) {
+    XR_API_BEGIN
+    XR_REQUIRE(g && iterations_out && status_out, XR_ERR_INVALID, "xr_graph_laplace_fill_dev: NULL argument");
+    XR_REQUIRE(K >= 0 && K < 65536, XR_ERR_INVALID, "xr_graph_laplace_fill_dev: K must be in [0, 65536)");
+    const int64_t n = g->n;
+    XR_REQUIRE((in_dev && out_dev) || n == 0 || K == 0, XR_ERR_INVALID, "xr_graph_laplace_fill_dev: NULL data");
+    XR_REQUIRE(!use_weights || g->has_data, XR_ERR_INVALID, "xr_graph_laplace_fill_dev: the graph has no weights");
+    if (K > 0) laplace_fill(g, in_dev, out_dev, K, use_weights, atol, rtol, maxiter, chunk, iterations_out, status_out);
+    XR_API_END
+}
+
+} // extern "C"
+
+namespace xr {
+static void laplace_fill(const xr_graph *g, const double *in_dev, double *out_dev, int64_t K, int use_weights, double atol,
+                         double rtol, int64_t maxiter, int64_t chunk, int64_t *iterations_out, int *status_out) {
+    const int64_t n = g->n;
+    if (chunk <= 0) chunk = 24;
+    const int64_t total = n * K;
+    const unsigned nb = div_up(std::max<int64_t>(n, 1), FB);
+    DevBuf<uint8_t> flags((size_t)total * 2 + 2 * (size_t)K); // comp_valid, unknown, has_valid, has_null
+    uint8_t *comp_valid = flags.get(), *unknown = flags.get() + total, *has_valid = unknown + total, *has_null = has_valid + K;
+    DevBuf<double> work((size_t)total * 6), partial((size_t)K * nb);
+    double *scale = work.get(), *x = scale + total, *r = x + total, *p[2] = {r + total, r + 2 * total}, *q = r + 3 * total;
+    DevBuf<CgState> st((size_t)K);
+    DevBuf<int32_t> active((size_t)K);
+    DevBuf<int64_t> iters((size_t)K);
+    DevBuf<int32_t> status((size_t)K);
+    XR_HIP(hipMemsetAsync(flags.get(), 0, flags.bytes(), launch_stream()));
+    const dim3 rows(nb, (unsigned)K);
+    if (n) {
+        XR_LAUNCH("fill_mark", k_fill_mark, rows, dim3(FB), 0, in_dev, g->labels.get(), n, comp_valid, has_valid, has_null);
+        XR_LAUNCH("fill_setup", k_fill_setup, rows, dim3(FB), 0, in_dev, g->indptr.get(), g->indices.get(), g->data.get(),
+                  use_weights, g->labels.get(), comp_valid, n, out_dev, unknown, scale, x, r, p[0], p[1], partial.get());
+    } else {
+        fill_f64(partial.get(), 0.0, (int64_t)K * nb);
+    }
+    XR_LAUNCH("cg_start", k_cg_start, dim3((unsigned)K), dim3(FB), 0, partial.get(), (int)nb, has_valid, has_null, atol, rtol,
+              maxiter, st.get(), active.get());
+    std::vector<int32_t> h_active((size_t)K);
+    d2h(h_active.data(), active.get(), sizeof(int32_t) * (size_t)K);
+    int64_t done = 0;
+    int parity = 0;
+    auto any_active = [&]() { return std::any_of(h_active.begin(), h_active.end(), [](int32_t a) { return a != 0; }); };
+    while (any_active() && done < maxiter) {
+        const int64_t steps = std::min(chunk, maxiter - done);
+        for (int64_t s = 0; s < steps; s++) {
+            XR_LAUNCH("cg_spmv", k_cg_spmv, rows, dim3(FB), 0, g->indptr.get(), g->indices.get(), g->data.get(), use_weights, n,
+                      unknown, scale, r, p[parity], p[parity ^ 1], q, st.get(), partial.get());
+            XR_LAUNCH("cg_alpha", k_cg_alpha, dim3((unsigned)K), dim3(FB), 0, partial.get(), (int)nb, st.get(), active.get());
+            XR_LAUNCH("cg_update", k_cg_update, rows, dim3(FB), 0, n, unknown, p[parity ^ 1], q, x, r, st.get(), partial.get());
+            XR_LAUNCH("cg_beta", k_cg_beta, dim3((unsigned)K), dim3(FB), 0, partial.get(), (int)nb, maxiter, st.get(), active.get());
+            parity ^= 1;
+        }
+        done += steps;
+        d2h(h_active.data(), active.get(), sizeof(int32_t) * (size_t)K);
+    }
+    if (total) XR_LAUNCH("fill_finish", k_fill_finish, dim3(div_up(total, FB)), dim3(FB), 0, n, total, unknown, scale, x, out_dev);
+    XR_LAUNCH("cg_report", k_cg_report, dim3(div_up(K, 64)), dim3(64), 0, st.get(), K, iters.get(), status.get());
+    d2h(iterations_out, iters.get(), sizeof(int64_t) * (size_t)K);
+    d2h(status_out, status.get(), sizeof(int32_t) * (size_t)K);
+}
+} // namespace xr
+
+extern "C" {
+
+int xr_nearest_fill_dev(const double *xy_dev, int64_t n, const double *in_dev, double *out_dev, int64_t K, double max_distance) {
+    XR_API_BEGIN
+    XR_REQUIRE(K >= 0 && K < 65536, XR_ERR_INVALID, "xr_nearest_fill_dev: K must be in [0, 65536)");
+    XR_REQUIRE((xy_dev && in_dev && out_dev) || n == 0 || K == 0, XR_ERR_INVALID, "xr_nearest_fill_dev: NULL argument");
+    XR_REQUIRE(n < INT32_MAX, XR_ERR_LIMIT, "xr_nearest_fill_dev: more than 2^31 points");
+    XR_REQUIRE(max_distance >= 0.0, XR_ERR_INVALID, "xr_nearest_fill_dev: max_distance must be non-negative");
+    if (n > 0 && K > 0) nearest_fill(xy_dev, n, in_dev, out_dev, K, max_distance);
+    dev_call_done();
+    XR_API_END
+}
+
+} // extern "C"
+
+namespace xr {
+static void nearest_fill(const double *xy_dev, int64_t n, const double *in_dev, double *out_dev, int64_t K, double max_distance) {
+    std::vector<uint8_t> mismatch((size_t)K, 0);
+    if (K > 1) {
+        DevBuf<uint8_t> mm((size_t)K);
+        XR_HIP(hipMemsetAsync(mm.get(), 0, (size_t)K, launch_stream()));
+        XR_LAUNCH("nn_mask_cmp", k_nn_mask_cmp, dim3(div_up(n, FB), (unsigned)(K - 1)), dim3(FB), 0, in_dev, n, mm.get());
+        d2h(mismatch.data(), mm.get(), (size_t)K);
+    }
+    std::vector<int64_t> same;
+    for (int64_t k = 0; k < K; k++)
+        if (!mismatch[(size_t)k]) same.push_back(k);
+    nearest_group(xy_dev, n, in_dev, out_dev, same, max_distance);
+    for (int64_t k = 1; k < K; k++)
+        if (mismatch[(size_t)k]) nearest_group(xy_dev, n, in_dev, out_dev, std::vector<int64_t>{k}, max_distance);
+}
+} // namespace xr

@@ -1,0 +1,216 @@
+"""
+Filling the NaN entries of mesh data on the device: ``laplace_interpolate`` (xugrid/ugrid/interpolate.py:207-330) and the
+nearest fill of ``UgridDataArrayAccessor.interpolate_na`` (xugrid/core/dataarray_accessor.py:761-886).  Kernels in
+``csrc/xr_fill.hip``.
+
+Arrays in, arrays out, like ``Regridder.regrid``: ``data`` is ``(..., n)``; the leading dims are K slices filled
+independently (the reference's ``apply_ufunc(vectorize=True)``).  numpy in -> numpy out; a device array in (torch tensor on
+the GPU, ``__cuda_array_interface__``) -> a float64 device array of the same kind, nothing crossing PCIe but the per-slice
+status words.  The input is never modified.
+
+Deviation: the reference preconditions CG with a sequential ILU0; the device runs unpreconditioned CG on
+the same diagonally scaled system under scipy's stopping rule.  ``delta`` / ``relax`` (ILU0 knobs) are accepted at 0.0 only;
+``direct_solve=True`` runs the device CG to ``rtol=1e-13, atol=0`` with ``maxiter = 10 n``.  ``maxiter`` counts device CG
+iterations, which for a wide hole are more than the reference's preconditioned ones.
+"""
+import ctypes
+import warnings
+
+import numpy as np
+
+from . import _lib, engine
+from ._lib import check
+
+CG_CHUNK = 24  # CG iterations enqueued between two reads of the slices' state
+_STATUS_MAXITER, _STATUS_BREAKDOWN, _STATUS_NODATA = 1, 2, 3
+
+# what the last fill reported per slice (tests and profiles read it: iteration counts of the device CG)
+last_iterations = None
+
+
+class DeviceGraph:
+    """A symmetric adjacency in HBM (include/xugrid_amd.h: xr_graph): CSR structure, the weights, component labels."""
+
+    def __init__(self, connectivity, labels=None, weights=None):
+        lib = _lib.load()
+        n, m = connectivity.shape
+        indptr = np.ascontiguousarray(connectivity.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(connectivity.indices, dtype=np.int64)
+        data = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.int64)
+        handle = ctypes.c_void_p()
+        check(lib.xr_graph_from_csr(
+            indptr.ctypes.data_as(ctypes.c_void_p), indices.ctypes.data_as(ctypes.c_void_p),
+            None if data is None else data.ctypes.data_as(ctypes.c_void_p), n, indices.size,
+            None if lab is None else lab.ctypes.data_as(ctypes.c_void_p), ctypes.byref(handle)))
+        self._h = handle
+        self.n, self.nnz, self.has_weights = n, indices.size, data is not None
+
+    def labels(self):
+        out = np.empty(self.n, dtype=np.int64)
+        check(_lib.load().xr_graph_download(self._h, None, None, None, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                _lib.load().xr_graph_destroy(h)
+            except Exception:  # noqa: BLE001
+                pass
+            self._h = None
+
+
+def _check_square(connectivity):
+    n, m = connectivity.shape
+    if n != m:
+        raise ValueError(f"connectivity is not a square matrix: ({n}, {m})")
+    return n
+
+
+def _check_ilu_options(delta, relax):
+    if delta != 0.0 or relax != 0.0:
+        raise ValueError(
+            "delta and relax tune the reference's ILU0 preconditioner; the device solver runs unpreconditioned CG on the "
+            "same scaled system (no ILU0), so they must be 0.0"
+        )
+
+
+def _as_slices(data, n):
+    """-> (kind, array, K, shape): kind 'device' (float64 contiguous device array) or 'host' (float64 numpy (K, n))."""
+    info = engine.device_array_info(data)
+    if info is not None:
+        ptr, shape, dtype = info
+        if dtype != np.float64:
+            if (type(data).__module__ or "").startswith("torch"):
+                data = data.double()
+                ptr, shape, dtype = engine.device_array_info(data)
+            else:
+                raise TypeError(f"device data must be float64, received {dtype}")
+        if len(shape) == 0 or shape[-1] != n:
+            raise ValueError(f"expected data of shape (..., {n}), received: {shape}")
+        K = int(np.prod(shape[:-1], dtype=np.int64))
+        return "device", data, K, shape
+    a = np.asarray(data, dtype=np.float64)
+    if a.ndim == 0 or a.shape[-1] != n:
+        raise ValueError(f"expected data of shape (..., {n}), received: {a.shape}")
+    return "host", np.ascontiguousarray(a), int(np.prod(a.shape[:-1], dtype=np.int64)), a.shape
+
+
+def _run(data, n, launch):
+    """Move ``data`` to the device if it is not there, run ``launch(in_ptr, out_ptr, K)``, return the same kind."""
+    kind, a, K, shape = _as_slices(data, n)
+    if kind == "device":
+        engine.sync_producer(a)
+        out, out_ptr = engine.empty_like_device(a, shape)
+        launch(engine.device_array_info(a)[0], out_ptr, K)
+        return out
+    if a.size == 0:
+        return a.copy()
+    src = engine.DeviceArray.from_host(a)
+    dst = engine.DeviceArray(a.shape)
+    launch(src.ptr, dst.ptr, K)
+    return dst.download()
+
+
+def laplace_fill(graph: DeviceGraph, data, use_weights, direct_solve=False, delta=0.0, relax=0.0, atol=1e-4, rtol=0.0,
+                 maxiter=500):
+    """Laplace fill of ``data`` (..., n) over ``graph`` (see the module docstring)."""
+    global last_iterations
+    _check_ilu_options(delta, relax)
+    if use_weights and not graph.has_weights:
+        raise ValueError("use_weights requires a connectivity with weights")
+    n = graph.n
+    if direct_solve:
+        atol, rtol, maxiter = 0.0, 1e-13, 10 * max(n, 1)
+    maxiter = int(maxiter)
+    result = {}
+
+    def launch(in_ptr, out_ptr, K):
+        iters = np.zeros(K, dtype=np.int64)
+        status = np.zeros(K, dtype=np.int32)
+        check(_lib.load().xr_graph_laplace_fill_dev(
+            graph._h, ctypes.c_void_p(in_ptr), ctypes.c_void_p(out_ptr), K, int(bool(use_weights)), float(atol),
+            float(rtol), maxiter, CG_CHUNK, iters.ctypes.data_as(ctypes.c_void_p), status.ctypes.data_as(ctypes.c_void_p)))
+        result["iters"], result["status"] = iters, status
+
+    out = _run(data, n, launch)
+    status = result.get("status", np.zeros(0, dtype=np.int32))
+    last_iterations = result.get("iters")
+    if (status == _STATUS_NODATA).any():
+        raise ValueError("data is fully nodata")
+    if (status == _STATUS_BREAKDOWN).any():
+        raise ValueError("conjugate gradient: illegal input or breakdown")
+    if (status == _STATUS_MAXITER).any():
+        warnings.warn(f"Failed to converge after {maxiter} iterations", UserWarning, stacklevel=3)
+    return out
+
+
+def nearest_fill(xy_dev: "engine.DeviceArray", data, max_distance=None):
+    """Nearest fill of ``data`` (..., n) at the points ``xy_dev`` (a float64 (n, 2) device array)."""
+    if max_distance is None:
+        max_distance = np.inf
+    max_distance = float(max_distance)
+    if not max_distance >= 0.0:
+        raise ValueError("max_distance must be non-negative")
+    n = xy_dev.shape[0]
+
+    def launch(in_ptr, out_ptr, K):
+        check(_lib.load().xr_nearest_fill_dev(ctypes.c_void_p(xy_dev.ptr), n, ctypes.c_void_p(in_ptr),
+                                              ctypes.c_void_p(out_ptr), K, max_distance))
+
+    return _run(data, n, launch)
+
+
+def laplace_interpolate(data, connectivity, components_labels, use_weights, direct_solve=False, delta=0.0, relax=0.0,
+                        atol=1e-4, rtol=0.0, maxiter=500):
+    """xugrid.ugrid.interpolate.laplace_interpolate on the device: 1-D ``data`` (n,), scipy CSR ``connectivity`` (n, n)
+    whose ``data`` are the weights when ``use_weights``, ``components_labels`` (n,) as scipy's ``connected_components``.
+    The solver is the device CG of the module docstring (no ILU0; ``delta`` / ``relax`` must be 0.0)."""
+    n = _check_square(connectivity)
+    shape = engine.device_array_info(data)
+    shape = shape[1] if shape is not None else np.shape(data)
+    if tuple(shape) != (n,):
+        raise ValueError(f"expected data of shape ({n},), received: {tuple(shape)}")
+    _check_ilu_options(delta, relax)
+    graph = DeviceGraph(connectivity, labels=components_labels, weights=connectivity.data if use_weights else None)
+    return laplace_fill(graph, data, use_weights, direct_solve, delta, relax, atol, rtol, maxiter)
+
+
+def connectivity_weights(connectivity, coordinates):
+    """ugridbase.py:962-970: mean(d) / d of the distances between the connected points, in the matrix' entry order."""
+    coo = connectivity.tocoo()
+    d = coordinates[coo.col] - coordinates[coo.row]
+    distance = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1])
+    return distance.mean() / distance
+
+
+class GridFill:
+    """The fills of one grid: device graphs and point arrays per dimension, built on first use and kept."""
+
+    def __init__(self):
+        self.graphs = {}
+        self.points = {}
+
+    def graph(self, key, make_connectivity, coordinates):
+        if key not in self.graphs:
+            conn = make_connectivity()
+            self.graphs[key] = DeviceGraph(conn, weights=connectivity_weights(conn, coordinates()))
+        return self.graphs[key]
+
+    def xy(self, key, coordinates):
+        if key not in self.points:
+            self.points[key] = engine.DeviceArray.from_host(np.ascontiguousarray(coordinates(), dtype=np.float64))
+        return self.points[key]
+
+
+def resolve_dim(grid, dim, facets):
+    """'node' / 'edge' / 'face' or the grid's dimension name -> facet name."""
+    names = {getattr(grid, f"{f}_dimension"): f for f in facets}
+    if dim is None:
+        dim = grid.core_dimension
+    if dim in facets:
+        return dim
+    if dim in names:
+        return names[dim]
+    raise ValueError(f"Expected one of {sorted(list(names) + list(facets))}; got: {dim}")

@@ -10,7 +10,7 @@ import numpy as np
 
 import ctypes
 
-from . import _lib, connectivity
+from . import _lib, connectivity, fill
 from .celltree import CellTree2d
 from .engine import FloatDType, IntDType
 
@@ -125,6 +125,14 @@ class Ugrid2d:
         return f"{self.name}_nFaces"
 
     @property
+    def node_dimension(self):
+        return f"{self.name}_nNodes"
+
+    @property
+    def edge_dimension(self):
+        return f"{self.name}_nEdges"
+
+    @property
     def core_dimension(self):
         return self.face_dimension
 
@@ -162,6 +170,7 @@ class Ugrid2d:
         the engine's pool cannot reclaim while the grid is alive).  The next regridder on this grid rebuilds them."""
         self._celltree = None
         self._voronoi_device_cache = None
+        self.__dict__.pop("_fill_cache", None)
 
     @property
     def device_mesh(self):
@@ -236,6 +245,73 @@ class Ugrid2d:
                 self.face_node_connectivity, n_rows=self.n_node
             )
         return self._node_face_connectivity
+
+    @property
+    def n_edge(self):
+        return self.edge_node_connectivity.shape[0]
+
+    @property
+    def edge_coordinates(self):
+        """(n_edge, 2) edge midpoints (ugridbase.py:606-609)."""
+        xy = self.node_coordinates_of(self.edge_node_connectivity.ravel()).reshape(-1, 2, 2)
+        return 0.5 * (xy[:, 0] + xy[:, 1])
+
+    @property
+    def face_face_connectivity(self):
+        """Faces sharing an edge, scipy CSR; data = the shared edge's id (ugrid2d.py:680-698)."""
+        return connectivity.face_face_connectivity(self.edge_face_connectivity, self.n_face)
+
+    @property
+    def node_node_connectivity(self):
+        """Nodes joined by an edge, scipy CSR; data = the edge's id."""
+        return connectivity.node_node_connectivity(self.edge_node_connectivity, self.n_node)
+
+    def get_connectivity_matrix(self, dim, xy_weights):
+        """ugrid2d.py:746-762: the face or node adjacency; with ``xy_weights`` its data are mean(d) / d of the centroid or
+        node distances (ugridbase.py:962-970)."""
+        facet = fill.resolve_dim(self, dim, ("node", "face"))
+        conn = self.node_node_connectivity if facet == "node" else self.face_face_connectivity
+        if xy_weights:
+            conn.data = fill.connectivity_weights(conn, self._fill_coordinates(facet))
+        return conn
+
+    # ---- filling NaN entries on the device (xugrid_amd/fill.py)
+    def _fill(self):
+        cache = self.__dict__.get("_fill_cache")
+        if cache is None:
+            cache = self.__dict__["_fill_cache"] = fill.GridFill()
+        return cache
+
+    def _fill_coordinates(self, facet):
+        if facet == "node":
+            return self.node_coordinates
+        if facet == "edge":
+            return self.edge_coordinates
+        return self.centroids
+
+    def laplace_interpolate(self, data, dim=None, xy_weights=True, direct_solve=False, delta=0.0, relax=0.0, rtol=0.0,
+                            atol=1e-4, maxiter=500):
+        """Fill the NaN entries of ``data`` (..., n) along ``dim`` (default: faces) by Laplace interpolation on the device
+        (UgridDataArrayAccessor.laplace_interpolate, dataarray_accessor.py:805-886).  Unpreconditioned CG instead of the
+        reference's ILU0-preconditioned one: ``delta`` / ``relax`` must be 0.0 and ``maxiter`` counts device iterations
+        (xugrid_amd/fill.py).  numpy in -> numpy out, device array in -> float64 device array out."""
+        facet = fill.resolve_dim(self, dim, ("node", "edge", "face"))
+        if facet == "edge":
+            raise ValueError("Laplace interpolation along edges is not allowed.")
+        fill._check_ilu_options(delta, relax)
+        conn = (lambda: self.node_node_connectivity) if facet == "node" else (lambda: self.face_face_connectivity)
+        graph = self._fill().graph(facet, conn, lambda: self._fill_coordinates(facet))
+        return fill.laplace_fill(graph, data, xy_weights, direct_solve, delta, relax, atol, rtol, maxiter)
+
+    def interpolate_na(self, data, dim=None, method="nearest", max_distance=None):
+        """Fill the NaN entries of ``data`` (..., n) along ``dim`` (default: faces) with the value of the nearest non-NaN
+        entry closer than ``max_distance`` (UgridDataArrayAccessor.interpolate_na): face centroids, nodes or edge
+        midpoints; among equidistant entries the lowest index wins."""
+        if method != "nearest":
+            raise ValueError(f'"{method}" is not a valid interpolator.')
+        facet = fill.resolve_dim(self, dim, ("node", "edge", "face"))
+        xy = self._fill().xy(facet, lambda: self._fill_coordinates(facet))
+        return fill.nearest_fill(xy, data, max_distance)
 
     # ---- structured -> unstructured (raster cells become CCW quads)
     @staticmethod
@@ -438,4 +514,5 @@ class DeviceUgrid2d(Ugrid2d):
     def drop_device_caches(self):
         # (the device mesh IS this grid: its derived arrays and index go, the raw arrays stay)
         self._voronoi_device_cache = None
+        self.__dict__.pop("_fill_cache", None)
         self._celltree.device_mesh.invalidate()
