@@ -111,3 +111,85 @@ def mixed_faces():
     xy = np.array([[0.0, 0.0], [1.0, 0.0], [2.0, 0.0], [0.0, 1.0], [1.0, 1.0], [2.0, 1.0], [1.0, 2.0], [2.6, 0.5]])
     faces = np.array([[0, 1, 4, 3], [1, 2, 5, 4], [3, 4, 6, -1], [4, 5, 6, -1], [2, 7, 5, -1]])
     return xy, faces
+
+
+def brute_nearest(xy, data, max_distance=np.inf, chunk=2048):
+    """Source index per point of the nearest fill of one slice, or -1: every valid point is its own source; a null point
+    takes the valid point of smallest squared distance ``dx*dx + dy*dy`` in float64 -- the kernel's own arithmetic (no
+    fused multiply-add), so decisions are bit-identical -- kept strictly below ``max_distance**2``, lowest index among
+    equal distances."""
+    xy = np.asarray(xy, dtype=np.float64)
+    valid = ~np.isnan(data)
+    src = np.where(valid, np.arange(len(data)), -1)
+    vidx = np.nonzero(valid)[0]
+    null = np.nonzero(~valid)[0]
+    if vidx.size == 0 or null.size == 0:
+        return src
+    md2 = max_distance * max_distance
+    vx, vy = xy[vidx, 0], xy[vidx, 1]
+    step = max(1, chunk * 4096 // max(vidx.size, 1))  # ~8M distances per chunk
+    for c0 in range(0, null.size, step):
+        rows = null[c0:c0 + step]
+        dx = vx[None, :] - xy[rows, 0][:, None]
+        dy = vy[None, :] - xy[rows, 1][:, None]
+        d2 = dx * dx + dy * dy
+        j = np.argmin(d2, axis=1)  # the first of equal minima: the lowest index (vidx is ascending)
+        best = d2[np.arange(rows.size), j]
+        src[rows] = np.where(best < md2, vidx[j], -1)
+    return src
+
+
+def kdtree_nearest(xy, data):
+    """``brute_nearest`` (no distance bound) for point sets too large for brute force: the KDTree distance, the candidates
+    in a ball slightly wider than it, then the kernel's squared distance and the lowest index among the closest."""
+    xy = np.asarray(xy, dtype=np.float64)
+    valid = ~np.isnan(data)
+    src = np.where(valid, np.arange(len(data)), -1)
+    vidx = np.nonzero(valid)[0]
+    null = np.nonzero(~valid)[0]
+    if vidx.size == 0 or null.size == 0:
+        return src
+    tree = KDTree(xy[vidx])
+    d, _ = tree.query(xy[null])
+    balls = tree.query_ball_point(xy[null], d * (1.0 + 1e-9) + 1e-300)
+    for i, cand in zip(null, balls):
+        j = vidx[np.sort(np.asarray(cand, dtype=np.int64))]
+        dx = xy[j, 0] - xy[i, 0]
+        dy = xy[j, 1] - xy[i, 1]
+        d2 = dx * dx + dy * dy
+        src[i] = j[np.argmin(d2)]
+    return src
+
+
+def reference_cg(A, b, atol=0.0, rtol=1e-5, maxiter=None):
+    """scipy 1.15's ``sparse.linalg.cg`` loop without a preconditioner, restated so every iterate is kept: x0 = 0;
+    ``||r|| < max(atol, rtol ||b||)`` is tested at the top of each pass; a loop that runs out reports ``maxiter``.
+    -> (iterates [x_0, x_1, ...], info, residual norms at the tests made, tolerance).  ``info`` 0 is convergence and
+    ``len(iterates) - 1`` the iteration count either way."""
+    b = np.asarray(b, dtype=np.float64)
+    bnrm2 = np.linalg.norm(b)
+    tol = max(float(atol), float(rtol) * float(bnrm2))
+    x = np.zeros_like(b)
+    iterates, norms = [x.copy()], []
+    if bnrm2 == 0:
+        return iterates, 0, norms, tol
+    if maxiter is None:
+        maxiter = 10 * len(b)
+    r = b.copy()
+    rho_prev, p = None, None
+    for iteration in range(maxiter):
+        norms.append(np.linalg.norm(r))
+        if norms[-1] < tol:
+            return iterates, 0, norms, tol
+        rho_cur = np.dot(r, r)
+        if iteration > 0:
+            p = p * (rho_cur / rho_prev) + r
+        else:
+            p = r.copy()
+        q = A @ p
+        alpha = rho_cur / np.dot(p, q)
+        x = x + alpha * p
+        r = r - alpha * q
+        rho_prev = rho_cur
+        iterates.append(x.copy())
+    return iterates, maxiter, norms, tol

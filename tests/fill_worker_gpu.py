@@ -13,7 +13,8 @@ sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
 import xugrid_amd as xa  # noqa: E402
-from xugrid_amd import meshgen  # noqa: E402
+from fill_cases import brute_nearest, scaled_residual  # noqa: E402
+from xugrid_amd import fill, meshgen  # noqa: E402
 
 
 def torch_route():
@@ -38,7 +39,8 @@ def torch_route():
 
 
 def regrid_then_fill():
-    """A device grid regridded onto a larger target (NaN outside the source), then both fills: no NaN left."""
+    """A device grid regridded onto a larger target (NaN outside the source), then both fills: no NaN left, the nearest
+    fill equal to a brute-force search on the regridded values, the Laplace fill within the CG's stopping rule."""
     sxy, sf = meshgen.triangle_mesh(2000, 0)
     txy, tf = meshgen.triangle_mesh(3000, 1, 0.0, 1.4)
     source = xa.Ugrid2d.from_device_arrays(torch.tensor(sxy, device="cuda:0"), torch.tensor(sf, device="cuda:0"))
@@ -48,9 +50,33 @@ def regrid_then_fill():
     assert isinstance(out, torch.Tensor) and torch.isnan(out).any()
     for filled in (target.interpolate_na(out), target.laplace_interpolate(out)):
         assert isinstance(filled, torch.Tensor) and not torch.isnan(filled).any()
+    regridded = out.cpu().numpy()
+    near = target.interpolate_na(out).cpu().numpy()
+    assert np.array_equal(near, regridded[brute_nearest(target.centroids, regridded)])
+    lap = target.laplace_interpolate(out).cpu().numpy()
+    conn = target.get_connectivity_matrix("face", xy_weights=True)
+    assert scaled_residual(lap, regridded, conn, True) < 1e-4
+
+
+def more_slices_than_one_launch_grid():
+    """tests/test_gpu_fill_edges.py::test_more_slices_than_one_launch_grid on a tensor: K = 70 000 slices, tiled."""
+    from test_gpu_fill_edges import K_BIG, SAMPLE, big_stack
+
+    grid, data = big_stack()
+    t = torch.tensor(data, device="cuda:0")
+    near = grid.interpolate_na(t)
+    lap = grid.laplace_interpolate(t)
+    iters = fill.last_iterations
+    assert tuple(near.shape) == tuple(lap.shape) == data.shape and iters.shape == (K_BIG,)
+    near, lap = near.cpu().numpy(), lap.cpu().numpy()
+    for k in SAMPLE:
+        assert np.array_equal(near[k].view(np.int64), grid.interpolate_na(data[k]).view(np.int64)), k
+        assert np.array_equal(lap[k].view(np.int64), grid.laplace_interpolate(data[k]).view(np.int64)), k
+        assert iters[k] == fill.last_iterations[0], k
 
 
 if __name__ == "__main__":
     torch_route()
     regrid_then_fill()
+    more_slices_than_one_launch_grid()
     print("TORCH_FILL_OK")

@@ -4,9 +4,10 @@ nearest fill of ``UgridDataArrayAccessor.interpolate_na`` (xugrid/core/dataarray
 ``csrc/xr_fill.hip``.
 
 Arrays in, arrays out, like ``Regridder.regrid``: ``data`` is ``(..., n)``; the leading dims are K slices filled
-independently (the reference's ``apply_ufunc(vectorize=True)``).  numpy in -> numpy out; a device array in (torch tensor on
-the GPU, ``__cuda_array_interface__``) -> a float64 device array of the same kind, nothing crossing PCIe but the per-slice
-status words.  The input is never modified.
+independently (the reference's ``apply_ufunc(vectorize=True)``).  K is unbounded: the kernels take at most 65 535 slices
+per call (the launch grid's y dimension), so ``_run`` hands them consecutive tiles of the slices.  numpy in -> numpy out;
+a device array in (torch tensor on the GPU, ``__cuda_array_interface__``) -> a float64 device array of the same kind,
+nothing crossing PCIe but the per-slice status words.  The input is never modified.
 
 Deviation: the reference preconditions CG with a sequential ILU0; the device runs unpreconditioned CG on
 the same diagonally scaled system under scipy's stopping rule.  ``delta`` / ``relax`` (ILU0 knobs) are accepted at 0.0 only;
@@ -22,6 +23,7 @@ from . import _lib, engine
 from ._lib import check
 
 CG_CHUNK = 24  # CG iterations enqueued between two reads of the slices' state
+MAX_SLICES = 65535  # slices per kernel call (xr_fill.hip puts the slice on gridDim.y)
 _STATUS_MAXITER, _STATUS_BREAKDOWN, _STATUS_NODATA = 1, 2, 3
 
 # what the last fill reported per slice (tests and profiles read it: iteration counts of the device CG)
@@ -97,19 +99,28 @@ def _as_slices(data, n):
     return "host", np.ascontiguousarray(a), int(np.prod(a.shape[:-1], dtype=np.int64)), a.shape
 
 
+def _tiles(in_ptr, out_ptr, n, K, launch):
+    """``launch(in_ptr, out_ptr, k)`` on consecutive tiles of at most MAX_SLICES slices (once, with k = 0, for K = 0).
+    Every slice is filled independently of the others, so the tiling changes no result."""
+    for k0 in range(0, max(K, 1), MAX_SLICES):
+        offset = k0 * n * 8  # float64 (K, n)
+        launch(in_ptr + offset, out_ptr + offset, min(MAX_SLICES, K - k0))
+
+
 def _run(data, n, launch):
-    """Move ``data`` to the device if it is not there, run ``launch(in_ptr, out_ptr, K)``, return the same kind."""
+    """Move ``data`` to the device if it is not there, run ``launch(in_ptr, out_ptr, k)`` per tile of slices (``_tiles``),
+    return the same kind."""
     kind, a, K, shape = _as_slices(data, n)
     if kind == "device":
         engine.sync_producer(a)
         out, out_ptr = engine.empty_like_device(a, shape)
-        launch(engine.device_array_info(a)[0], out_ptr, K)
+        _tiles(engine.device_array_info(a)[0], out_ptr, n, K, launch)
         return out
     if a.size == 0:
         return a.copy()
     src = engine.DeviceArray.from_host(a)
     dst = engine.DeviceArray(a.shape)
-    launch(src.ptr, dst.ptr, K)
+    _tiles(src.ptr, dst.ptr, n, K, launch)
     return dst.download()
 
 
@@ -124,7 +135,7 @@ def laplace_fill(graph: DeviceGraph, data, use_weights, direct_solve=False, delt
     if direct_solve:
         atol, rtol, maxiter = 0.0, 1e-13, 10 * max(n, 1)
     maxiter = int(maxiter)
-    result = {}
+    tiles = []  # (iterations, status) per tile of slices: checked together below, as for one call
 
     def launch(in_ptr, out_ptr, K):
         iters = np.zeros(K, dtype=np.int64)
@@ -132,11 +143,11 @@ def laplace_fill(graph: DeviceGraph, data, use_weights, direct_solve=False, delt
         check(_lib.load().xr_graph_laplace_fill_dev(
             graph._h, ctypes.c_void_p(in_ptr), ctypes.c_void_p(out_ptr), K, int(bool(use_weights)), float(atol),
             float(rtol), maxiter, CG_CHUNK, iters.ctypes.data_as(ctypes.c_void_p), status.ctypes.data_as(ctypes.c_void_p)))
-        result["iters"], result["status"] = iters, status
+        tiles.append((iters, status))
 
     out = _run(data, n, launch)
-    status = result.get("status", np.zeros(0, dtype=np.int32))
-    last_iterations = result.get("iters")
+    status = np.concatenate([s for _, s in tiles]) if tiles else np.zeros(0, dtype=np.int32)
+    last_iterations = np.concatenate([i for i, _ in tiles]) if tiles else None
     if (status == _STATUS_NODATA).any():
         raise ValueError("data is fully nodata")
     if (status == _STATUS_BREAKDOWN).any():
