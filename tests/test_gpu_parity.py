@@ -967,6 +967,52 @@ def test_apply_host_arrays_in_chunks(hip, oracle, monkeypatch, xr_option):
         assert np.array_equal(csr.apply(v32, 7, 50.0), csr.apply(v32.astype(np.float64), 7, 50.0), equal_nan=True)
 
 
+def test_apply_entry_points_refuse_unknown_ids(hip, xr_option):
+    """Every apply entry point refuses an unknown reducer id and, where it takes one, an unknown source dtype id; the
+    entry points of the partial states refuse a reducer that does not decompose over source shards (mode).  Where one
+    call has two bad ids, the dtype wins on the applies and decomposability on the partial apply."""
+    from xugrid_amd import _lib
+    from xugrid_amd import engine as E
+
+    lib = _lib.load()
+    ay = (np.array([0, 2, 3, 3]), np.array([0, 1, 1]), np.array([0.5, 1.5, 2.0]))
+    ax = (np.array([0, 1, 3]), np.array([2, 0, 1]), np.array([1.0, 0.25, 0.75]))
+    csr, outer = E.DeviceCSR.from_outer(ay, 2, ax, 3), E.DeviceOuter(ay, 2, ax, 3)
+    K, unknown, bad_dtype, mode = 2, 11, 2, E.METHOD_IDS["mode"]
+    src = np.arange(K * csr.m, dtype=np.float64).reshape(K, csr.m)
+    out = np.empty((K, csr.n))
+    d_src = E.DeviceArray.from_host(src)
+    d_out = E.DeviceArray((4, K, csr.n))  # room for the partial planes (at most 4 components)
+    d_indptr = E.DeviceArray.from_host(np.array([0, 1], dtype=np.int64))
+    d_order = E.DeviceArray.from_host(np.array([0], dtype=np.int64))
+
+    def refuses(match, rc):
+        with pytest.raises(ValueError, match=match):
+            _lib.check(rc)
+
+    for path in ("free", "csr"):
+        xr_option("outer_apply", path)
+        for h, host, dev in ((csr._h, lib.xr_apply_csr, lib.xr_apply_csr_dev),
+                             (outer._h, lib.xr_apply_outer, lib.xr_apply_outer_dev)):
+            for fn, s, o in ((host, src.ctypes.data, out.ctypes.data), (dev, d_src.ptr, d_out.ptr)):
+                refuses("unknown reducer id 11", fn(h, unknown, 0.0, s, E.XR_F64, K, o))
+                refuses("unknown reducer id -1", fn(h, -1, 0.0, s, E.XR_F32, K, o))
+                refuses("unsupported source dtype id 2", fn(h, 0, 0.0, s, bad_dtype, K, o))
+                refuses("unsupported source dtype id 2", fn(h, unknown, 0.0, s, bad_dtype, K, o))
+                refuses(r"percentile must be in the range \[0, 100\]", fn(h, 7, 150.0, s, E.XR_F64, K, o))
+    for method in (unknown, mode):
+        msg = f"reducer {method} does not decompose over source shards"
+        for k in (1, K):
+            refuses(msg, lib.xr_apply_partial_dev(csr._h, method, d_src.ptr, E.XR_F64, k, d_out.ptr, 0))
+            refuses(msg, lib.xr_apply_partial_dev(csr._h, method, d_src.ptr, bad_dtype, k, d_out.ptr, 1))
+            refuses(msg, lib.xr_partial_fill_identity_dev(method, d_out.ptr, k, csr.n))
+            refuses(msg, lib.xr_finalize_partial_dev(method, d_out.ptr, k, csr.n, d_out.ptr))
+            refuses(msg, lib.xr_reduce_partial_rows_dev(method, d_src.ptr, d_indptr.ptr, d_order.ptr, 1, k, d_out.ptr))
+    refuses("unsupported source dtype id 2", lib.xr_apply_partial_dev(csr._h, 0, d_src.ptr, bad_dtype, K, d_out.ptr, 0))
+    # nothing was left half done: the same objects still apply
+    assert same_or_nan(outer.apply(src, E.METHOD_IDS["sum"]), csr.apply(src, E.METHOD_IDS["sum"])).all()
+
+
 def test_apply_columns_renumbered_by_spatial_key(hip, oracle):
     """xr_csr_set_col_keys: the columns (source cells) are renumbered by a spatial key so that the gathers of a row
     block are neighbours in memory; entry order inside the rows is untouched -> results bit-identical, downloads in

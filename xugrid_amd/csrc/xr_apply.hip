@@ -13,6 +13,7 @@
 // CSR = indptr i32[T+1], indices i32[nnz], data f64[nnz].
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include <memory>
@@ -1964,6 +1965,51 @@ static inline const int32_t *row_order_of(const xr_csr *csr) {
     return (csr->has_row_order && !csr->output_stored) ? csr->row_order.get() : nullptr;
 }
 
+// k_apply_plan over the matrix's plan: KT variables per tile, SUBS row blocks per workgroup (MERGED: one value table for
+// the workgroup's SUBS = PLAN_GROUP row blocks).  LDS is sized for the largest planned block, so typical matrices run
+// three blocks per CU instead of two.
+// (tuning hooks: row blocks per workgroup, variables per tile, the L2-blocked order of k_apply_plan: super tiles of
+// `super_blocks` workgroups x items of `item_tiles` variable tiles)
+template <int METHOD, typename SRC, int KT, int SUBS, bool MERGED, bool FAST>
+static void launch_plan(const xr_csr *csr, const SRC *src, int64_t K, double *out) {
+    // default: items of 64 variables, super tile = the XCD's whole range of row blocks -- every XCD sweeps its row blocks
+    // once per 64 variables (the source planes in flight: 0.5 GB instead of all K of them; what the host-side split
+    // into groups of 128 variables did until round 4, without its extra launches, forks and joins)
+    const int plan_dbg = (int)option(OPT_PLAN_DBG); // measurement: 1 no gathers, 2 no stores, 4 plain instead of non-temporal stores
+    // LDS per row block: a tile of distinct source values + the block's entries (weight + 16-bit local column), sized for
+    // the largest planned block of the matrix.  4 row blocks per workgroup: tiles of 4 variables (4 x 34 KB)
+    const int lmax = csr->plan_lmax;
+    const size_t sub_bytes = ((sizeof(double) * ((size_t)KT * PLAN_UMAX + lmax) + sizeof(uint16_t) * lmax) + 15) / 16 * 16;
+    const size_t stage_bytes = ((sizeof(double) * (size_t)lmax + sizeof(uint16_t) * (size_t)lmax) + 15) / 16 * 16;
+    const size_t shmem = MERGED ? sizeof(double) * (size_t)KT * PLAN_GUMAX + stage_bytes * PLAN_GROUP : sub_bytes * SUBS;
+    XR_REQUIRE(shmem <= (size_t)160 * 1024, XR_ERR_LIMIT, "internal: apply plan needs %zu bytes of LDS", shmem);
+    // (dynamic LDS beyond 64 KB has to be allowed per kernel; applies run concurrently under the shared scope, so the
+    // high-water mark of this instantiation sits behind a mutex)
+    {
+        static std::mutex attr_mutex;
+        static size_t granted = 0;
+        std::lock_guard<std::mutex> lock(attr_mutex);
+        if (shmem > granted) {
+            XR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_apply_plan<METHOD, SRC, KT, SUBS, MERGED, FAST>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+            granted = shmem;
+        }
+    }
+    const int64_t n_groups = div_up(div_up(csr->n, AP_BLOCK), SUBS);
+    const int item_tiles = 64 / KT;
+    const int super_blocks = K > (int64_t)KT * item_tiles ? (int)std::min<int64_t>((n_groups + 7) / 8, 1 << 30) : 0;
+    int64_t plan_grid = (n_groups + 7) / 8 * 8;
+    if (super_blocks > 0) {
+        const int64_t per_xcd = (n_groups + 7) / 8;
+        const int64_t n_items = div_up(K, (int64_t)KT * item_tiles);
+        plan_grid = 8 * div_up(per_xcd, super_blocks) * super_blocks * n_items;
+    }
+    XR_LAUNCH("apply_plan", (k_apply_plan<METHOD, SRC, KT, SUBS, MERGED, FAST>), dim3((unsigned)plan_grid), dim3(AP_BLOCK * SUBS),
+              shmem, csr->indptr.get(), csr->indices.get(), csr->data.get(), csr->plan_ucol.get(), csr->plan_nuniq.get(),
+              csr->plan_loc.get(), row_order_of(csr), csr->has_long, csr->n, csr->m, src, K, out, csr->plan_lmax, super_blocks,
+              item_tiles, plan_dbg);
+}
+
 template <int METHOD, typename SRC>
 static void launch_stream(const xr_csr *csr, const SRC *src, int64_t K, double *out) {
     // The long rows (hull slivers: a few hundred latency-bound rows).  With many variables they run on the side stream BESIDE
@@ -2035,62 +2081,13 @@ static void launch_stream(const xr_csr *csr, const SRC *src, int64_t K, double *
         if (use_plan) {
             // many variables: rows regrouped into 2-D tiles, then a blocked CSR with per-block distinct-column
             // lists (both built once per matrix, above)
-            // LDS: one tile of distinct source values + the block's entries (weight + 16-bit local column); sized
-            // for the largest planned block, so typical matrices run three blocks per CU instead of two
-            // (tuning hooks: row blocks per workgroup, variables per tile, the L2-blocked order of k_apply_plan: super tiles of
-            // `super_blocks` workgroups x items of `item_tiles` variable tiles)
-            const bool merged = csr->plan_merged;
-            const int plan_subs = merged ? PLAN_GROUP : 1;
             // contracted products + one reciprocal per row (k_apply_plan, FAST): opt-in
             constexpr bool FAST_OK = METHOD == XR_MEAN || METHOD == XR_FIRST_ORDER_CONSERVATIVE;
             const bool fast = FAST_OK && option(OPT_APPLY_CONTRACT) != 0;
-            // default: items of 64 variables, super tile = the XCD's whole range of row blocks -- every XCD sweeps its row blocks
-            // once per 64 variables (the source planes in flight: 0.5 GB instead of all K of them; what the host-side split
-            // into groups of 128 variables did until round 4, without its extra launches, forks and joins)
-            const int plan_dbg = (int)option(OPT_PLAN_DBG); // measurement: 1 no gathers, 2 no stores, 4 plain instead of non-temporal stores
-            // LDS per row block: a tile of distinct source values + the block's entries (weight + 16-bit local column), sized for
-            // the largest planned block of the matrix.  4 row blocks per workgroup: tiles of 4 variables (4 x 34 KB)
-            const int plan_kt = plan_subs > 1 ? 4 : PLAN_KT;
-            auto sub_bytes = [&](int kt, int lmax) {
-                return ((sizeof(double) * ((size_t)kt * PLAN_UMAX + lmax) + sizeof(uint16_t) * lmax) + 15) / 16 * 16;
-            };
-            const size_t stage_bytes = ((sizeof(double) * (size_t)csr->plan_lmax + sizeof(uint16_t) * (size_t)csr->plan_lmax) + 15) / 16 * 16;
-            const size_t shmem = merged ? sizeof(double) * (size_t)plan_kt * PLAN_GUMAX + stage_bytes * PLAN_GROUP
-                                        : sub_bytes(plan_kt, csr->plan_lmax) * plan_subs;
-            XR_REQUIRE(shmem <= (size_t)160 * 1024, XR_ERR_LIMIT, "internal: apply plan needs %zu bytes of LDS", shmem);
-            // (dynamic LDS beyond 64 KB has to be allowed per kernel; applies run concurrently under the shared scope, so the
-            // high-water mark per instantiation sits behind a mutex)
-            auto allow_lds = [&](const void *kernel, size_t &granted) {
-                static std::mutex attr_mutex;
-                std::lock_guard<std::mutex> lock(attr_mutex);
-                if (shmem <= granted) return;
-                XR_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-                granted = shmem;
-            };
-            static size_t granted1 = 0, granted_m = 0, granted1f = 0, granted_mf = 0;
-            if (merged && fast) allow_lds(reinterpret_cast<const void *>(&k_apply_plan<METHOD, SRC, 4, PLAN_GROUP, true, FAST_OK>), granted_mf);
-            else if (merged) allow_lds(reinterpret_cast<const void *>(&k_apply_plan<METHOD, SRC, 4, PLAN_GROUP, true>), granted_m);
-            else if (fast) allow_lds(reinterpret_cast<const void *>(&k_apply_plan<METHOD, SRC, PLAN_KT, 1, false, FAST_OK>), granted1f);
-            else allow_lds(reinterpret_cast<const void *>(&k_apply_plan<METHOD, SRC, PLAN_KT, 1>), granted1);
-            const int64_t n_groups = div_up(div_up(csr->n, AP_BLOCK), plan_subs);
-            const int item_tiles = 64 / plan_kt;
-            const int super_blocks = K > (int64_t)plan_kt * item_tiles ? (int)std::min<int64_t>((n_groups + 7) / 8, 1 << 30) : 0;
-            int64_t plan_grid = (n_groups + 7) / 8 * 8;
-            if (super_blocks > 0) {
-                const int64_t per_xcd = (n_groups + 7) / 8;
-                const int64_t n_items = div_up(K, (int64_t)plan_kt * item_tiles);
-                plan_grid = 8 * div_up(per_xcd, super_blocks) * super_blocks * n_items;
-            }
-#define XR_PLAN_LAUNCH(KT, SUBS, MERGED, FASTF)                                                                                      \
-    XR_LAUNCH("apply_plan", (k_apply_plan<METHOD, SRC, KT, SUBS, MERGED, FASTF>), dim3((unsigned)plan_grid), dim3(AP_BLOCK * SUBS),   \
-              shmem, csr->indptr.get(), csr->indices.get(), csr->data.get(), csr->plan_ucol.get(), csr->plan_nuniq.get(),            \
-              csr->plan_loc.get(), row_order_of(csr), csr->has_long, csr->n, csr->m, src, K, out, csr->plan_lmax, super_blocks,      \
-              item_tiles, plan_dbg)
-            if (merged && fast) XR_PLAN_LAUNCH(4, PLAN_GROUP, true, FAST_OK);
-            else if (merged) XR_PLAN_LAUNCH(4, PLAN_GROUP, true, false);
-            else if (fast) XR_PLAN_LAUNCH(PLAN_KT, 1, false, FAST_OK);
-            else XR_PLAN_LAUNCH(PLAN_KT, 1, false, false);
-#undef XR_PLAN_LAUNCH
+            if (csr->plan_merged && fast) launch_plan<METHOD, SRC, 4, PLAN_GROUP, true, FAST_OK>(csr, src, K, out);
+            else if (csr->plan_merged) launch_plan<METHOD, SRC, 4, PLAN_GROUP, true, false>(csr, src, K, out);
+            else if (fast) launch_plan<METHOD, SRC, PLAN_KT, 1, false, FAST_OK>(csr, src, K, out);
+            else launch_plan<METHOD, SRC, PLAN_KT, 1, false, false>(csr, src, K, out);
             if (side_late) {
                 SideScope side(true);
                 launch_long_rows(false);
@@ -2135,29 +2132,60 @@ static void launch_workspace(const xr_csr *csr, const SRC *src, int64_t K, doubl
     }
 }
 
+// ---- host dispatch: run-time source dtype and reducer ids -> template arguments.  Every table below is the only one of
+// its kind; a reducer a kernel family does not serve is excluded with `if constexpr`, never instantiated.
+
+// f(SRC()) with SRC the element type of a source dtype id
+template <typename F> static void with_source_type(int dtype, F &&f) {
+    XR_REQUIRE(dtype == XR_F64 || dtype == XR_F32, XR_ERR_INVALID, "unsupported source dtype id %d", dtype);
+    if (dtype == XR_F64) f(double());
+    else f(float());
+}
+
+static size_t source_size(int dtype) {
+    size_t size = 0;
+    with_source_type(dtype, [&](auto tag) { size = sizeof(tag); });
+    return size;
+}
+
+// f(std::integral_constant<int, ID>()) for the ID of IDS that equals `id`; false if there is none
+template <int... IDS, typename F> static bool with_id(int id, F &&f) {
+    return ((id == IDS && (f(std::integral_constant<int, IDS>()), true)) || ...);
+}
+
+// every reducer
+template <typename F> static void with_reducer(int method, F &&f) {
+    const bool known = with_id<XR_MEAN, XR_HARMONIC_MEAN, XR_GEOMETRIC_MEAN, XR_SUM, XR_MINIMUM, XR_MAXIMUM, XR_MODE,
+                               XR_PERCENTILE, XR_FIRST_ORDER_CONSERVATIVE, XR_MAX_OVERLAP, XR_SELECT>(method, f);
+    XR_REQUIRE(known, XR_ERR_INVALID, "unknown reducer id %d", method);
+}
+
+// mode and percentiles need a row's values side by side (launch_workspace); every other reducer streams over a row
+template <int METHOD> constexpr bool streamed_reducer = METHOD != XR_MODE && METHOD != XR_PERCENTILE;
+
+// the reducers whose partial states combine over source shards (partial_components > 0)
+template <typename F> static void with_decomposable(int method, F &&f) {
+    const bool known = with_id<XR_MEAN, XR_FIRST_ORDER_CONSERVATIVE, XR_SUM, XR_HARMONIC_MEAN, XR_GEOMETRIC_MEAN,
+                               XR_MINIMUM, XR_MAXIMUM>(method, f);
+    XR_REQUIRE(known, XR_ERR_INVALID, "reducer %d does not decompose over source shards", method);
+}
+
 template <typename SRC>
 static void apply_dispatch(const xr_csr *csr, int method, double p, const SRC *src, int64_t K, double *out) {
     if (csr->n == 0 || K == 0) return;
     // (Until round 4 many variables were walked in host-side groups of 128; since round 5 the many-variable kernel orders its
     // own work by groups of 64 variables -- k_apply_plan, L2-blocked order.)
-    switch (method) {
-    case XR_MEAN: launch_stream<XR_MEAN, SRC>(csr, src, K, out); break;
-    case XR_HARMONIC_MEAN: launch_stream<XR_HARMONIC_MEAN, SRC>(csr, src, K, out); break;
-    case XR_GEOMETRIC_MEAN: launch_stream<XR_GEOMETRIC_MEAN, SRC>(csr, src, K, out); break;
-    case XR_SUM: launch_stream<XR_SUM, SRC>(csr, src, K, out); break;
-    case XR_MINIMUM: launch_stream<XR_MINIMUM, SRC>(csr, src, K, out); break;
-    case XR_MAXIMUM: launch_stream<XR_MAXIMUM, SRC>(csr, src, K, out); break;
-    case XR_FIRST_ORDER_CONSERVATIVE: launch_stream<XR_FIRST_ORDER_CONSERVATIVE, SRC>(csr, src, K, out); break;
-    case XR_MAX_OVERLAP: launch_stream<XR_MAX_OVERLAP, SRC>(csr, src, K, out); break;
-    case XR_SELECT: launch_stream<XR_SELECT, SRC>(csr, src, K, out); break;
-    case XR_MODE: launch_workspace<XR_MODE, SRC>(csr, src, K, p, out); break;
-    case XR_PERCENTILE:
-        XR_REQUIRE(p >= 0.0 && p <= 100.0, XR_ERR_INVALID,
-                   "percentile must be in the range [0, 100], received: %g", p);
-        launch_workspace<XR_PERCENTILE, SRC>(csr, src, K, p, out);
-        break;
-    default: XR_REQUIRE(false, XR_ERR_INVALID, "unknown reducer id %d", method);
-    }
+    with_reducer(method, [&](auto m) {
+        constexpr int METHOD = decltype(m)::value;
+        if constexpr (streamed_reducer<METHOD>) {
+            launch_stream<METHOD, SRC>(csr, src, K, out);
+        } else {
+            if (METHOD == XR_PERCENTILE)
+                XR_REQUIRE(p >= 0.0 && p <= 100.0, XR_ERR_INVALID,
+                           "percentile must be in the range [0, 100], received: %g", p);
+            launch_workspace<METHOD, SRC>(csr, src, K, p, out);
+        }
+    });
 }
 
 // the caller's source block into the stored column order: dst[k][j] = src[k][col_of[j]] (every source line is read once;
@@ -2171,31 +2199,26 @@ k_permute_source(const SRC *__restrict__ src, const int32_t *__restrict__ col_of
 }
 
 // -> the source block in the STORED column order (the caller's block itself unless the columns were renumbered)
-static const void *stored_source(const xr_csr *csr, const void *src, int dtype, int64_t K, DevBuf<char> &permuted) {
+template <typename SRC>
+static const SRC *stored_source(const xr_csr *csr, const SRC *src, int64_t K, DevBuf<char> &permuted) {
     if (!(csr->has_col_perm && !csr->source_permuted && K > 0 && csr->m > 0)) return src;
-    const size_t esz = dtype == XR_F64 ? 8 : 4;
-    permuted.alloc((size_t)K * (size_t)csr->m * esz);
+    permuted.alloc((size_t)K * (size_t)csr->m * sizeof(SRC));
+    SRC *dst = reinterpret_cast<SRC *>(permuted.get());
     for (int64_t k0 = 0; k0 < K; k0 += 65535) {
         const int64_t kc = std::min<int64_t>(K - k0, 65535);
         dim3 grid(div_up(csr->m, 256), (unsigned)kc);
-        if (dtype == XR_F64)
-            XR_LAUNCH("permute_source", k_permute_source<double>, grid, dim3(256), 0,
-                      static_cast<const double *>(src) + k0 * csr->m, csr->col_of.get(), csr->m,
-                      reinterpret_cast<double *>(permuted.get()) + k0 * csr->m);
-        else
-            XR_LAUNCH("permute_source", k_permute_source<float>, grid, dim3(256), 0,
-                      static_cast<const float *>(src) + k0 * csr->m, csr->col_of.get(), csr->m,
-                      reinterpret_cast<float *>(permuted.get()) + k0 * csr->m);
+        XR_LAUNCH("permute_source", k_permute_source<SRC>, grid, dim3(256), 0, src + k0 * csr->m, csr->col_of.get(), csr->m,
+                  dst + k0 * csr->m);
     }
-    return permuted.get();
+    return dst;
 }
 
 static void apply_dev(const xr_csr *csr, int method, double p, const void *src, int dtype, int64_t K, double *out) {
-    XR_REQUIRE(dtype == XR_F64 || dtype == XR_F32, XR_ERR_INVALID, "unsupported source dtype id %d", dtype);
-    DevBuf<char> permuted; // (goes back to the pool at return; the pool hands blocks out in stream order)
-    src = stored_source(csr, src, dtype, K, permuted);
-    if (dtype == XR_F64) apply_dispatch<double>(csr, method, p, static_cast<const double *>(src), K, out);
-    else apply_dispatch<float>(csr, method, p, static_cast<const float *>(src), K, out);
+    with_source_type(dtype, [&](auto tag) {
+        using SRC = decltype(tag);
+        DevBuf<char> permuted; // (goes back to the pool at return; the pool hands blocks out in stream order)
+        apply_dispatch<SRC>(csr, method, p, stored_source(csr, static_cast<const SRC *>(src), K, permuted), K, out);
+    });
 }
 
 void csr_apply_dev(const xr_csr *csr, int method, double percentile, const void *src_dev, int dtype, int64_t K, double *out_dev) {
@@ -2525,45 +2548,49 @@ static xr_csr *outer_materialise(const xr_outer *o) {
 // x-lists make neighbouring lanes gather columns that lie a whole list apart; there the stored product with its
 // cooperative long-row kernels is the faster engine (and the only one for mode / percentiles, which need a row's
 // values side by side).  Products too large to store (>= 2^31 entries) stay matrix-free.
-static bool outer_matrix_free(const xr_outer *o, int method) {
+static bool outer_matrix_free(const xr_outer *o) {
     const int64_t force = option(OPT_OUTER_APPLY); // test hook: 1 "free" | 2 "csr"
-    const bool reducible = method != XR_MODE && method != XR_PERCENTILE;
     const bool fits = o->Py == 0 || o->Px < (((int64_t)1 << 31) - 1) / o->Py;
-    if (!reducible) return false;
     if (!fits) return true;
     if (force == 1) return true;
     if (force == 2) return false;
     return o->max_cx <= 4;
 }
 
-template <typename SRC>
-static void apply_outer_dispatch(xr_outer *o, int method, double p, const SRC *src, int64_t K, double *out) {
-    if (!outer_matrix_free(o, method)) {
-        if (!o->csr) o->csr = outer_materialise(o);
-        apply_dispatch<SRC>(o->csr, method, p, src, K, out);
-        return;
-    }
-    switch (method) {
-    case XR_MEAN: launch_outer<XR_MEAN, SRC>(o, src, K, out); break;
-    case XR_HARMONIC_MEAN: launch_outer<XR_HARMONIC_MEAN, SRC>(o, src, K, out); break;
-    case XR_GEOMETRIC_MEAN: launch_outer<XR_GEOMETRIC_MEAN, SRC>(o, src, K, out); break;
-    case XR_SUM: launch_outer<XR_SUM, SRC>(o, src, K, out); break;
-    case XR_MINIMUM: launch_outer<XR_MINIMUM, SRC>(o, src, K, out); break;
-    case XR_MAXIMUM: launch_outer<XR_MAXIMUM, SRC>(o, src, K, out); break;
-    case XR_FIRST_ORDER_CONSERVATIVE: launch_outer<XR_FIRST_ORDER_CONSERVATIVE, SRC>(o, src, K, out); break;
-    case XR_MAX_OVERLAP: launch_outer<XR_MAX_OVERLAP, SRC>(o, src, K, out); break;
-    case XR_SELECT: launch_outer<XR_SELECT, SRC>(o, src, K, out); break;
-    default: XR_REQUIRE(false, XR_ERR_INVALID, "unknown reducer id %d", method);
-    }
-}
-
 static void apply_outer_dev(xr_outer *o, int method, double p, const void *src, int dtype, int64_t K, double *out) {
-    XR_REQUIRE(dtype == XR_F64 || dtype == XR_F32, XR_ERR_INVALID, "unsupported source dtype id %d", dtype);
-    XR_REQUIRE(method >= 0 && method <= XR_SELECT, XR_ERR_INVALID, "unknown reducer id %d", method);
-    if (dtype == XR_F64) apply_outer_dispatch<double>(o, method, p, static_cast<const double *>(src), K, out);
-    else apply_outer_dispatch<float>(o, method, p, static_cast<const float *>(src), K, out);
+    with_source_type(dtype, [&](auto tag) {
+        using SRC = decltype(tag);
+        with_reducer(method, [&](auto m) {
+            constexpr int METHOD = decltype(m)::value;
+            if constexpr (streamed_reducer<METHOD>) {
+                if (outer_matrix_free(o)) {
+                    launch_outer<METHOD, SRC>(o, static_cast<const SRC *>(src), K, out);
+                    return;
+                }
+            }
+            if (!o->csr) o->csr = outer_materialise(o);
+            apply_dispatch<SRC>(o->csr, METHOD, p, static_cast<const SRC *>(src), K, out);
+        });
+    });
 }
 
+// A host-array apply: the stacked variables go through the device in chunks of at most ~4 GiB of staging (n_src source
+// elements of esz bytes + n_out float64 results per variable), so any K works whatever the size of HBM; every variable is
+// independent, results do not depend on the chunking.  chunk(k0, kc, src, dst) moves and applies variables k0 ... k0 + kc.
+template <typename F> static void staged_chunks(int64_t K, int64_t n_src, size_t esz, int64_t n_out, F &&chunk) {
+    const size_t per_k = (size_t)n_src * esz + (size_t)n_out * sizeof(double);
+    const int64_t chunk_opt = option(OPT_APPLY_CHUNK_BYTES); // test hook
+    const size_t budget = chunk_opt > 0 ? (size_t)chunk_opt : ((size_t)4 << 30);
+    int64_t kchunk = per_k > 0 ? (int64_t)(budget / per_k) : K;
+    if (kchunk < 1) kchunk = 1;
+    if (kchunk > K) kchunk = K;
+    DevBuf<char> src((size_t)kchunk * (size_t)n_src * esz);
+    DevBuf<double> dst((size_t)kchunk * (size_t)n_out);
+    for (int64_t k0 = 0; k0 < K; k0 += kchunk) {
+        chunk(k0, (K - k0) < kchunk ? (K - k0) : kchunk, src.get(), dst.get());
+        stream_sync();
+    }
+}
 
 extern "C" {
 
@@ -2764,25 +2791,13 @@ int xr_apply_outer(xr_outer *o, int method, double percentile, const void *sourc
     XR_API_BEGIN
     XR_REQUIRE(o && (source || K == 0) && (out || K == 0), XR_ERR_INVALID, "xr_apply_outer: NULL argument");
     XR_REQUIRE(K >= 0, XR_ERR_INVALID, "xr_apply_outer: negative K");
-    XR_REQUIRE(source_dtype == XR_F64 || source_dtype == XR_F32, XR_ERR_INVALID, "unsupported source dtype id %d",
-               source_dtype);
-    const size_t esz = source_dtype == XR_F64 ? 8 : 4;
+    const size_t esz = source_size(source_dtype);
     const int64_t n = o->nty * o->ntx, m = o->nsy * o->nsx;
-    const size_t per_k = (size_t)m * esz + (size_t)n * sizeof(double);
-    const int64_t chunk_opt = option(OPT_APPLY_CHUNK_BYTES); // test hook
-    const size_t budget = chunk_opt > 0 ? (size_t)chunk_opt : ((size_t)4 << 30);
-    int64_t kchunk = per_k > 0 ? (int64_t)(budget / per_k) : K;
-    if (kchunk < 1) kchunk = 1;
-    if (kchunk > K) kchunk = K;
-    DevBuf<char> src((size_t)kchunk * (size_t)m * esz);
-    DevBuf<double> dst((size_t)kchunk * (size_t)n);
-    for (int64_t k0 = 0; k0 < K; k0 += kchunk) {
-        const int64_t kc = (K - k0) < kchunk ? (K - k0) : kchunk;
-        h2d(src.get(), static_cast<const char *>(source) + (size_t)k0 * (size_t)m * esz, (size_t)kc * (size_t)m * esz);
-        apply_outer_dev(o, method, percentile, src.get(), source_dtype, kc, dst.get());
-        d2h(out + (size_t)k0 * (size_t)n, dst.get(), (size_t)kc * (size_t)n * sizeof(double));
-        stream_sync();
-    }
+    staged_chunks(K, m, esz, n, [&](int64_t k0, int64_t kc, char *src, double *dst) {
+        h2d(src, static_cast<const char *>(source) + (size_t)k0 * (size_t)m * esz, (size_t)kc * (size_t)m * esz);
+        apply_outer_dev(o, method, percentile, src, source_dtype, kc, dst);
+        d2h(out + (size_t)k0 * (size_t)n, dst, (size_t)kc * (size_t)n * sizeof(double));
+    });
     XR_API_END
 }
 
@@ -2954,27 +2969,13 @@ int xr_apply_csr(const xr_csr *csr, int method, double percentile, const void *s
     XR_REQUIRE(csr && (source || csr->m == 0 || K == 0) && (out || csr->n == 0 || K == 0), XR_ERR_INVALID,
                "xr_apply_csr: NULL argument");
     XR_REQUIRE(K >= 0, XR_ERR_INVALID, "xr_apply_csr: negative K");
-    XR_REQUIRE(source_dtype == XR_F64 || source_dtype == XR_F32, XR_ERR_INVALID, "unsupported source dtype id %d",
-               source_dtype);
-    const size_t esz = source_dtype == XR_F64 ? 8 : 4;
-    // The stacked variables go through the device in chunks of at most ~4 GiB of staging (source + result), so any
-    // K works whatever the size of HBM; every variable is independent, results do not depend on the chunking.
-    const size_t per_k = (size_t)csr->m * esz + (size_t)csr->n * sizeof(double);
-    const int64_t chunk_opt = option(OPT_APPLY_CHUNK_BYTES); // test hook
-    const size_t budget = chunk_opt > 0 ? (size_t)chunk_opt : ((size_t)4 << 30);
-    int64_t kchunk = per_k > 0 ? (int64_t)(budget / per_k) : K;
-    if (kchunk < 1) kchunk = 1;
-    if (kchunk > K) kchunk = K;
-    DevBuf<char> src((size_t)kchunk * (size_t)csr->m * esz);
-    DevBuf<double> dst((size_t)kchunk * (size_t)csr->n);
-    for (int64_t k0 = 0; k0 < K; k0 += kchunk) {
-        const int64_t kc = (K - k0) < kchunk ? (K - k0) : kchunk;
+    const size_t esz = source_size(source_dtype);
+    staged_chunks(K, csr->m, esz, csr->n, [&](int64_t k0, int64_t kc, char *src, double *dst) {
         const size_t n_src = (size_t)kc * (size_t)csr->m, n_out = (size_t)kc * (size_t)csr->n;
-        h2d_big(src.get(), static_cast<const char *>(source) + (size_t)k0 * (size_t)csr->m * esz, n_src * esz);
-        apply_dev(csr, method, percentile, src.get(), source_dtype, kc, dst.get());
-        if (n_out > 0) d2h_big(out + (size_t)k0 * (size_t)csr->n, dst.get(), n_out * sizeof(double));
-        stream_sync();
-    }
+        h2d_big(src, static_cast<const char *>(source) + (size_t)k0 * (size_t)csr->m * esz, n_src * esz);
+        apply_dev(csr, method, percentile, src, source_dtype, kc, dst);
+        if (n_out > 0) d2h_big(out + (size_t)k0 * (size_t)csr->n, dst, n_out * sizeof(double));
+    });
     XR_API_END
 }
 
@@ -2982,13 +2983,11 @@ int xr_apply_coo(const int64_t *row, const int64_t *col, int64_t nnz, int64_t T,
                  int64_t K, int64_t S, double *out) {
     XR_API_BEGIN
     XR_REQUIRE(nnz >= 0 && T >= 0 && K >= 0 && S >= 0, XR_ERR_INVALID, "xr_apply_coo: negative sizes");
-    XR_REQUIRE(source_dtype == XR_F64 || source_dtype == XR_F32, XR_ERR_INVALID, "unsupported source dtype id %d",
-               source_dtype);
+    const size_t esz = source_size(source_dtype);
     XR_REQUIRE(T < ((int64_t)1 << 31) && S < ((int64_t)1 << 31) && K < 65536, XR_ERR_LIMIT, "xr_apply_coo: too large");
     for (int64_t i = 0; i < nnz; i++)
         XR_REQUIRE(row[i] >= 0 && row[i] < T && col[i] >= 0 && col[i] < S, XR_ERR_INVALID,
                    "xr_apply_coo: entry %lld out of range", (long long)i);
-    const size_t esz = source_dtype == XR_F64 ? 8 : 4;
     const size_t n_src = (size_t)K * (size_t)S, n_out = (size_t)K * (size_t)T;
     DevBuf<char> src(n_src * esz);
     DevBuf<double> dst(n_out);
@@ -2999,12 +2998,11 @@ int xr_apply_coo(const int64_t *row, const int64_t *col, int64_t nnz, int64_t T,
     fill_f64(dst.get(), NAN, (int64_t)n_out);
     if (nnz > 0 && K > 0) {
         dim3 grid(div_up(nnz, 256), (unsigned)K);
-        if (source_dtype == XR_F64)
-            XR_LAUNCH("apply_coo", k_apply_coo<double>, grid, dim3(256), 0, r32.get(), c32.get(), nnz, T, S,
-                      reinterpret_cast<const double *>(src.get()), dst.get());
-        else
-            XR_LAUNCH("apply_coo", k_apply_coo<float>, grid, dim3(256), 0, r32.get(), c32.get(), nnz, T, S,
-                      reinterpret_cast<const float *>(src.get()), dst.get());
+        with_source_type(source_dtype, [&](auto tag) {
+            using SRC = decltype(tag);
+            XR_LAUNCH("apply_coo", k_apply_coo<SRC>, grid, dim3(256), 0, r32.get(), c32.get(), nnz, T, S,
+                      reinterpret_cast<const SRC *>(src.get()), dst.get());
+        });
     }
     if (n_out > 0) {
         XR_HIP(hipMemcpyAsync(out, dst.get(), n_out * sizeof(double), hipMemcpyDeviceToHost, launch_stream()));
@@ -3023,90 +3021,50 @@ int xr_partial_combine_is_max(int method) { return partial_is_max(method) ? 1 : 
 void xr::csr_partial_dev(const xr_csr *csr, int method, const void *source_dev, int source_dtype, int64_t K, double *out_dev,
                          int rows_layout) {
     XR_REQUIRE(partial_components(method) > 0, XR_ERR_INVALID, "reducer %d does not decompose over source shards", method);
-    XR_REQUIRE(source_dtype == XR_F64 || source_dtype == XR_F32, XR_ERR_INVALID, "unsupported source dtype id %d", source_dtype);
-    XR_REQUIRE(K >= 0 && K < 65536, XR_ERR_LIMIT, "xr_apply_partial_dev: K out of range (tile the variables)");
-    const int32_t *gate = csr->apply_gated ? csr->n_long.get() + 1 : (const int32_t *)nullptr;
-    XR_REQUIRE(!gate || K == 1, XR_ERR_INVALID, "internal: a gated partial apply is one variable");
-    if (csr->n > 0 && K > 0) {
+    with_source_type(source_dtype, [&](auto tag) {
+        using SRC = decltype(tag);
+        XR_REQUIRE(K >= 0 && K < 65536, XR_ERR_LIMIT, "xr_apply_partial_dev: K out of range (tile the variables)");
+        const int32_t *gate = csr->apply_gated ? csr->n_long.get() + 1 : (const int32_t *)nullptr;
+        XR_REQUIRE(!gate || K == 1, XR_ERR_INVALID, "internal: a gated partial apply is one variable");
+        if (csr->n == 0 || K == 0) return;
         XR_REQUIRE(source_dev || csr->m == 0, XR_ERR_INVALID, "xr_apply_partial_dev: NULL source");
         DevBuf<char> permuted;
-        source_dev = stored_source(csr, source_dev, source_dtype, K, permuted);
+        const SRC *src = stored_source(csr, static_cast<const SRC *>(source_dev), K, permuted);
         constexpr int PKT = 8;
         bool long_done = false; // (the long rows went with the short ones)
-        constexpr bool one_var = false; // (the one-variable-per-thread kernels serve K < 8 only)
-        if (K >= PKT && !one_var && rows_layout != 0) {
+        if (K >= PKT && rows_layout != 0) {
             dim3 grid(div_up(csr->n, 128), (unsigned)div_up(K, PKT));
             const size_t rows_shmem = sizeof(double) * 128 * (size_t)(partial_components(method) * PKT + 1);
-            if (source_dtype == XR_F64)
-                XR_LAUNCH("apply_partial", (k_apply_partial_rows<double, PKT>), grid, dim3(128), rows_shmem, method, csr->indptr.get(),
-                          csr->indices.get(), csr->data.get(), row_order_of(csr), csr->n, csr->m,
-                          static_cast<const double *>(source_dev), K, out_dev, csr->has_long);
-            else
-                XR_LAUNCH("apply_partial", (k_apply_partial_rows<float, PKT>), grid, dim3(128), rows_shmem, method, csr->indptr.get(),
-                          csr->indices.get(), csr->data.get(), row_order_of(csr), csr->n, csr->m,
-                          static_cast<const float *>(source_dev), K, out_dev, csr->has_long);
-        } else if (K >= PKT && !one_var) {
+            XR_LAUNCH("apply_partial", (k_apply_partial_rows<SRC, PKT>), grid, dim3(128), rows_shmem, method, csr->indptr.get(),
+                      csr->indices.get(), csr->data.get(), row_order_of(csr), csr->n, csr->m, src, K, out_dev, csr->has_long);
+        } else if (K >= PKT) {
             dim3 grid(div_up(csr->n, 256), (unsigned)div_up(K, PKT));
-            if (source_dtype == XR_F64)
-                XR_LAUNCH("apply_partial", (k_apply_partial_kt<double, PKT>), grid, dim3(256), 0, method, csr->indptr.get(),
-                          csr->indices.get(), csr->data.get(), row_order_of(csr), csr->n, csr->m,
-                          static_cast<const double *>(source_dev), K, out_dev, rows_layout != 0, csr->has_long);
-            else
-                XR_LAUNCH("apply_partial", (k_apply_partial_kt<float, PKT>), grid, dim3(256), 0, method, csr->indptr.get(),
-                          csr->indices.get(), csr->data.get(), row_order_of(csr), csr->n, csr->m,
-                          static_cast<const float *>(source_dev), K, out_dev, rows_layout != 0, csr->has_long);
-        } else if (K == 1 && !one_var) {
+            XR_LAUNCH("apply_partial", (k_apply_partial_kt<SRC, PKT>), grid, dim3(256), 0, method, csr->indptr.get(),
+                      csr->indices.get(), csr->data.get(), row_order_of(csr), csr->n, csr->m, src, K, out_dev,
+                      rows_layout != 0, csr->has_long);
+        } else if (K == 1) {
             // one variable: the wave-window kernel, one specialisation per reducer; the long rows in its first blocks
             const int n_long_blocks = csr->has_long ? engine().num_cu / 2 : 0;
             dim3 grid((unsigned)(div_up(csr->n, AP_BLOCK) + n_long_blocks));
             long_done = true;
-#define XR_PARTIAL_W1(M)                                                                                                            \
-    case M:                                                                                                                         \
-        if (source_dtype == XR_F64)                                                                                                 \
-            XR_LAUNCH("apply_partial", (k_apply_partial_w1<M, double>), grid, dim3(AP_BLOCK), 0, csr->indptr.get(),                 \
-                      csr->indices.get(), csr->data.get(), row_order_of(csr), csr->n, csr->m,                                       \
-                      static_cast<const double *>(source_dev), out_dev, rows_layout != 0, csr->has_long, gate,                      \
-                      csr->long_rows.get(), csr->n_long.get(), n_long_blocks);                                                      \
-        else                                                                                                                        \
-            XR_LAUNCH("apply_partial", (k_apply_partial_w1<M, float>), grid, dim3(AP_BLOCK), 0, csr->indptr.get(),                  \
-                      csr->indices.get(), csr->data.get(), row_order_of(csr), csr->n, csr->m,                                       \
-                      static_cast<const float *>(source_dev), out_dev, rows_layout != 0, csr->has_long, gate,                       \
-                      csr->long_rows.get(), csr->n_long.get(), n_long_blocks);                                                      \
-        break;
-            switch (method) {
-                XR_PARTIAL_W1(XR_MEAN)
-                XR_PARTIAL_W1(XR_FIRST_ORDER_CONSERVATIVE)
-                XR_PARTIAL_W1(XR_SUM)
-                XR_PARTIAL_W1(XR_HARMONIC_MEAN)
-                XR_PARTIAL_W1(XR_GEOMETRIC_MEAN)
-                XR_PARTIAL_W1(XR_MINIMUM)
-                XR_PARTIAL_W1(XR_MAXIMUM)
-            default: XR_REQUIRE(false, XR_ERR_INVALID, "reducer %d does not decompose over source shards", method);
-            }
-#undef XR_PARTIAL_W1
-        } else {
-        dim3 grid(div_up(csr->n, 256), (unsigned)K);
-        if (source_dtype == XR_F64)
-            XR_LAUNCH("apply_partial", k_apply_partial<double>, grid, dim3(256), 0, method, csr->indptr.get(),
-                      csr->indices.get(), csr->data.get(), row_order_of(csr), csr->n, csr->m,
-                      static_cast<const double *>(source_dev), K, out_dev, rows_layout != 0, csr->has_long);
-        else
-            XR_LAUNCH("apply_partial", k_apply_partial<float>, grid, dim3(256), 0, method, csr->indptr.get(),
-                      csr->indices.get(), csr->data.get(), row_order_of(csr), csr->n, csr->m,
-                      static_cast<const float *>(source_dev), K, out_dev, rows_layout != 0, csr->has_long);
+            with_decomposable(method, [&](auto m) {
+                XR_LAUNCH("apply_partial", (k_apply_partial_w1<decltype(m)::value, SRC>), grid, dim3(AP_BLOCK), 0,
+                          csr->indptr.get(), csr->indices.get(), csr->data.get(), row_order_of(csr), csr->n, csr->m, src,
+                          out_dev, rows_layout != 0, csr->has_long, gate, csr->long_rows.get(), csr->n_long.get(),
+                          n_long_blocks);
+            });
+        } else { // K = 2 ... 7: one thread per (stored row, variable)
+            dim3 grid(div_up(csr->n, 256), (unsigned)K);
+            XR_LAUNCH("apply_partial", k_apply_partial<SRC>, grid, dim3(256), 0, method, csr->indptr.get(), csr->indices.get(),
+                      csr->data.get(), row_order_of(csr), csr->n, csr->m, src, K, out_dev, rows_layout != 0, csr->has_long);
         }
         if (csr->has_long && !long_done) {
             dim3 lgrid(64, (unsigned)K);
-            if (source_dtype == XR_F64)
-                XR_LAUNCH("apply_partial_long", k_apply_partial_long<double>, lgrid, dim3(256), 0, method, csr->indptr.get(),
-                          csr->indices.get(), csr->data.get(), row_order_of(csr), csr->long_rows.get(), csr->n_long.get(),
-                          csr->n, csr->m, static_cast<const double *>(source_dev), K, out_dev, rows_layout != 0, gate);
-            else
-                XR_LAUNCH("apply_partial_long", k_apply_partial_long<float>, lgrid, dim3(256), 0, method, csr->indptr.get(),
-                          csr->indices.get(), csr->data.get(), row_order_of(csr), csr->long_rows.get(), csr->n_long.get(),
-                          csr->n, csr->m, static_cast<const float *>(source_dev), K, out_dev, rows_layout != 0, gate);
+            XR_LAUNCH("apply_partial_long", k_apply_partial_long<SRC>, lgrid, dim3(256), 0, method, csr->indptr.get(),
+                      csr->indices.get(), csr->data.get(), row_order_of(csr), csr->long_rows.get(), csr->n_long.get(),
+                      csr->n, csr->m, src, K, out_dev, rows_layout != 0, gate);
         }
-    }
+    });
 }
 
 extern "C" {
@@ -3153,25 +3111,12 @@ int xr_reduce_partial_rows_dev(int method, const double *rows_dev, const int64_t
     XR_REQUIRE(n_targets >= 0 && K >= 0, XR_ERR_INVALID, "xr_reduce_partial_rows_dev: negative size");
     if (n_targets * K > 0) {
         XR_REQUIRE(indptr_dev && out_dev, XR_ERR_INVALID, "xr_reduce_partial_rows_dev: NULL argument");
-        constexpr bool plain = false;
-        if (K == 1 && !plain && (reinterpret_cast<uintptr_t>(rows_dev) & 15) == 0) {
-#define XR_REDUCE_K1(M)                                                                                                             \
-    case M:                                                                                                                         \
-        XR_LAUNCH("reduce_partial_rows", k_reduce_partial_rows_k1<M>, dim3(div_up(n_targets, 256)), dim3(256), 0, rows_dev,         \
-                  indptr_dev, order_dev, n_targets, out_dev);                                                                       \
-        break;
-            switch (method) {
-                XR_REDUCE_K1(XR_MEAN)
-                XR_REDUCE_K1(XR_FIRST_ORDER_CONSERVATIVE)
-                XR_REDUCE_K1(XR_SUM)
-                XR_REDUCE_K1(XR_HARMONIC_MEAN)
-                XR_REDUCE_K1(XR_GEOMETRIC_MEAN)
-                XR_REDUCE_K1(XR_MINIMUM)
-                XR_REDUCE_K1(XR_MAXIMUM)
-            default: XR_REQUIRE(false, XR_ERR_INVALID, "reducer %d does not decompose over source shards", method);
-            }
-#undef XR_REDUCE_K1
-        } else if (K >= 8 && !plain)
+        if (K == 1 && (reinterpret_cast<uintptr_t>(rows_dev) & 15) == 0) {
+            with_decomposable(method, [&](auto m) {
+                XR_LAUNCH("reduce_partial_rows", k_reduce_partial_rows_k1<decltype(m)::value>, dim3(div_up(n_targets, 256)),
+                          dim3(256), 0, rows_dev, indptr_dev, order_dev, n_targets, out_dev);
+            });
+        } else if (K >= 8)
             XR_LAUNCH("reduce_partial_rows", k_reduce_partial_rows_t, dim3(div_up(n_targets, 64), (unsigned)std::min<int64_t>(div_up(K, 32), 64)),
                       dim3(256), 0, method, rows_dev, indptr_dev, order_dev, n_targets, K, out_dev);
         else

@@ -676,6 +676,26 @@ def _axis_arrays(axis_y, axis_x):
     return arrays
 
 
+def _apply_host(fn, weights, source, method_id, percentile, out):
+    """The host-array apply of DeviceCSR / DeviceOuter through the C entry point ``fn``: (K, S) -> float64 (K, T)."""
+    src, dtype = _source_2d(source)
+    if src.shape[1] != weights.m:
+        raise ValueError(f"source has {src.shape[1]} cells, weights expect {weights.m}")
+    K = src.shape[0]
+    if out is None:
+        out = np.empty((K, weights.n), dtype=np.float64)
+    elif out.shape != (K, weights.n) or out.dtype != np.float64 or not out.flags.c_contiguous:
+        raise ValueError(f"out must be a C-contiguous float64 array of shape {(K, weights.n)}")
+    check(fn(weights._h, int(method_id), float(percentile), _ptr(src), dtype, K, _ptr(out)))
+    return out
+
+
+def _apply_dev(fn, weights, source_ptr, dtype, K, out_ptr, method_id, percentile):
+    """The device-pointer apply of DeviceCSR / DeviceOuter through the C entry point ``fn``."""
+    check(fn(weights._h, int(method_id), float(percentile), ctypes.c_void_p(source_ptr), int(dtype), int(K),
+             ctypes.c_void_p(out_ptr)))
+
+
 class DeviceCSR:
     """MatrixCSR resident in HBM: rows = target faces, columns = source faces."""
 
@@ -803,25 +823,11 @@ class DeviceCSR:
         """make_regrid(f)._regrid(source, A, size): (K, S) -> float64 (K, T).  ``out``: optional preallocated
         C-contiguous float64 (K, T) array to reuse (for large K the first touch and the release of a fresh result
         array cost more than the transfer itself)."""
-        src, dtype = _source_2d(source)
-        if src.shape[1] != self.m:
-            raise ValueError(f"source has {src.shape[1]} cells, weights expect {self.m}")
-        K = src.shape[0]
-        if out is None:
-            out = np.empty((K, self.n), dtype=np.float64)
-        elif out.shape != (K, self.n) or out.dtype != np.float64 or not out.flags.c_contiguous:
-            raise ValueError(f"out must be a C-contiguous float64 array of shape {(K, self.n)}")
-        check(_lib.load().xr_apply_csr(self._h, int(method_id), float(percentile), _ptr(src), dtype, K, _ptr(out)))
-        return out
+        return _apply_host(_lib.load().xr_apply_csr, self, source, method_id, percentile, out)
 
     def apply_dev(self, source_ptr, dtype, K, out_ptr, method_id=0, percentile=0.0):
         """Device-pointer variant (e.g. torch tensor .data_ptr()); no host transfer."""
-        check(
-            _lib.load().xr_apply_csr_dev(
-                self._h, int(method_id), float(percentile), ctypes.c_void_p(source_ptr), int(dtype), int(K),
-                ctypes.c_void_p(out_ptr),
-            )
-        )
+        _apply_dev(_lib.load().xr_apply_csr_dev, self, source_ptr, dtype, K, out_ptr, method_id, percentile)
 
     def partial_dev(self, source_ptr, dtype, K, out_ptr, method_id, rows_layout):
         """partial reducer state over this matrix' columns (multi-GPU split): planes [C, K, n] or rows [n, C * K]"""
@@ -871,24 +877,10 @@ class DeviceOuter:
         return self.csr().download()
 
     def apply(self, source, method_id=0, percentile=0.0, out=None):
-        src, dtype = _source_2d(source)
-        if src.shape[1] != self.m:
-            raise ValueError(f"source has {src.shape[1]} cells, weights expect {self.m}")
-        K = src.shape[0]
-        if out is None:
-            out = np.empty((K, self.n), dtype=np.float64)
-        elif out.shape != (K, self.n) or out.dtype != np.float64 or not out.flags.c_contiguous:
-            raise ValueError(f"out must be a C-contiguous float64 array of shape {(K, self.n)}")
-        check(_lib.load().xr_apply_outer(self._h, int(method_id), float(percentile), _ptr(src), dtype, K, _ptr(out)))
-        return out
+        return _apply_host(_lib.load().xr_apply_outer, self, source, method_id, percentile, out)
 
     def apply_dev(self, source_ptr, dtype, K, out_ptr, method_id=0, percentile=0.0):
-        check(
-            _lib.load().xr_apply_outer_dev(
-                self._h, int(method_id), float(percentile), ctypes.c_void_p(source_ptr), int(dtype), int(K),
-                ctypes.c_void_p(out_ptr),
-            )
-        )
+        _apply_dev(_lib.load().xr_apply_outer_dev, self, source_ptr, dtype, K, out_ptr, method_id, percentile)
 
 
 SHARD_MODES = {"hash": 0, "morton": 1, "balanced": 2}
