@@ -2485,30 +2485,25 @@ static xr_outer *outer_create(const int64_t *indptr_y, const int64_t *source_y, 
                "separable weights: target grid exceeds the int32 index range");
     XR_REQUIRE(n_source_y == 0 || n_source_x <= lim / n_source_y, XR_ERR_LIMIT,
                "separable weights: source grid exceeds the int32 index range");
-    xr_outer *o = new xr_outer();
-    try {
-        o->nty = n_target_y; o->nsy = n_source_y; o->ntx = n_target_x; o->nsx = n_source_x; o->Py = Py; o->Px = Px;
-        o->ipy.alloc((size_t)n_target_y + 1); o->ipx.alloc((size_t)n_target_x + 1);
-        o->sy.alloc((size_t)Py); o->sx.alloc((size_t)Px); o->tx.alloc((size_t)Px);
-        o->wy.alloc((size_t)Py); o->wx.alloc((size_t)Px);
-        upload_narrow(indptr_y, n_target_y + 1, o->ipy.get());
-        upload_narrow(indptr_x, n_target_x + 1, o->ipx.get());
-        upload_narrow(source_y, Py, o->sy.get());
-        upload_narrow(source_x, Px, o->sx.get());
-        h2d(o->wy.get(), weight_y, sizeof(double) * (size_t)Py);
-        h2d(o->wx.get(), weight_x, sizeof(double) * (size_t)Px);
-        std::vector<int32_t> owner((size_t)Px);
-        for (int64_t it = 0; it < n_target_x; it++)
-            for (int64_t q = indptr_x[it]; q < indptr_x[it + 1]; q++) owner[(size_t)q] = (int32_t)it;
-        h2d(o->tx.get(), owner.data(), sizeof(int32_t) * (size_t)Px);
-        for (int64_t j = 0; j < n_target_y; j++) o->max_cy = std::max(o->max_cy, indptr_y[j + 1] - indptr_y[j]);
-        for (int64_t i = 0; i < n_target_x; i++) o->max_cx = std::max(o->max_cx, indptr_x[i + 1] - indptr_x[i]);
-        stream_sync();
-    } catch (...) {
-        delete o;
-        throw;
-    }
-    return o;
+    Building<xr_outer> o;
+    o->nty = n_target_y; o->nsy = n_source_y; o->ntx = n_target_x; o->nsx = n_source_x; o->Py = Py; o->Px = Px;
+    o->ipy.alloc((size_t)n_target_y + 1); o->ipx.alloc((size_t)n_target_x + 1);
+    o->sy.alloc((size_t)Py); o->sx.alloc((size_t)Px); o->tx.alloc((size_t)Px);
+    o->wy.alloc((size_t)Py); o->wx.alloc((size_t)Px);
+    upload_narrow(indptr_y, n_target_y + 1, o->ipy.get());
+    upload_narrow(indptr_x, n_target_x + 1, o->ipx.get());
+    upload_narrow(source_y, Py, o->sy.get());
+    upload_narrow(source_x, Px, o->sx.get());
+    h2d(o->wy.get(), weight_y, sizeof(double) * (size_t)Py);
+    h2d(o->wx.get(), weight_x, sizeof(double) * (size_t)Px);
+    std::vector<int32_t> owner((size_t)Px);
+    for (int64_t it = 0; it < n_target_x; it++)
+        for (int64_t q = indptr_x[it]; q < indptr_x[it + 1]; q++) owner[(size_t)q] = (int32_t)it;
+    h2d(o->tx.get(), owner.data(), sizeof(int32_t) * (size_t)Px);
+    for (int64_t j = 0; j < n_target_y; j++) o->max_cy = std::max(o->max_cy, indptr_y[j + 1] - indptr_y[j]);
+    for (int64_t i = 0; i < n_target_x; i++) o->max_cx = std::max(o->max_cx, indptr_x[i + 1] - indptr_x[i]);
+    stream_sync();
+    return o.release();
 }
 
 // the CSR of the outer product, assembled on the device (closed-form offsets: no sort, no scan)
@@ -2517,31 +2512,26 @@ static xr_csr *outer_materialise(const xr_outer *o) {
     XR_REQUIRE(o->Py == 0 || o->Px < lim / o->Py, XR_ERR_LIMIT, "separable weights: %lld x %lld entries exceed the int32 range",
                (long long)o->Py, (long long)o->Px);
     const int64_t n = o->nty * o->ntx, m = o->nsy * o->nsx, nnz = o->Py * o->Px;
-    xr_csr *csr = new xr_csr();
-    try {
-        csr->n = n; csr->m = m; csr->nnz = nnz;
-        csr->indptr.alloc((size_t)n + 1);
-        csr->indices.alloc((size_t)nnz);
-        csr->data.alloc((size_t)nnz);
-        csr->long_rows.alloc((size_t)(nnz / XR_APPLY_LONG_ROW + 1));
-        csr->n_long.alloc(1);
-        XR_HIP(hipMemsetAsync(csr->n_long.get(), 0, sizeof(int32_t), launch_stream()));
-        XR_LAUNCH("outer_indptr", k_outer_indptr, dim3(div_up(n + 1, 256)), dim3(256), 0, o->ipy.get(), o->ipx.get(), o->nty,
-                  o->ntx, o->Px, nnz, csr->indptr.get(), csr->long_rows.get(), csr->n_long.get());
-        if (nnz > 0) {
-            const int64_t gx = std::min<int64_t>(div_up(o->max_cy * o->Px, 256), 1 << 16);
-            const int64_t gy = std::min<int64_t>(o->nty, 32768);
-            XR_LAUNCH("outer_fill", k_outer_fill, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, o->ipy.get(), o->sy.get(),
-                      o->wy.get(), o->ipx.get(), o->sx.get(), o->wx.get(), o->tx.get(), o->nty, o->nsx, o->Px,
-                      csr->indices.get(), csr->data.get());
-        }
-        const int32_t nl = read_scalar(csr->n_long.get());
-        csr->has_long = nl > 0;
-    } catch (...) {
-        delete csr;
-        throw;
+    Building<xr_csr> csr;
+    csr->n = n; csr->m = m; csr->nnz = nnz;
+    csr->indptr.alloc((size_t)n + 1);
+    csr->indices.alloc((size_t)nnz);
+    csr->data.alloc((size_t)nnz);
+    csr->long_rows.alloc((size_t)(nnz / XR_APPLY_LONG_ROW + 1));
+    csr->n_long.alloc(1);
+    XR_HIP(hipMemsetAsync(csr->n_long.get(), 0, sizeof(int32_t), launch_stream()));
+    XR_LAUNCH("outer_indptr", k_outer_indptr, dim3(div_up(n + 1, 256)), dim3(256), 0, o->ipy.get(), o->ipx.get(), o->nty,
+              o->ntx, o->Px, nnz, csr->indptr.get(), csr->long_rows.get(), csr->n_long.get());
+    if (nnz > 0) {
+        const int64_t gx = std::min<int64_t>(div_up(o->max_cy * o->Px, 256), 1 << 16);
+        const int64_t gy = std::min<int64_t>(o->nty, 32768);
+        XR_LAUNCH("outer_fill", k_outer_fill, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, o->ipy.get(), o->sy.get(),
+                  o->wy.get(), o->ipx.get(), o->sx.get(), o->wx.get(), o->tx.get(), o->nty, o->nsx, o->Px,
+                  csr->indices.get(), csr->data.get());
     }
-    return csr;
+    const int32_t nl = read_scalar(csr->n_long.get());
+    csr->has_long = nl > 0;
+    return csr.release();
 }
 
 // x-lists of at most 4 entries (similar resolutions, refinement, any coarsening along y only): matrix-free.  Longer
@@ -2658,25 +2648,20 @@ int xr_csr_upload(const double *data, const int64_t *indices, const int64_t *ind
     for (int64_t i = 0; i < nnz; i++)
         XR_REQUIRE(indices[i] >= 0 && indices[i] < m, XR_ERR_INVALID,
                    "xr_csr_upload: column index %lld outside [0,%lld)", (long long)indices[i], (long long)m);
-    xr_csr *csr = new xr_csr();
-    try {
-        csr->n = n; csr->m = m; csr->nnz = nnz;
-        csr->indptr.alloc((size_t)n + 1);
-        csr->indices.alloc((size_t)nnz);
-        csr->data.alloc((size_t)nnz);
-        upload_narrow(indptr, n + 1, csr->indptr.get());
-        upload_narrow(indices, nnz, csr->indices.get());
-        h2d(csr->data.get(), data, sizeof(double) * (size_t)nnz);
-        std::vector<int32_t> longs;
-        for (int64_t i = 0; i < n; i++)
-            if (indptr[i + 1] - indptr[i] > APPLY_LONG) longs.push_back((int32_t)i);
-        set_long_rows(csr, longs);
-        stream_sync();
-    } catch (...) {
-        delete csr;
-        throw;
-    }
-    *out = csr;
+    Building<xr_csr> csr;
+    csr->n = n; csr->m = m; csr->nnz = nnz;
+    csr->indptr.alloc((size_t)n + 1);
+    csr->indices.alloc((size_t)nnz);
+    csr->data.alloc((size_t)nnz);
+    upload_narrow(indptr, n + 1, csr->indptr.get());
+    upload_narrow(indices, nnz, csr->indices.get());
+    h2d(csr->data.get(), data, sizeof(double) * (size_t)nnz);
+    std::vector<int32_t> longs;
+    for (int64_t i = 0; i < n; i++)
+        if (indptr[i + 1] - indptr[i] > APPLY_LONG) longs.push_back((int32_t)i);
+    set_long_rows(csr.get(), longs);
+    stream_sync();
+    *out = csr.release();
     XR_API_END
 }
 
@@ -2694,31 +2679,26 @@ int xr_csr_from_triplet(const int64_t *row, const int64_t *col, const double *da
         XR_REQUIRE(i == 0 || row[i] >= row[i - 1], XR_ERR_INVALID,
                    "xr_csr_from_triplet: rows must be sorted (core/sparse.py:65)");
     }
-    xr_csr *csr = new xr_csr();
-    try {
-        csr->n = n; csr->m = m; csr->nnz = nnz;
-        csr->indptr.alloc((size_t)n + 1);
-        csr->indices.alloc((size_t)nnz);
-        csr->data.alloc((size_t)nnz);
-        DevBuf<int32_t> row32((size_t)nnz), count((size_t)(n > 0 ? n : 1));
-        upload_narrow(row, nnz, row32.get());
-        upload_narrow(col, nnz, csr->indices.get());
-        h2d(csr->data.get(), data, sizeof(double) * (size_t)nnz);
-        XR_HIP(hipMemsetAsync(count.get(), 0, sizeof(int32_t) * (size_t)(n > 0 ? n : 1), launch_stream()));
-        if (nnz > 0) XR_LAUNCH("bincount", k_bincount, dim3(div_up(nnz, 256)), dim3(256), 0, row32.get(), nnz, count.get());
-        exclusive_scan_i32(count.get(), csr->indptr.get(), n);
-        std::vector<int32_t> longs;
-        for (int64_t i = 0, j = 0; i < nnz; i = j) { // rows are sorted: run lengths
-            while (j < nnz && row[j] == row[i]) j++;
-            if (j - i > APPLY_LONG) longs.push_back((int32_t)row[i]);
-        }
-        set_long_rows(csr, longs);
-        stream_sync();
-    } catch (...) {
-        delete csr;
-        throw;
+    Building<xr_csr> csr;
+    csr->n = n; csr->m = m; csr->nnz = nnz;
+    csr->indptr.alloc((size_t)n + 1);
+    csr->indices.alloc((size_t)nnz);
+    csr->data.alloc((size_t)nnz);
+    DevBuf<int32_t> row32((size_t)nnz), count((size_t)(n > 0 ? n : 1));
+    upload_narrow(row, nnz, row32.get());
+    upload_narrow(col, nnz, csr->indices.get());
+    h2d(csr->data.get(), data, sizeof(double) * (size_t)nnz);
+    XR_HIP(hipMemsetAsync(count.get(), 0, sizeof(int32_t) * (size_t)(n > 0 ? n : 1), launch_stream()));
+    if (nnz > 0) XR_LAUNCH("bincount", k_bincount, dim3(div_up(nnz, 256)), dim3(256), 0, row32.get(), nnz, count.get());
+    exclusive_scan_i32(count.get(), csr->indptr.get(), n);
+    std::vector<int32_t> longs;
+    for (int64_t i = 0, j = 0; i < nnz; i = j) { // rows are sorted: run lengths
+        while (j < nnz && row[j] == row[i]) j++;
+        if (j - i > APPLY_LONG) longs.push_back((int32_t)row[i]);
     }
-    *out = csr;
+    set_long_rows(csr.get(), longs);
+    stream_sync();
+    *out = csr.release();
     XR_API_END
 }
 
@@ -2727,17 +2707,9 @@ int xr_csr_from_outer(const int64_t *indptr_y, const int64_t *source_y, const do
                       int64_t n_target_x, int64_t n_source_x, xr_csr **out) {
     XR_API_BEGIN
     XR_REQUIRE(out, XR_ERR_INVALID, "xr_csr_from_outer: NULL argument");
-    xr_outer *o = outer_create(indptr_y, source_y, weight_y, n_target_y, n_source_y, indptr_x, source_x, weight_x,
-                               n_target_x, n_source_x);
-    xr_csr *csr = nullptr;
-    try {
-        csr = outer_materialise(o);
-    } catch (...) {
-        delete o;
-        throw;
-    }
-    delete o;
-    *out = csr;
+    const std::unique_ptr<xr_outer> o(outer_create(indptr_y, source_y, weight_y, n_target_y, n_source_y, indptr_x, source_x,
+                                                   weight_x, n_target_x, n_source_x));
+    *out = outer_materialise(o.get());
     XR_API_END
 }
 

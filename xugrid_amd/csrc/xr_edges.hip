@@ -836,14 +836,12 @@ static void edge_length_csr(xr_mesh *tree, const double *edge_xy_host, int64_t n
         XR_LAUNCH("edges_walk_big", k_edge_walk_big, dim3(grid_persistent), dim3(256), 0, edge_xy, g, tree->cell_start.get(),
                   tree->rec_bb.get(), queue.get(), region_cap, counters.get(), big_list.get());
         // (a persistent grid of what is resident: 92-96 registers with the next round's operands in flight, five waves per SIMD)
-#define XR_EDGE_CLIP(MC)                                                                                                           \
-    XR_LAUNCH("edges_clip", k_edge_clip<MC>, dim3(engine().num_cu * (MC > 0 ? 5 : 7)), dim3(256), 0, edge_xy, tree->rec_fxy.get(), tree->rec_len.get(), \
-              tree->record_off(), tree->m, tree->rec_face.get(), queue.get(), queue_len.get(), queue_rank.get(), region_cap,        \
-              counters.get(), row_count.get())
-        if (tree->record_off() == nullptr && tree->m == 3) XR_EDGE_CLIP(3);
-        else if (tree->record_off() == nullptr && tree->m == 4) XR_EDGE_CLIP(4);
-        else XR_EDGE_CLIP(0);
-#undef XR_EDGE_CLIP
+        // (the flat vertex blocks of a polygon mesh: the run-time form)
+        with_nodes_per_face(tree->ragged() ? 0 : tree->m, [&](auto mc) {
+            XR_LAUNCH("edges_clip", k_edge_clip<mc()>, dim3(engine().num_cu * (mc() > 0 ? 5 : 7)), dim3(256), 0, edge_xy,
+                      tree->rec_fxy.get(), tree->rec_len.get(), tree->record_off(), tree->m, tree->rec_face.get(), queue.get(),
+                      queue_len.get(), queue_rank.get(), region_cap, counters.get(), row_count.get());
+        });
         exclusive_scan_i32(row_count.get(), csr->indptr.get(), F);
         // The fill needs the row pointers, not the host: it goes into arrays sized by a guess (five pieces per edge; the benchmark
         // network has four) BEFORE the host reads the cursors and nnz -- the two read-backs, two allocations and the launch no
@@ -914,15 +912,10 @@ int xr_edge_length_csr(xr_mesh *tree, const double *edge_xy, int64_t n_edge, xr_
     XR_API_BEGIN
     XR_REQUIRE(tree && out && (edge_xy || n_edge == 0), XR_ERR_INVALID, "xr_edge_length_csr: NULL argument");
     XR_REQUIRE(n_edge >= 0 && n_edge < ((int64_t)1 << 30), XR_ERR_LIMIT, "xr_edge_length_csr: too many edges");
-    xr_csr *csr = new xr_csr();
-    try {
-        edge_length_csr(tree, edge_xy, n_edge, csr);
-        stream_sync();
-    } catch (...) {
-        delete csr;
-        throw;
-    }
-    *out = csr;
+    Building<xr_csr> csr;
+    edge_length_csr(tree, edge_xy, n_edge, csr.get());
+    stream_sync();
+    *out = csr.release();
     XR_API_END
 }
 
@@ -930,15 +923,10 @@ int xr_edge_length_csr_dev(xr_mesh *tree, const double *edge_xy_dev, int64_t n_e
     XR_API_BEGIN
     XR_REQUIRE(tree && out && (edge_xy_dev || n_edge == 0), XR_ERR_INVALID, "xr_edge_length_csr_dev: NULL argument");
     XR_REQUIRE(n_edge >= 0 && n_edge < ((int64_t)1 << 30), XR_ERR_LIMIT, "xr_edge_length_csr_dev: too many edges");
-    xr_csr *csr = new xr_csr();
-    try {
-        edge_length_csr(tree, nullptr, n_edge, csr, edge_xy_dev);
-        stream_sync();
-    } catch (...) {
-        delete csr;
-        throw;
-    }
-    *out = csr;
+    Building<xr_csr> csr;
+    edge_length_csr(tree, nullptr, n_edge, csr.get(), edge_xy_dev);
+    stream_sync();
+    *out = csr.release();
     XR_API_END
 }
 

@@ -13,6 +13,7 @@
 #include <mutex>
 #include <shared_mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/xugrid_amd.h"
@@ -328,6 +329,50 @@ enum Option : int {
 int64_t option(Option o);
 
 inline unsigned div_up(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
+
+// f(std::integral_constant<int, MC>()): MC = nodes per face as a compile-time constant for triangle (3) and quadrilateral
+// (4) meshes, 0 = any (the kernel reads the run-time m).  The one table behind every kernel with an MC template parameter.
+template <typename F> void with_nodes_per_face(int m, F &&f) {
+    if (m == 3) f(std::integral_constant<int, 3>());
+    else if (m == 4) f(std::integral_constant<int, 4>());
+    else f(std::integral_constant<int, 0>());
+}
+
+// KERNEL may be launched with up to `bytes` of dynamic LDS (beyond the 64 KB any kernel may ask for): set on first use,
+// once per kernel (every caller of one kernel passes the same size).
+template <auto KERNEL> void allow_dynamic_lds(size_t bytes) {
+    static const bool set = [&] {
+        XR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        return true;
+    }();
+    (void)set;
+}
+
+// A handle under construction (xr_mesh, xr_csr, ...): owned here until release() hands it to the caller; a failure on the
+// way frees it while the exception passes through.  Temporaries of the failed call have gone back to the block pool by
+// then either way; the pool reuses blocks in stream order on the engine's stream, which is why most sites do not wait.
+// Pass WaitFirst where the call enqueued kernels that read or write device memory of the CALLER (the *_dev entry points,
+// which may also run asynchronously or on the caller's stream): the stream is then drained before the handle is freed, so
+// an error return means nothing in flight still touches the caller's arrays.  Entry points that only touch memory the
+// library owns construct without it.
+enum class OnFailure { FreeOnly, WaitFirst };
+template <typename T> struct Building {
+    std::unique_ptr<T> p{new T()};
+    OnFailure rule;
+    explicit Building(OnFailure r = OnFailure::FreeOnly) : rule(r) {}
+    Building(const Building &) = delete;
+    Building &operator=(const Building &) = delete;
+    ~Building() {
+        if (!p || rule != OnFailure::WaitFirst) return;
+        try {
+            stream_sync();
+        } catch (const Failure &) { // (unwinding already: the first failure is the one reported)
+        }
+    }
+    T *operator->() const { return p.get(); }
+    T *get() const { return p.get(); }
+    T *release() { return p.release(); }
+};
 
 // ---------------------------------------------------------------------------------------------
 // device primitives implemented in xr_scan.hip

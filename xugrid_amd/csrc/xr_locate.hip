@@ -837,125 +837,117 @@ static void barycentric_csr(xr_mesh *voronoi, xr_mesh *source, xr_mesh *query, c
         XR_REQUIRE(vertex_face[i - n_identity] >= 0 && vertex_face[i - n_identity] < source->n_face, XR_ERR_INVALID,
                    "xr_barycentric_csr: vertex_face[%lld] outside the source grid", (long long)i);
     const int m = voronoi->m;
-    xr_csr *csr = new xr_csr();
-    try {
-        csr->n = n; csr->m = source->n_face; csr->nnz = 0;
-        csr->indptr.alloc((size_t)n + 1);
-        if (n == 0 || voronoi->n_face == 0 || source->n_face == 0) {
-            fill_i32(csr->indptr.get(), 0, n + 1);
-            csr->indices.alloc(0);
-            csr->data.alloc(0);
-            stream_sync();
-        } else {
-            mesh_prepare(voronoi, false); mesh_build_index(voronoi);
-            const double tol = resolve_tolerance(voronoi, tolerance);
-            PointsBuf own_pts;
-            DevBuf<double> w((size_t)n * m);
-            DevBuf<uint8_t> own_inside;
-            const double tol_source = pre ? pre->tol_source : prepare_points(source, query, points, n, own_pts, own_inside);
-            bool join_later = false;
-            if (pre && pre->on_side) { // (filled on the side stream)
-                if (pre->pts_marked) { // the points now, the flags in front of bary_fix_count
-                    XR_HIP(hipStreamWaitEvent(engine().stream, engine().aux_event, 0));
-                    join_later = true;
-                } else {
-                    side_join();
-                    pre->on_side = false;
-                }
-            }
-            PointsBuf &pts = pre ? pre->pts : own_pts;
-            DevBuf<uint8_t> &inside = pre ? pre->inside : own_inside;
-            // the vertex table the weight slots are paired with: the caller's order as the reference does
-            // (unstructured.py:175,193) = the mesh's own int32 connectivity, read as it is; or -- tree_order -- the tree's
-            // counter-clockwise-normalised copy, materialised as a table first
-            // (vertex -> face table and the interpolation map behind it in ONE buffer: their host parts are adjacent, one upload)
-            DevBuf<int64_t> face((size_t)n), faces_ccw((size_t)(reference_order ? 1 : voronoi->n_face * m));
-            DevBuf<int32_t> count((size_t)n);
-            // (vertices below n_identity are their own face -- the centroids --: bary_fill never reads their table entries)
-            // The table and the flags of the cells with a substitute vertex stay on the tessellation: a second construction
-            // on it (another target, another tolerance) finds them there.
-            {
-                const size_t n_tail = (size_t)(nv - n_identity), n_map = (size_t)(2 * n_extra);
-                std::vector<int64_t> host(n_tail + n_map);
-                if (n_tail > 0) memcpy(host.data(), vertex_face, sizeof(int64_t) * n_tail);
-                if (n_map > 0) memcpy(host.data() + n_tail, node_to_node_map, sizeof(int64_t) * n_map);
-                const bool same = voronoi->bary_ids.get() && voronoi->bary_n_identity == n_identity &&
-                                  voronoi->bary_n_extra == n_extra && voronoi->bary_ids_host == host;
-                if (!same) {
-                    voronoi->bary_flag_valid = false;
-                    voronoi->bary_ids.alloc((size_t)(nv + 2 * n_extra + 1));
-                    if (!host.empty()) h2d(voronoi->bary_ids.get() + n_identity, host.data(), sizeof(int64_t) * host.size());
-                    voronoi->bary_ids_host = std::move(host);
-                    voronoi->bary_n_identity = n_identity;
-                    voronoi->bary_n_extra = n_extra;
-                }
-            }
-            int64_t *const vface = voronoi->bary_ids.get(), *const n2n = voronoi->bary_ids.get() + nv;
-            if (!reference_order) mesh_faces_ccw_dev(voronoi, faces_ccw.get(), false);
-            DevBuf<uint8_t> n_pos((size_t)n);
-            if (!voronoi->bary_flag_valid) {
-                voronoi->bary_cell_flag.alloc((size_t)voronoi->n_face);
-                XR_LAUNCH("bary_cell_flag", k_bary_cell_flag, dim3(div_up(voronoi->n_face, 256)), dim3(256), 0, voronoi->faces_raw.get(),
-                          voronoi->n_face, m, nv - n_extra, voronoi->bary_cell_flag.get());
-                voronoi->bary_flag_valid = true;
-            }
-            const uint8_t *const cell_flag_p = voronoi->bary_cell_flag.get();
-            XR_LAUNCH("barycentric", k_barycentric_cm, dim3(div_up(n, 256)), dim3(256), 0, voronoi->rec_fxy.get(),
-                      voronoi->rec_len.get(), voronoi->record_off(), m, voronoi->grid, voronoi->cell_start.get(), voronoi->rec_bb.get(),
-                      voronoi->rec_face.get(), voronoi->n_face, pts.get(), n, tol, face.get(), w.get(), cell_flag_p, n_pos.get());
-            if (join_later) {
+    Building<xr_csr> csr;
+    csr->n = n; csr->m = source->n_face; csr->nnz = 0;
+    csr->indptr.alloc((size_t)n + 1);
+    if (n == 0 || voronoi->n_face == 0 || source->n_face == 0) {
+        fill_i32(csr->indptr.get(), 0, n + 1);
+        csr->indices.alloc(0);
+        csr->data.alloc(0);
+        stream_sync();
+    } else {
+        mesh_prepare(voronoi, false); mesh_build_index(voronoi);
+        const double tol = resolve_tolerance(voronoi, tolerance);
+        PointsBuf own_pts;
+        DevBuf<double> w((size_t)n * m);
+        DevBuf<uint8_t> own_inside;
+        const double tol_source = pre ? pre->tol_source : prepare_points(source, query, points, n, own_pts, own_inside);
+        bool join_later = false;
+        if (pre && pre->on_side) { // (filled on the side stream)
+            if (pre->pts_marked) { // the points now, the flags in front of bary_fix_count
+                XR_HIP(hipStreamWaitEvent(engine().stream, engine().aux_event, 0));
+                join_later = true;
+            } else {
                 side_join();
                 pre->on_side = false;
             }
-            // the flags from the faces around each point's cell, behind the barycentric kernel
-            const int64_t *vface_tab = voronoi->bary_ids.get();
-            mesh_face_coords(source); // (its face-major vertex block in the caller's order: built once per mesh)
-            mesh_prepare(source, false); // (the index for the points the star leaves open: still there unless the mesh was
-            mesh_build_index(source);    // invalidated since the handle was made)
-#define XR_STAR(MSV)                                                                                                                 \
-    XR_LAUNCH("star_flag", k_star_flag<MSV>, dim3(div_up(n, 256)), dim3(256), 0, face.get(), voronoi->faces_raw.get(), m, n_identity,  \
-              vface_tab, nv - n_extra, source->fxy.get(), source->len.get(), source->caller_off(), source->m, pts.get(), n,           \
-              tol_source, inside.get())
-            if (source->m == 3 && !source->ragged()) XR_STAR(3);
-            else if (source->m == 4 && !source->ragged()) XR_STAR(4);
-            else XR_STAR(0);
-#undef XR_STAR
-            XR_LAUNCH("locate_flag", k_locate_flag, dim3(div_up(n, 256)), dim3(256), 0, source->rec_fxy.get(),
-                      source->rec_len.get(), source->record_off(), source->m, source->grid, source->cell_start.get(),
-                      source->rec_bb.get(), source->rec_face.get(), source->n_face, pts.get(), n, tol_source, inside.get());
-            if (reference_order)
-                XR_LAUNCH("bary_fix_count", k_bary_fix_count<int32_t>, dim3(div_up(n, 256)), dim3(256), 0, face.get(), w.get(), m,
-                          voronoi->faces_raw.get(), voronoi->node_xy.get(), n2n, nv - n_extra, inside.get(), n, count.get(), n_pos.get());
-            else
-                XR_LAUNCH("bary_fix_count", k_bary_fix_count<int64_t>, dim3(div_up(n, 256)), dim3(256), 0, face.get(), w.get(), m,
-                          faces_ccw.get(), voronoi->node_xy.get(), n2n, nv - n_extra, inside.get(), n, count.get(), n_pos.get());
-            exclusive_scan_i32(count.get(), csr->indptr.get(), n);
-            // The fill needs the row pointers, not the host: it is launched into arrays sized by a guess -- seven entries per point
-            // (a Delaunay source gives six) -- BEFORE the host reads the number of entries, so that read-back, the two allocations and
-            // the launch no longer sit between the scan and the fill (55 us of an idle device per construction, timeline).  A
-            // matrix that does not fit is filled again into arrays of its real size.
-            auto fill = [&](int64_t capacity) {
-                csr->indices.alloc((size_t)capacity);
-                csr->data.alloc((size_t)capacity);
-                if (reference_order)
-                    XR_LAUNCH("bary_fill", k_bary_fill<int32_t>, dim3(div_up(n, 256)), dim3(256), 0, face.get(), w.get(), m,
-                              voronoi->faces_raw.get(), vface, csr->indptr.get(), n, csr->indices.get(), csr->data.get(), n_identity,
-                              capacity);
-                else
-                    XR_LAUNCH("bary_fill", k_bary_fill<int64_t>, dim3(div_up(n, 256)), dim3(256), 0, face.get(), w.get(), m,
-                              faces_ccw.get(), vface, csr->indptr.get(), n, csr->indices.get(), csr->data.get(), n_identity, capacity);
-            };
-            const int64_t guess = std::min<int64_t>(n * (int64_t)m, 7 * n + ((int64_t)1 << 16));
-            const int64_t nnz = read_scalar(csr->indptr.get() + n, [&] { fill(guess); }); // (the fill behind the copy: it runs while nnz travels)
-            csr->nnz = nnz;
-            if (nnz > guess) fill(nnz);
-            stream_sync();
         }
-    } catch (...) {
-        delete csr;
-        throw;
+        PointsBuf &pts = pre ? pre->pts : own_pts;
+        DevBuf<uint8_t> &inside = pre ? pre->inside : own_inside;
+        // the vertex table the weight slots are paired with: the caller's order as the reference does
+        // (unstructured.py:175,193) = the mesh's own int32 connectivity, read as it is; or -- tree_order -- the tree's
+        // counter-clockwise-normalised copy, materialised as a table first
+        // (vertex -> face table and the interpolation map behind it in ONE buffer: their host parts are adjacent, one upload)
+        DevBuf<int64_t> face((size_t)n), faces_ccw((size_t)(reference_order ? 1 : voronoi->n_face * m));
+        DevBuf<int32_t> count((size_t)n);
+        // (vertices below n_identity are their own face -- the centroids --: bary_fill never reads their table entries)
+        // The table and the flags of the cells with a substitute vertex stay on the tessellation: a second construction
+        // on it (another target, another tolerance) finds them there.
+        {
+            const size_t n_tail = (size_t)(nv - n_identity), n_map = (size_t)(2 * n_extra);
+            std::vector<int64_t> host(n_tail + n_map);
+            if (n_tail > 0) memcpy(host.data(), vertex_face, sizeof(int64_t) * n_tail);
+            if (n_map > 0) memcpy(host.data() + n_tail, node_to_node_map, sizeof(int64_t) * n_map);
+            const bool same = voronoi->bary_ids.get() && voronoi->bary_n_identity == n_identity &&
+                              voronoi->bary_n_extra == n_extra && voronoi->bary_ids_host == host;
+            if (!same) {
+                voronoi->bary_flag_valid = false;
+                voronoi->bary_ids.alloc((size_t)(nv + 2 * n_extra + 1));
+                if (!host.empty()) h2d(voronoi->bary_ids.get() + n_identity, host.data(), sizeof(int64_t) * host.size());
+                voronoi->bary_ids_host = std::move(host);
+                voronoi->bary_n_identity = n_identity;
+                voronoi->bary_n_extra = n_extra;
+            }
+        }
+        int64_t *const vface = voronoi->bary_ids.get(), *const n2n = voronoi->bary_ids.get() + nv;
+        if (!reference_order) mesh_faces_ccw_dev(voronoi, faces_ccw.get(), false);
+        DevBuf<uint8_t> n_pos((size_t)n);
+        if (!voronoi->bary_flag_valid) {
+            voronoi->bary_cell_flag.alloc((size_t)voronoi->n_face);
+            XR_LAUNCH("bary_cell_flag", k_bary_cell_flag, dim3(div_up(voronoi->n_face, 256)), dim3(256), 0, voronoi->faces_raw.get(),
+                      voronoi->n_face, m, nv - n_extra, voronoi->bary_cell_flag.get());
+            voronoi->bary_flag_valid = true;
+        }
+        const uint8_t *const cell_flag_p = voronoi->bary_cell_flag.get();
+        XR_LAUNCH("barycentric", k_barycentric_cm, dim3(div_up(n, 256)), dim3(256), 0, voronoi->rec_fxy.get(),
+                  voronoi->rec_len.get(), voronoi->record_off(), m, voronoi->grid, voronoi->cell_start.get(), voronoi->rec_bb.get(),
+                  voronoi->rec_face.get(), voronoi->n_face, pts.get(), n, tol, face.get(), w.get(), cell_flag_p, n_pos.get());
+        if (join_later) {
+            side_join();
+            pre->on_side = false;
+        }
+        // the flags from the faces around each point's cell, behind the barycentric kernel
+        const int64_t *vface_tab = voronoi->bary_ids.get();
+        mesh_face_coords(source); // (its face-major vertex block in the caller's order: built once per mesh)
+        mesh_prepare(source, false); // (the index for the points the star leaves open: still there unless the mesh was
+        mesh_build_index(source);    // invalidated since the handle was made)
+        with_nodes_per_face(source->ragged() ? 0 : source->m, [&](auto msv) {
+            XR_LAUNCH("star_flag", k_star_flag<msv()>, dim3(div_up(n, 256)), dim3(256), 0, face.get(), voronoi->faces_raw.get(), m,
+                      n_identity, vface_tab, nv - n_extra, source->fxy.get(), source->len.get(), source->caller_off(), source->m,
+                      pts.get(), n, tol_source, inside.get());
+        });
+        XR_LAUNCH("locate_flag", k_locate_flag, dim3(div_up(n, 256)), dim3(256), 0, source->rec_fxy.get(),
+                  source->rec_len.get(), source->record_off(), source->m, source->grid, source->cell_start.get(),
+                  source->rec_bb.get(), source->rec_face.get(), source->n_face, pts.get(), n, tol_source, inside.get());
+        if (reference_order)
+            XR_LAUNCH("bary_fix_count", k_bary_fix_count<int32_t>, dim3(div_up(n, 256)), dim3(256), 0, face.get(), w.get(), m,
+                      voronoi->faces_raw.get(), voronoi->node_xy.get(), n2n, nv - n_extra, inside.get(), n, count.get(), n_pos.get());
+        else
+            XR_LAUNCH("bary_fix_count", k_bary_fix_count<int64_t>, dim3(div_up(n, 256)), dim3(256), 0, face.get(), w.get(), m,
+                      faces_ccw.get(), voronoi->node_xy.get(), n2n, nv - n_extra, inside.get(), n, count.get(), n_pos.get());
+        exclusive_scan_i32(count.get(), csr->indptr.get(), n);
+        // The fill needs the row pointers, not the host: it is launched into arrays sized by a guess -- seven entries per point
+        // (a Delaunay source gives six) -- BEFORE the host reads the number of entries, so that read-back, the two allocations and
+        // the launch no longer sit between the scan and the fill (55 us of an idle device per construction, timeline).  A
+        // matrix that does not fit is filled again into arrays of its real size.
+        auto fill = [&](int64_t capacity) {
+            csr->indices.alloc((size_t)capacity);
+            csr->data.alloc((size_t)capacity);
+            if (reference_order)
+                XR_LAUNCH("bary_fill", k_bary_fill<int32_t>, dim3(div_up(n, 256)), dim3(256), 0, face.get(), w.get(), m,
+                          voronoi->faces_raw.get(), vface, csr->indptr.get(), n, csr->indices.get(), csr->data.get(), n_identity,
+                          capacity);
+            else
+                XR_LAUNCH("bary_fill", k_bary_fill<int64_t>, dim3(div_up(n, 256)), dim3(256), 0, face.get(), w.get(), m,
+                          faces_ccw.get(), vface, csr->indptr.get(), n, csr->indices.get(), csr->data.get(), n_identity, capacity);
+        };
+        const int64_t guess = std::min<int64_t>(n * (int64_t)m, 7 * n + ((int64_t)1 << 16));
+        const int64_t nnz = read_scalar(csr->indptr.get() + n, [&] { fill(guess); }); // (the fill behind the copy: it runs while nnz travels)
+        csr->nnz = nnz;
+        if (nnz > guess) fill(nnz);
+        stream_sync();
     }
-    *out = csr;
+    *out = csr.release();
     }
 }
 
@@ -984,38 +976,33 @@ int xr_locate_flags_begin(xr_mesh *source, xr_mesh *query, const double *points,
                "xr_locate_flags_begin: give either a query mesh (its face centroids are the points) or points");
     if (query) n = query->n_face;
     XR_REQUIRE(n >= 0 && n < ((int64_t)1 << 31) - 1, XR_ERR_LIMIT, "xr_locate_flags_begin: too many points");
-    xr_points *h = new xr_points();
-    try {
-        h->n = n;
-        h->source = source;
-        if (n > 0 && source->n_face > 0) {
-            mesh_prepare(source, false);
-            mesh_build_index(source);
-            h->tol_source = resolve_tolerance(source, -1.0); // unstructured.py:189: default tolerance
-            h->inside.alloc((size_t)n);
-            h->query = query;
-            if (!query) { // (a query mesh: its centroids, shared with the mesh, when the kernels are launched -- launch_points)
-                h->pts.alloc((size_t)n * 2);
-                h2d(h->pts.get(), points, sizeof(double) * 2 * (size_t)n);
-            }
-            h->deferred = true; // launched by flush_pending_points
-            pending_points().push_back(h);
+    Building<xr_points> h;
+    h->n = n;
+    h->source = source;
+    if (n > 0 && source->n_face > 0) {
+        mesh_prepare(source, false);
+        mesh_build_index(source);
+        h->tol_source = resolve_tolerance(source, -1.0); // unstructured.py:189: default tolerance
+        h->inside.alloc((size_t)n);
+        h->query = query;
+        if (!query) { // (a query mesh: its centroids, shared with the mesh, when the kernels are launched -- launch_points)
+            h->pts.alloc((size_t)n * 2);
+            h2d(h->pts.get(), points, sizeof(double) * 2 * (size_t)n);
         }
-        else if (n > 0) { // (no source faces: every point is outside)
-            h->inside.alloc((size_t)n);
-            XR_HIP(hipMemsetAsync(h->inside.get(), 0, (size_t)n, launch_stream()));
-            if (query) {
-                h->pts.share(mesh_centroids_shared(query));
-            } else {
-                h->pts.alloc((size_t)n * 2);
-                h2d(h->pts.get(), points, sizeof(double) * 2 * (size_t)n);
-            }
-        }
-    } catch (...) {
-        delete h;
-        throw;
+        h->deferred = true; // launched by flush_pending_points
+        pending_points().push_back(h.get());
     }
-    *out = h; // (no wait: the kernels run on the side stream beside whatever the caller does next)
+    else if (n > 0) { // (no source faces: every point is outside)
+        h->inside.alloc((size_t)n);
+        XR_HIP(hipMemsetAsync(h->inside.get(), 0, (size_t)n, launch_stream()));
+        if (query) {
+            h->pts.share(mesh_centroids_shared(query));
+        } else {
+            h->pts.alloc((size_t)n * 2);
+            h2d(h->pts.get(), points, sizeof(double) * 2 * (size_t)n);
+        }
+    }
+    *out = h.release(); // (no wait: the kernels run on the side stream beside whatever the caller does next)
     XR_API_END
 }
 
@@ -1088,45 +1075,40 @@ int xr_locate_csr(xr_mesh *tree, xr_mesh *query, const double *points, int64_t n
                "xr_locate_csr: give either a query mesh (its face centroids are the points) or points");
     if (query) n = query->n_face;
     XR_REQUIRE(n >= 0 && n < ((int64_t)1 << 31) - 1, XR_ERR_LIMIT, "xr_locate_csr: too many points");
-    xr_csr *csr = new xr_csr();
-    try {
-        csr->n = n; csr->m = tree->n_face; csr->nnz = 0;
-        csr->indptr.alloc((size_t)n + 1);
-        if (n == 0 || tree->n_face == 0) {
-            fill_i32(csr->indptr.get(), 0, n + 1);
-            csr->indices.alloc(0);
-            csr->data.alloc(0);
-            stream_sync();
+    Building<xr_csr> csr;
+    csr->n = n; csr->m = tree->n_face; csr->nnz = 0;
+    csr->indptr.alloc((size_t)n + 1);
+    if (n == 0 || tree->n_face == 0) {
+        fill_i32(csr->indptr.get(), 0, n + 1);
+        csr->indices.alloc(0);
+        csr->data.alloc(0);
+        stream_sync();
+    } else {
+        mesh_prepare(tree, false);
+        mesh_build_index(tree);
+        const double tol = resolve_tolerance(tree, tolerance);
+        PointsBuf pts;
+        if (query) {
+            pts.share(mesh_centroids_shared(query));
         } else {
-            mesh_prepare(tree, false);
-            mesh_build_index(tree);
-            const double tol = resolve_tolerance(tree, tolerance);
-            PointsBuf pts;
-            if (query) {
-                pts.share(mesh_centroids_shared(query));
-            } else {
-                pts.alloc((size_t)n * 2);
-                h2d(pts.get(), points, sizeof(double) * 2 * (size_t)n);
-            }
-            DevBuf<int32_t> col((size_t)n), found((size_t)n);
-            XR_LAUNCH("locate_col", k_locate_col, dim3(div_up(n, 256)), dim3(256), 0, tree->rec_fxy.get(),
-                      tree->rec_len.get(), tree->record_off(), tree->m, tree->grid, tree->cell_start.get(), tree->rec_bb.get(),
-                      tree->rec_face.get(), tree->n_face, pts.get(), n, tol, col.get(), found.get());
-            exclusive_scan_i32(found.get(), csr->indptr.get(), n);
-            // (a point has at most one entry: the arrays hold n, and the fill is enqueued in front of the read-back of nnz)
-            csr->indices.alloc((size_t)n);
-            csr->data.alloc((size_t)n);
-            csr->nnz = read_scalar(csr->indptr.get() + n, [&] {
-                XR_LAUNCH("locate_fill", k_locate_fill, dim3(div_up(n, 256)), dim3(256), 0, col.get(), csr->indptr.get(), n,
-                          csr->indices.get(), csr->data.get());
-            });
-            stream_sync();
+            pts.alloc((size_t)n * 2);
+            h2d(pts.get(), points, sizeof(double) * 2 * (size_t)n);
         }
-    } catch (...) {
-        delete csr;
-        throw;
+        DevBuf<int32_t> col((size_t)n), found((size_t)n);
+        XR_LAUNCH("locate_col", k_locate_col, dim3(div_up(n, 256)), dim3(256), 0, tree->rec_fxy.get(),
+                  tree->rec_len.get(), tree->record_off(), tree->m, tree->grid, tree->cell_start.get(), tree->rec_bb.get(),
+                  tree->rec_face.get(), tree->n_face, pts.get(), n, tol, col.get(), found.get());
+        exclusive_scan_i32(found.get(), csr->indptr.get(), n);
+        // (a point has at most one entry: the arrays hold n, and the fill is enqueued in front of the read-back of nnz)
+        csr->indices.alloc((size_t)n);
+        csr->data.alloc((size_t)n);
+        csr->nnz = read_scalar(csr->indptr.get() + n, [&] {
+            XR_LAUNCH("locate_fill", k_locate_fill, dim3(div_up(n, 256)), dim3(256), 0, col.get(), csr->indptr.get(), n,
+                      csr->indices.get(), csr->data.get());
+        });
+        stream_sync();
     }
-    *out = csr;
+    *out = csr.release();
     XR_API_END
 }
 

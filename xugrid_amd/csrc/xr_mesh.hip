@@ -217,7 +217,7 @@ k_prepare_faces(const double *__restrict__ node_xy, const int32_t *__restrict__ 
             a0 = fmin(a0, lds[0][w]); a1 = fmax(a1, lds[1][w]); a2 = fmin(a2, lds[2][w]);
             a3 = fmax(a3, lds[3][w]); a4 += lds[4][w]; a5 = fmax(a5, lds[5][w]); a6 = fmax(a6, lds[6][w]); a7 += lds[7][w];
         }
-        if (tail.done == nullptr) { // (separate reduction kernel behind this one: XR_STATS_TAIL=0)
+        if (tail.done == nullptr) { // (separate reduction kernel behind this one)
             double *p = partials + (int64_t)blockIdx.x * 8;
             p[0] = a0; p[1] = a1; p[2] = a2; p[3] = a3; p[4] = a4; p[5] = a5; p[6] = a6; p[7] = a7;
         }
@@ -291,7 +291,7 @@ k_sample_stats(const double *__restrict__ node_xy, int64_t n_node, const int32_t
             a0 = fmin(a0, lds[0][w]); a1 = fmax(a1, lds[1][w]); a2 = fmin(a2, lds[2][w]);
             a3 = fmax(a3, lds[3][w]); a4 += lds[4][w]; a5 = fmax(a5, lds[5][w]); a6 = fmax(a6, lds[6][w]); a7 += lds[7][w];
         }
-        if (tail.done == nullptr) { // (separate reduction kernel behind this one: XR_STATS_TAIL=0)
+        if (tail.done == nullptr) { // (separate reduction kernel behind this one)
             double *p = partials + (int64_t)blockIdx.x * 8;
             p[0] = a0; p[1] = a1; p[2] = a2; p[3] = a3; p[4] = a4; p[5] = a5; p[6] = a6; p[7] = a7;
         }
@@ -447,7 +447,7 @@ void mesh_face_coords(xr_mesh *mesh) {
 static constexpr int64_t SAMPLE_MIN_FACES = 1 << 17; // smaller meshes: the full pass costs a launch either way
 static constexpr int SAMPLE_STRIDE = 8;              // every 8th block of 256 faces
 
-// pinned statistics page + (unless XR_STATS_TAIL=0) the hand-off words of the in-kernel reduction
+// pinned statistics page + the hand-off words of the in-kernel reduction
 static constexpr int64_t STATS_TAIL_MAX_BLOCKS = 1024;
 static StatsTail stats_tail_for(xr_mesh *mesh, double *partials, int64_t nb) {
     if (!mesh->stats_host) {
@@ -463,11 +463,10 @@ static StatsTail stats_tail_for(xr_mesh *mesh, double *partials, int64_t nb) {
     // for (16 instead of 12 + 10 + 20 us until the tree's statistics are there), but +15 us for the 3900 blocks of
     // prepare_faces, whose statistics are only read after the index build -- those keep the one-block kernel on the side
     // stream (measured, 1M x 1M step: never 0.507, always 0.520, default see DESIGN section 5).
-    constexpr int tail_mode = 2;
     mesh->stats_seq += 1.0;
     mesh->stats_polled = true; // (both forms end with the sequence word)
     // (the in-kernel form is for the engine's own main stream)
-    if (tail_mode == 0 || (tail_mode == 2 && nb > STATS_TAIL_MAX_BLOCKS) || stream_override() || current_lane() || engine().on_side)
+    if (nb > STATS_TAIL_MAX_BLOCKS || stream_override() || current_lane() || engine().on_side)
         return StatsTail{partials, nullptr, nullptr, nullptr, mesh->stats_seq};
     if (!mesh->stats_done.get()) {
         mesh->stats_done.alloc(16 * (1 + STATS_SHARDS));
@@ -494,15 +493,10 @@ void mesh_prepare(xr_mesh *mesh, bool want_fxy, bool stats_on_side, bool allow_s
         DevBuf<double> partials((size_t)nb * 8);
         dim3 grid((unsigned)nb), block(PREP_BLOCK);
         const StatsTail tail = stats_tail_for(mesh, partials.get(), nb);
-        if (m == 3)
-            XR_LAUNCH("sample_stats", k_sample_stats<3>, grid, block, 0, mesh->node_xy.get(), mesh->n_node, mesh->faces_raw.get(),
+        with_nodes_per_face(m, [&](auto mc) {
+            XR_LAUNCH("sample_stats", k_sample_stats<mc()>, grid, block, 0, mesh->node_xy.get(), mesh->n_node, mesh->faces_raw.get(),
                       F, m, SAMPLE_STRIDE, partials.get(), tail);
-        else if (m == 4)
-            XR_LAUNCH("sample_stats", k_sample_stats<4>, grid, block, 0, mesh->node_xy.get(), mesh->n_node, mesh->faces_raw.get(),
-                      F, m, SAMPLE_STRIDE, partials.get(), tail);
-        else
-            XR_LAUNCH("sample_stats", k_sample_stats<0>, grid, block, 0, mesh->node_xy.get(), mesh->n_node, mesh->faces_raw.get(),
-                      F, m, SAMPLE_STRIDE, partials.get(), tail);
+        });
         if (!tail.done) {
             std::unique_ptr<SideScope> side;
             if (stats_on_side) side.reset(new SideScope);
@@ -530,21 +524,14 @@ void mesh_prepare(xr_mesh *mesh, bool want_fxy, bool stats_on_side, bool allow_s
     DevBuf<double> partials((size_t)nb * 8);
     dim3 grid((unsigned)nb), block(PREP_BLOCK);
     const StatsTail tail = stats_tail_for(mesh, partials.get(), nb);
-#define XR_PREP(MC)                                                                                                    \
-    do {                                                                                                               \
-        if (want_fxy)                                                                                                  \
-            XR_LAUNCH("prepare_faces", (k_prepare_faces<MC, false>), grid, block, 0, mesh->node_xy.get(),              \
-                      mesh->faces_raw.get(), F, m, dense_fxy ? mesh->fxy.get() : (double *)nullptr, mesh->len.get(),  \
-                      mesh->bbox.get(), partials.get(), tail);                                                         \
-        else                                                                                                           \
-            XR_LAUNCH("prepare_stats", (k_prepare_faces<MC, true>), grid, block, 0, mesh->node_xy.get(),               \
-                      mesh->faces_raw.get(), F, m, (double *)nullptr, (uint8_t *)nullptr, (double *)nullptr,           \
-                      partials.get(), tail);                                                                           \
-    } while (0)
-    if (m == 3) XR_PREP(3);
-    else if (m == 4) XR_PREP(4);
-    else XR_PREP(0);
-#undef XR_PREP
+    with_nodes_per_face(m, [&](auto mc) {
+        if (want_fxy)
+            XR_LAUNCH("prepare_faces", (k_prepare_faces<mc(), false>), grid, block, 0, mesh->node_xy.get(), mesh->faces_raw.get(), F,
+                      m, dense_fxy ? mesh->fxy.get() : (double *)nullptr, mesh->len.get(), mesh->bbox.get(), partials.get(), tail);
+        else
+            XR_LAUNCH("prepare_stats", (k_prepare_faces<mc(), true>), grid, block, 0, mesh->node_xy.get(), mesh->faces_raw.get(), F,
+                      m, (double *)nullptr, (uint8_t *)nullptr, (double *)nullptr, partials.get(), tail);
+    });
     if (!tail.done) {
         // (a one-block kernel that ends with writes to pinned host memory: ~10 us, which only the host waits for)
         std::unique_ptr<SideScope> side;
@@ -564,15 +551,10 @@ const double *mesh_area(xr_mesh *mesh) {
     mesh->area.alloc((size_t)F);
     if (F > 0) {
         const dim3 grid(div_up(F, 256)), block(256);
-        if (mesh->m == 3)
-            XR_LAUNCH("face_area", k_face_area<3>, grid, block, 0, mesh->node_xy.get(), mesh->faces_raw.get(), F, mesh->m,
+        with_nodes_per_face(mesh->m, [&](auto mc) {
+            XR_LAUNCH("face_area", k_face_area<mc()>, grid, block, 0, mesh->node_xy.get(), mesh->faces_raw.get(), F, mesh->m,
                       mesh->area.get());
-        else if (mesh->m == 4)
-            XR_LAUNCH("face_area", k_face_area<4>, grid, block, 0, mesh->node_xy.get(), mesh->faces_raw.get(), F, mesh->m,
-                      mesh->area.get());
-        else
-            XR_LAUNCH("face_area", k_face_area<0>, grid, block, 0, mesh->node_xy.get(), mesh->faces_raw.get(), F, mesh->m,
-                      mesh->area.get());
+        });
     }
     mesh->area_valid = true;
     return mesh->area.get();
@@ -762,7 +744,8 @@ static void spatial_sort(xr_mesh *mesh, const GridParams &g, const MortonParams 
                          int32_t *bucket_start, int32_t *perm, double *o_fxy, uint8_t *o_len, double *o_bbox,
                          float *o_recbb) {
     const int64_t F = mesh->n_face;
-    // (polygon meshes are always prepared with their caller-order boxes and lengths, mesh_prepare)
+    // (polygon meshes are always prepared with their caller-order boxes and lengths, mesh_prepare; both null for triangles and
+    // quadrilaterals, whose kernels read the vertices instead)
     const double *boxes = mesh->has_attrs && mesh->m != 3 && mesh->m != 4 ? mesh->bbox.get() : nullptr;
     const uint8_t *lens = boxes ? mesh->len.get() : nullptr;
     // The histogram lives in the engine's zero-at-rest scratch: the count pass raises it, the scatter pass hands the slots
@@ -779,29 +762,19 @@ static void spatial_sort(xr_mesh *mesh, const GridParams &g, const MortonParams 
     if (F > 0) {
         const char *name = INDEX ? "index_count" : "order_count";
         const dim3 grid(div_up(F, 256)), block(256);
-        if (mesh->m == 3)
-            XR_LAUNCH(name, (k_spatial_count<INDEX, 3>), grid, block, 0, mesh->node_xy.get(), mesh->faces_raw.get(), F,
-                      mesh->m, g, mp, key.get(), count);
-        else if (mesh->m == 4)
-            XR_LAUNCH(name, (k_spatial_count<INDEX, 4>), grid, block, 0, mesh->node_xy.get(), mesh->faces_raw.get(), F,
-                      mesh->m, g, mp, key.get(), count);
-        else
-            XR_LAUNCH(name, (k_spatial_count<INDEX, 0>), grid, block, 0, mesh->node_xy.get(), mesh->faces_raw.get(), F,
+        with_nodes_per_face(mesh->m, [&](auto mc) {
+            XR_LAUNCH(name, (k_spatial_count<INDEX, mc()>), grid, block, 0, mesh->node_xy.get(), mesh->faces_raw.get(), F,
                       mesh->m, g, mp, key.get(), count, boxes);
+        });
     }
     exclusive_scan_i32(count, bucket_start, n_buckets);
     if (F > 0) {
         const char *name = INDEX ? "index_scatter" : "order_scatter";
         const dim3 grid(div_up(F, 256)), block(256);
-        if (mesh->m == 3)
-            XR_LAUNCH(name, (k_spatial_scatter<INDEX, 3>), grid, block, 0, key.get(), F, mesh->m, bucket_start, count,
-                      mesh->node_xy.get(), mesh->faces_raw.get(), perm, o_fxy, o_len, o_bbox, o_recbb, g.x0, g.y0);
-        else if (mesh->m == 4)
-            XR_LAUNCH(name, (k_spatial_scatter<INDEX, 4>), grid, block, 0, key.get(), F, mesh->m, bucket_start, count,
-                      mesh->node_xy.get(), mesh->faces_raw.get(), perm, o_fxy, o_len, o_bbox, o_recbb, g.x0, g.y0);
-        else
-            XR_LAUNCH(name, (k_spatial_scatter<INDEX, 0>), grid, block, 0, key.get(), F, mesh->m, bucket_start, count,
+        with_nodes_per_face(mesh->m, [&](auto mc) {
+            XR_LAUNCH(name, (k_spatial_scatter<INDEX, mc()>), grid, block, 0, key.get(), F, mesh->m, bucket_start, count,
                       mesh->node_xy.get(), mesh->faces_raw.get(), perm, o_fxy, o_len, o_bbox, o_recbb, g.x0, g.y0, boxes, lens);
+        });
     }
     if (cached) zero_scratch_done(0);
 }
@@ -1015,27 +988,22 @@ int xr_mesh_create_rectilinear(const double *x_vertices, int64_t nx, const doubl
     for (int64_t j = 0; j <= ny; j++)
         XR_REQUIRE(y_vertices[j] == y_vertices[j], XR_ERR_INVALID, "xr_mesh_create_rectilinear: NaN y vertex %lld", (long long)j);
     engine();
-    xr_mesh *mesh = new xr_mesh();
-    try {
-        mesh->n_node = n_node;
-        mesh->n_face = n_face;
-        mesh->m = 4;
-        mesh->node_xy.alloc((size_t)n_node * 2);
-        mesh->faces_raw.alloc((size_t)n_face * 4);
-        DevBuf<double> xv((size_t)nx + 1), yv((size_t)ny + 1);
-        h2d(xv.get(), x_vertices, sizeof(double) * (size_t)(nx + 1));
-        h2d(yv.get(), y_vertices, sizeof(double) * (size_t)(ny + 1));
-        XR_LAUNCH("rect_nodes", k_rect_nodes, dim3(div_up(n_node, 256)), dim3(256), 0, xv.get(), yv.get(), nx + 1, n_node,
-                  mesh->node_xy.get());
-        // (ugrid2d.py:1904-1909: the tests read the flattened vertex arrays; see _from_intervals_helper in ugrid2d.py)
-        XR_LAUNCH("rect_faces", k_rect_faces, dim3(div_up(n_face, 256)), dim3(256), 0, nx, n_face,
-                  x_vertices[1] < x_vertices[0], y_vertices[1] < y_vertices[0], mesh->faces_raw.get());
-        stream_sync();
-    } catch (...) {
-        delete mesh;
-        throw;
-    }
-    *out = mesh;
+    Building<xr_mesh> mesh;
+    mesh->n_node = n_node;
+    mesh->n_face = n_face;
+    mesh->m = 4;
+    mesh->node_xy.alloc((size_t)n_node * 2);
+    mesh->faces_raw.alloc((size_t)n_face * 4);
+    DevBuf<double> xv((size_t)nx + 1), yv((size_t)ny + 1);
+    h2d(xv.get(), x_vertices, sizeof(double) * (size_t)(nx + 1));
+    h2d(yv.get(), y_vertices, sizeof(double) * (size_t)(ny + 1));
+    XR_LAUNCH("rect_nodes", k_rect_nodes, dim3(div_up(n_node, 256)), dim3(256), 0, xv.get(), yv.get(), nx + 1, n_node,
+              mesh->node_xy.get());
+    // (ugrid2d.py:1904-1909: the tests read the flattened vertex arrays; see _from_intervals_helper in ugrid2d.py)
+    XR_LAUNCH("rect_faces", k_rect_faces, dim3(div_up(n_face, 256)), dim3(256), 0, nx, n_face,
+              x_vertices[1] < x_vertices[0], y_vertices[1] < y_vertices[0], mesh->faces_raw.get());
+    stream_sync();
+    *out = mesh.release();
     XR_API_END
 }
 
@@ -1061,83 +1029,78 @@ int xr_mesh_create(const double *node_xy, int64_t n_node, const void *faces, int
     // (Meshes of less than 1 MB take the device-side ingest: two plain copies and a kernel, no pinned staging buffers --
     // those are 2 x 64 MiB of pinned host memory, allocated on first use.)
     const bool device_ingest = cnt * (size_t)faces_itemsize + sizeof(double) * 2 * (size_t)n_node < ((size_t)1 << 20);
-    xr_mesh *mesh = new xr_mesh();
-    try {
-        mesh->n_node = n_node;
-        mesh->n_face = n_face;
-        mesh->m = (int)n_max_node;
-        mesh->node_xy.alloc((size_t)n_node * 2);
-        mesh->faces_raw.alloc(cnt);
-        if (device_ingest) {
-            h2d_big(mesh->node_xy.get(), node_xy, sizeof(double) * 2 * (size_t)n_node);
-        } else {
-            const char *xy_bytes = reinterpret_cast<const char *>(node_xy);
-            h2d_staged(mesh->node_xy.get(), sizeof(double) * 2 * (size_t)n_node, [=](char *dst, size_t off, size_t n) {
-                parallel_ranges(n, 64, [=](size_t b, size_t e) { memcpy(dst + b, xy_bytes + off + b, e - b); });
-            });
-        }
-        if (cnt > 0 && !device_ingest) {
-            std::atomic<int64_t> bad_short(INT64_MAX), bad_node(INT64_MAX);
-            const int m = (int)n_max_node;
-            auto narrow = [&](auto *raw) {
-                h2d_staged(mesh->faces_raw.get(), cnt * sizeof(int32_t), [&, raw](char *dst, size_t off, size_t n) {
-                    int32_t *out32 = reinterpret_cast<int32_t *>(dst);
-                    const size_t k0 = off / sizeof(int32_t), nk = n / sizeof(int32_t);
-                    parallel_ranges(nk, 16, [&, raw, out32, k0](size_t b, size_t e) {
-                        int64_t first_short = INT64_MAX, first_node = INT64_MAX;
-                        for (size_t i = b; i < e; i++) {
-                            const size_t k = k0 + i;
-                            const int64_t v = (int64_t)raw[k];
-                            if (v == fill_value || v == -1) {
-                                if ((int)(k % (size_t)m) < 3 && first_short == INT64_MAX) first_short = (int64_t)(k / (size_t)m);
-                                out32[i] = -1;
-                            } else {
-                                if ((v < 0 || v >= n_node) && first_node == INT64_MAX) first_node = (int64_t)(k / (size_t)m);
-                                out32[i] = (int32_t)v;
-                            }
-                        }
-                        int64_t cur = bad_short.load();
-                        while (first_short < cur && !bad_short.compare_exchange_weak(cur, first_short)) {}
-                        cur = bad_node.load();
-                        while (first_node < cur && !bad_node.compare_exchange_weak(cur, first_node)) {}
-                    });
-                });
-            };
-            if (faces_itemsize == 8) narrow(static_cast<const int64_t *>(faces));
-            else narrow(static_cast<const int32_t *>(faces));
-            if (bad_short.load() != INT64_MAX || bad_node.load() != INT64_MAX) stream_sync(); // (the handle is dropped below)
-            XR_REQUIRE(bad_short.load() == INT64_MAX, XR_ERR_INVALID, "xr_mesh_create: face %lld has fewer than 3 nodes",
-                       (long long)bad_short.load());
-            XR_REQUIRE(bad_node.load() == INT64_MAX, XR_ERR_INVALID,
-                       "xr_mesh_create: face %lld references a node outside [0,%lld)", (long long)bad_node.load(),
-                       (long long)n_node);
-        } else if (cnt > 0) {
-            DevBuf<char> raw(cnt * (size_t)faces_itemsize);
-            DevBuf<int64_t> err(2); // [0] first face with fewer than 3 nodes, [1] first face with a node id out of range
-            const int64_t none[2] = {INT64_MAX, INT64_MAX};
-            h2d(err.get(), none, sizeof(none));
-            h2d_big(raw.get(), faces, cnt * (size_t)faces_itemsize);
-            if (faces_itemsize == 8)
-                XR_LAUNCH("ingest_faces", k_ingest_faces<int64_t>, dim3(div_up((int64_t)cnt, 256)), dim3(256), 0,
-                          reinterpret_cast<const int64_t *>(raw.get()), (int64_t)cnt, (int)n_max_node, fill_value, n_node,
-                          mesh->faces_raw.get(), err.get());
-            else
-                XR_LAUNCH("ingest_faces", k_ingest_faces<int32_t>, dim3(div_up((int64_t)cnt, 256)), dim3(256), 0,
-                          reinterpret_cast<const int32_t *>(raw.get()), (int64_t)cnt, (int)n_max_node, fill_value, n_node,
-                          mesh->faces_raw.get(), err.get());
-            int64_t h_err[2];
-            d2h(h_err, err.get(), sizeof(h_err));
-            XR_REQUIRE(h_err[0] == INT64_MAX, XR_ERR_INVALID, "xr_mesh_create: face %lld has fewer than 3 nodes",
-                       (long long)h_err[0]);
-            XR_REQUIRE(h_err[1] == INT64_MAX, XR_ERR_INVALID,
-                       "xr_mesh_create: face %lld references a node outside [0,%lld)", (long long)h_err[1],
-                       (long long)n_node);
-        }
-    } catch (...) {
-        delete mesh;
-        throw;
+    Building<xr_mesh> mesh;
+    mesh->n_node = n_node;
+    mesh->n_face = n_face;
+    mesh->m = (int)n_max_node;
+    mesh->node_xy.alloc((size_t)n_node * 2);
+    mesh->faces_raw.alloc(cnt);
+    if (device_ingest) {
+        h2d_big(mesh->node_xy.get(), node_xy, sizeof(double) * 2 * (size_t)n_node);
+    } else {
+        const char *xy_bytes = reinterpret_cast<const char *>(node_xy);
+        h2d_staged(mesh->node_xy.get(), sizeof(double) * 2 * (size_t)n_node, [=](char *dst, size_t off, size_t n) {
+            parallel_ranges(n, 64, [=](size_t b, size_t e) { memcpy(dst + b, xy_bytes + off + b, e - b); });
+        });
     }
-    *out = mesh;
+    if (cnt > 0 && !device_ingest) {
+        std::atomic<int64_t> bad_short(INT64_MAX), bad_node(INT64_MAX);
+        const int m = (int)n_max_node;
+        auto narrow = [&](auto *raw) {
+            h2d_staged(mesh->faces_raw.get(), cnt * sizeof(int32_t), [&, raw](char *dst, size_t off, size_t n) {
+                int32_t *out32 = reinterpret_cast<int32_t *>(dst);
+                const size_t k0 = off / sizeof(int32_t), nk = n / sizeof(int32_t);
+                parallel_ranges(nk, 16, [&, raw, out32, k0](size_t b, size_t e) {
+                    int64_t first_short = INT64_MAX, first_node = INT64_MAX;
+                    for (size_t i = b; i < e; i++) {
+                        const size_t k = k0 + i;
+                        const int64_t v = (int64_t)raw[k];
+                        if (v == fill_value || v == -1) {
+                            if ((int)(k % (size_t)m) < 3 && first_short == INT64_MAX) first_short = (int64_t)(k / (size_t)m);
+                            out32[i] = -1;
+                        } else {
+                            if ((v < 0 || v >= n_node) && first_node == INT64_MAX) first_node = (int64_t)(k / (size_t)m);
+                            out32[i] = (int32_t)v;
+                        }
+                    }
+                    int64_t cur = bad_short.load();
+                    while (first_short < cur && !bad_short.compare_exchange_weak(cur, first_short)) {}
+                    cur = bad_node.load();
+                    while (first_node < cur && !bad_node.compare_exchange_weak(cur, first_node)) {}
+                });
+            });
+        };
+        if (faces_itemsize == 8) narrow(static_cast<const int64_t *>(faces));
+        else narrow(static_cast<const int32_t *>(faces));
+        if (bad_short.load() != INT64_MAX || bad_node.load() != INT64_MAX) stream_sync(); // (the handle is dropped below)
+        XR_REQUIRE(bad_short.load() == INT64_MAX, XR_ERR_INVALID, "xr_mesh_create: face %lld has fewer than 3 nodes",
+                   (long long)bad_short.load());
+        XR_REQUIRE(bad_node.load() == INT64_MAX, XR_ERR_INVALID,
+                   "xr_mesh_create: face %lld references a node outside [0,%lld)", (long long)bad_node.load(),
+                   (long long)n_node);
+    } else if (cnt > 0) {
+        DevBuf<char> raw(cnt * (size_t)faces_itemsize);
+        DevBuf<int64_t> err(2); // [0] first face with fewer than 3 nodes, [1] first face with a node id out of range
+        const int64_t none[2] = {INT64_MAX, INT64_MAX};
+        h2d(err.get(), none, sizeof(none));
+        h2d_big(raw.get(), faces, cnt * (size_t)faces_itemsize);
+        if (faces_itemsize == 8)
+            XR_LAUNCH("ingest_faces", k_ingest_faces<int64_t>, dim3(div_up((int64_t)cnt, 256)), dim3(256), 0,
+                      reinterpret_cast<const int64_t *>(raw.get()), (int64_t)cnt, (int)n_max_node, fill_value, n_node,
+                      mesh->faces_raw.get(), err.get());
+        else
+            XR_LAUNCH("ingest_faces", k_ingest_faces<int32_t>, dim3(div_up((int64_t)cnt, 256)), dim3(256), 0,
+                      reinterpret_cast<const int32_t *>(raw.get()), (int64_t)cnt, (int)n_max_node, fill_value, n_node,
+                      mesh->faces_raw.get(), err.get());
+        int64_t h_err[2];
+        d2h(h_err, err.get(), sizeof(h_err));
+        XR_REQUIRE(h_err[0] == INT64_MAX, XR_ERR_INVALID, "xr_mesh_create: face %lld has fewer than 3 nodes",
+                   (long long)h_err[0]);
+        XR_REQUIRE(h_err[1] == INT64_MAX, XR_ERR_INVALID,
+                   "xr_mesh_create: face %lld references a node outside [0,%lld)", (long long)h_err[1],
+                   (long long)n_node);
+    }
+    *out = mesh.release();
     XR_API_END
 }
 
@@ -1155,43 +1118,38 @@ int xr_mesh_create_dev(const double *node_xy_dev, int64_t n_node, const void *fa
     XR_REQUIRE((node_xy_dev && faces_dev) || n_face == 0, XR_ERR_INVALID, "xr_mesh_create_dev: NULL arrays");
     engine();
     const size_t cnt = (size_t)n_face * (size_t)n_max_node;
-    xr_mesh *mesh = new xr_mesh();
-    try {
-        mesh->n_node = n_node;
-        mesh->n_face = n_face;
-        mesh->m = (int)n_max_node;
-        mesh->node_xy.alloc((size_t)n_node * 2);
-        mesh->faces_raw.alloc(cnt);
-        if (n_node > 0)
-            XR_HIP(hipMemcpyAsync(mesh->node_xy.get(), node_xy_dev, sizeof(double) * 2 * (size_t)n_node, hipMemcpyDeviceToDevice,
-                                  launch_stream()));
-        if (cnt > 0) {
-            // [0] first face with fewer than 3 nodes, [1] first face with a node id out of range
-            DevBuf<int64_t> err(2);
-            XR_HIP(hipMemsetAsync(err.get(), 0xff, 2 * sizeof(int64_t), launch_stream())); // (all ones: "none" for the unsigned atomicMin)
-            if (faces_itemsize == 8)
-                XR_LAUNCH("ingest_faces", k_ingest_faces<int64_t>, dim3(div_up((int64_t)cnt, 256)), dim3(256), 0,
-                          reinterpret_cast<const int64_t *>(faces_dev), (int64_t)cnt, (int)n_max_node, fill_value, n_node,
-                          mesh->faces_raw.get(), err.get());
-            else
-                XR_LAUNCH("ingest_faces", k_ingest_faces<int32_t>, dim3(div_up((int64_t)cnt, 256)), dim3(256), 0,
-                          reinterpret_cast<const int32_t *>(faces_dev), (int64_t)cnt, (int)n_max_node, fill_value, n_node,
-                          mesh->faces_raw.get(), err.get());
-            uint64_t h_err[2];
-            d2h(h_err, err.get(), sizeof(h_err));
-            XR_REQUIRE(h_err[0] == UINT64_MAX, XR_ERR_INVALID, "xr_mesh_create_dev: face %lld has fewer than 3 nodes",
-                       (long long)h_err[0]);
-            XR_REQUIRE(h_err[1] == UINT64_MAX, XR_ERR_INVALID,
-                       "xr_mesh_create_dev: face %lld references a node outside [0,%lld)", (long long)h_err[1],
-                       (long long)n_node);
-        } else {
-            stream_sync();
-        }
-    } catch (...) {
-        delete mesh;
-        throw;
+    Building<xr_mesh> mesh;
+    mesh->n_node = n_node;
+    mesh->n_face = n_face;
+    mesh->m = (int)n_max_node;
+    mesh->node_xy.alloc((size_t)n_node * 2);
+    mesh->faces_raw.alloc(cnt);
+    if (n_node > 0)
+        XR_HIP(hipMemcpyAsync(mesh->node_xy.get(), node_xy_dev, sizeof(double) * 2 * (size_t)n_node, hipMemcpyDeviceToDevice,
+                              launch_stream()));
+    if (cnt > 0) {
+        // [0] first face with fewer than 3 nodes, [1] first face with a node id out of range
+        DevBuf<int64_t> err(2);
+        XR_HIP(hipMemsetAsync(err.get(), 0xff, 2 * sizeof(int64_t), launch_stream())); // (all ones: "none" for the unsigned atomicMin)
+        if (faces_itemsize == 8)
+            XR_LAUNCH("ingest_faces", k_ingest_faces<int64_t>, dim3(div_up((int64_t)cnt, 256)), dim3(256), 0,
+                      reinterpret_cast<const int64_t *>(faces_dev), (int64_t)cnt, (int)n_max_node, fill_value, n_node,
+                      mesh->faces_raw.get(), err.get());
+        else
+            XR_LAUNCH("ingest_faces", k_ingest_faces<int32_t>, dim3(div_up((int64_t)cnt, 256)), dim3(256), 0,
+                      reinterpret_cast<const int32_t *>(faces_dev), (int64_t)cnt, (int)n_max_node, fill_value, n_node,
+                      mesh->faces_raw.get(), err.get());
+        uint64_t h_err[2];
+        d2h(h_err, err.get(), sizeof(h_err));
+        XR_REQUIRE(h_err[0] == UINT64_MAX, XR_ERR_INVALID, "xr_mesh_create_dev: face %lld has fewer than 3 nodes",
+                   (long long)h_err[0]);
+        XR_REQUIRE(h_err[1] == UINT64_MAX, XR_ERR_INVALID,
+                   "xr_mesh_create_dev: face %lld references a node outside [0,%lld)", (long long)h_err[1],
+                   (long long)n_node);
+    } else {
+        stream_sync();
     }
-    *out = mesh;
+    *out = mesh.release();
     XR_API_END
 }
 

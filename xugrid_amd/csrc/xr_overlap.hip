@@ -49,7 +49,6 @@ __device__ __forceinline__ bool rec_hit(float4 b, float qx0, float qx1, float qy
 // kernel instead.
 static constexpr int SLOTS = 16;
 static constexpr int QCUR_STRIDE = 32; // words between the cursors of the regular queue's eight regions: a 128-byte line each
-static constexpr int QCUR_BASE = 32;   // first of them in the control words of overlap_tri
 static constexpr int TILE_RUN = 16; // rows per run in the tiling hint (128-byte output stores per variable).  Measured, K = 256 on
                                     // the benchmark matrix: runs of 64 rows / tiles of 24 extents 2.10 ms, 16 / 12: 1.72 ms (a qhull-numbered
                                     // target: long runs of consecutive ids are not compact); a lattice-numbered pair 0.99 ms either way
@@ -377,7 +376,6 @@ __device__ __forceinline__ int wave_excl_scan_i32(int v, int lane) {
 // regrew it.  (The two-walk version -- count, reserve, fill -- took twice as long per face, and a big face is a
 // chain of dependent phases: the kernel's duration is the slowest face's.)
 static constexpr int BIG_STAGE = 5120; // size of the stage (dynamic LDS; 3072 / 2048 / 1024 / 512 measured in round 5: no gain)
-static int big_stage_entries() { return BIG_STAGE; }
 static constexpr int BIG_RANK_MAX = 1 << 16; // big faces ranked by id (all-pairs, inside k_search_big); longer lists keep their order
 
 template <bool FUSED>
@@ -1194,6 +1192,8 @@ static constexpr int BM_BITS = BM_WORDS * 32;   // ids per chunk
 static constexpr int BM_SEG = BM_WORDS / 256;   // words per thread segment
 static constexpr int BM_STAGE = 4096;           // candidates parked in LDS (16 KiB); longer rows re-read HBM
 static constexpr size_t ROW_FILL_LIGHT_LDS = sizeof(int32_t) * (8 + BM_STAGE); // LDS of a k_row_fill_long launch with row_class = 1
+static constexpr size_t ROW_FILL_LONG_LDS =                                    // ... of any other: + segment bases, bitmap, group counts
+    ROW_FILL_LIGHT_LDS + sizeof(uint32_t) * (256 + BM_WORDS) + sizeof(uint16_t) * (BM_WORDS / 8);
 
 __global__ void __launch_bounds__(256)
 k_row_fill_long(const int32_t *__restrict__ cand_off, const int32_t *__restrict__ cand_count,
@@ -1374,12 +1374,10 @@ k_row_fill_long(const int32_t *__restrict__ cand_off, const int32_t *__restrict_
 namespace xr {
 
 static bool debug_fused() { return (option(OPT_DEBUG) & 1) != 0; }
-static int xcd_remap_mask() {
-    // bit 0 clip, bit 1 search, bit 2 row_fill: the XCD-aware block order for clip + search -- 15 % fewer HBM bytes fetched by
-    // both (PMC: clip 161 -> 130 MB, search 56 -> 48 MB per launch) at an unchanged clip time and a 5 % shorter search;
-    // row_fill loses more on the then interleaved queue than it gains.
-    return 3;
-}
+// Which kernels take the XCD-aware block order (xcd_block): clip + search fetch 15 % fewer HBM bytes with it (PMC: clip
+// 161 -> 130 MB, search 56 -> 48 MB per launch) at an unchanged clip time and a 5 % shorter search; row_fill loses more on
+// the then interleaved queue than it gains.
+static constexpr bool REMAP_CLIP = true, REMAP_SEARCH = true, REMAP_ROW_FILL = false;
 static unsigned xcd_grid(int64_t n_blocks, bool remap) { return (unsigned)(remap ? (n_blocks + 7) / 8 * 8 : n_blocks); }
 
 // Upper bound, for every pair of faces of the two meshes, of the area the clip can return for a pair the reference's pre-clip
@@ -1403,13 +1401,8 @@ template <int MAXV, int BLOCK>
 static void launch_clip(const xr_mesh *tree, const xr_mesh *query, const int32_t *cand_tgt, const int32_t *cand_src,
                         int64_t C, double *cand_area, bool redo_only, int32_t *cand_sid, int32_t *overflow_count,
                         int32_t *nnz_row) {
-    const size_t shmem = (size_t)2 * MAXV * BLOCK * sizeof(double2);
-    static bool attr_set = false;
-    if (!attr_set) {
-        XR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_clip<MAXV, BLOCK>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-        attr_set = true;
-    }
+    constexpr size_t shmem = (size_t)2 * MAXV * BLOCK * sizeof(double2);
+    allow_dynamic_lds<&k_clip<MAXV, BLOCK>>(shmem);
     XR_LAUNCH(MAXV == 8 ? "clip_v8" : (MAXV == 16 ? "clip_v16" : "clip_v64"), (k_clip<MAXV, BLOCK>),
               dim3(div_up(C, BLOCK)), dim3(BLOCK), shmem, query->qo_fxy(), query->qo_len(), query->qo_off(), query->m,
               query->qo_perm(), tree->rec_fxy.get(), tree->rec_len.get(), tree->record_off(), tree->m, cand_tgt, cand_src, C, cand_area,
@@ -1420,32 +1413,97 @@ static void launch_clip_for(const xr_mesh *tree, const xr_mesh *query, const int
                             int64_t C, double *cand_area, int32_t *cand_sid, int32_t *overflow_count,
                             int32_t *nnz_row) {
     const int vmax = query->m + tree->m;
-    const bool remap = xcd_remap_mask() & 1;
+    if (vmax > 16) return launch_clip<64, 64>(tree, query, cand_tgt, cand_src, C, cand_area, false, cand_sid, overflow_count, nnz_row);
+    if (vmax > 8) return launch_clip<16, 128>(tree, query, cand_tgt, cand_src, C, cand_area, false, cand_sid, overflow_count, nnz_row);
+    constexpr int BLOCK = 256;
+    const bool remap = REMAP_CLIP;
+    const dim3 grid(xcd_grid(div_up(C, BLOCK), remap));
     const double dust = overlap_dust_threshold(tree, query);
     if (vmax <= 6) {
         // triangle x triangle: the clipped polygon never has more than 6 vertices
-        constexpr int MAXV = 6, BLOCK = 256;
+        constexpr int MAXV = 6;
         const size_t shmem = (size_t)(MAXV + 1) * BLOCK * sizeof(double2); // + one trash row for clamped pushes
-        XR_LAUNCH("clip_tri", (k_clip_tri<BLOCK>), dim3(xcd_grid(div_up(C, BLOCK), remap)), dim3(BLOCK), shmem,
+        XR_LAUNCH("clip_tri", (k_clip_tri<BLOCK>), grid, dim3(BLOCK), shmem,
                       query->qo_fxy(), query->m, tree->rec_fxy.get(), tree->m, cand_tgt, cand_src, C, cand_area,
                       tree->rec_face.get(), cand_sid, overflow_count, nnz_row, remap, dust);
     } else if (query->m == 4 && tree->m == 3 && option(OPT_CLIP_QUAD) != 0) {
         // quadrilateral targets (a raster) x triangle source (option "clip_quad" = 0: the slot-loop kernel, test switch)
-        constexpr int BLOCK = 256;
         const size_t shmem = (size_t)(QUAD_MAXV + 2) * BLOCK * sizeof(double2);
-        XR_LAUNCH("clip_quad_tri", (k_clip_quad_tri<BLOCK>), dim3(xcd_grid(div_up(C, BLOCK), remap)), dim3(BLOCK), shmem,
+        XR_LAUNCH("clip_quad_tri", (k_clip_quad_tri<BLOCK>), grid, dim3(BLOCK), shmem,
                   query->qo_fxy(), query->qo_len(), tree->rec_fxy.get(), cand_tgt, cand_src, C, cand_area, tree->rec_face.get(),
                   cand_sid, overflow_count, nnz_row, remap, dust);
-    } else if (vmax <= 8) {
-        constexpr int MAXV = 8, BLOCK = 256;
+    } else {
+        constexpr int MAXV = 8;
         const size_t shmem = (size_t)(MAXV + 1) * BLOCK * sizeof(double2); // + one trash row for clamped pushes
-        XR_LAUNCH("clip_small", (k_clip_small<MAXV, BLOCK, false>), dim3(xcd_grid(div_up(C, BLOCK), remap)), dim3(BLOCK),
+        XR_LAUNCH("clip_small", (k_clip_small<MAXV, BLOCK, false>), grid, dim3(BLOCK),
                   shmem, query->qo_fxy(), query->qo_len(), query->qo_off(), query->m, query->qo_perm(), tree->rec_fxy.get(),
                   tree->rec_len.get(), tree->record_off(), tree->m, cand_tgt, cand_src, C, cand_area, tree->rec_face.get(), cand_sid,
                   overflow_count, nnz_row, remap, dust);
     }
-    else if (vmax <= 16) launch_clip<16, 128>(tree, query, cand_tgt, cand_src, C, cand_area, false, cand_sid, overflow_count, nnz_row);
-    else launch_clip<64, 64>(tree, query, cand_tgt, cand_src, C, cand_area, false, cand_sid, overflow_count, nnz_row);
+}
+
+// ---- launches both pipelines share --------------------------------------------------------------------------------------
+// what the search leaves per target face and per block of 256 of them
+struct SearchLists {
+    DevBuf<int32_t> cand_count, cand_off, big_list, pending, nnz_row;
+    DevBuf<uint8_t> is_big;
+    DevBuf<int2> block_seg;
+    explicit SearchLists(int64_t T)
+        : cand_count((size_t)T), cand_off((size_t)T + 1), big_list((size_t)T), pending((size_t)T), nnz_row((size_t)T),
+          is_big((size_t)T), block_seg((size_t)div_up(T, 256)) {}
+};
+// the pair queue a kernel appends to
+struct PairQueue {
+    int32_t *tgt, *src, *cursor;
+    int64_t capacity; // (of one region where the queue is the fused pipeline's eight regions with a cursor each)
+};
+
+// k_search over every target face.  PACKED: the owner byte rides in the record id's top byte where the tree has at most
+// 2^24 faces.  blk_rows / blk_surv: the fused pipeline's per-block counts; its queue is then eight regions.
+static void launch_search(const xr_mesh *tree, const xr_mesh *query, const SearchLists &l, const PairQueue &q, int32_t *n_big,
+                          const MortonParams &tile, int32_t *tile_key, int32_t *blk_rows = nullptr, int32_t *blk_surv = nullptr) {
+    const int64_t T = query->n_face;
+    const dim3 grid(xcd_grid(div_up(T, 256), REMAP_SEARCH));
+    auto launch = [&](auto packed) {
+        XR_LAUNCH("search", (k_search<decltype(packed)::value>), grid, dim3(256), 0, query->qo_bbox(), T, tree->grid, tree->n_face,
+                  tree->cell_start.get(), tree->rec_bb.get(), l.cand_count.get(), l.cand_off.get(), q.tgt, q.src, q.cursor,
+                  l.block_seg.get(), l.is_big.get(), l.big_list.get(), n_big, tile, tile_key, l.nnz_row.get(), REMAP_SEARCH,
+                  blk_rows, blk_surv, blk_rows ? (int)q.capacity : 0);
+    };
+    if (tree->n_face <= ((int64_t)1 << 24)) launch(std::true_type());
+    else launch(std::false_type());
+}
+
+// k_search_big<true>: the listed big faces, one block each, into `q`; faces that do not fit it are listed in l.pending
+static void launch_search_big(const xr_mesh *tree, const xr_mesh *query, const SearchLists &l, const PairQueue &q,
+                              const int32_t *n_big, int32_t *n_pending, int32_t *slot_face = nullptr) {
+    XR_LAUNCH("search_big", k_search_big<true>, dim3(engine().num_cu * 8), dim3(256), sizeof(int32_t) * (size_t)BIG_STAGE,
+              query->qo_bbox(), query->qo_fxy(), query->qo_len(), query->qo_off(), query->m, tree->grid, tree->cell_start.get(),
+              tree->rec_bb.get(), tree->rec_face.get(), l.big_list.get(), n_big, l.cand_off.get(), l.cand_count.get(), q.tgt,
+              q.src, q.cursor, q.capacity, l.pending.get(), n_pending, BIG_STAGE, slot_face);
+}
+
+// k_row_fill_long over one class of the listed rows: 0 every row; 1 the rows of at most ROW_BLOCK candidates (16 KB of LDS:
+// six blocks per CU, resident beside other kernels); 2 the longer ones (the bitmap: a CU per block).
+struct LongRows { // (the kernel's arguments of the same names)
+    const int32_t *cand_sid;
+    const double *cand_area;
+    const int32_t *indptr;
+    int32_t *indices;
+    double *data;
+    const int32_t *long_rows, *n_long;
+    int64_t row_base;
+    const int32_t *skip_if = nullptr, *scan_nnz = nullptr;
+    int32_t *scan_indptr = nullptr, *scan_total = nullptr;
+};
+static void launch_row_fill_long(int row_class, const xr_mesh *tree, const SearchLists &l, const double *tree_area, bool relative,
+                                 const LongRows &r) {
+    allow_dynamic_lds<&k_row_fill_long>(ROW_FILL_LONG_LDS);
+    const bool light = row_class == 1;
+    XR_LAUNCH(row_class == 2 ? "row_fill_huge" : "row_fill_long", k_row_fill_long, dim3(engine().num_cu * (light ? 6 : 1)), dim3(256),
+              light ? ROW_FILL_LIGHT_LDS : ROW_FILL_LONG_LDS, l.cand_off.get(), l.cand_count.get(), r.cand_sid, r.cand_area,
+              r.indptr, tree_area, relative, tree->n_face, r.indices, r.data, r.long_rows, r.n_long, r.row_base, r.skip_if,
+              r.scan_nnz, r.scan_indptr, r.scan_total, row_class);
 }
 
 // Triangle x triangle pairs (xr_overlap_fused.h): search -> persistent clip -> assembly with a look-back scan, the big
@@ -1463,10 +1521,9 @@ struct EarlyApply {
 static bool overlap_tri(xr_mesh *tree, xr_mesh *query, const double *tree_area, bool relative, xr_csr *csr,
                         const MortonParams &tile, EarlyApply *early) {
     const int64_t T = query->n_face;
-    const GridParams &g = tree->grid;
     hipStream_t st = launch_stream();
     const int64_t n_blocks = div_up(T, FB);
-    const bool remap = xcd_remap_mask() & 2;
+    const bool remap = REMAP_SEARCH;
     const unsigned grid = xcd_grid(n_blocks, remap);
     const int64_t margin_opt = option(OPT_QUEUE_MARGIN); // test hook: a tiny margin forces the regrow path
     int64_t big_capacity = margin_opt > 0 ? margin_opt : ((int64_t)4 << 20);
@@ -1476,13 +1533,9 @@ static bool overlap_tri(xr_mesh *tree, xr_mesh *query, const double *tree_area, 
     const int64_t reg_capacity = 8 * region_cap;
     int64_t per_face = 8; // CSR entries reserved per target face (+ the big queue); regrown if the matrix is denser
     int32_t *mail = const_cast<int32_t *>(engine().mailbox);
-    static_assert(sizeof(FusedCounters) == 32, "FusedCounters layout");
-    // ctl: [0] regular queue cursor, [1] big queue cursor, [2] big faces, [3] big faces that did not fit, [4] clip
-    // overflows among the big pairs | FusedCounters
-    // | per block of 256 target faces: survivors (clip), regular faces (search)
-    // The 16 counter words come from the engine's zero-at-rest scratch (k_publish_all clears them again after copying them
-    // to the mailbox) and k_search clears its block's survivor count: no memset in front of the search.
-    constexpr size_t CTL_HEAD = QCUR_BASE + 8 * QCUR_STRIDE; // (the eight region cursors of the regular queue behind the 16 counters: a line each)
+    // The control words (CtlWord, xr_overlap_fused.h) come from the engine's zero-at-rest scratch (k_publish_all clears them
+    // again after copying them to the mailbox); behind them, per block of 256 target faces: survivors (clip), regular faces
+    // (search) -- k_search clears its block's survivor count: no memset in front of the search.
     DevBuf<int32_t> ctl_tail(2 * (size_t)grid), ctl_own;
     int32_t *blk_surv = ctl_tail.get(), *blk_rows = blk_surv + grid;
     DevBuf<int32_t> blk_base(2 * (size_t)grid); // first stored row / CSR base of every hardware block (k_assemble_scan)
@@ -1492,10 +1545,8 @@ static bool overlap_tri(xr_mesh *tree, xr_mesh *query, const double *tree_area, 
     // assembly provides them (scan_mode 1, as until round 3).  (Until round 5 a decoupled look-back inside k_assemble was a third
     // form, behind a switch; it lost in round 3 and is gone.)
     const int scan_mode = grid <= 8192 ? 2 : 1;
-    DevBuf<int32_t> cand_count((size_t)T), cand_off((size_t)T + 1), big_list((size_t)T), pending((size_t)T), nnz_row((size_t)T),
-        slot_face((size_t)T), big_indptr((size_t)T + 1);
-    DevBuf<uint8_t> is_big((size_t)T);
-    DevBuf<int2> block_seg((size_t)n_blocks);
+    SearchLists l(T);
+    DevBuf<int32_t> slot_face((size_t)T), big_indptr((size_t)T + 1);
     // (measured and removed: the clip writing only its survivors, compacted in place over the queue -- the HBM bytes drop, but the
     // assembly becomes three passes of dependent loads, 0.066 -> 0.087 ms, DESIGN_HISTORY.md round 3)
     DevBuf<int32_t> cand_tgt((size_t)reg_capacity), cand_src((size_t)reg_capacity), cand_sid((size_t)reg_capacity);
@@ -1503,20 +1554,25 @@ static bool overlap_tri(xr_mesh *tree, xr_mesh *query, const double *tree_area, 
     csr->n_long.alloc(2); // [0] rows of more than XR_APPLY_LONG_ROW entries, [1] gate of an apply enqueued behind the build
     csr->row_order.alloc((size_t)T);
     csr->has_row_order = true;
-    const int big_grid = engine().num_cu * 8;
-    constexpr int CLIP_BLOCK = 256;
-    // triangle x triangle: the flag / compaction clip of xr_clip_tri.h; any other pair of dense meshes (<= 4 nodes per face:
-    // quadrilaterals, mixed meshes with fill values, a raster against triangles): the register / LDS clip of k_clip_small<8>
+    int32_t *const tile_key = csr->has_tile_key ? csr->tile_key.get() : nullptr;
+    // k_clip_tri_queue, persistent, over a pair queue.  KIND 0, triangle x triangle: the flag / compaction clip of xr_clip_tri.h;
+    // KIND 1, any other pair of dense meshes (<= 4 nodes per face: quadrilaterals, mixed meshes with fill values, a raster
+    // against triangles): the register / LDS clip of k_clip_small<8>, which also reads the faces' lengths.
+    // COUNT 2: the big faces' queue, survivors per face; COUNT 1: the regular queue's eight regions, survivors per block.
     const bool tri_pair = tree->m == 3 && query->m == 3;
-    const size_t clip_shmem = tri_pair ? (size_t)(TRI_MAXV + 1) * CLIP_BLOCK * sizeof(double2) : (size_t)(8 + 1) * CLIP_BLOCK * sizeof(double2);
     const double dust = overlap_dust_threshold(tree, query);
-    const size_t fill_shmem = sizeof(uint32_t) * (BM_WORDS + 256) + sizeof(int32_t) * (8 + BM_STAGE) + sizeof(uint16_t) * (BM_WORDS / 8);
-    static bool attr_set = false;
-    if (!attr_set) {
-        XR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_row_fill_long),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)fill_shmem));
-        attr_set = true;
-    }
+    auto launch_clip_queue = [&](const char *name, auto count, int blocks_per_cu, const PairQueue &q, double *area, int32_t *sid,
+                                 int32_t *error, int32_t *nnz_row, const int32_t *skip_if, int32_t *blk_surv) {
+        constexpr int BLOCK = 256;
+        const int64_t capacity = count() == 1 ? -q.capacity : q.capacity; // (< 0: eight regions of that many pairs)
+        auto launch = [&](auto kind, size_t maxv, const uint8_t *q_len, const uint8_t *s_len) {
+            XR_LAUNCH(name, (k_clip_tri_queue<BLOCK, count(), kind()>), dim3(engine().num_cu * blocks_per_cu), dim3(BLOCK),
+                      (maxv + 1) * BLOCK * sizeof(double2), query->qo_fxy(), tree->rec_fxy.get(), tree->rec_face.get(), q.tgt, q.src,
+                      q.cursor, capacity, area, sid, error, nnz_row, skip_if, blk_surv, dust, q_len, s_len, query->m, tree->m);
+        };
+        if (tri_pair) launch(std::integral_constant<int, 0>(), TRI_MAXV, nullptr, nullptr);
+        else launch(std::integral_constant<int, 1>(), 8, query->qo_len(), tree->rec_len.get());
+    };
     for (int attempt = 0;; attempt++) {
         XR_REQUIRE(attempt < 8, XR_ERR_LIMIT, "xr_overlap: the weight matrix does not fit the device buffers");
         const int64_t cap = per_face * T + big_capacity;
@@ -1527,98 +1583,68 @@ static bool overlap_tri(xr_mesh *tree, xr_mesh *query, const double *tree_area, 
         DevBuf<int32_t> big_tgt((size_t)big_capacity), big_src((size_t)big_capacity), big_sid((size_t)big_capacity),
             big_indices((size_t)big_capacity);
         DevBuf<double> big_area((size_t)big_capacity), big_data((size_t)big_capacity);
-        int32_t *ctl_head = zero_scratch(1, CTL_HEAD);
-        const bool ctl_cached = ctl_head != nullptr;
+        int32_t *ctl = zero_scratch(1, CTL_WORDS);
+        const bool ctl_cached = ctl != nullptr;
         if (!ctl_cached) {
-            ctl_own.alloc(CTL_HEAD);
-            ctl_head = ctl_own.get();
-            XR_HIP(hipMemsetAsync(ctl_head, 0, CTL_HEAD * sizeof(int32_t), st));
+            ctl_own.alloc(CTL_WORDS);
+            ctl = ctl_own.get();
+            XR_HIP(hipMemsetAsync(ctl, 0, CTL_WORDS * sizeof(int32_t), st));
         }
-        FusedCounters *fc = reinterpret_cast<FusedCounters *>(ctl_head + 8);
-#define XR_SEARCH_LAUNCH(PACKED)                                                                                                    \
-    XR_LAUNCH("search", (k_search<PACKED>), dim3(grid), dim3(256), 0, query->qo_bbox(), T, g, tree->n_face,                            \
-              tree->cell_start.get(), tree->rec_bb.get(), cand_count.get(), cand_off.get(), cand_tgt.get(), cand_src.get(),          \
-              ctl_head + QCUR_BASE, block_seg.get(), is_big.get(), big_list.get(), ctl_head + 2, tile, (int32_t *)nullptr, nnz_row.get(),   \
-              remap, blk_rows, blk_surv, (int)region_cap)
-        // (the owner byte rides in the record id's top byte where the tree has at most 2^24 faces)
-        if (tree->n_face <= ((int64_t)1 << 24)) XR_SEARCH_LAUNCH(true);
-        else XR_SEARCH_LAUNCH(false);
-#undef XR_SEARCH_LAUNCH
+        FusedCounters *fc = reinterpret_cast<FusedCounters *>(ctl + CTL_COUNTERS);
+        int32_t *const region_cursors = ctl + CTL_REGION_CURSOR, *const big_cursor = ctl + CTL_BIG_CURSOR,
+                       *const n_big_dev = ctl + CTL_N_BIG, *const n_pending_dev = ctl + CTL_N_PENDING;
+        const PairQueue reg_queue{cand_tgt.get(), cand_src.get(), region_cursors, region_cap},
+            big_queue{big_tgt.get(), big_src.get(), big_cursor, big_capacity};
+        launch_search(tree, query, l, reg_queue, n_big_dev, tile, nullptr, blk_rows, blk_surv);
         {
             // ---- side stream: everything about the big faces except their final placement
             SideScope side;
-            XR_LAUNCH("search_big", k_search_big<true>, dim3(big_grid), dim3(256), sizeof(int32_t) * (size_t)big_stage_entries(),
-                      query->qo_bbox(), query->qo_fxy(),
-                      query->qo_len(), query->qo_off(), query->m, g, tree->cell_start.get(), tree->rec_bb.get(), tree->rec_face.get(),
-                      big_list.get(), ctl_head + 2, cand_off.get(), cand_count.get(), big_tgt.get(), big_src.get(),
-                      ctl_head + 1, big_capacity, pending.get(), ctl_head + 3, big_stage_entries(), slot_face.get());
+            launch_search_big(tree, query, l, big_queue, n_big_dev, n_pending_dev, slot_face.get());
             // (pairs of a face that did not fit are missing: the error is seen at the end and everything is redone)
-            if (tri_pair)
-                XR_LAUNCH("clip_big", (k_clip_tri_queue<CLIP_BLOCK, 2>), dim3(engine().num_cu), dim3(CLIP_BLOCK), clip_shmem,
-                          query->qo_fxy(), tree->rec_fxy.get(), tree->rec_face.get(), big_tgt.get(), big_src.get(), ctl_head + 1,
-                          big_capacity, big_area.get(), big_sid.get(), &fc->error, nnz_row.get(), ctl_head + 3, (int32_t *)nullptr,
-                          dust);
-            else
-                XR_LAUNCH("clip_big", (k_clip_tri_queue<CLIP_BLOCK, 2, false, 1>), dim3(engine().num_cu), dim3(CLIP_BLOCK), clip_shmem,
-                          query->qo_fxy(), tree->rec_fxy.get(), tree->rec_face.get(), big_tgt.get(), big_src.get(), ctl_head + 1,
-                          big_capacity, big_area.get(), big_sid.get(), &fc->error, nnz_row.get(), ctl_head + 3, (int32_t *)nullptr,
-                          dust, query->qo_len(), tree->rec_len.get(), query->m, tree->m);
+            launch_clip_queue("clip_big", std::integral_constant<int, 2>(), 1, big_queue, big_area.get(), big_sid.get(),
+                              &fc->error, l.nnz_row.get(), n_pending_dev, nullptr);
             // (rows in face order: ranked inside search_big; their offsets: scanned inside row_fill_long -- two launches less
             // in what is the critical path of the whole weight build)
             // Two launches: the rows of at most ROW_BLOCK candidates (all but a handful) with 16 KB of LDS per block -- a block
             // per row, resident beside the clip and the assembly -- and the few longer ones with the bitmap (150 KB, a CU per
             // block).  As ONE launch every block needed a whole CU: it could not start before the clip's blocks had left and
-            // then walked ~5 rows in turn -- 54-64 us, ending after the assembly (round-4 timeline).  XR_ROWFILL_SPLIT=0: one launch.
+            // then walked ~5 rows in turn -- 54-64 us, ending after the assembly (round-4 timeline).
             // (round 6: the two launches are independent -- each scans the row lengths itself and fills only its own class of
             // rows -- so the bitmap rows go to a SECOND side stream and run beside the light ones: the big faces' chain
             // behind the clip is one launch shorter where it is the step's critical path, 0.506 -> 0.500 ms in an A/B)
+            const LongRows big_rows{big_sid.get(), big_area.get(), big_indptr.get(), big_indices.get(), big_data.get(), slot_face.get(),
+                                    n_big_dev, 0, n_pending_dev, l.nnz_row.get(), big_indptr.get(), &fc->p_big};
             SideForkScope fork;
-            XR_LAUNCH("row_fill_huge", k_row_fill_long, dim3(engine().num_cu), dim3(256), fill_shmem, cand_off.get(),
-                      cand_count.get(), big_sid.get(), big_area.get(), big_indptr.get(), tree_area, relative,
-                      tree->n_face, big_indices.get(), big_data.get(), slot_face.get(), ctl_head + 2, (int64_t)0, ctl_head + 3,
-                      nnz_row.get(), big_indptr.get(), &fc->p_big, 2);
+            launch_row_fill_long(2, tree, l, tree_area, relative, big_rows);
             fork.end_launches();
-            XR_LAUNCH("row_fill_long", k_row_fill_long, dim3(engine().num_cu * 6), dim3(256), ROW_FILL_LIGHT_LDS, cand_off.get(),
-                      cand_count.get(), big_sid.get(), big_area.get(), big_indptr.get(), tree_area, relative,
-                      tree->n_face, big_indices.get(), big_data.get(), slot_face.get(), ctl_head + 2, (int64_t)0, ctl_head + 3,
-                      nnz_row.get(), big_indptr.get(), &fc->p_big, 1);
+            launch_row_fill_long(1, tree, l, tree_area, relative, big_rows);
         }
         // Persistent blocks per CU: five fill the LDS and the register files (best for the clip alone).  The big faces' chain
         // on the side stream then gets few wave slots while the clip runs; with its kernels at raised wave priority and only
         // three launches long (search_big -> clip -> row_fill_long) it still ends about when k_assemble does: 3, 4 and 5
         // blocks per CU all give the same step (0.635 ms) -- measured after the chain lost two launches; before, 3 was
         // 4 % faster because the chain was the critical path.
-        // (slot-major LDS columns -- k_clip_tri_queue's SOA form -- were measured in round 3 and lost; the template parameter is all
-        // that is left of them)
-        if (!tri_pair)
-            // (k_clip_small's LDS columns: 36 KB per block, four persistent blocks per CU)
-            XR_LAUNCH("clip_small", (k_clip_tri_queue<CLIP_BLOCK, 1, false, 1>), dim3(engine().num_cu * 4), dim3(CLIP_BLOCK), clip_shmem,
-                      query->qo_fxy(), tree->rec_fxy.get(), tree->rec_face.get(), cand_tgt.get(), cand_src.get(),
-                      ctl_head + QCUR_BASE, -region_cap, cand_area.get(), cand_sid.get(), &fc->error, (int32_t *)nullptr,
-                      (const int32_t *)nullptr, blk_surv, dust, query->qo_len(), tree->rec_len.get(), query->m, tree->m);
-        else
-            XR_LAUNCH("clip_tri", (k_clip_tri_queue<CLIP_BLOCK, 1, false>), dim3(engine().num_cu * 5), dim3(CLIP_BLOCK), clip_shmem,
-                      query->qo_fxy(), tree->rec_fxy.get(), tree->rec_face.get(), cand_tgt.get(), cand_src.get(),
-                      ctl_head + QCUR_BASE, -region_cap, cand_area.get(), cand_sid.get(), &fc->error, (int32_t *)nullptr,
-                      (const int32_t *)nullptr, blk_surv, dust);
+        // (KIND 1: k_clip_small's LDS columns are 36 KB per block, four persistent blocks per CU)
+        launch_clip_queue(tri_pair ? "clip_tri" : "clip_small", std::integral_constant<int, 1>(), tri_pair ? 5 : 4, reg_queue,
+                          cand_area.get(), cand_sid.get(), &fc->error, nullptr, nullptr, blk_surv);
         if (scan_mode == 1)
             XR_LAUNCH("assemble_scan", k_assemble_scan, dim3(1), dim3(1024), 0, blk_rows, blk_surv, (int64_t)n_blocks, (int)grid,
                       remap, blk_base.get(), blk_base.get() + grid, fc, csr->indptr.get());
         XR_LAUNCH("assemble", k_assemble, dim3(grid), dim3(FB), 0, query->qo_bbox(), query->qo_perm(), T, cand_tgt.get(),
-                  cand_off.get(), cand_count.get(), block_seg.get(), is_big.get(), cand_area.get(), cand_sid.get(),
-                  tree_area, relative, tile, csr->has_tile_key ? csr->tile_key.get() : (int32_t *)nullptr, fc,
+                  l.cand_off.get(), l.cand_count.get(), l.block_seg.get(), l.is_big.get(), cand_area.get(), cand_sid.get(),
+                  tree_area, relative, tile, tile_key, fc,
                   csr->indptr.get(), csr->indices.get(), csr->data.get(), csr->row_order.get(),
                   csr->long_rows.get(), cap, remap, scan_mode == 1 ? blk_base.get() : (const int32_t *)nullptr,
                   scan_mode == 1 ? blk_base.get() + grid : (const int32_t *)nullptr,
                   scan_mode == 2 ? blk_rows : (const int32_t *)nullptr, scan_mode == 2 ? blk_surv : (const int32_t *)nullptr);
         side_join();
-        XR_LAUNCH("place_big", k_place_big, dim3(64), dim3(256), 0, ctl_head + 2, slot_face.get(), big_indptr.get(),
+        XR_LAUNCH("place_big", k_place_big, dim3(64), dim3(256), 0, n_big_dev, slot_face.get(), big_indptr.get(),
                   big_indices.get(), big_data.get(), T, query->qo_perm(), query->qo_bbox(), tile,
-                  csr->has_tile_key ? csr->tile_key.get() : (int32_t *)nullptr, fc, csr->indptr.get(), csr->indices.get(),
-                  csr->data.get(), csr->row_order.get(), csr->long_rows.get(), cap, ctl_head + 3);
+                  tile_key, fc, csr->indptr.get(), csr->indices.get(),
+                  csr->data.get(), csr->row_order.get(), csr->long_rows.get(), cap, n_pending_dev);
         host_stamp(5);
         const int32_t seq = mailbox_next_seq();
-        XR_LAUNCH("publish", k_publish_all, dim3(1), dim3(64), 0, ctl_head, fc, csr->n_long.get(), mail, seq, cap, big_capacity);
+        XR_LAUNCH("publish", k_publish_all, dim3(1), dim3(64), 0, ctl, fc, csr->n_long.get(), mail, seq, cap, big_capacity);
         if (ctl_cached) zero_scratch_done(1); // (the counters are zero again behind k_publish_all)
         if (early) {
             // sizes unknown on the host yet: pessimistic flags (long rows possible, of any length) -- they only add blocks
@@ -1633,15 +1659,20 @@ static bool overlap_tri(xr_mesh *tree, xr_mesh *query, const double *tree_area, 
         host_stamp(6);
         mailbox_wait_seq(seq);
         host_stamp(7);
-        const int32_t C_reg = mail[0], C_big = mail[1], n_big = mail[2], n_pending = mail[3], big_overflow = mail[4];
-        const int32_t err = mail[5], rows_regular = mail[6], p_regular = mail[8], p_big = mail[9];
+        const int32_t C_reg = mail[MAIL_REG_PAIRS], C_big = mail[MAIL_BIG_PAIRS], n_big = mail[MAIL_N_BIG], n_pending = mail[MAIL_N_PENDING];
+        const int32_t err = mail[MAIL_ERROR], rows_regular = mail[MAIL_ROWS_REGULAR], n_apply_long = mail[MAIL_N_APPLY_LONG],
+                      p_regular = mail[MAIL_P_REGULAR], p_big = mail[MAIL_P_BIG];
         XR_REQUIRE(C_reg >= 0 && C_big >= 0, XR_ERR_LIMIT, "candidate pair count exceeds the int32 range");
-        if (debug_fused())
+        if (debug_fused()) {
+            const int32_t *len = mail + MAIL_REGION_LEN;
             fprintf(stderr, "[tri] T=%lld C=%d big: %d faces %d pairs (%d pending) p_regular=%d p_big=%d err=%d rows=%d long=%d regions %d %d %d %d %d %d %d %d of %lld\n",
-                    (long long)T, C_reg, n_big, C_big, n_pending, p_regular, p_big, err, rows_regular, mail[7], mail[11], mail[12], mail[13],
-                    mail[14], mail[15], mail[16], mail[17], mail[18], (long long)region_cap);
-        (void)big_overflow;
-        if (err & 1) return false;
+                    (long long)T, C_reg, n_big, C_big, n_pending, p_regular, p_big, err, rows_regular, n_apply_long, len[0], len[1], len[2],
+                    len[3], len[4], len[5], len[6], len[7], (long long)region_cap);
+        }
+        if (err & 1) {
+            csr->has_row_order = false; // (the general pipeline stores the rows in query order)
+            return false;
+        }
         if (n_pending > 0 || C_big > big_capacity) { // some big faces needed more room than the margin
             big_capacity = (int64_t)C_big + 1024;
             continue;
@@ -1653,10 +1684,133 @@ static bool overlap_tri(xr_mesh *tree, xr_mesh *query, const double *tree_area, 
         XR_REQUIRE(rows_regular == T - n_big, XR_ERR_INVALID, "xr_overlap: internal row count mismatch");
         tree->last_candidates = (int64_t)C_reg + C_big;
         csr->nnz = (int64_t)p_regular + p_big;
-        csr->has_long = mail[7] > 0;   // rows of more than XR_APPLY_LONG_ROW entries (none: the apply skips their kernels)
-        csr->max_row_len = mail[7] > 0 ? mail[10] : XR_APPLY_LONG_ROW;
+        csr->has_long = n_apply_long > 0; // rows of more than XR_APPLY_LONG_ROW entries (none: the apply skips their kernels)
+        csr->max_row_len = n_apply_long > 0 ? mail[MAIL_MAX_ROW] : XR_APPLY_LONG_ROW;
         if (early) early->done = true; // (the apply enqueued in THIS attempt saw the final matrix)
         return true;
+    }
+}
+
+// Rows kept in the caller's (coherent, but typically strip-like) numbering get a coarse Morton key each: tiles of 12-24 mean
+// target extents, runs of TILE_RUN consecutive rows kept together.  A Morton-sorted query order is tiled already.
+// -> the key's parameters; csr->tile_key allocated, csr->has_tile_key / tile_key_range set
+static MortonParams tile_key_params(const xr_mesh *query, xr_csr *csr) {
+    MortonParams tile{};
+    csr->has_tile_key = false;
+    if (!query->query_identity) return tile;
+    const int64_t T = query->n_face;
+    const double *hs = query->h_stats;
+    double span = std::max(hs[1] - hs[0], hs[3] - hs[2]);
+    if (!(span > 0)) span = 1.0;
+    // tile edge <= 12 mean extents (the side count is a power of two): about one block of 256 triangles per tile
+    double h = 12.0 * hs[4] / (double)T;
+    if (!(h > 0)) h = span;
+    int bits = 0;
+    while (bits < 12 && ldexp(h, bits) < span) bits++;
+    tile = MortonParams{hs[0], hs[2], (double)(1 << bits) / (span * (1.0 + 1e-9)), 1 << bits};
+    tile.n_run = TILE_RUN;
+    csr->tile_key.alloc((size_t)T);
+    csr->tile_key_range = (int64_t)1 << (2 * bits);
+    csr->has_tile_key = bits > 0;
+    return tile;
+}
+
+// The general kernel chain (the head of this file), all on the engine stream: two host round trips, rows in query order.
+static void overlap_general(xr_mesh *tree, xr_mesh *query, const double *tree_area, bool relative, xr_csr *csr,
+                            const MortonParams &tile) {
+    const int64_t T = query->n_face;
+    hipStream_t st = launch_stream();
+    DevBuf<int32_t> counters(GEN_WORDS); // (GenWord, xr_overlap_fused.h)
+    auto word = [&](GenWord w) { return counters.get() + w; };
+    XR_HIP(hipMemsetAsync(counters.get(), 0, sizeof(int32_t) * GEN_WORDS, st));
+    // --- candidate search.  k_search appends the candidates of its 256 faces to the pair queue itself (one
+    // atomic reservation per block); the few "big" faces are counted, reserve their stretch, and are filled by
+    // the block-per-face kernels.  The queue is sized for the regular faces (at most SLOTS candidates each) plus
+    // a margin for the big ones; if the big faces need more, it is regrown before they are filled (rare).
+    SearchLists l(T);
+    const int64_t margin_opt = option(OPT_QUEUE_MARGIN); // test hook: a tiny margin forces the regrow path
+    int64_t capacity = T * SLOTS + (margin_opt > 0 ? margin_opt : ((int64_t)4 << 20));
+    XR_REQUIRE(capacity < ((int64_t)1 << 31), XR_ERR_LIMIT, "candidate pair queue exceeds the int32 range");
+    DevBuf<int32_t> cand_tgt((size_t)capacity), cand_src((size_t)capacity);
+    const PairQueue queue{cand_tgt.get(), cand_src.get(), word(GEN_QUEUE_CURSOR), capacity};
+    launch_search(tree, query, l, queue, word(GEN_N_BIG), tile, csr->has_tile_key ? csr->tile_key.get() : nullptr);
+    launch_search_big(tree, query, l, queue, word(GEN_N_BIG), word(GEN_N_PENDING));
+    // queue length and number of big faces still to be filled -> host
+    int32_t *mail = const_cast<int32_t *>(engine().mailbox);
+    XR_LAUNCH("publish", k_publish, dim3(1), dim3(64), 0, word(GEN_QUEUE_CURSOR), mail + GMAIL_PAIRS, word(GEN_N_PENDING),
+              mail + GMAIL_N_PENDING);
+    mailbox_wait();
+    const int32_t C32 = mail[GMAIL_PAIRS], n_pending = mail[GMAIL_N_PENDING];
+    XR_REQUIRE(C32 >= 0, XR_ERR_LIMIT, "candidate pair count exceeds the int32 range");
+    const int64_t C = C32;
+    tree->last_candidates = C;
+    if (n_pending > 0) {
+        // some big faces need more room than the margin: move what is there to a larger queue, then fill them
+        DevBuf<int32_t> bigger_tgt((size_t)C), bigger_src((size_t)C);
+        XR_HIP(hipMemcpyAsync(bigger_tgt.get(), cand_tgt.get(), sizeof(int32_t) * (size_t)capacity, hipMemcpyDeviceToDevice, st));
+        XR_HIP(hipMemcpyAsync(bigger_src.get(), cand_src.get(), sizeof(int32_t) * (size_t)capacity, hipMemcpyDeviceToDevice, st));
+        stream_sync();
+        cand_tgt = std::move(bigger_tgt);
+        cand_src = std::move(bigger_src);
+        capacity = C;
+        h2d(word(GEN_N_PENDING), &n_pending, sizeof(int32_t)); // (k_publish zeroed the device copy)
+        XR_LAUNCH("search_big_fill", k_search_big<false>, dim3(engine().num_cu * 8), dim3(256), sizeof(int32_t), query->qo_bbox(),
+                  query->qo_fxy(), query->qo_len(), query->qo_off(), query->m, tree->grid, tree->cell_start.get(), tree->rec_bb.get(),
+                  tree->rec_face.get(), l.pending.get(), word(GEN_N_PENDING), l.cand_off.get(), l.cand_count.get(), cand_tgt.get(),
+                  cand_src.get(), (int32_t *)nullptr, capacity, (int32_t *)nullptr, (int32_t *)nullptr, 0);
+        XR_HIP(hipMemsetAsync(word(GEN_N_PENDING), 0, sizeof(int32_t), st));
+    }
+    // (the word of GEN_N_PENDING is zero again: from here on it is GEN_N_LONG_ROWS)
+    DevBuf<int32_t> cand_sid((size_t)C);
+    DevBuf<double> cand_area((size_t)C);
+    if (C > 0) {
+        // --- clip (+ per-row survivor counts)
+        launch_clip_for(tree, query, cand_tgt.get(), cand_src.get(), C, cand_area.get(), cand_sid.get(), word(GEN_CLIP_OVERFLOW),
+                        l.nnz_row.get());
+    }
+    // --- rows
+    // P is needed on the host anyway; the overflow counter travels in the same mailbox round trip
+    exclusive_scan_i32(l.nnz_row.get(), csr->indptr.get(), T, mail + GMAIL_NNZ, word(GEN_CLIP_OVERFLOW), mail + GMAIL_CLIP_OVERFLOW);
+    mailbox_wait();
+    int32_t nnz = mail[GMAIL_NNZ];
+    if (mail[GMAIL_CLIP_OVERFLOW] > 0) {
+        // polygon buffer overflow in the small-MAXV kernel (floating-point degenerate pairs):
+        // redo those pairs with the oracle's buffer size, then recount every row.
+        XR_HIP(hipMemsetAsync(word(GEN_CLIP_OVERFLOW), 0, sizeof(int32_t), st));
+        XR_HIP(hipMemsetAsync(l.nnz_row.get(), 0, sizeof(int32_t) * (size_t)T, st));
+        launch_clip<64, 64>(tree, query, cand_tgt.get(), cand_src.get(), C, cand_area.get(), true, cand_sid.get(),
+                            word(GEN_CLIP_OVERFLOW), l.nnz_row.get());
+        XR_LAUNCH("row_recount", k_row_count, dim3(div_up(T, 256)), dim3(256), 0, l.cand_off.get(), l.cand_count.get(),
+                  cand_area.get(), T, query->qo_perm(), l.nnz_row.get());
+        exclusive_scan_i32(l.nnz_row.get(), csr->indptr.get(), T);
+        nnz = read_scalar(csr->indptr.get() + T);
+    }
+    XR_REQUIRE(nnz >= 0, XR_ERR_LIMIT, "nnz exceeds the int32 range");
+    const int64_t P = nnz;
+    csr->nnz = P;
+    csr->indices.alloc((size_t)P);
+    csr->data.alloc((size_t)P);
+    // rows are best processed in the query mesh's spatial order (apply kernels)
+    if (query->qo_perm()) {
+        csr->row_order.alloc((size_t)T);
+        XR_HIP(hipMemcpyAsync(csr->row_order.get(), query->qo_perm(), sizeof(int32_t) * (size_t)T,
+                              hipMemcpyDeviceToDevice, st));
+        csr->has_row_order = true;
+    }
+    if (P > 0) {
+        DevBuf<int32_t> long_rows((size_t)T);
+        csr->long_rows.alloc((size_t)(P / XR_APPLY_LONG_ROW + 1));
+        csr->n_long.alloc(1);
+        csr->has_long = true;
+        XR_HIP(hipMemsetAsync(csr->n_long.get(), 0, sizeof(int32_t), st));
+        const bool remap = REMAP_ROW_FILL;
+        XR_LAUNCH("row_fill", k_row_fill, dim3(xcd_grid(div_up(T, 256), remap)), dim3(256), 0, l.cand_off.get(), l.cand_count.get(),
+                  l.block_seg.get(), l.is_big.get(), cand_tgt.get(), cand_sid.get(), cand_area.get(), T, csr->indptr.get(), tree_area, relative,
+                  csr->indices.get(), csr->data.get(), long_rows.get(), word(GEN_N_LONG_ROWS), csr->long_rows.get(),
+                  csr->n_long.get(), remap);
+        launch_row_fill_long(0, tree, l, tree_area, relative,
+                             LongRows{cand_sid.get(), cand_area.get(), csr->indptr.get(), csr->indices.get(), csr->data.get(),
+                                      long_rows.get(), word(GEN_N_LONG_ROWS), -1});
     }
 }
 
@@ -1688,152 +1842,13 @@ static void overlap(xr_mesh *tree, xr_mesh *query, bool relative, xr_csr *csr, E
         csr->data.alloc(0);
         return;
     }
-    const GridParams &g = tree->grid;
-    hipStream_t st = launch_stream();
-    // Rows kept in the caller's (coherent, but typically strip-like) numbering get a coarse Morton key each:
-    // tiles of 12-24 mean target extents, runs of TILE_RUN consecutive rows kept together.  A Morton-sorted query order is tiled already.
-    MortonParams tile{};
-    csr->has_tile_key = false;
-    if (query->query_identity) {
-        const double *hs = query->h_stats;
-        double span = std::max(hs[1] - hs[0], hs[3] - hs[2]);
-        if (!(span > 0)) span = 1.0;
-        // tile edge <= 12 mean extents (the side count is a power of two): about one block of 256 triangles per tile
-        double h = 12.0 * hs[4] / (double)T;
-        if (!(h > 0)) h = span;
-        int bits = 0;
-        while (bits < 12 && ldexp(h, bits) < span) bits++;
-        tile = MortonParams{hs[0], hs[2], (double)(1 << bits) / (span * (1.0 + 1e-9)), 1 << bits};
-        tile.n_run = TILE_RUN;
-        csr->tile_key.alloc((size_t)T);
-        csr->tile_key_range = (int64_t)1 << (2 * bits);
-        csr->has_tile_key = bits > 0;
-    }
-    {
-        // triangle x triangle: the single-round-trip pipeline of xr_overlap_fused.h (option "overlap_fused" = 0: test /
-        // measurement switch back to the general kernel chain)
-        const bool fused_on = option(OPT_OVERLAP_FUSED) != 0;
-        if (fused_on && tree->m <= DENSE_MAX_NODES && query->m <= DENSE_MAX_NODES && (T + 8 * FB) * SLOTS < ((int64_t)1 << 31)) {
-            if (overlap_tri(tree, query, tree_area, relative, csr, tile, early)) return;
-            csr->has_row_order = false; // (the general pipeline below stores the rows in query order)
-        }
-    }
-    // counters: [0] clip overflow, [1] number of long rows, [2] number of big query faces, [3] pair-queue cursor
-    DevBuf<int32_t> counters(4);
-    XR_HIP(hipMemsetAsync(counters.get(), 0, sizeof(int32_t) * 4, st));
-    // --- candidate search.  k_search appends the candidates of its 256 faces to the pair queue itself (one
-    // atomic reservation per block); the few "big" faces are counted, reserve their stretch, and are filled by
-    // the block-per-face kernels.  The queue is sized for the regular faces (at most SLOTS candidates each) plus
-    // a margin for the big ones; if the big faces need more, it is regrown before they are filled (rare).
-    DevBuf<int32_t> cand_count((size_t)T), cand_off((size_t)T + 1), big_list((size_t)T);
-    DevBuf<uint8_t> is_big((size_t)T);
-    const int big_grid = engine().num_cu * 8;
-    const int64_t n_blocks = div_up(T, 256);
-    DevBuf<int2> block_seg((size_t)n_blocks);
-    const int64_t margin_opt = option(OPT_QUEUE_MARGIN); // test hook: a tiny margin forces the regrow path
-    int64_t capacity = T * SLOTS + (margin_opt > 0 ? margin_opt : ((int64_t)4 << 20));
-    XR_REQUIRE(capacity < ((int64_t)1 << 31), XR_ERR_LIMIT, "candidate pair queue exceeds the int32 range");
-    DevBuf<int32_t> cand_tgt((size_t)capacity), cand_src((size_t)capacity), nnz_row((size_t)T);
-    const bool remap_search = xcd_remap_mask() & 2, remap_rows = xcd_remap_mask() & 4;
-    if (tree->n_face <= ((int64_t)1 << 24))
-        XR_LAUNCH("search", (k_search<true>), dim3(xcd_grid(div_up(T, 256), remap_search)), dim3(256), 0, query->qo_bbox(), T, g,
-                  tree->n_face, tree->cell_start.get(), tree->rec_bb.get(), cand_count.get(), cand_off.get(), cand_tgt.get(),
-                  cand_src.get(), counters.get() + 3, block_seg.get(), is_big.get(), big_list.get(), counters.get() + 2, tile,
-                  csr->has_tile_key ? csr->tile_key.get() : (int32_t *)nullptr, nnz_row.get(), remap_search);
-    else
-        XR_LAUNCH("search", (k_search<false>), dim3(xcd_grid(div_up(T, 256), remap_search)), dim3(256), 0, query->qo_bbox(), T, g,
-                  tree->n_face, tree->cell_start.get(), tree->rec_bb.get(), cand_count.get(), cand_off.get(), cand_tgt.get(),
-                  cand_src.get(), counters.get() + 3, block_seg.get(), is_big.get(), big_list.get(), counters.get() + 2, tile,
-                  csr->has_tile_key ? csr->tile_key.get() : (int32_t *)nullptr, nnz_row.get(), remap_search);
-    DevBuf<int32_t> pending((size_t)T);
-    XR_LAUNCH("search_big", k_search_big<true>, dim3(big_grid), dim3(256), sizeof(int32_t) * (size_t)big_stage_entries(),
-              query->qo_bbox(), query->qo_fxy(),
-              query->qo_len(), query->qo_off(), query->m, g, tree->cell_start.get(), tree->rec_bb.get(), tree->rec_face.get(),
-              big_list.get(), counters.get() + 2, cand_off.get(), cand_count.get(), cand_tgt.get(), cand_src.get(),
-              counters.get() + 3, capacity, pending.get(), counters.get() + 1, big_stage_entries());
-    // queue length and number of big faces still to be filled -> host
-    int32_t *mail = const_cast<int32_t *>(engine().mailbox);
-    XR_LAUNCH("publish", k_publish, dim3(1), dim3(64), 0, counters.get() + 3, mail + 0, counters.get() + 1, mail + 3);
-    mailbox_wait();
-    const int32_t C32 = mail[0], n_pending = mail[3];
-    XR_REQUIRE(C32 >= 0, XR_ERR_LIMIT, "candidate pair count exceeds the int32 range");
-    const int64_t C = C32;
-    tree->last_candidates = C;
-    if (n_pending > 0) {
-        // some big faces need more room than the margin: move what is there to a larger queue, then fill them
-        DevBuf<int32_t> bigger_tgt((size_t)C), bigger_src((size_t)C);
-        XR_HIP(hipMemcpyAsync(bigger_tgt.get(), cand_tgt.get(), sizeof(int32_t) * (size_t)capacity, hipMemcpyDeviceToDevice, st));
-        XR_HIP(hipMemcpyAsync(bigger_src.get(), cand_src.get(), sizeof(int32_t) * (size_t)capacity, hipMemcpyDeviceToDevice, st));
-        stream_sync();
-        cand_tgt = std::move(bigger_tgt);
-        cand_src = std::move(bigger_src);
-        capacity = C;
-        h2d(counters.get() + 1, &n_pending, sizeof(int32_t)); // (k_publish zeroed the device copy)
-        XR_LAUNCH("search_big_fill", k_search_big<false>, dim3(big_grid), dim3(256), sizeof(int32_t), query->qo_bbox(), query->qo_fxy(),
-                  query->qo_len(), query->qo_off(), query->m, g, tree->cell_start.get(), tree->rec_bb.get(), tree->rec_face.get(),
-                  pending.get(), counters.get() + 1, cand_off.get(), cand_count.get(), cand_tgt.get(), cand_src.get(),
-                  (int32_t *)nullptr, capacity, (int32_t *)nullptr, (int32_t *)nullptr, 0);
-        XR_HIP(hipMemsetAsync(counters.get() + 1, 0, sizeof(int32_t), st));
-    }
-    // (counters[1], zeroed again by k_publish, is reused below as the number of long rows)
-    DevBuf<int32_t> cand_sid((size_t)C);
-    DevBuf<double> cand_area((size_t)C);
-    if (C > 0) {
-        // --- clip (+ per-row survivor counts)
-        launch_clip_for(tree, query, cand_tgt.get(), cand_src.get(), C, cand_area.get(), cand_sid.get(), counters.get(),
-                        nnz_row.get());
-    }
-    // --- rows
-    // P is needed on the host anyway; the overflow counter travels in the same mailbox round trip
-    exclusive_scan_i32(nnz_row.get(), csr->indptr.get(), T, mail + 1, counters.get(), mail + 2);
-    mailbox_wait();
-    int32_t tail[4] = {mail[2], 0, 0, mail[1]};
-    if (tail[0] > 0) {
-        // polygon buffer overflow in the small-MAXV kernel (floating-point degenerate pairs):
-        // redo those pairs with the oracle's buffer size, then recount every row.
-        XR_HIP(hipMemsetAsync(counters.get(), 0, sizeof(int32_t), st));
-        XR_HIP(hipMemsetAsync(nnz_row.get(), 0, sizeof(int32_t) * (size_t)T, st));
-        launch_clip<64, 64>(tree, query, cand_tgt.get(), cand_src.get(), C, cand_area.get(), true, cand_sid.get(),
-                            counters.get(), nnz_row.get());
-        XR_LAUNCH("row_recount", k_row_count, dim3(div_up(T, 256)), dim3(256), 0, cand_off.get(), cand_count.get(),
-                  cand_area.get(), T,
-                  query->qo_perm(), nnz_row.get());
-        exclusive_scan_i32(nnz_row.get(), csr->indptr.get(), T);
-        tail[3] = read_scalar(csr->indptr.get() + T);
-    }
-    XR_REQUIRE(tail[3] >= 0, XR_ERR_LIMIT, "nnz exceeds the int32 range");
-    const int64_t P = tail[3];
-    csr->nnz = P;
-    csr->indices.alloc((size_t)P);
-    csr->data.alloc((size_t)P);
-    // rows are best processed in the query mesh's spatial order (apply kernels)
-    if (query->qo_perm()) {
-        csr->row_order.alloc((size_t)T);
-        XR_HIP(hipMemcpyAsync(csr->row_order.get(), query->qo_perm(), sizeof(int32_t) * (size_t)T,
-                              hipMemcpyDeviceToDevice, st));
-        csr->has_row_order = true;
-    }
-    if (P > 0) {
-        DevBuf<int32_t> long_rows((size_t)T);
-        csr->long_rows.alloc((size_t)(P / XR_APPLY_LONG_ROW + 1));
-        csr->n_long.alloc(1);
-        csr->has_long = true;
-        XR_HIP(hipMemsetAsync(csr->n_long.get(), 0, sizeof(int32_t), st));
-        XR_LAUNCH("row_fill", k_row_fill, dim3(xcd_grid(div_up(T, 256), remap_rows)), dim3(256), 0, cand_off.get(), cand_count.get(),
-                  block_seg.get(), is_big.get(), cand_tgt.get(), cand_sid.get(), cand_area.get(), T, csr->indptr.get(), tree_area, relative,
-                  csr->indices.get(), csr->data.get(), long_rows.get(), counters.get() + 1, csr->long_rows.get(),
-                  csr->n_long.get(), remap_rows);
-        const size_t shmem = sizeof(uint32_t) * (BM_WORDS + 256) + sizeof(int32_t) * (8 + BM_STAGE) + sizeof(uint16_t) * (BM_WORDS / 8);
-        static bool attr_set = false;
-        if (!attr_set) {
-            XR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_row_fill_long),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-            attr_set = true;
-        }
-        XR_LAUNCH("row_fill_long", k_row_fill_long, dim3(engine().num_cu), dim3(256), shmem, cand_off.get(),
-                  cand_count.get(), cand_sid.get(), cand_area.get(), csr->indptr.get(), tree_area, relative, tree->n_face,
-                  csr->indices.get(), csr->data.get(), long_rows.get(), counters.get() + 1, (int64_t)-1, (const int32_t *)nullptr);
-    }
+    const MortonParams tile = tile_key_params(query, csr);
+    // dense meshes of at most 4 nodes per face: the single-round-trip pipeline of xr_overlap_fused.h (option "overlap_fused"
+    // = 0: test / measurement switch back to the general kernel chain)
+    const bool fused = option(OPT_OVERLAP_FUSED) != 0 && tree->m <= DENSE_MAX_NODES && query->m <= DENSE_MAX_NODES &&
+                       (T + 8 * FB) * SLOTS < ((int64_t)1 << 31);
+    if (fused && overlap_tri(tree, query, tree_area, relative, csr, tile, early)) return;
+    overlap_general(tree, query, tree_area, relative, csr, tile);
 }
 
 } // namespace xr
@@ -1845,15 +1860,10 @@ extern "C" {
 int xr_overlap(xr_mesh *tree, xr_mesh *query, int relative, xr_csr **out) {
     XR_API_BEGIN
     XR_REQUIRE(tree && query && out, XR_ERR_INVALID, "xr_overlap: NULL argument");
-    xr_csr *csr = new xr_csr();
-    try {
-        overlap(tree, query, relative != 0, csr);
-        stream_sync();
-    } catch (...) {
-        delete csr;
-        throw;
-    }
-    *out = csr;
+    Building<xr_csr> csr;
+    overlap(tree, query, relative != 0, csr.get());
+    stream_sync();
+    *out = csr.release();
     XR_API_END
 }
 
@@ -1865,23 +1875,17 @@ int xr_overlap_apply_dev(xr_mesh *tree, xr_mesh *query, int relative, int method
                "xr_overlap_apply_dev: NULL data argument");
     XR_REQUIRE(source_dtype == XR_F64 || source_dtype == XR_F32, XR_ERR_INVALID, "unsupported source dtype id %d", source_dtype);
     host_stamp(0);
-    xr_csr *csr = new xr_csr();
-    try {
-        EarlyApply early;
-        early.fn = [&](const xr_csr *c) { csr_apply_dev(c, method, percentile, source_dev, source_dtype, K, out_dev); };
-        // one variable and a streaming reducer: the apply is one launch that needs no size on the host
-        const bool can_early = K == 1 && method != XR_MODE && method != XR_PERCENTILE;
-        overlap(tree, query, relative != 0, csr, can_early ? &early : nullptr);
-        host_stamp(8);
-        if (!early.done && K > 0) csr_apply_dev(csr, method, percentile, source_dev, source_dtype, K, out_dev);
-        dev_call_done(); // (xr_set_async(1): returns with the apply in flight)
-        host_stamp(9);
-    } catch (...) {
-        stream_sync();
-        delete csr;
-        throw;
-    }
-    *out = csr;
+    Building<xr_csr> csr(OnFailure::WaitFirst);
+    EarlyApply early;
+    early.fn = [&](const xr_csr *c) { csr_apply_dev(c, method, percentile, source_dev, source_dtype, K, out_dev); };
+    // one variable and a streaming reducer: the apply is one launch that needs no size on the host
+    const bool can_early = K == 1 && method != XR_MODE && method != XR_PERCENTILE;
+    overlap(tree, query, relative != 0, csr.get(), can_early ? &early : nullptr);
+    host_stamp(8);
+    if (!early.done && K > 0) csr_apply_dev(csr.get(), method, percentile, source_dev, source_dtype, K, out_dev);
+    dev_call_done(); // (xr_set_async(1): returns with the apply in flight)
+    host_stamp(9);
+    *out = csr.release();
     XR_API_END
 }
 
@@ -1895,20 +1899,14 @@ int xr_overlap_partial_dev(xr_mesh *tree, xr_mesh *query, int relative, int meth
     XR_REQUIRE(xr_partial_components(method) > 0, XR_ERR_INVALID, "xr_overlap_partial_dev: method %d has no partial state", method);
     XR_REQUIRE(source_dtype == XR_F32 || source_dtype == XR_F64, XR_ERR_INVALID, "xr_overlap_partial_dev: source_dtype must be XR_F32 or XR_F64");
     XR_REQUIRE(K < 65536, XR_ERR_LIMIT, "xr_overlap_partial_dev: at most 65535 variables per call");
-    xr_csr *csr = new xr_csr();
-    try {
-        EarlyApply early;
-        early.fn = [&](const xr_csr *c) { csr_partial_dev(c, method, source_dev, source_dtype, K, out_dev, rows_layout); };
-        const bool can_early = K == 1; // (one variable: the wave-window kernel needs no size on the host)
-        overlap(tree, query, relative != 0, csr, can_early ? &early : nullptr);
-        if (!early.done && K > 0) csr_partial_dev(csr, method, source_dev, source_dtype, K, out_dev, rows_layout);
-        dev_call_done();
-    } catch (...) {
-        stream_sync();
-        delete csr;
-        throw;
-    }
-    *out = csr;
+    Building<xr_csr> csr(OnFailure::WaitFirst);
+    EarlyApply early;
+    early.fn = [&](const xr_csr *c) { csr_partial_dev(c, method, source_dev, source_dtype, K, out_dev, rows_layout); };
+    const bool can_early = K == 1; // (one variable: the wave-window kernel needs no size on the host)
+    overlap(tree, query, relative != 0, csr.get(), can_early ? &early : nullptr);
+    if (!early.done && K > 0) csr_partial_dev(csr.get(), method, source_dev, source_dtype, K, out_dev, rows_layout);
+    dev_call_done();
+    *out = csr.release();
     XR_API_END
 }
 

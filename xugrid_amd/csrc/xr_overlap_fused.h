@@ -43,9 +43,54 @@ struct FusedCounters {                    // device words, zeroed before the lau
     int32_t max_row;                      // entries of the longest row (atomicMax)
     int32_t pad2;
 };
-static_assert(offsetof(FusedCounters, error) == 4 && offsetof(FusedCounters, p_regular) == 8 && offsetof(FusedCounters, rows_regular) == 12 &&
-                  offsetof(FusedCounters, p_big) == 16 && offsetof(FusedCounters, max_row) == 24,
-              "k_publish_all addresses the fields by word");
+
+// ---- the words device and host share: ONE description, used by the kernels' launches, k_publish_all and overlap_tri ----
+// Control block of a fused build: CTL_WORDS device words, zero at rest (the engine's zero-at-rest scratch; k_publish_all
+// clears what the build raised), indexed by CtlWord.
+enum CtlWord : int {
+    CTL_REG_CURSOR = 0,     // pairs of the regular queue; the eight region cursors below count them, k_publish_all puts their sum here
+    CTL_BIG_CURSOR = 1,     // pairs in the big faces' queue (k_search_big)
+    CTL_N_BIG = 2,          // big faces (k_search)
+    CTL_N_PENDING = 3,      // big faces whose pairs did not fit their queue: > 0 makes the side-stream kernels skip, the host regrows
+    CTL_BIG_OVERFLOW = 4,   // clip overflows among the big pairs (reserved: they are reported through FusedCounters::error)
+    CTL_COUNTERS = 8,       // FusedCounters
+    CTL_LINE = 16,          // words [0, CTL_LINE) are one 64-byte stretch that k_publish_all fetches with one load per lane
+    CTL_REGION_CURSOR = 32, // cursors of the regular queue's eight regions (one per XCD), QCUR_STRIDE words = a 128-byte line apart
+    CTL_WORDS = CTL_REGION_CURSOR + 8 * QCUR_STRIDE
+};
+#define XR_CTL_COUNTER(field) (xr::CTL_COUNTERS + (int)(offsetof(xr::FusedCounters, field) / sizeof(int32_t))) // control word of a FusedCounters field
+static_assert(CTL_COUNTERS + sizeof(FusedCounters) / sizeof(int32_t) <= CTL_LINE && CTL_BIG_OVERFLOW < CTL_COUNTERS &&
+                  CTL_LINE <= CTL_REGION_CURSOR && CTL_LINE + 8 <= 64,
+              "the counters lie inside the line k_publish_all's one wave fetches, the region cursors behind it");
+// Mailbox record k_publish_all leaves for the host (pinned memory, engine().mailbox), indexed by MailSlot.
+enum MailSlot : int {
+    MAIL_REG_PAIRS = 0,      // = CTL_REG_CURSOR ... the first five control words as they are
+    MAIL_BIG_PAIRS = 1,
+    MAIL_N_BIG = 2,
+    MAIL_N_PENDING = 3,
+    MAIL_BIG_OVERFLOW = 4,   // (reserved, like its control word)
+    MAIL_ERROR = 5,          // the FusedCounters fields in the order the host reads them
+    MAIL_ROWS_REGULAR = 6,
+    MAIL_N_APPLY_LONG = 7,
+    MAIL_P_REGULAR = 8,
+    MAIL_P_BIG = 9,
+    MAIL_MAX_ROW = 10,
+    MAIL_REGION_LEN = 11,    // [8] the regions' own lengths (read by the `debug` option's line only)
+    MAIL_FUSED_SLOTS = MAIL_REGION_LEN + 8
+};
+static_assert(MAIL_BIG_OVERFLOW - MAIL_REG_PAIRS == CTL_BIG_OVERFLOW - CTL_REG_CURSOR && MAIL_FUSED_SLOTS <= MAIL_SEQ_SLOT,
+              "the first control words map to the first mailbox slots one to one");
+
+// The general chain (overlap_general) keeps four device words and uses four mailbox slots of its own.
+enum GenWord : int {
+    GEN_CLIP_OVERFLOW = 0, // pairs whose clipped polygon did not fit the small buffer (redone with the oracle's size)
+    GEN_N_PENDING = 1,     // big faces that did not fit the queue; k_publish hands it to the host and zeroes it ...
+    GEN_N_LONG_ROWS = 1,   // ... so that the same word then counts the rows k_row_fill leaves to k_row_fill_long
+    GEN_N_BIG = 2,         // big faces (k_search)
+    GEN_QUEUE_CURSOR = 3,  // pairs in the queue
+    GEN_WORDS = 4
+};
+enum GenMailSlot : int { GMAIL_PAIRS = 0, GMAIL_NNZ = 1, GMAIL_CLIP_OVERFLOW = 2, GMAIL_N_PENDING = 3 };
 
 // block-wide exclusive scan of one int per thread (FB threads); returns the exclusive value, total in *total
 __device__ __forceinline__ int block_excl_scan(int v, int *sh_wave /*[FWAVES]*/, int *total) {
@@ -74,16 +119,14 @@ __device__ __forceinline__ int block_excl_scan(int v, int *sh_wave /*[FWAVES]*/,
 // k_search wrote it in: the vertex blocks are in that XCD's L2).
 // COUNT: which survivor counts the kernel keeps (two instantiations: both paths in one kernel cost registers -> scratch)
 //   0 none, 1 per block of FB target faces (regular queue: blk_surv), 2 per target face (big faces' queue: nnz_row)
-//   SOA: the LDS columns slot-major (slot s of lane l at s * BLOCK + l: every 16-byte access of a wave -- static or
-//   dynamic slot -- falls on the banks of its lane alone) instead of lane-major (7 consecutive slots per lane: the dynamic-index
-//   reads of a stage conflict, 18 % of the LDS cycles, round-3 PMC)
+//   (the LDS columns are lane-major, 7 consecutive slots per lane; slot-major columns were measured in round 3 and lost)
 // KIND 1 (round 5): dense meshes of up to 4 nodes per face on either side (quadrilaterals, mixed triangle / quadrilateral
 // meshes with fill values -- the usual D-Flow FM mesh, a raster paired with a triangle mesh): the register / LDS clip of
 // k_clip_small<8> (the oracle's arithmetic in the oracle's order) inside the same persistent loop, so that these pairs take
 // the one-round-trip pipeline too.  q_len / s_len / q_m / s_m are only read then.
 // (waves per SIMD: the persistent grid is sized for five resident blocks per CU -- four for KIND 1 -- and a single register beyond
 // 96 would leave only four: the block that does not fit runs BEHIND the others, +40 % on the kernel -- measured when one crept in)
-template <int BLOCK, int COUNT, bool SOA = false, int KIND = 0>
+template <int BLOCK, int COUNT, int KIND = 0>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(KIND == 0 ? 5 : 4)))
 k_clip_tri_queue(const double *__restrict__ q_fxy, const double *__restrict__ rec_fxy,
                  const int32_t *__restrict__ rec_face, const int32_t *cand_tgt,
@@ -95,9 +138,9 @@ k_clip_tri_queue(const double *__restrict__ q_fxy, const double *__restrict__ re
                  double dust = 0.0 /* areas up to this are confirmed by the reference's pre-clip tests (xr_overlap.hip: confirm_dust) */,
                  const uint8_t *__restrict__ q_len = nullptr, const uint8_t *__restrict__ s_len = nullptr, int q_m = 3, int s_m = 3) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int CS = SOA ? BLOCK : 1;
+    constexpr int CS = 1; // (stride between a lane's slots)
     constexpr int SMALL_MAXV = 8;
-    double2 *col = reinterpret_cast<double2 *>(smem) + (KIND == 1 || SOA ? threadIdx.x : threadIdx.x * (TRI_MAXV + 1)); // the lane's slots
+    double2 *col = reinterpret_cast<double2 *>(smem) + (KIND == 1 ? threadIdx.x : threadIdx.x * (TRI_MAXV + 1)); // the lane's slots
     __shared__ uint2 sh_lut[KIND == 1 ? 1 : TRI_LUT];
     if (skip_if) __builtin_amdgcn_s_setprio(3); // (the big faces' queue, on the side stream: issue priority over the main clip)
     if (skip_if && *skip_if > 0) return; // (big faces that did not fit their queue: the host redoes everything)
@@ -492,45 +535,45 @@ k_place_big(const int32_t *__restrict__ n_big_dev, const int32_t *__restrict__ s
 // sizes, error bits and the long-row count -> host mailbox / device word of the matrix (after everything else)
 // ... and clears all of them behind itself: the counter words are the engine's zero-at-rest scratch (the next xr_overlap
 // starts without a memset).  One wave.
-__global__ void k_publish_all(int32_t *c /* search counters, FusedCounters right behind them (c + 8) */, FusedCounters *fc,
-                              int32_t *__restrict__ n_apply_long_out, int32_t *mail, int32_t seq, int64_t cap,
+__global__ void k_publish_all(int32_t *c /* the control block (CtlWord) */, FusedCounters *fc,
+                              int32_t *__restrict__ n_apply_long_out, int32_t *mail /* MailSlot */, int32_t seq, int64_t cap,
                               int64_t big_capacity) {
-    // one load per lane (the 16 words are one line), so the host's wait is one round trip long
+    // one load per lane (the CTL_LINE words are one line), so the host's wait is one round trip long
     const int t = threadIdx.x;
     int32_t w = 0;
-    if (t < 16) w = c[t];
-    // (the cursors of the eight regions of the regular pair queue, a line each: their sum is the number of regular pairs, which
-    // takes the place of the single cursor of word 0)
-    const int32_t cur = (t >= 16 && t < 24) ? c[QCUR_BASE + (t - 16) * QCUR_STRIDE] : 0;
+    if (t < CTL_LINE) w = c[t];
+    // (the cursors of the eight regions of the regular pair queue, a line each, read by the eight lanes behind: their sum is the
+    // number of regular pairs, which takes the place of the single cursor CTL_REG_CURSOR)
+    const bool region_lane = t >= CTL_LINE && t < CTL_LINE + 8;
+    const int32_t cur = region_lane ? c[CTL_REGION_CURSOR + (t - CTL_LINE) * QCUR_STRIDE] : 0;
     int32_t c_reg_sum = cur;
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) c_reg_sum += __shfl_xor(c_reg_sum, d, 64);
-    if (t == 0) w = c_reg_sum;
-    // mailbox slot of word t: [0..4] regular pairs, big pairs, big faces, not fitting, (unused); then the FusedCounters
-    // fields in the order the host reads them: error, rows_regular, n_apply_long, p_regular, p_big, max_row
-    int slot = -1;
-    if (t < 5) slot = t;
-    else if (t == 8 + 1) slot = 5;
-    else if (t == 8 + 3) slot = 6;
-    else if (t == 8 + 0) slot = 7;
-    else if (t == 8 + 2) slot = 8;
-    else if (t == 8 + 4) slot = 9;
-    else if (t == 8 + 6) slot = 10;
+    if (t == CTL_REG_CURSOR) w = c_reg_sum;
+    int slot = -1; // mailbox slot of control word t
+    if (t <= CTL_BIG_OVERFLOW) slot = MAIL_REG_PAIRS + t;
+    else if (t == XR_CTL_COUNTER(error)) slot = MAIL_ERROR;
+    else if (t == XR_CTL_COUNTER(rows_regular)) slot = MAIL_ROWS_REGULAR;
+    else if (t == XR_CTL_COUNTER(n_apply_long)) slot = MAIL_N_APPLY_LONG;
+    else if (t == XR_CTL_COUNTER(p_regular)) slot = MAIL_P_REGULAR;
+    else if (t == XR_CTL_COUNTER(p_big)) slot = MAIL_P_BIG;
+    else if (t == XR_CTL_COUNTER(max_row)) slot = MAIL_MAX_ROW;
     if (slot >= 0) mail[slot] = w;
-    if (t >= 16 && t < 24) mail[11 + (t - 16)] = cur; // (the regions' own lengths: XR_DEBUG_FUSED)
-    if (t == 8) *n_apply_long_out = w;
+    if (region_lane) mail[MAIL_REGION_LEN + (t - CTL_LINE)] = cur;
+    if (t == XR_CTL_COUNTER(n_apply_long)) *n_apply_long_out = w;
     if (t == 0) {
         // gate of an apply enqueued right behind this kernel (xr_overlap_apply_dev): open only if THIS attempt produced the
         // final matrix -- the very conditions the host checks after its read-back (overlap_tri); a failed attempt leaves
         // row pointers no kernel may follow
-        const int32_t c_reg = c_reg_sum, c_big = c[1], n_pending = c[3], err = c[8 + 1], p_reg = c[8 + 2], p_big = c[8 + 4];
+        const int32_t c_reg = c_reg_sum, c_big = c[CTL_BIG_CURSOR], n_pending = c[CTL_N_PENDING], err = c[XR_CTL_COUNTER(error)],
+                      p_reg = c[XR_CTL_COUNTER(p_regular)], p_big = c[XR_CTL_COUNTER(p_big)];
         const bool ok = c_reg >= 0 && c_big >= 0 && !(err & (1 | 4 | 8)) && n_pending == 0 && (int64_t)c_big <= big_capacity &&
                         (int64_t)p_reg + p_big <= cap;
         n_apply_long_out[1] = ok ? 1 : 0;
     }
     __builtin_amdgcn_s_waitcnt(0); // (every load above has returned before the words are cleared)
-    if (t < 16) c[t] = 0;
-    if (t >= 16 && t < 24) c[QCUR_BASE + (t - 16) * QCUR_STRIDE] = 0;
+    if (t < CTL_LINE) c[t] = 0;
+    if (region_lane) c[CTL_REGION_CURSOR + (t - CTL_LINE) * QCUR_STRIDE] = 0;
     (void)fc;
     // the host polls the sequence word (mailbox_wait_seq): it goes out BEHIND the words above (one wave: a system-scope
     // release covers the stores of all its lanes)

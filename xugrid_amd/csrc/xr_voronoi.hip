@@ -682,84 +682,79 @@ extern "C" {
 int xr_voronoi_create(xr_mesh *mesh, xr_voronoi **out) {
     XR_API_BEGIN
     XR_REQUIRE(mesh && out, XR_ERR_INVALID, "xr_voronoi_create: NULL argument");
-    xr_voronoi *v = new xr_voronoi();
-    try {
-        const int64_t N = mesh->n_node, F = mesh->n_face;
-        const int m = mesh->m;
-        const int64_t total = F * m;
-        v->mesh = mesh; v->n_node = N; v->n_face = F;
-        DevBuf<int32_t> count_cursor(2 * ((size_t)N + 1)); // (histogram and scatter cursors: one buffer, one fill)
-        int32_t *const count = count_cursor.get(), *const cursor = count_cursor.get() + N + 1;
-        v->indptr.alloc((size_t)N + 1);
-        fill_i32(count_cursor.get(), 0, 2 * (N + 1));
-        if (total > 0)
-            XR_LAUNCH("vor_count", k_vor_count, dim3(div_up(total, VOR_SLOTS)), dim3(256), 0, mesh->faces_raw.get(), total, count);
-        exclusive_scan_i32(count, v->indptr.get(), N);
-        // (sized by the slot count, an upper bound of the entries: their number is read at the end with the other counters --
-        // the whole construction has TWO host round trips, counters and exterior edges, instead of seven)
-        v->faces_asc.alloc((size_t)std::max<int64_t>(total, 1));
-        v->faces_ccw.alloc((size_t)std::max<int64_t>(total, 1));
-        v->interior.alloc((size_t)N);
-        v->cell_rank.alloc((size_t)N + 1);
-        v->centroids.alloc((size_t)F * 2);
-        DevBuf<uint8_t> on_boundary((size_t)N);
-        DevBuf<int32_t> flag32((size_t)N), counters(8), e_all((size_t)std::max<int64_t>(3 * total, 1));
-        XR_HIP(hipMemsetAsync(on_boundary.get(), 0, (size_t)(N > 0 ? N : 1), launch_stream()));
-        // counters: [0] exterior edges, [1] min / [2] max interior degree, [3] interior nodes, [4] entries of the node -> face rows
-        XR_LAUNCH("vor_init", k_vor_init_counters, dim3(1), dim3(64), 0, counters.get());
-        if (total > 0) {
-            XR_LAUNCH("vor_scatter", k_vor_scatter, dim3(div_up(total, VOR_SLOTS)), dim3(256), 0, mesh->faces_raw.get(), total, m,
-                      v->indptr.get(), cursor, v->faces_asc.get());
-            XR_LAUNCH("vor_sort_rows", k_vor_sort_rows, dim3(div_up(N, 256)), dim3(256), 0, v->indptr.get(), N,
-                      v->faces_asc.get());
-            XR_LAUNCH("vor_exterior", k_vor_exterior, dim3(div_up(total, 256)), dim3(256), 0, mesh->faces_raw.get(), F, m,
-                      v->indptr.get(), v->faces_asc.get(), on_boundary.get(), counters.get(), e_all.get());
-        }
-        mesh_centroids_dev(mesh, v->centroids.get());
-        if (N > 0)
-            XR_LAUNCH("vor_interior", k_vor_interior, dim3(div_up(N, VOR_BLOCK)), dim3(VOR_BLOCK), 0, mesh->node_xy.get(),
-                      v->centroids.get(), v->indptr.get(), v->faces_asc.get(), on_boundary.get(), N, v->faces_ccw.get(),
-                      v->interior.get(), flag32.get(), counters.get() + 1);
-        exclusive_scan_i32(flag32.get(), v->cell_rank.get(), N);
-        XR_LAUNCH("vor_totals", k_vor_totals, dim3(1), dim3(64), 0, v->cell_rank.get() + N, v->indptr.get() + N, counters.get());
-        // (every kernel of the O(n) part is enqueued; from here on the host reads counters and lists back -- the device idles for
-        // most of the next 0.2-0.3 ms.  A pending source-side locate pass of a barycentric construction goes out here.)
-        flush_pending_points();
-        int32_t h[8];
-        d2h(h, counters.get(), sizeof(h));
-        v->n_interior = h[3];
-        v->nnz = h[4];
-        v->min_degree = v->n_interior > 0 ? h[1] : 0;
-        v->max_degree = h[2];
-        const int64_t ne = h[0];
-        std::vector<int32_t> lo((size_t)ne), hi((size_t)ne), fc((size_t)ne);
-        if (ne > 0) {
-            std::vector<int32_t> all((size_t)(3 * ne));
-            d2h(all.data(), e_all.get(), sizeof(int32_t) * all.size());
-            for (int64_t i = 0; i < ne; i++) {
-                lo[(size_t)i] = all[3 * (size_t)i];
-                hi[(size_t)i] = all[3 * (size_t)i + 1];
-                fc[(size_t)i] = all[3 * (size_t)i + 2];
-            }
-        }
-        std::vector<int64_t> order((size_t)ne);
-        for (int64_t i = 0; i < ne; i++) order[(size_t)i] = i;
-        std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
-            if (lo[(size_t)a] != lo[(size_t)b]) return lo[(size_t)a] < lo[(size_t)b];
-            if (hi[(size_t)a] != hi[(size_t)b]) return hi[(size_t)a] < hi[(size_t)b];
-            return fc[(size_t)a] < fc[(size_t)b];
-        });
-        v->edge_lo.resize((size_t)ne); v->edge_hi.resize((size_t)ne); v->edge_face.resize((size_t)ne);
-        for (int64_t i = 0; i < ne; i++) {
-            v->edge_lo[(size_t)i] = lo[(size_t)order[(size_t)i]];
-            v->edge_hi[(size_t)i] = hi[(size_t)order[(size_t)i]];
-            v->edge_face[(size_t)i] = fc[(size_t)order[(size_t)i]];
-        }
-    } catch (...) {
-        delete v;
-        throw;
+    Building<xr_voronoi> v;
+    const int64_t N = mesh->n_node, F = mesh->n_face;
+    const int m = mesh->m;
+    const int64_t total = F * m;
+    v->mesh = mesh; v->n_node = N; v->n_face = F;
+    DevBuf<int32_t> count_cursor(2 * ((size_t)N + 1)); // (histogram and scatter cursors: one buffer, one fill)
+    int32_t *const count = count_cursor.get(), *const cursor = count_cursor.get() + N + 1;
+    v->indptr.alloc((size_t)N + 1);
+    fill_i32(count_cursor.get(), 0, 2 * (N + 1));
+    if (total > 0)
+        XR_LAUNCH("vor_count", k_vor_count, dim3(div_up(total, VOR_SLOTS)), dim3(256), 0, mesh->faces_raw.get(), total, count);
+    exclusive_scan_i32(count, v->indptr.get(), N);
+    // (sized by the slot count, an upper bound of the entries: their number is read at the end with the other counters --
+    // the whole construction has TWO host round trips, counters and exterior edges, instead of seven)
+    v->faces_asc.alloc((size_t)std::max<int64_t>(total, 1));
+    v->faces_ccw.alloc((size_t)std::max<int64_t>(total, 1));
+    v->interior.alloc((size_t)N);
+    v->cell_rank.alloc((size_t)N + 1);
+    v->centroids.alloc((size_t)F * 2);
+    DevBuf<uint8_t> on_boundary((size_t)N);
+    DevBuf<int32_t> flag32((size_t)N), counters(8), e_all((size_t)std::max<int64_t>(3 * total, 1));
+    XR_HIP(hipMemsetAsync(on_boundary.get(), 0, (size_t)(N > 0 ? N : 1), launch_stream()));
+    // counters: [0] exterior edges, [1] min / [2] max interior degree, [3] interior nodes, [4] entries of the node -> face rows
+    XR_LAUNCH("vor_init", k_vor_init_counters, dim3(1), dim3(64), 0, counters.get());
+    if (total > 0) {
+        XR_LAUNCH("vor_scatter", k_vor_scatter, dim3(div_up(total, VOR_SLOTS)), dim3(256), 0, mesh->faces_raw.get(), total, m,
+                  v->indptr.get(), cursor, v->faces_asc.get());
+        XR_LAUNCH("vor_sort_rows", k_vor_sort_rows, dim3(div_up(N, 256)), dim3(256), 0, v->indptr.get(), N,
+                  v->faces_asc.get());
+        XR_LAUNCH("vor_exterior", k_vor_exterior, dim3(div_up(total, 256)), dim3(256), 0, mesh->faces_raw.get(), F, m,
+                  v->indptr.get(), v->faces_asc.get(), on_boundary.get(), counters.get(), e_all.get());
     }
-    *out = v;
+    mesh_centroids_dev(mesh, v->centroids.get());
+    if (N > 0)
+        XR_LAUNCH("vor_interior", k_vor_interior, dim3(div_up(N, VOR_BLOCK)), dim3(VOR_BLOCK), 0, mesh->node_xy.get(),
+                  v->centroids.get(), v->indptr.get(), v->faces_asc.get(), on_boundary.get(), N, v->faces_ccw.get(),
+                  v->interior.get(), flag32.get(), counters.get() + 1);
+    exclusive_scan_i32(flag32.get(), v->cell_rank.get(), N);
+    XR_LAUNCH("vor_totals", k_vor_totals, dim3(1), dim3(64), 0, v->cell_rank.get() + N, v->indptr.get() + N, counters.get());
+    // (every kernel of the O(n) part is enqueued; from here on the host reads counters and lists back -- the device idles for
+    // most of the next 0.2-0.3 ms.  A pending source-side locate pass of a barycentric construction goes out here.)
+    flush_pending_points();
+    int32_t h[8];
+    d2h(h, counters.get(), sizeof(h));
+    v->n_interior = h[3];
+    v->nnz = h[4];
+    v->min_degree = v->n_interior > 0 ? h[1] : 0;
+    v->max_degree = h[2];
+    const int64_t ne = h[0];
+    std::vector<int32_t> lo((size_t)ne), hi((size_t)ne), fc((size_t)ne);
+    if (ne > 0) {
+        std::vector<int32_t> all((size_t)(3 * ne));
+        d2h(all.data(), e_all.get(), sizeof(int32_t) * all.size());
+        for (int64_t i = 0; i < ne; i++) {
+            lo[(size_t)i] = all[3 * (size_t)i];
+            hi[(size_t)i] = all[3 * (size_t)i + 1];
+            fc[(size_t)i] = all[3 * (size_t)i + 2];
+        }
+    }
+    std::vector<int64_t> order((size_t)ne);
+    for (int64_t i = 0; i < ne; i++) order[(size_t)i] = i;
+    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
+        if (lo[(size_t)a] != lo[(size_t)b]) return lo[(size_t)a] < lo[(size_t)b];
+        if (hi[(size_t)a] != hi[(size_t)b]) return hi[(size_t)a] < hi[(size_t)b];
+        return fc[(size_t)a] < fc[(size_t)b];
+    });
+    v->edge_lo.resize((size_t)ne); v->edge_hi.resize((size_t)ne); v->edge_face.resize((size_t)ne);
+    for (int64_t i = 0; i < ne; i++) {
+        v->edge_lo[(size_t)i] = lo[(size_t)order[(size_t)i]];
+        v->edge_hi[(size_t)i] = hi[(size_t)order[(size_t)i]];
+        v->edge_face[(size_t)i] = fc[(size_t)order[(size_t)i]];
+    }
+    *out = v.release();
     XR_API_END
 }
 
@@ -863,34 +858,29 @@ int xr_voronoi_mesh(const xr_voronoi *v, const double *extra_xy, int64_t n_extra
             table[(size_t)(r * mb + j)] = (int32_t)c;
         }
     }
-    xr_mesh *mesh = new xr_mesh();
-    try {
-        mesh->n_node = n_vertex;
-        mesh->n_face = n_cell;
-        mesh->m = m;
-        mesh->node_xy.alloc((size_t)n_vertex * 2);
-        mesh->faces_raw.alloc((size_t)(n_cell * m));
-        if (v->n_face > 0)
-            XR_HIP(hipMemcpyAsync(mesh->node_xy.get(), v->centroids.get(), sizeof(double) * 2 * (size_t)v->n_face,
-                                  hipMemcpyDeviceToDevice, launch_stream()));
-        if (n_extra_vertex > 0)
-            h2d(mesh->node_xy.get() + 2 * v->n_face, extra_xy, sizeof(double) * 2 * (size_t)n_extra_vertex);
-        if (v->n_node > 0 && v->n_interior > 0)
-            XR_LAUNCH("vor_cells", k_vor_cells, dim3(div_up(v->n_node * m, 256)), dim3(256), 0, v->indptr.get(),
-                      v->faces_ccw.get(), v->interior.get(), v->cell_rank.get(), v->n_node, m, mesh->faces_raw.get());
-        if (n_boundary_cell > 0) {
-            DevBuf<int32_t> dtable((size_t)(n_boundary_cell * mb));
-            h2d(dtable.get(), table.data(), sizeof(int32_t) * (size_t)(n_boundary_cell * mb));
-            XR_LAUNCH("vor_boundary_cells", k_vor_boundary_cells, dim3(div_up(n_boundary_cell * m, 256)), dim3(256), 0,
-                      dtable.get(), n_boundary_cell, mb, m, mesh->faces_raw.get() + v->n_interior * m);
-            stream_sync();
-        }
+    Building<xr_mesh> mesh;
+    mesh->n_node = n_vertex;
+    mesh->n_face = n_cell;
+    mesh->m = m;
+    mesh->node_xy.alloc((size_t)n_vertex * 2);
+    mesh->faces_raw.alloc((size_t)(n_cell * m));
+    if (v->n_face > 0)
+        XR_HIP(hipMemcpyAsync(mesh->node_xy.get(), v->centroids.get(), sizeof(double) * 2 * (size_t)v->n_face,
+                              hipMemcpyDeviceToDevice, launch_stream()));
+    if (n_extra_vertex > 0)
+        h2d(mesh->node_xy.get() + 2 * v->n_face, extra_xy, sizeof(double) * 2 * (size_t)n_extra_vertex);
+    if (v->n_node > 0 && v->n_interior > 0)
+        XR_LAUNCH("vor_cells", k_vor_cells, dim3(div_up(v->n_node * m, 256)), dim3(256), 0, v->indptr.get(),
+                  v->faces_ccw.get(), v->interior.get(), v->cell_rank.get(), v->n_node, m, mesh->faces_raw.get());
+    if (n_boundary_cell > 0) {
+        DevBuf<int32_t> dtable((size_t)(n_boundary_cell * mb));
+        h2d(dtable.get(), table.data(), sizeof(int32_t) * (size_t)(n_boundary_cell * mb));
+        XR_LAUNCH("vor_boundary_cells", k_vor_boundary_cells, dim3(div_up(n_boundary_cell * m, 256)), dim3(256), 0,
+                  dtable.get(), n_boundary_cell, mb, m, mesh->faces_raw.get() + v->n_interior * m);
         stream_sync();
-    } catch (...) {
-        delete mesh;
-        throw;
     }
-    *out = mesh;
+    stream_sync();
+    *out = mesh.release();
     XR_API_END
 }
 
