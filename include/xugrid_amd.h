@@ -484,6 +484,40 @@ int xr_graph_laplace_fill_dev(const xr_graph *graph, const double *in_dev, doubl
  * NaN.  XR_ERR_INVALID "All values are NA." for a slice without any value. */
 int xr_nearest_fill_dev(const double *xy_dev, int64_t n, const double *in_dev, double *out_dev, int64_t K, double max_distance);
 
+/* ---- sampling mesh data at points and along lines (xugrid sel_points / sel / intersect_line / locate_nearest_*) ---- */
+/* Nearest-neighbour index over n fixed points xy_dev float64 [n, 2] (a device pointer): what Ugrid2d.node_kdtree /
+ * edge_kdtree / face_kdtree are in the reference (scipy KDTree, xugrid/ugrid/ugridbase.py:1113-1123, ugrid2d.py:902-906).
+ * A uniform grid of about two points per cell; the handle keeps its own copy of the coordinates in cell order, so the
+ * caller's array may go.  n = 0 is XR_ERR_INVALID. */
+typedef struct xr_nn xr_nn;
+int xr_nn_create_dev(const double *xy_dev, int64_t n, xr_nn **out);
+/* ... over the nodes or the face centroids (connectivity.centroids) of a mesh, straight from its device arrays: the index
+ * of a grid made by Ugrid2d.from_device_arrays needs no host copy of the mesh. */
+#define XR_FACET_NODE 0
+#define XR_FACET_FACE 2
+int xr_nn_create_mesh(xr_mesh *mesh, int facet, xr_nn **out);
+int xr_nn_info(const xr_nn *index, int64_t *n, int64_t *n_cell);
+int xr_nn_destroy(xr_nn *index);
+/* KDTree.query(points, distance_upper_bound=max_distance) as locate_nearest_node / _edge / _face call it
+ * (ugridbase.py:1261-1303, ugrid2d.py:1007-1027): query_xy_dev float64 [n_query, 2] -> index_out_dev int64 [n_query], the id
+ * of the nearest indexed point or -1.  Squared distance dx * dx + dy * dy in float64; a point counts only STRICTLY below
+ * max_distance (scipy's rule; INFINITY: no limit); the lowest id wins among equidistant points (scipy's choice there is
+ * arbitrary); a query with a NaN coordinate gets -1. */
+int xr_nn_query_dev(const xr_nn *index, const double *query_xy_dev, int64_t n_query, double max_distance,
+                    int64_t *index_out_dev);
+/* obj.isel(points).where(valid, fill_value) of sel_points (ugridbase.py:1240-1258) for K slices: in_dev [K, n] of dtype
+ * XR_F64 / XR_F32, index_dev int64 [n_point] -> out_dev float64 [K, n_point], out[k, p] = in[k, index[p]], fill_value where
+ * index[p] < 0.  An index >= n is XR_ERR_INVALID (checked once per call, before anything is read through it). */
+int xr_gather_points_dev(const void *in_dev, int dtype, int64_t K, int64_t n, const int64_t *index_dev, int64_t n_point,
+                         double fill_value, double *out_dev);
+/* Coordinates of a line section (intersect_linestring, ugridbase.py:1438-1452; section_coordinates_2d,
+ * selection_utils.py:27-32): pieces_dev float64 [n_piece, 2, 2] as xr_edge_pieces returns them, piece_segment_dev int64
+ * [n_piece] the segment each piece was cut from, segment_xy_dev float64 [n_segment, 2, 2] the line's segments in order.
+ * mid = 0.5 (p0 + p1) -> mid_xy_out_dev [n_piece, 2]; s = |mid - start of the segment| + summed length of the segments in
+ * front of it -> s_out_dev [n_piece].  All pointers are device pointers; the caller orders the pieces by s. */
+int xr_section_coords_dev(const double *pieces_dev, const int64_t *piece_segment_dev, int64_t n_piece,
+                          const double *segment_xy_dev, int64_t n_segment, double *mid_xy_out_dev, double *s_out_dev);
+
 /* ---- raw HBM helpers for hosts that do not bring their own allocator -------------------- */
 int xr_dev_alloc(int64_t bytes, void **ptr_out);
 int xr_dev_free(void *ptr);

@@ -125,6 +125,13 @@ SIGNATURES = {
     "xr_graph_destroy": (c_int, [vp]),
     "xr_graph_laplace_fill_dev": (c_int, [vp, vp, vp, c_i64, c_int, c_f64, c_f64, c_i64, c_i64, vp, vp]),
     "xr_nearest_fill_dev": (c_int, [vp, c_i64, vp, vp, c_i64, c_f64]),
+    "xr_nn_create_dev": (c_int, [vp, c_i64, p_vp]),
+    "xr_nn_create_mesh": (c_int, [vp, c_int, p_vp]),
+    "xr_nn_info": (c_int, [vp, p_i64, p_i64]),
+    "xr_nn_destroy": (c_int, [vp]),
+    "xr_nn_query_dev": (c_int, [vp, vp, c_i64, c_f64, vp]),
+    "xr_gather_points_dev": (c_int, [vp, c_int, c_i64, c_i64, vp, c_i64, c_f64, vp]),
+    "xr_section_coords_dev": (c_int, [vp, vp, c_i64, vp, c_i64, vp, vp]),
     "xr_dev_alloc": (c_int, [c_i64, p_vp]),
     "xr_dev_free": (c_int, [vp]),
     "xr_dev_upload": (c_int, [vp, vp, c_i64]),

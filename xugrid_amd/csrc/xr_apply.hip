@@ -2135,12 +2135,7 @@ static void launch_workspace(const xr_csr *csr, const SRC *src, int64_t K, doubl
 // ---- host dispatch: run-time source dtype and reducer ids -> template arguments.  Every table below is the only one of
 // its kind; a reducer a kernel family does not serve is excluded with `if constexpr`, never instantiated.
 
-// f(SRC()) with SRC the element type of a source dtype id
-template <typename F> static void with_source_type(int dtype, F &&f) {
-    XR_REQUIRE(dtype == XR_F64 || dtype == XR_F32, XR_ERR_INVALID, "unsupported source dtype id %d", dtype);
-    if (dtype == XR_F64) f(double());
-    else f(float());
-}
+// (with_source_type, the table of the source dtypes, is in xr_internal.h: xr_sample.hip gathers through it too)
 
 static size_t source_size(int dtype) {
     size_t size = 0;

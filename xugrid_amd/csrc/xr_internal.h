@@ -324,6 +324,7 @@ enum Option : int {
     OPT_EDGE_STAGE,        // > 0: candidates a wave of 64 edges may stage (<= 1024; tests force the overflow into the wave-per-edge kernel)
     OPT_EDGE_QUEUE,        // > 0: candidate pairs the edge queue holds at first (tests force the regrow path with a tiny one)
     OPT_EDGE_SORT,         // 1: the edges are walked in the order of the grid tiles of their midpoints; 0: as they come
+    OPT_NN_QUERY_SORT,     // -1: nearest queries are binned by index cell from NN_SORT_MIN_QUERIES on (xr_sample.hip); 0 / 1: never / always
     OPT_COUNT
 };
 int64_t option(Option o);
@@ -336,6 +337,13 @@ template <typename F> void with_nodes_per_face(int m, F &&f) {
     if (m == 3) f(std::integral_constant<int, 3>());
     else if (m == 4) f(std::integral_constant<int, 4>());
     else f(std::integral_constant<int, 0>());
+}
+
+// f(SRC()) with SRC the element type of a source dtype id (XR_F64 / XR_F32): the one table of the source dtypes
+template <typename F> void with_source_type(int dtype, F &&f) {
+    XR_REQUIRE(dtype == XR_F64 || dtype == XR_F32, XR_ERR_INVALID, "unsupported source dtype id %d", dtype);
+    if (dtype == XR_F64) f(double());
+    else f(float());
 }
 
 // KERNEL may be launched with up to `bytes` of dynamic LDS (beyond the 64 KB any kernel may ask for): set on first use,

@@ -7,7 +7,7 @@ the regridding hot path (out of scope).
 """
 import numpy as np
 
-from . import connectivity, fill
+from . import connectivity, fill, sample
 from .engine import FloatDType, IntDType
 
 FILL_VALUE = -1
@@ -115,6 +115,29 @@ class Ugrid1d:
         facet = fill.resolve_dim(self, dim, ("node", "edge"))
         coords = (lambda: self.node_coordinates) if facet == "node" else (lambda: self.edge_coordinates)
         return fill.nearest_fill(self._fill().xy(facet, coords), data, max_distance)
+
+    # ---- nearest node / edge on the device (xugrid_amd/sample.py; the Ugrid2d methods of the same name)
+    def _nearest_index(self, facet):
+        cache = self.__dict__.get("_sample_cache")
+        if cache is None:
+            cache = self.__dict__["_sample_cache"] = sample.GridSample()
+        coords = (lambda: self.node_coordinates) if facet == "node" else (lambda: self.edge_coordinates)
+        return cache.index(facet, lambda: sample.NearestIndex.from_points(coords()))
+
+    def locate_nearest_node(self, points, max_distance=np.inf):
+        """Index of the nearest node per point ``(n_point, 2)``, -1 for none (ugridbase.py:1261-1281); see
+        ``Ugrid2d.locate_nearest_node``."""
+        return self._nearest_index("node").query(points, max_distance)
+
+    def locate_nearest_edge(self, points, max_distance=np.inf):
+        """Index of the nearest edge midpoint per point, -1 for none (ugridbase.py:1283-1303)."""
+        return self._nearest_index("edge").query(points, max_distance)
+
+    def drop_device_caches(self):
+        """Release what this grid keeps in HBM: the fills' graphs and point arrays and the nearest-neighbour indices (built
+        from the coordinates as they were on first use)."""
+        self.__dict__.pop("_fill_cache", None)
+        self.__dict__.pop("_sample_cache", None)
 
     @property
     def bounds(self):

@@ -10,7 +10,7 @@ import numpy as np
 
 import ctypes
 
-from . import _lib, connectivity, fill
+from . import _lib, connectivity, fill, sample
 from .celltree import CellTree2d
 from .engine import FloatDType, IntDType
 
@@ -171,6 +171,7 @@ class Ugrid2d:
         self._celltree = None
         self._voronoi_device_cache = None
         self.__dict__.pop("_fill_cache", None)
+        self.__dict__.pop("_sample_cache", None)
 
     @property
     def device_mesh(self):
@@ -312,6 +313,78 @@ class Ugrid2d:
         facet = fill.resolve_dim(self, dim, ("node", "edge", "face"))
         xy = self._fill().xy(facet, lambda: self._fill_coordinates(facet))
         return fill.nearest_fill(xy, data, max_distance)
+
+    # ---- reading data at points and along lines on the device (xugrid_amd/sample.py)
+    def _sample(self):
+        cache = self.__dict__.get("_sample_cache")
+        if cache is None:
+            cache = self.__dict__["_sample_cache"] = sample.GridSample()
+        return cache
+
+    def _nearest_index(self, facet):
+        """The nearest-neighbour index of a facet's points: nodes and face centroids are read from the device mesh where they
+        are; edge midpoints come from ``edge_coordinates``."""
+        if facet == "edge":
+            return self._sample().index(facet, lambda: sample.NearestIndex.from_points(self.edge_coordinates))
+        return self._sample().index(facet, lambda: sample.NearestIndex.from_mesh(self.device_mesh, facet))
+
+    def _locate_nearest(self, facet, points, max_distance=np.inf):
+        if facet not in sample.FACETS:
+            raise ValueError(f"Expected facet as one of {sample.FACETS}, received: {facet}")
+        return self._nearest_index(facet).query(points, max_distance)
+
+    def locate_nearest_node(self, points, max_distance=np.inf):
+        """Index of the nearest node per point ``(n_point, 2)``, -1 for none (ugridbase.py:1261-1281): strictly closer
+        than ``max_distance`` as scipy's ``distance_upper_bound``; the lowest index among equidistant nodes.  Host points
+        -> numpy; a float64 device array -> an int64 device array of the same kind."""
+        return self._locate_nearest("node", points, max_distance)
+
+    def locate_nearest_edge(self, points, max_distance=np.inf):
+        """... the nearest edge midpoint (ugridbase.py:1283-1303).  The edges are derived on the host
+        (``connectivity.edge_connectivity``), so on a grid made by ``from_device_arrays`` this facet -- and only this one --
+        materialises the host copy of the mesh."""
+        return self._locate_nearest("edge", points, max_distance)
+
+    def locate_nearest_face(self, points, max_distance=np.inf):
+        """... the nearest face centroid (ugrid2d.py:1007-1027)."""
+        return self._locate_nearest("face", points, max_distance)
+
+    def intersect_edges(self, edges):
+        """ugridbase.py:1325-1343: ``(edge_index, face_index, intersections (n, 2, 2))`` of segments ``(n_edge, 2, 2)``."""
+        return self.celltree.intersect_edges(edges)
+
+    def locate_bounding_box(self, xmin, ymin, xmax, ymax):
+        """Indices of the faces whose centroid lies in the half-open box ``xmin <= x < xmax``, ``ymin <= y < ymax``
+        (ugrid2d.py:1029-1052)."""
+        return sample.locate_bounding_box(self, xmin, ymin, xmax, ymax)
+
+    def sel_points(self, data, x, y, dim=None, method=None, out_of_bounds="warn", fill_value=np.nan, tolerance=None):
+        """Values of ``data`` (..., n) along ``dim`` (default: faces) at the points ``(x[i], y[i])`` (ugridbase.py:1125-1259)
+        -> ``(values (..., n_sel), index (n_sel,), x, y)``.  Containment (``locate_points`` with ``tolerance``) decides which
+        points are in bounds.  Face data takes the containing face, or the nearest centroid with ``method="nearest"``; node
+        and edge data always take the nearest entity.  ``out_of_bounds``: "raise", "warn" / "ignore" (``fill_value``, a
+        scalar, at those points) or "drop" (``index`` then tells which of the caller's points remain).  numpy in -> numpy
+        out, device array in -> float64 device array out; the gather runs on the device."""
+        return sample.sel_points(self, data, x, y, dim, method, out_of_bounds, fill_value, tolerance)
+
+    def sel(self, data, x=None, y=None, dim=None):
+        """Selection in x and y (ugridbase.py:1462-1506): scalars, lists, arrays or slices with a step give orthogonal points
+        through ``sel_points``; a slice without step paired with one value gives a line across the grid's bounds
+        (``intersect_line``); two slices give the faces whose centroid lies in the box, open ends taken from the grid's
+        bounds -> ``(values (..., n_sel), face_index)``.  (The reference also returns the sub-grid of a box; this package
+        has no ``topology_subset`` and stops at the index.)"""
+        return sample.sel(self, data, x, y, dim)
+
+    def intersect_line(self, data, start, end):
+        """Values of face data (..., n_face) in the faces the line from ``start`` to ``end`` crosses (ugridbase.py:1345-1378)
+        -> ``(values (..., n_piece), face_index, x, y, s)`` ordered by ``s``, the distance of each piece's midpoint
+        ``(x, y)`` from ``start``.  A torch tensor in gives tensors out."""
+        return sample.intersect_line(self, data, start, end)
+
+    def intersect_linestring(self, data, xy):
+        """``intersect_line`` along the vertices ``xy (n_vertex, 2)`` (ugridbase.py:1412-1460; an array instead of a shapely
+        geometry): ``s`` runs along the whole line."""
+        return sample.intersect_linestring(self, data, xy)
 
     # ---- structured -> unstructured (raster cells become CCW quads)
     @staticmethod
@@ -515,4 +588,5 @@ class DeviceUgrid2d(Ugrid2d):
         # (the device mesh IS this grid: its derived arrays and index go, the raw arrays stay)
         self._voronoi_device_cache = None
         self.__dict__.pop("_fill_cache", None)
+        self.__dict__.pop("_sample_cache", None)
         self._celltree.device_mesh.invalidate()
