@@ -518,6 +518,36 @@ int xr_gather_points_dev(const void *in_dev, int dtype, int64_t K, int64_t n, co
 int xr_section_coords_dev(const double *pieces_dev, const int64_t *piece_segment_dev, int64_t n_piece,
                           const double *segment_xy_dev, int64_t n_segment, double *mid_xy_out_dev, double *s_out_dev);
 
+/* ---- burning vector geometry into the faces of a mesh (xugrid.burn_vector_geometry, xugrid/ugrid/burn.py) ---------------- */
+/* All pointers are device pointers; coordinates float64 [n, 2], offsets int64.  A winner array int32 [n_face] holds per face
+ * the HIGHEST id of a geometry that covers it (the reference's sequential loop: later geometries overwrite earlier ones),
+ * -1 for none.  Offsets must start at 0, end at the count they index and never decrease (XR_ERR_INVALID).
+ * xr_burn_polygons_dev (_locate_polygon / _burn_polygons, burn.py:59-137): the layout of shapely.to_ragged_array -- ring r
+ * holds the vertices [ring_offsets[r], ring_offsets[r + 1]), polygon g the rings [polygon_offsets[g], polygon_offsets[g + 1]),
+ * the first its exterior, the others holes; rings are cyclic, closed (first == last) or open.  Face f is in polygon g iff its
+ * centroid (connectivity.centroids) passes the per-segment rule of xr_locate_points with the mesh's default tolerance --
+ * within tolerance of a segment, or an odd number of crossings -- over all ring segments of g.  all_touched != 0 adds every
+ * face in which a ring segment of g has a piece of positive length (the rule of xr_edge_length_csr), unless the segment
+ * lies exactly on the line of one of the face's edges (a border drawn along a mesh line touches neither neighbour, as in
+ * the reference).  No triangulation.
+ * Option "burn_strips" (> 0) forces the number of strips of the segment index; no result depends on it.  XR_ERR_LIMIT when
+ * the strips would list 2^31 segments or more. */
+int xr_burn_polygons_dev(xr_mesh *mesh, const double *coords_dev, int64_t n_vertex, const int64_t *ring_offsets_dev,
+                         int64_t n_ring, const int64_t *polygon_offsets_dev, int64_t n_polygon, int all_touched,
+                         int32_t *winner_dev);
+/* _burn_lines (burn.py:153-181): line l joins the consecutive vertices [line_offsets[l], line_offsets[l + 1]); a face is
+ * covered where a segment has a piece of positive length in it. */
+int xr_burn_lines_dev(xr_mesh *mesh, const double *coords_dev, int64_t n_vertex, const int64_t *line_offsets_dev, int64_t n_line,
+                      int32_t *winner_dev);
+/* _burn_points (burn.py:140-150): the face xr_locate_points finds with the default tolerance.  A point in no face burns
+ * nothing (the reference writes it into the LAST face through the index -1). */
+int xr_burn_points_dev(xr_mesh *mesh, const double *coords_dev, int64_t n_point, int32_t *winner_dev);
+/* out[f] = value of the point winner, else of the line winner, else of the polygon winner, else fill (burn.py:253-260:
+ * polygons, then lines, then points).  A NULL winner array: no geometry of that kind; NULL values: 1.0 (column=None). */
+int xr_burn_combine_dev(int64_t n_face, const int32_t *polygon_winner_dev, const double *polygon_values_dev,
+                        const int32_t *line_winner_dev, const double *line_values_dev, const int32_t *point_winner_dev,
+                        const double *point_values_dev, double fill, double *out_dev);
+
 /* ---- raw HBM helpers for hosts that do not bring their own allocator -------------------- */
 int xr_dev_alloc(int64_t bytes, void **ptr_out);
 int xr_dev_free(void *ptr);

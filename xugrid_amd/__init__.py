@@ -8,6 +8,7 @@ fallback: without ``libxugrid_amd.so`` and a HIP device every compute call raise
 """
 from . import engine, meshgen  # noqa: F401
 from ._lib import XugridAmdError  # noqa: F401
+from .burn import burn_vector_geometry, locate_polygon  # noqa: F401
 from .celltree import CellTree2d  # noqa: F401
 from .fill import laplace_interpolate  # noqa: F401
 from .regrid import (  # noqa: F401

@@ -132,6 +132,10 @@ SIGNATURES = {
     "xr_nn_query_dev": (c_int, [vp, vp, c_i64, c_f64, vp]),
     "xr_gather_points_dev": (c_int, [vp, c_int, c_i64, c_i64, vp, c_i64, c_f64, vp]),
     "xr_section_coords_dev": (c_int, [vp, vp, c_i64, vp, c_i64, vp, vp]),
+    "xr_burn_polygons_dev": (c_int, [vp, vp, c_i64, vp, c_i64, vp, c_i64, c_int, vp]),
+    "xr_burn_lines_dev": (c_int, [vp, vp, c_i64, vp, c_i64, vp]),
+    "xr_burn_points_dev": (c_int, [vp, vp, c_i64, vp]),
+    "xr_burn_combine_dev": (c_int, [c_i64, vp, vp, vp, vp, vp, vp, c_f64, vp]),
     "xr_dev_alloc": (c_int, [c_i64, p_vp]),
     "xr_dev_free": (c_int, [vp]),
     "xr_dev_upload": (c_int, [vp, vp, c_i64]),

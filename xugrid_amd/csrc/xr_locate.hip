@@ -651,6 +651,20 @@ static double resolve_tolerance(xr_mesh *mesh, double tolerance) {
     return 1e-12 * mesh->h_stats[6]; // ugridbase.py:1165-1170
 }
 
+// the locate pass of xr_locate_points on points that are already in HBM, for other translation units (xr_burn.hip):
+// tolerance < 0 = the default; pts_dev float64 [n, 2] -> out_dev int64 [n] on the calling thread's launch stream.
+// -> the tolerance used
+double locate_points_dev(xr_mesh *mesh, const double *pts_dev, int64_t n, double tolerance, int64_t *out_dev) {
+    mesh_prepare(mesh, false);
+    mesh_build_index(mesh);
+    const double tol = resolve_tolerance(mesh, tolerance);
+    if (n > 0)
+        XR_LAUNCH("locate_points", k_locate, dim3(div_up(n, 256)), dim3(256), 0, mesh->rec_fxy.get(), mesh->rec_len.get(),
+                  mesh->record_off(), mesh->m, mesh->grid, mesh->cell_start.get(), mesh->rec_bb.get(), mesh->rec_face.get(),
+                  mesh->n_face, pts_dev, n, tol, out_dev);
+    return tol;
+}
+
 static void launch_points(xr_points *h) {
     if (h->query) h->pts.share(mesh_centroids_shared(h->query));
     if (engine().on_side && !current_lane()) {

@@ -175,5 +175,7 @@ void csr_apply_dev(const xr_csr *csr, int method, double percentile, const void 
 void csr_partial_dev(const xr_csr *csr, int method, const void *src_dev, int dtype, int64_t K, double *out_dev, int rows_layout);
 void mesh_centroids_dev(xr_mesh *mesh, double *cxy_dev);    // connectivity.centroids into device memory [n_face*2]
 std::shared_ptr<xr::DevBuf<double>> mesh_centroids_shared(xr_mesh *mesh); // ... computed once per mesh, shared with the callers
+// locate_points on device-resident points (xr_locate.hip); tolerance < 0: the mesh's default.  The mesh must have faces.  -> the tolerance used
+double locate_points_dev(xr_mesh *mesh, const double *pts_dev, int64_t n, double tolerance, int64_t *out_dev);
 void mesh_faces_ccw_dev(xr_mesh *mesh, int64_t *faces_dev, bool caller_order = false); // CCW-normalised (or the caller's) connectivity [n_face*m]
 } // namespace xr

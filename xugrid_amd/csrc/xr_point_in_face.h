@@ -40,6 +40,27 @@ __device__ __forceinline__ bool left_of_crossing(double px, double num, double w
     return px < num / wy + v0x;
 }
 
+// One directed segment v0 -> v1 of the test below on its own, for callers that walk segments rather than faces (the ring
+// segments of xr_burn.hip): sets on_edge / flips odd exactly where point_in_face_impl would return true / flip c.
+__device__ __forceinline__ void point_vs_segment(P2 v0, P2 v1, P2 p, double tol, bool &on_edge, bool &odd) {
+    const double wx = v1.x - v0.x, wy = v1.y - v0.y;
+    const double len2 = wx * wx + wy * wy;
+    if (len2 > 0) {
+        const double ux = p.x - v0.x, uy = p.y - v0.y;
+        const double twice_area = fabs(wx * uy - wy * ux);
+        if (!edge_certainly_far(twice_area, len2, tol)) {
+            const double len = sqrt(len2);
+            if (twice_area < tol * len) {
+                const double tpar = ux * wx + uy * wy;
+                if (tpar >= 0 && tpar <= len2) on_edge = true;
+            }
+        }
+        if ((v0.y > p.y) != (v1.y > p.y)) {
+            if (left_of_crossing(p.x, wx * (p.y - v0.y), wy, v0.x)) odd = !odd;
+        }
+    }
+}
+
 // load(i) -> vertex i of the face (CCW)
 template <typename Load> __device__ __forceinline__ bool point_in_face_impl(Load load, int n, P2 p, double tol) {
     bool c = false;
