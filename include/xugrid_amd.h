@@ -484,6 +484,56 @@ int xr_graph_laplace_fill_dev(const xr_graph *graph, const double *in_dev, doubl
  * NaN.  XR_ERR_INVALID "All values are NA." for a slice without any value. */
 int xr_nearest_fill_dev(const double *xy_dev, int64_t n, const double *in_dev, double *out_dev, int64_t K, double max_distance);
 
+/* ---- edge topology of a device mesh (xugrid_amd/connectivity.py: edge_connectivity, invert_dense, face_face_connectivity,
+ * node_node_connectivity) built where the mesh is, from its faces_raw; every array in the caller's numbering and equal,
+ * element for element, to what the host route gives for the same faces:
+ *   edge_node [n_edge, 2]  unique undirected edges (lower, higher node), lexicographic; the edge id is the rank
+ *   face_edge [n_face, m]  edge of slot k (node k -> its successor, the last node closing onto node 0), valid entries
+ *                          compacted to the left, -1 trailing; a slot whose two nodes are equal is no edge
+ *   edge_face [n_edge, 2]  the faces of each edge ascending, -1 in column 1 for an exterior edge
+ *   face_face CSR          one entry per pair of faces sharing an edge, columns ascending, data = the edge id (the SUM of
+ *                          the ids where two faces share several edges, as scipy's coo -> csr)
+ *   node_node CSR          over all n_node nodes (unused nodes: empty rows), columns ascending, data = the edge id
+ *   exterior_edge [n_edge], exterior_face [n_face]  flags (a face with at least one exterior edge)
+ * An edge with more than two faces does not fit two columns: the builder counts those (n_nonmanifold), keeps nothing else
+ * when there are any and still returns XR_OK; every other call on such a handle but xr_topology_info / _destroy is
+ * XR_ERR_INVALID.  `mesh` must outlive the handle. */
+typedef struct xr_topology xr_topology;
+int xr_topology_create(xr_mesh *mesh, xr_topology **out);
+/* any pointer may be NULL */
+int xr_topology_info(const xr_topology *topology, int64_t *n_edge, int64_t *n_exterior_edge, int64_t *face_face_nnz,
+                     int64_t *node_node_nnz, int64_t *n_nonmanifold);
+/* nodes with more distinct neighbours than the per-thread list holds (16): those the wave-per-node kernel listed */
+int xr_topology_long_nodes(const xr_topology *topology, int64_t *n_long_nodes);
+/* int64 outputs, any pointer may be NULL: edge_node [n_edge*2], face_edge [n_face*m], edge_face [n_edge*2], ff_indptr
+ * [n_face+1], ff_indices / ff_data [face_face_nnz], nn_indptr [n_node+1], nn_indices / nn_data [node_node_nnz],
+ * exterior_edge [n_edge], exterior_face [n_face] (0 / 1) */
+int xr_topology_download(const xr_topology *topology, int64_t *edge_node, int64_t *face_edge, int64_t *edge_face,
+                         int64_t *ff_indptr, int64_t *ff_indices, int64_t *ff_data, int64_t *nn_indptr, int64_t *nn_indices,
+                         int64_t *nn_data, int64_t *exterior_edge, int64_t *exterior_face);
+/* edge midpoints 0.5 * (a + b) into xy_dev float64 [n_edge, 2] (a device pointer) */
+int xr_topology_edge_xy_dev(const xr_topology *topology, double *xy_dev);
+/* exterior_face as uint8 [n_face] into a device buffer (the `exterior` argument of xr_graph_binary_iterate_dev) */
+int xr_topology_exterior_face_dev(const xr_topology *topology, uint8_t *flags_dev);
+int xr_topology_destroy(xr_topology *topology);
+/* The xr_graph of the faces (facet 2, XR_FACET_FACE below) or nodes (0, XR_FACET_NODE) straight from the device CSR: component labels by the
+ * label kernels, weights mean(d) / d (ugridbase.py:962-970) with d the distance between the connected face centroids or
+ * nodes; the mean is a fixed-order sum of block partials (the same bits on every run). */
+int xr_graph_from_topology(const xr_topology *topology, int facet, xr_graph **out);
+/* rounds of minimum-label propagation the component labelling of this graph took (0: labels given by the caller) */
+int xr_graph_label_rounds(const xr_graph *graph, int64_t *rounds);
+
+/* ---- graph operations (xugrid connected_components / binary_dilation / binary_erosion) --------------------------- */
+/* labels_dev int64 [n] (a device pointer): components numbered 0 .. n_components-1 in the order of their smallest member,
+ * which is the numbering of scipy.sparse.csgraph.connected_components */
+int xr_graph_components_dev(const xr_graph *graph, int64_t *labels_dev, int64_t *n_components);
+/* `iterations` (>= 1) Jacobi steps of xugrid/ugrid/connectivity.py _binary_iterate on K slices in_dev uint8 [K, n] ->
+ * out_dev [K, n] (in_dev is not modified): an entry becomes `value` iff a neighbour's old state differs from its own; then
+ * entries flagged in mask_dev uint8 [n] (or NULL) are set to !value (sic: the reference's `output[mask] = not value`);
+ * after the FIRST step only, entries flagged in exterior_dev uint8 [n] (or NULL) are set to `value`. */
+int xr_graph_binary_iterate_dev(const xr_graph *graph, const uint8_t *in_dev, uint8_t *out_dev, int64_t K, int value,
+                                int64_t iterations, const uint8_t *mask_dev, const uint8_t *exterior_dev);
+
 /* ---- sampling mesh data at points and along lines (xugrid sel_points / sel / intersect_line / locate_nearest_*) ---- */
 /* Nearest-neighbour index over n fixed points xy_dev float64 [n, 2] (a device pointer): what Ugrid2d.node_kdtree /
  * edge_kdtree / face_kdtree are in the reference (scipy KDTree, xugrid/ugrid/ugridbase.py:1113-1123, ugrid2d.py:902-906).

@@ -11,6 +11,7 @@ from ._lib import XugridAmdError  # noqa: F401
 from .burn import burn_vector_geometry, locate_polygon  # noqa: F401
 from .celltree import CellTree2d  # noqa: F401
 from .fill import laplace_interpolate  # noqa: F401
+from .graph import binary_dilation, binary_erosion, connected_components  # noqa: F401
 from .regrid import (  # noqa: F401
     BarycentricInterpolator,
     CentroidLocatorRegridder,
@@ -20,6 +21,7 @@ from .regrid import (  # noqa: F401
     RelativeOverlapRegridder,
 )
 from .sparse import MatrixCOO, MatrixCSR  # noqa: F401
+from .topology import DeviceTopology  # noqa: F401
 from .ugrid1d import Ugrid1d  # noqa: F401
 from .ugrid2d import Ugrid2d  # noqa: F401
 

@@ -125,6 +125,17 @@ SIGNATURES = {
     "xr_graph_destroy": (c_int, [vp]),
     "xr_graph_laplace_fill_dev": (c_int, [vp, vp, vp, c_i64, c_int, c_f64, c_f64, c_i64, c_i64, vp, vp]),
     "xr_nearest_fill_dev": (c_int, [vp, c_i64, vp, vp, c_i64, c_f64]),
+    "xr_topology_create": (c_int, [vp, p_vp]),
+    "xr_topology_info": (c_int, [vp, p_i64, p_i64, p_i64, p_i64, p_i64]),
+    "xr_topology_long_nodes": (c_int, [vp, p_i64]),
+    "xr_topology_download": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "xr_topology_edge_xy_dev": (c_int, [vp, vp]),
+    "xr_topology_exterior_face_dev": (c_int, [vp, vp]),
+    "xr_topology_destroy": (c_int, [vp]),
+    "xr_graph_from_topology": (c_int, [vp, c_int, p_vp]),
+    "xr_graph_label_rounds": (c_int, [vp, p_i64]),
+    "xr_graph_components_dev": (c_int, [vp, vp, p_i64]),
+    "xr_graph_binary_iterate_dev": (c_int, [vp, vp, vp, c_i64, c_int, c_i64, vp, vp]),
     "xr_nn_create_dev": (c_int, [vp, c_i64, p_vp]),
     "xr_nn_create_mesh": (c_int, [vp, c_int, p_vp]),
     "xr_nn_info": (c_int, [vp, p_i64, p_i64]),

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "xr_objects.h"
+#include "xr_topology.h"
 
 struct xr_graph {
     int64_t n = 0, nnz = 0;
@@ -25,6 +26,7 @@ struct xr_graph {
     xr::DevBuf<double> data;     // [nnz] weights (1.0 when the caller gave none)
     xr::DevBuf<int32_t> labels;  // [n] connected component: the smallest node id of the component
     bool has_data = false;
+    int64_t label_rounds = 0; // rounds of k_label_round the labelling took (0: labels given by the caller)
 };
 
 namespace xr {
@@ -468,6 +470,21 @@ static void nearest_group(const double *xy, int64_t n, const double *in, double 
     }
 }
 
+// labels = the smallest member id of every component: rounds of k_label_round until none lowers a label
+static void label_components(xr_graph *g) {
+    const int64_t n = g->n;
+    if (n <= 0) return;
+    DevBuf<int32_t> changed(1);
+    XR_LAUNCH("label_init", k_label_init, dim3(div_up(n, FB)), dim3(FB), 0, g->labels.get(), n);
+    for (;;) {
+        fill_i32(changed.get(), 0, 1);
+        XR_LAUNCH("label_round", k_label_round, dim3(div_up(n, FB)), dim3(FB), 0, g->indptr.get(), g->indices.get(), n,
+                  g->labels.get(), changed.get());
+        g->label_rounds++;
+        if (!read_scalar(changed.get())) break;
+    }
+}
+
 static void laplace_fill(const xr_graph *g, const double *in_dev, double *out_dev, int64_t K, int use_weights, double atol,
                          double rtol, int64_t maxiter, int64_t chunk, int64_t *iterations_out, int *status_out);
 static void nearest_fill(const double *xy_dev, int64_t n, const double *in_dev, double *out_dev, int64_t K, double max_distance);
@@ -516,14 +533,7 @@ int xr_graph_from_csr(const int64_t *indptr, const int64_t *indices, const doubl
     if (labels) {
         if (n) h2d(g->labels.get(), lb.data(), sizeof(int32_t) * lb.size());
     } else if (n) {
-        DevBuf<int32_t> changed(1);
-        XR_LAUNCH("label_init", k_label_init, dim3(div_up(n, FB)), dim3(FB), 0, g->labels.get(), n);
-        for (;;) {
-            fill_i32(changed.get(), 0, 1);
-            XR_LAUNCH("label_round", k_label_round, dim3(div_up(n, FB)), dim3(FB), 0, g->indptr.get(), g->indices.get(), n,
-                      g->labels.get(), changed.get());
-            if (!read_scalar(changed.get())) break;
-        }
+        label_components(g.get());
     }
     stream_sync();
     *out = g.release();
@@ -665,3 +675,158 @@ static void nearest_fill(const double *xy_dev, int64_t n, const double *in_dev, 
         if (mismatch[(size_t)k]) nearest_group(xy_dev, n, in_dev, out_dev, std::vector<int64_t>{k}, max_distance);
 }
 } // namespace xr
+
+// ---------------------------------------------------------------------------------------------
+// graphs from the device topology; graph operations
+// ---------------------------------------------------------------------------------------------
+namespace xr {
+
+// d[e] = distance between the points of row i and column indices[e] (ugridbase.py:962-970: sqrt(dx*dx + dy*dy) of col - row);
+// block partial of their sum
+__global__ void __launch_bounds__(FB)
+k_graph_distance(const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices, const double *__restrict__ xy, int64_t n,
+                 double *__restrict__ d, double *__restrict__ partial) {
+    __shared__ double sh[FB / 64];
+    const int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
+    double sum = 0.0;
+    if (i < n) {
+        const double x = xy[2 * i], y = xy[2 * i + 1];
+        for (int e = indptr[i]; e < indptr[i + 1]; e++) {
+            const int64_t j = indices[e];
+            const double dx = xy[2 * j] - x, dy = xy[2 * j + 1] - y;
+            const double v = sqrt(dx * dx + dy * dy);
+            d[e] = v;
+            sum += v;
+        }
+    }
+    const double t = block_sum(sum, sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = t;
+}
+
+// one block: the partials in a fixed order -> total[0]
+__global__ void __launch_bounds__(FB) k_graph_distance_total(const double *__restrict__ partial, int nb, double *__restrict__ total) {
+    __shared__ double sh[FB / 64];
+    const double t = sum_partials(partial, nb, sh);
+    if (threadIdx.x == 0) total[0] = t;
+}
+
+// d -> mean(d) / d
+__global__ void __launch_bounds__(FB) k_graph_weights(double *__restrict__ d, int64_t nnz, const double *__restrict__ total) {
+    const int64_t e = (int64_t)blockIdx.x * FB + threadIdx.x;
+    if (e < nnz) d[e] = (total[0] / (double)nnz) / d[e];
+}
+
+__global__ void __launch_bounds__(FB) k_comp_flag(const int32_t *__restrict__ lab, int64_t n, int32_t *__restrict__ flag) {
+    const int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
+    if (i < n) flag[i] = lab[i] == (int32_t)i;
+}
+// rank[i] = components whose smallest member lies below i; a member's number is the rank of its label
+__global__ void __launch_bounds__(FB)
+k_comp_number(const int32_t *__restrict__ lab, const int32_t *__restrict__ rank, int64_t n, int64_t *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
+    if (i < n) out[i] = rank[lab[i]];
+}
+
+// one Jacobi step of the binary iteration on a snapshot: in -> out, slice on gridDim.y
+__global__ void __launch_bounds__(FB)
+k_binary_step(const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices, int64_t n, const uint8_t *__restrict__ in,
+              uint8_t *__restrict__ out, uint8_t value, const uint8_t *__restrict__ mask, const uint8_t *__restrict__ exterior) {
+    const int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t *src = in + (int64_t)blockIdx.y * n;
+    const bool own = src[i] != 0;
+    bool differs = false;
+    for (int e = indptr[i]; e < indptr[i + 1] && !differs; e++) differs = (src[indices[e]] != 0) != own;
+    uint8_t r = differs ? value : (uint8_t)own;
+    if (mask && mask[i]) r = !value; // (sic: the reference's `output[mask] = not value`)
+    if (exterior && exterior[i]) r = value;
+    out[(int64_t)blockIdx.y * n + i] = r;
+}
+
+} // namespace xr
+
+extern "C" {
+
+int xr_graph_from_topology(const xr_topology *t, int facet, xr_graph **out) {
+    XR_API_BEGIN
+    XR_REQUIRE(t && out, XR_ERR_INVALID, "xr_graph_from_topology: NULL argument");
+    XR_REQUIRE(facet == XR_FACET_NODE || facet == XR_FACET_FACE, XR_ERR_INVALID,
+               "xr_graph_from_topology: facet must be XR_FACET_NODE or XR_FACET_FACE");
+    XR_REQUIRE(t->n_nonmanifold == 0, XR_ERR_INVALID, "xr_graph_from_topology: the mesh has edges with more than two faces");
+    const bool face = facet == XR_FACET_FACE;
+    const int64_t n = face ? t->n_face : t->n_node, nnz = face ? t->ff_nnz : t->nn_nnz;
+    const int32_t *ptr = face ? t->ff_ptr.get() : t->nn_ptr.get(), *idx = face ? t->ff_idx.get() : t->nn_idx.get();
+    Building<xr_graph> g;
+    g->n = n, g->nnz = nnz, g->has_data = true;
+    g->indptr.alloc((size_t)n + 1);
+    g->indices.alloc((size_t)std::max<int64_t>(nnz, 1));
+    g->data.alloc((size_t)std::max<int64_t>(nnz, 1));
+    g->labels.alloc((size_t)std::max<int64_t>(n, 1));
+    XR_HIP(hipMemcpyAsync(g->indptr.get(), ptr, sizeof(int32_t) * (size_t)(n + 1), hipMemcpyDeviceToDevice, launch_stream()));
+    if (nnz > 0) {
+        XR_HIP(hipMemcpyAsync(g->indices.get(), idx, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToDevice, launch_stream()));
+        const auto centroids = face ? mesh_centroids_shared(t->mesh) : nullptr;
+        const double *xy = face ? centroids->get() : t->mesh->node_xy.get();
+        const unsigned nb = div_up(n, FB);
+        DevBuf<double> partial((size_t)nb + 1);
+        XR_LAUNCH("graph_distance", k_graph_distance, dim3(nb), dim3(FB), 0, g->indptr.get(), g->indices.get(), xy, n, g->data.get(),
+                  partial.get());
+        XR_LAUNCH("graph_distance_total", k_graph_distance_total, dim3(1), dim3(FB), 0, partial.get(), (int)nb, partial.get() + nb);
+        XR_LAUNCH("graph_weights", k_graph_weights, dim3(div_up(nnz, FB)), dim3(FB), 0, g->data.get(), nnz, partial.get() + nb);
+    }
+    label_components(g.get());
+    stream_sync();
+    *out = g.release();
+    XR_API_END
+}
+
+int xr_graph_label_rounds(const xr_graph *g, int64_t *rounds) {
+    XR_API_BEGIN
+    XR_REQUIRE(g && rounds, XR_ERR_INVALID, "xr_graph_label_rounds: NULL argument");
+    *rounds = g->label_rounds;
+    XR_API_END
+}
+
+int xr_graph_components_dev(const xr_graph *g, int64_t *labels_dev, int64_t *n_components) {
+    XR_API_BEGIN
+    XR_REQUIRE(g && n_components && (labels_dev || g->n == 0), XR_ERR_INVALID, "xr_graph_components_dev: NULL argument");
+    const int64_t n = g->n;
+    *n_components = 0;
+    if (n > 0) {
+        DevBuf<int32_t> flag((size_t)n), rank((size_t)n + 1);
+        XR_LAUNCH("comp_flag", k_comp_flag, dim3(div_up(n, FB)), dim3(FB), 0, g->labels.get(), n, flag.get());
+        exclusive_scan_i32(flag.get(), rank.get(), n);
+        XR_LAUNCH("comp_number", k_comp_number, dim3(div_up(n, FB)), dim3(FB), 0, g->labels.get(), rank.get(), n, labels_dev);
+        *n_components = read_scalar(rank.get() + n);
+    }
+    XR_API_END
+}
+
+int xr_graph_binary_iterate_dev(const xr_graph *g, const uint8_t *in_dev, uint8_t *out_dev, int64_t K, int value,
+                                int64_t iterations, const uint8_t *mask_dev, const uint8_t *exterior_dev) {
+    XR_API_BEGIN
+    XR_REQUIRE(g, XR_ERR_INVALID, "xr_graph_binary_iterate_dev: NULL handle");
+    XR_REQUIRE(K >= 0 && K < 65536, XR_ERR_INVALID, "xr_graph_binary_iterate_dev: K must be in [0, 65536)");
+    XR_REQUIRE(iterations >= 1, XR_ERR_INVALID, "xr_graph_binary_iterate_dev: iterations must be at least 1");
+    const int64_t n = g->n;
+    XR_REQUIRE((in_dev && out_dev) || n == 0 || K == 0, XR_ERR_INVALID, "xr_graph_binary_iterate_dev: NULL data");
+    if (n > 0 && K > 0) {
+        // ping-pong between out_dev and one scratch buffer so that the last step lands in out_dev; the input is only read
+        DevBuf<uint8_t> scratch(iterations > 1 ? (size_t)(n * K) : 1);
+        uint8_t *buf[2] = {out_dev, scratch.get()};
+        int at = (int)((iterations - 1) & 1); // step s writes buf[(iterations - 1 - s) & 1]
+        const uint8_t *src = in_dev;
+        const dim3 grid(div_up(n, FB), (unsigned)K);
+        for (int64_t s = 0; s < iterations; s++) {
+            XR_LAUNCH("binary_step", k_binary_step, grid, dim3(FB), 0, g->indptr.get(), g->indices.get(), n, src, buf[at],
+                      (uint8_t)(value != 0), mask_dev, s == 0 ? exterior_dev : nullptr);
+            src = buf[at];
+            at ^= 1;
+        }
+        stream_sync(); // (the scratch goes back to the pool behind its last reader)
+    }
+    dev_call_done();
+    XR_API_END
+}
+
+} // extern "C"

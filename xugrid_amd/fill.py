@@ -48,6 +48,30 @@ class DeviceGraph:
         self._h = handle
         self.n, self.nnz, self.has_weights = n, indices.size, data is not None
 
+    @classmethod
+    def from_handle(cls, handle, has_weights):
+        """Wrap an ``xr_graph`` made by the library (``DeviceTopology.graph``: nothing came from the host)."""
+        self = object.__new__(cls)
+        n, nnz = ctypes.c_int64(), ctypes.c_int64()
+        check(_lib.load().xr_graph_info(handle, ctypes.byref(n), ctypes.byref(nnz)))
+        self._h = handle
+        self.n, self.nnz, self.has_weights = n.value, nnz.value, has_weights
+        return self
+
+    def label_rounds(self):
+        """Rounds of minimum-label propagation the component labelling took (0: the labels were given)."""
+        rounds = ctypes.c_int64()
+        check(_lib.load().xr_graph_label_rounds(self._h, ctypes.byref(rounds)))
+        return rounds.value
+
+    def download(self):
+        """-> (indptr, indices, data) as numpy."""
+        indptr, indices = np.empty(self.n + 1, dtype=np.int64), np.empty(self.nnz, dtype=np.int64)
+        data = np.empty(self.nnz, dtype=np.float64)
+        check(_lib.load().xr_graph_download(self._h, indptr.ctypes.data_as(ctypes.c_void_p), indices.ctypes.data_as(ctypes.c_void_p),
+                                            data.ctypes.data_as(ctypes.c_void_p), None))
+        return indptr, indices, data
+
     def labels(self):
         out = np.empty(self.n, dtype=np.int64)
         check(_lib.load().xr_graph_download(self._h, None, None, None, out.ctypes.data_as(ctypes.c_void_p)))
@@ -203,15 +227,23 @@ class GridFill:
         self.graphs = {}
         self.points = {}
 
-    def graph(self, key, make_connectivity, coordinates):
+    def graph(self, key, make_connectivity, coordinates, topology=None):
+        """``topology``: a manifold ``DeviceTopology`` -- the graph is then made from it on the device (no scipy matrix, no
+        host weights, no upload); otherwise from the host connectivity."""
         if key not in self.graphs:
-            conn = make_connectivity()
-            self.graphs[key] = DeviceGraph(conn, weights=connectivity_weights(conn, coordinates()))
+            if topology is not None:
+                self.graphs[key] = topology.graph(key)
+            else:
+                conn = make_connectivity()
+                self.graphs[key] = DeviceGraph(conn, weights=connectivity_weights(conn, coordinates()))
         return self.graphs[key]
 
     def xy(self, key, coordinates):
         if key not in self.points:
-            self.points[key] = engine.DeviceArray.from_host(np.ascontiguousarray(coordinates(), dtype=np.float64))
+            xy = coordinates()  # (a DeviceArray where the points are in HBM already: the edge midpoints of a device topology)
+            if not isinstance(xy, engine.DeviceArray):
+                xy = engine.DeviceArray.from_host(np.ascontiguousarray(xy, dtype=np.float64))
+            self.points[key] = xy
         return self.points[key]
 
 

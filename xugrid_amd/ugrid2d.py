@@ -10,7 +10,7 @@ import numpy as np
 
 import ctypes
 
-from . import _lib, connectivity, fill, sample
+from . import _lib, connectivity, fill, graph, sample
 from .celltree import CellTree2d
 from .engine import FloatDType, IntDType
 
@@ -172,6 +172,7 @@ class Ugrid2d:
         self._voronoi_device_cache = None
         self.__dict__.pop("_fill_cache", None)
         self.__dict__.pop("_sample_cache", None)
+        self.__dict__.pop("_topology_cache", None)
 
     @property
     def device_mesh(self):
@@ -287,8 +288,72 @@ class Ugrid2d:
         if facet == "node":
             return self.node_coordinates
         if facet == "edge":
-            return self.edge_coordinates
+            return self._edge_points()
         return self.centroids
+
+    def _edge_points(self):
+        """Edge midpoints for the nearest fill and the nearest index: a host array here, a device array where the grid has
+        its topology in HBM (DeviceUgrid2d)."""
+        return self.edge_coordinates
+
+    def _fill_topology(self):
+        """The ``DeviceTopology`` the fill graphs are made from, or None: the host connectivity (host-built grids)."""
+        return None
+
+    def _graph(self, facet):
+        """The device graph (structure, weights, component labels) of the faces or nodes, built on first use and kept."""
+        conn = (lambda: self.node_node_connectivity) if facet == "node" else (lambda: self.face_face_connectivity)
+        return self._fill().graph(facet, conn, lambda: self._fill_coordinates(facet), topology=self._fill_topology())
+
+    # ---- the edge topology in HBM and the graph operations on it (xugrid_amd/topology.py, xugrid_amd/graph.py)
+    def device_topology(self):
+        """The grid's ``DeviceTopology``: edges and adjacencies built on the device from the device mesh (kept until
+        ``drop_device_caches``)."""
+        from .topology import DeviceTopology
+
+        cache = self.__dict__.get("_topology_cache")
+        if cache is None:
+            cache = self.__dict__["_topology_cache"] = DeviceTopology(self.device_mesh)
+        return cache
+
+    @property
+    def exterior_edges(self):
+        """Ascending indices of the edges with one face only (ugrid2d.py:877-887)."""
+        edge_face = self.edge_face_connectivity
+        if edge_face.shape[1] < 2:  # (the host table is as wide as the busiest edge: no edge has two faces)
+            return np.arange(edge_face.shape[0])
+        return np.nonzero(edge_face[:, 1] == FILL_VALUE)[0]
+
+    @property
+    def exterior_faces(self):
+        """Ascending indices of the faces with an unshared edge (ugrid2d.py:889-900)."""
+        faces = self.edge_face_connectivity[self.exterior_edges].ravel()
+        return np.unique(faces[faces != FILL_VALUE])
+
+    def _exterior_face_flags(self):
+        flags = np.zeros(self.n_face, dtype=bool)
+        flags[self.exterior_faces] = True
+        return flags
+
+    def connected_components(self, dim=None):
+        """int64 ``(n,)`` component number of every face (default) or node, numbered like
+        ``scipy.sparse.csgraph.connected_components`` on the adjacency (dataarray_accessor.py:691-708); labelled on the device."""
+        facet = fill.resolve_dim(self, dim, ("node", "face"))
+        return graph.components(self._graph(facet))
+
+    def _binary(self, data, value, iterations, mask, border_value):
+        exterior = self._exterior_face_flags() if bool(border_value) == bool(value) else None
+        return graph.binary_iterate(self._graph("face"), data, value, iterations, mask, exterior, border_value)
+
+    def binary_dilation(self, data, iterations=1, mask=None, border_value=False):
+        """Expand the True entries of the bool face data ``data`` (..., n_face) over the face adjacency, ``iterations`` times
+        (dataarray_accessor.py:643-665); leading dims are independent slices.  ``mask`` (n_face,) and ``border_value`` as
+        in the reference (xugrid_amd/graph.py).  numpy in -> numpy out, device bool / uint8 in -> the same kind out."""
+        return self._binary(data, True, iterations, mask, border_value)
+
+    def binary_erosion(self, data, iterations=1, mask=None, border_value=False):
+        """Shrink the True entries of ``data`` (dataarray_accessor.py:667-689); see ``binary_dilation``."""
+        return self._binary(data, False, iterations, mask, border_value)
 
     def laplace_interpolate(self, data, dim=None, xy_weights=True, direct_solve=False, delta=0.0, relax=0.0, rtol=0.0,
                             atol=1e-4, maxiter=500):
@@ -300,9 +365,7 @@ class Ugrid2d:
         if facet == "edge":
             raise ValueError("Laplace interpolation along edges is not allowed.")
         fill._check_ilu_options(delta, relax)
-        conn = (lambda: self.node_node_connectivity) if facet == "node" else (lambda: self.face_face_connectivity)
-        graph = self._fill().graph(facet, conn, lambda: self._fill_coordinates(facet))
-        return fill.laplace_fill(graph, data, xy_weights, direct_solve, delta, relax, atol, rtol, maxiter)
+        return fill.laplace_fill(self._graph(facet), data, xy_weights, direct_solve, delta, relax, atol, rtol, maxiter)
 
     def interpolate_na(self, data, dim=None, method="nearest", max_distance=None):
         """Fill the NaN entries of ``data`` (..., n) along ``dim`` (default: faces) with the value of the nearest non-NaN
@@ -325,7 +388,7 @@ class Ugrid2d:
         """The nearest-neighbour index of a facet's points: nodes and face centroids are read from the device mesh where they
         are; edge midpoints come from ``edge_coordinates``."""
         if facet == "edge":
-            return self._sample().index(facet, lambda: sample.NearestIndex.from_points(self.edge_coordinates))
+            return self._sample().index(facet, lambda: sample.NearestIndex.from_points(self._edge_points()))
         return self._sample().index(facet, lambda: sample.NearestIndex.from_mesh(self.device_mesh, facet))
 
     def _locate_nearest(self, facet, points, max_distance=np.inf):
@@ -340,9 +403,8 @@ class Ugrid2d:
         return self._locate_nearest("node", points, max_distance)
 
     def locate_nearest_edge(self, points, max_distance=np.inf):
-        """... the nearest edge midpoint (ugridbase.py:1283-1303).  The edges are derived on the host
-        (``connectivity.edge_connectivity``), so on a grid made by ``from_device_arrays`` this facet -- and only this one --
-        materialises the host copy of the mesh."""
+        """... the nearest edge midpoint (ugridbase.py:1283-1303).  On a host-built grid the edges are derived on the host
+        (``connectivity.edge_connectivity``); a grid made by ``from_device_arrays`` takes them from its device topology."""
         return self._locate_nearest("edge", points, max_distance)
 
     def locate_nearest_face(self, points, max_distance=np.inf):
@@ -589,4 +651,49 @@ class DeviceUgrid2d(Ugrid2d):
         self._voronoi_device_cache = None
         self.__dict__.pop("_fill_cache", None)
         self.__dict__.pop("_sample_cache", None)
+        self.__dict__.pop("_topology_cache", None)
         self._celltree.device_mesh.invalidate()
+
+    # ---- edge connectivity from the device topology.  An edge with more than two faces does not fit its two-column tables: such
+    # a grid takes the host route of the base class (download the mesh, numpy), exactly as before.
+    def _fill_topology(self):
+        topology = self.device_topology()
+        return topology if topology.manifold else None
+
+    def _from_topology(name):  # noqa: N805  (property factory, used in the class body only)
+        def get(self):
+            topology = self._fill_topology()
+            if topology is None:
+                return getattr(Ugrid2d, name).fget(self)
+            return getattr(topology, name)
+
+        return property(get, doc=getattr(Ugrid2d, name).__doc__)
+
+    edge_node_connectivity = _from_topology("edge_node_connectivity")
+    face_edge_connectivity = _from_topology("face_edge_connectivity")
+    edge_face_connectivity = _from_topology("edge_face_connectivity")  # (always two columns; the host table has one when no edge is shared)
+    face_face_connectivity = _from_topology("face_face_connectivity")
+    node_node_connectivity = _from_topology("node_node_connectivity")
+    exterior_edges = _from_topology("exterior_edges")
+    exterior_faces = _from_topology("exterior_faces")
+    del _from_topology
+
+    @property
+    def n_edge(self):
+        topology = self._fill_topology()
+        return topology.n_edge if topology is not None else Ugrid2d.n_edge.fget(self)
+
+    @property
+    def edge_coordinates(self):
+        topology = self._fill_topology()
+        if topology is None:
+            return Ugrid2d.edge_coordinates.fget(self)
+        return topology.edge_coordinates_device().download()
+
+    def _edge_points(self):
+        topology = self._fill_topology()
+        return topology.edge_coordinates_device() if topology is not None else self.edge_coordinates
+
+    def _exterior_face_flags(self):
+        topology = self._fill_topology()
+        return topology.exterior_face_flags_device() if topology is not None else Ugrid2d._exterior_face_flags(self)
