@@ -239,6 +239,53 @@ def test_slice_grouping(slice0_has_nan):
         assert np.array_equal(out[k], data[k][brute_nearest(xy, data[k])]), k
 
 
+def brute_fill(xy, data, max_distance):
+    src = brute_nearest(xy, data, np.inf if max_distance is None else max_distance)
+    return np.where(src >= 0, data[np.maximum(src, 0)], np.nan)
+
+
+def test_nearest_fill_equals_brute_force_bit_for_bit():
+    """The whole fill -- index of the valid points, lookup of the null ones, gather -- against the argmin of
+    ``dx * dx + dy * dy`` over the valid points (lowest id on ties, strictly below ``max_distance``), from one point to
+    several blocks.  The points sit on an integer lattice of about n / 2 sites: neighbours tie and points coincide at
+    every size, and with ``max_distance`` one spacing only a coincident valid point may fill."""
+    rng = np.random.default_rng(26)
+    strict = 0
+    for n in (1, 63, 64, 65, 257, 1500):
+        side = int(np.ceil(np.sqrt(n / 2)))
+        site = rng.integers(0, side * side, n)
+        xy = np.column_stack([site % side, site // side]).astype(np.float64)
+        assert n == 1 or len(np.unique(site)) < n
+        grid = point_grid(xy)
+        values = rng.normal(size=(3, n))
+        half, other, single = rng.random(n) < 0.5, rng.random(n) < 0.5, np.ones(n, dtype=bool)
+        for m in (half, other, single):
+            m[rng.integers(0, n)] = False  # (at least one valid point; the only one of `single`)
+        masks = {"half": half, "none": np.zeros(n, dtype=bool), "single": single}
+        for max_distance in (None, 1.0):
+            for name, null in masks.items():
+                data = np.where(null, np.nan, values[0])
+                out = grid.interpolate_na(data, dim="node", max_distance=max_distance)
+                expected = brute_fill(xy, data, max_distance)
+                assert np.array_equal(out.view(np.int64), expected.view(np.int64)), (n, name, max_distance)
+                if max_distance is not None:  # nulls whose nearest valid point is exactly one spacing away stay null
+                    at_bound = null & ~np.isnan(brute_fill(xy, data, None)) & np.isnan(expected)
+                    at_bound &= ~np.isnan(brute_fill(xy, data, np.nextafter(1.0, 2.0)))
+                    strict += int(at_bound.sum())
+            batch = np.where(np.stack([half, other, half]), np.nan, values)  # slices 0 and 2 share a mask, 1 has its own
+            out = grid.interpolate_na(batch, dim="node", max_distance=max_distance)
+            expected = np.stack([brute_fill(xy, b, max_distance) for b in batch])
+            assert np.array_equal(out.view(np.int64), expected.view(np.int64)), (n, "batch", max_distance)
+    assert strict > 100
+    # two coincident valid points (ids 2 and 4) with different values: the null on them and the null beside them take the
+    # lower id's value, each valid point keeps its own
+    xy = np.array([[5.0, 5.0], [1.0, 0.0], [0.0, 0.0], [9.0, 2.0], [0.0, 0.0], [0.0, 0.0]])
+    data = np.array([1.5, np.nan, 20.0, -3.0, 10.0, np.nan])
+    out = point_grid(xy).interpolate_na(data, dim="node")
+    assert np.array_equal(out.view(np.int64), np.array([1.5, 20.0, 20.0, -3.0, 10.0, 20.0]).view(np.int64))
+    assert np.array_equal(out.view(np.int64), brute_fill(xy, data, None).view(np.int64))
+
+
 # ---- Laplace: component labels, CG iterates, spsolve on harder systems
 def csr(rows, cols, n):
     rows, cols = np.asarray(rows, dtype=np.int64), np.asarray(cols, dtype=np.int64)

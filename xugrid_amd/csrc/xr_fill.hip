@@ -10,12 +10,13 @@
 // dot product is a block partial combined in a fixed order, so results are bit-identical run to run and independent of K.
 // A slice that stops freezes; the host enqueues chunks of iterations and reads the K active words once per chunk.
 //
-// Nearest: one lane per null point searches a uniform grid of the valid points ring by ring (exact f64 squared distances,
-// lowest index among equidistant candidates).  Slices with the same NaN mask as slice 0 share one search.
+// Nearest: the null points of a slice are looked up in an xr_nn index of its valid points (xr_nn.h: exact f64 squared
+// distances, lowest index among equidistant candidates).  Slices with the same NaN mask as slice 0 share one search.
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
+#include "xr_nn.h"
 #include "xr_objects.h"
 #include "xr_topology.h"
 
@@ -290,178 +291,34 @@ k_nn_mask_cmp(const double *__restrict__ in, int64_t n, uint8_t *__restrict__ mi
     if ((a != a) != (b != b)) mismatch[k] = 1;
 }
 
-// per block: valid count, null count and the bbox of the valid points -> partial[b * 6 ..]
+// a valid entry keeps its own value; a null one takes the value at src (the search's answer, read for null entries only)
 __global__ void __launch_bounds__(FB)
-k_nn_stats(const double *__restrict__ xy, const double *__restrict__ v, int64_t n, double *__restrict__ partial) {
-    __shared__ double sh[6][FB / 64];
-    const int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
-    double c = 0.0, cn = 0.0, x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
-    if (i < n) {
-        if (v[i] == v[i]) {
-            c = 1.0;
-            x0 = x1 = xy[2 * i];
-            y0 = y1 = xy[2 * i + 1];
-        } else {
-            cn = 1.0;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        c += __shfl_xor(c, o, 64);
-        cn += __shfl_xor(cn, o, 64);
-        x0 = fmin(x0, __shfl_xor(x0, o, 64));
-        x1 = fmax(x1, __shfl_xor(x1, o, 64));
-        y0 = fmin(y0, __shfl_xor(y0, o, 64));
-        y1 = fmax(y1, __shfl_xor(y1, o, 64));
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        sh[0][w] = c, sh[1][w] = cn, sh[2][w] = x0, sh[3][w] = x1, sh[4][w] = y0, sh[5][w] = y1;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int u = 1; u < FB / 64; u++) {
-            sh[0][0] += sh[0][u], sh[1][0] += sh[1][u];
-            sh[2][0] = fmin(sh[2][0], sh[2][u]), sh[3][0] = fmax(sh[3][0], sh[3][u]);
-            sh[4][0] = fmin(sh[4][0], sh[4][u]), sh[5][0] = fmax(sh[5][0], sh[5][u]);
-        }
-        for (int u = 0; u < 6; u++) partial[(int64_t)blockIdx.x * 6 + u] = sh[u][0];
-    }
-}
-
-__global__ void __launch_bounds__(FB) k_nn_stats_final(const double *__restrict__ partial, int nb, double *__restrict__ out) {
-    if (threadIdx.x) return;
-    double a[6] = {0.0, 0.0, INFINITY, -INFINITY, INFINITY, -INFINITY};
-    for (int b = 0; b < nb; b++) {
-        const double *p = partial + (int64_t)b * 6;
-        a[0] += p[0], a[1] += p[1];
-        a[2] = fmin(a[2], p[2]), a[3] = fmax(a[3], p[3]), a[4] = fmin(a[4], p[4]), a[5] = fmax(a[5], p[5]);
-    }
-    for (int u = 0; u < 6; u++) out[u] = a[u];
-}
-
-struct NnGrid {
-    double x0, y0, inv_h, h;
-    int nx, ny;
-};
-
-__device__ __forceinline__ int nn_cell_x(const NnGrid &g, double x) {
-    const double t = (x - g.x0) * g.inv_h;
-    return t < 0.0 ? 0 : t >= (double)(g.nx - 1) ? g.nx - 1 : (int)t;
-}
-__device__ __forceinline__ int nn_cell_y(const NnGrid &g, double y) {
-    const double t = (y - g.y0) * g.inv_h;
-    return t < 0.0 ? 0 : t >= (double)(g.ny - 1) ? g.ny - 1 : (int)t;
-}
-
-__global__ void __launch_bounds__(FB)
-k_nn_count(const double *__restrict__ xy, const double *__restrict__ v, int64_t n, NnGrid g, int32_t *__restrict__ count) {
-    const int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
-    if (i >= n || v[i] != v[i]) return;
-    atomicAdd(&count[(int64_t)nn_cell_y(g, xy[2 * i + 1]) * g.nx + nn_cell_x(g, xy[2 * i])], 1);
-}
-
-__global__ void __launch_bounds__(FB)
-k_nn_scatter(const double *__restrict__ xy, const double *__restrict__ v, int64_t n, NnGrid g, const int32_t *__restrict__ start,
-             int32_t *__restrict__ cursor, int32_t *__restrict__ items) {
-    const int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
-    if (i >= n || v[i] != v[i]) return;
-    const int64_t c = (int64_t)nn_cell_y(g, xy[2 * i + 1]) * g.nx + nn_cell_x(g, xy[2 * i]);
-    items[start[c] + atomicAdd(&cursor[c], 1)] = (int32_t)i;
-}
-
-// one lane per null point: rings of cells around the point's cell.  After ring R every point within the block of cells
-// [cx - R, cx + R] x [cy - R, cy + R] has been seen; an unseen point is at least as far as the nearest side of that block.
-__global__ void __launch_bounds__(FB)
-k_nn_search(const double *__restrict__ xy, const double *__restrict__ v, int64_t n, NnGrid g, const int32_t *__restrict__ start,
-            const int32_t *__restrict__ items, double md2, double max_distance, int32_t *__restrict__ src) {
-    const int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
-    if (i >= n) return;
-    if (v[i] == v[i]) {
-        src[i] = (int32_t)i;
-        return;
-    }
-    const double px = xy[2 * i], py = xy[2 * i + 1];
-    const int cx = nn_cell_x(g, px), cy = nn_cell_y(g, py);
-    const int rmax = max(g.nx, g.ny);
-    double best = INFINITY;
-    int32_t bj = -1;
-    for (int R = 0; R <= rmax; R++) {
-        const int ylo = cy - R, yhi = cy + R, xlo = cx - R, xhi = cx + R;
-        for (int yy = max(ylo, 0); yy <= min(yhi, g.ny - 1); yy++) {
-            const bool edge_row = yy == ylo || yy == yhi;
-            // the ring's cells of this row: all of it on the two edge rows, its two ends elsewhere
-            for (int xx = edge_row ? max(xlo, 0) : xlo; xx <= min(xhi, g.nx - 1); xx = edge_row || xx == xhi ? xx + 1 : xhi) {
-                if (xx < 0) continue;
-                const int64_t c = (int64_t)yy * g.nx + xx;
-                for (int e = start[c]; e < start[c + 1]; e++) {
-                    const int32_t j = items[e];
-                    const double dx = xy[2 * (int64_t)j] - px, dy = xy[2 * (int64_t)j + 1] - py;
-                    const double d2 = dx * dx + dy * dy;
-                    if (d2 < md2 && (d2 < best || (d2 == best && j < bj))) {
-                        best = d2;
-                        bj = j;
-                    }
-                }
-            }
-        }
-        // distance from the point to the outside of the block seen so far
-        const double lx = px - (g.x0 + (double)(cx - R) * g.h), hx = g.x0 + (double)(cx + R + 1) * g.h - px;
-        const double ly = py - (g.y0 + (double)(cy - R) * g.h), hy = g.y0 + (double)(cy + R + 1) * g.h - py;
-        const double lb = fmax(0.0, fmin(fmin(lx, hx), fmin(ly, hy)));
-        if (lb * lb > best || lb >= max_distance) break;
-    }
-    src[i] = bj;
-}
-
-__global__ void __launch_bounds__(FB)
-k_nn_gather(const double *__restrict__ in, int64_t n, const int32_t *__restrict__ src, const int64_t *__restrict__ slices,
+k_nn_gather(const double *__restrict__ in, int64_t n, const int64_t *__restrict__ src, const int64_t *__restrict__ slices,
             double *__restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
     if (i >= n) return;
     const int64_t k = slices[blockIdx.y];
-    const int32_t j = src[i];
-    out[k * n + i] = j >= 0 ? in[k * n + j] : NAN;
+    double v = in[k * n + i];
+    if (v != v) {
+        const int64_t j = src[i];
+        v = j >= 0 ? in[k * n + j] : NAN;
+    }
+    out[k * n + i] = v;
 }
 
+// the slices share the NaN mask of slices[0]: an index of its valid points (xr_nn.h), one search for its null points
 static void nearest_group(const double *xy, int64_t n, const double *in, double *out, const std::vector<int64_t> &slices,
                           double max_distance) {
-    const int64_t k0 = slices[0];
-    const double *v = in + k0 * n;
+    const double *v = in + slices[0] * n;
+    const NnExtent valid = nn_extent(xy, n, v);
+    XR_REQUIRE(valid.n > 0, XR_ERR_INVALID, "All values are NA.");
+    DevBuf<int64_t> src((size_t)n);
+    std::unique_ptr<xr_nn> nn;
+    if (valid.n < n) { // (without a null entry there is nothing to build or search)
+        nn.reset(nn_build(xy, n, v, valid));
+        nn_query(nn.get(), xy, n, max_distance, src.get(), v, n - valid.n);
+    }
     const unsigned nb = div_up(n, FB);
-    DevBuf<double> partial((size_t)nb * 6), stats(6);
-    XR_LAUNCH("nn_stats", k_nn_stats, dim3(nb), dim3(FB), 0, xy, v, n, partial.get());
-    XR_LAUNCH("nn_stats_final", k_nn_stats_final, dim3(1), dim3(64), 0, partial.get(), (int)nb, stats.get());
-    double h[6];
-    d2h(h, stats.get(), sizeof(h));
-    const int64_t nv = (int64_t)h[0], nnull = (int64_t)h[1];
-    XR_REQUIRE(nv > 0, XR_ERR_INVALID, "All values are NA.");
-    NnGrid g{};
-    const double w = std::max(h[3] - h[2], 0.0), ht = std::max(h[5] - h[4], 0.0);
-    const double target = std::max<double>(1.0, (double)nv / 2.0); // ~2 valid points per cell
-    double cell = std::sqrt(std::max(w * ht, 0.0) / target);
-    if (!(cell > 0.0)) cell = std::max(std::max(w, ht) / target, 0.0);
-    if (!(cell > 0.0) || !std::isfinite(cell)) cell = 1.0;
-    int64_t nx = std::min<int64_t>((int64_t)(w / cell) + 1, 1 << 15), ny = std::min<int64_t>((int64_t)(ht / cell) + 1, 1 << 15);
-    while (nx * ny > 4 * nv + 16) { // (degenerate boxes)
-        cell *= 1.5;
-        nx = (int64_t)(w / cell) + 1;
-        ny = (int64_t)(ht / cell) + 1;
-    }
-    g.x0 = h[2], g.y0 = h[4], g.h = cell, g.inv_h = 1.0 / cell, g.nx = (int)nx, g.ny = (int)ny;
-    const int64_t nc = nx * ny;
-    DevBuf<int32_t> count_cursor(2 * (size_t)nc), start((size_t)nc + 1), items((size_t)nv), src((size_t)n);
-    fill_i32(count_cursor.get(), 0, 2 * nc);
-    if (nnull > 0) {
-        XR_LAUNCH("nn_count", k_nn_count, dim3(nb), dim3(FB), 0, xy, v, n, g, count_cursor.get());
-        exclusive_scan_i32(count_cursor.get(), start.get(), nc);
-        XR_LAUNCH("nn_scatter", k_nn_scatter, dim3(nb), dim3(FB), 0, xy, v, n, g, start.get(), count_cursor.get() + nc, items.get());
-        const double md2 = std::isinf(max_distance) ? INFINITY : max_distance * max_distance;
-        XR_LAUNCH("nn_search", k_nn_search, dim3(nb), dim3(FB), 0, xy, v, n, g, start.get(), items.get(), md2, max_distance,
-                  src.get());
-    } else {
-        XR_LAUNCH("nn_identity", k_label_init, dim3(nb), dim3(FB), 0, src.get(), n);
-    }
     DevBuf<int64_t> sl(slices.size());
     h2d(sl.get(), slices.data(), sizeof(int64_t) * slices.size());
     for (size_t s0 = 0; s0 < slices.size(); s0 += 65535) {

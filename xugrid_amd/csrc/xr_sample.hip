@@ -7,12 +7,14 @@
 // in cell order next to the caller's ids, so a query that walks a cell reads consecutive 16-byte pairs.  One lane per query
 // walks rings of cells around the query's cell (exact f64 squared distances, strictly below max_distance, lowest id among
 // equidistant points).  From NN_SORT_MIN_QUERIES queries on the queries are first binned by index cell (counting sort) and
-// searched in that order: neighbouring lanes then walk the same cells.  The answers do not depend on either order.
+// searched in that order: neighbouring lanes then walk the same cells.  The answers do not depend on either order.  The
+// nearest fill (xr_fill.hip) is the second caller: it indexes the valid points of a slice and looks up the null ones, both
+// picked by the slice's values (xr_nn.h).
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
-#include "xr_objects.h"
+#include "xr_nn.h"
 
 namespace xr {
 
@@ -27,11 +29,6 @@ static constexpr int SB = 256; // threads per block
 // about 384 000 queries on (even there, a fifth faster at 512 000), so the constant sits at the first size the sort clearly wins.
 static constexpr int64_t NN_SORT_MIN_QUERIES = 1 << 19;
 
-struct SampleGrid {
-    double x0, y0, inv_h, h;
-    int nx, ny;
-};
-
 // (comparisons written so that a NaN coordinate lands in cell 0)
 __device__ __forceinline__ int sp_cell_x(const SampleGrid &g, double x) {
     const double t = (x - g.x0) * g.inv_h;
@@ -45,74 +42,78 @@ __device__ __forceinline__ int64_t sp_cell(const SampleGrid &g, double2 p) {
     return (int64_t)sp_cell_y(g, p.y) * g.nx + sp_cell_x(g, p.x);
 }
 
-// per block: the bounding box of its points -> partial[b * 4 ..] = xmin, xmax, ymin, ymax (NaN coordinates are passed over)
-__global__ void __launch_bounds__(SB) k_sp_bbox(const double2 *__restrict__ xy, int64_t n, double *__restrict__ partial) {
-    __shared__ double sh[4][SB / 64];
+// the subset a pass works on: every point without `values`, else the points whose value is NaN (want_nan) or is not
+__device__ __forceinline__ bool sp_takes_part(const double *__restrict__ values, bool want_nan, int64_t i) {
+    return !values || (values[i] != values[i]) == want_nan;
+}
+
+// block reduction of a box and a count; thread 0 writes out[0..4] = xmin, xmax, ymin, ymax, count.  c is the count of the
+// caller's WAVE already: the kernel over the points lives on its cross-lane operations (12.4 us for 1M points with the four
+// box values, 15.1 us with a fifth value in the butterfly), and a ballot counts a wave for nothing.
+__device__ __forceinline__ void sp_box_reduce(double x0, double x1, double y0, double y1, double c, double *__restrict__ out) {
+    __shared__ double sh[5][SB / 64];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        x0 = fmin(x0, __shfl_xor(x0, o, 64));
+        x1 = fmax(x1, __shfl_xor(x1, o, 64));
+        y0 = fmin(y0, __shfl_xor(y0, o, 64));
+        y1 = fmax(y1, __shfl_xor(y1, o, 64));
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) sh[0][w] = x0, sh[1][w] = x1, sh[2][w] = y0, sh[3][w] = y1, sh[4][w] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int u = 1; u < SB / 64; u++) {
+            sh[0][0] = fmin(sh[0][0], sh[0][u]), sh[1][0] = fmax(sh[1][0], sh[1][u]);
+            sh[2][0] = fmin(sh[2][0], sh[2][u]), sh[3][0] = fmax(sh[3][0], sh[3][u]);
+            sh[4][0] += sh[4][u];
+        }
+        for (int u = 0; u < 5; u++) out[u] = sh[u][0];
+    }
+}
+
+// per block: the bounding box of its points that take part and their number -> partial[b * 5 ..] (NaN coordinates are
+// passed over by the box and counted)
+__global__ void __launch_bounds__(SB)
+k_sp_bbox(const double2 *__restrict__ xy, const double *__restrict__ values, int64_t n, double *__restrict__ partial) {
     const int64_t i = (int64_t)blockIdx.x * SB + threadIdx.x;
     double x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
-    if (i < n) {
+    const bool mine = i < n && sp_takes_part(values, false, i);
+    if (mine) {
         const double2 p = xy[i];
         x0 = fmin(x0, p.x), x1 = fmax(x1, p.x), y0 = fmin(y0, p.y), y1 = fmax(y1, p.y);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        x0 = fmin(x0, __shfl_xor(x0, o, 64));
-        x1 = fmax(x1, __shfl_xor(x1, o, 64));
-        y0 = fmin(y0, __shfl_xor(y0, o, 64));
-        y1 = fmax(y1, __shfl_xor(y1, o, 64));
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) sh[0][w] = x0, sh[1][w] = x1, sh[2][w] = y0, sh[3][w] = y1;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int u = 1; u < SB / 64; u++) {
-            sh[0][0] = fmin(sh[0][0], sh[0][u]), sh[1][0] = fmax(sh[1][0], sh[1][u]);
-            sh[2][0] = fmin(sh[2][0], sh[2][u]), sh[3][0] = fmax(sh[3][0], sh[3][u]);
-        }
-        for (int u = 0; u < 4; u++) partial[(int64_t)blockIdx.x * 4 + u] = sh[u][0];
-    }
+    sp_box_reduce(x0, x1, y0, y1, (double)__popcll(__ballot(mine)), partial + (int64_t)blockIdx.x * 5);
 }
 
 __global__ void __launch_bounds__(SB) k_sp_bbox_final(const double *__restrict__ partial, int nb, double *__restrict__ out) {
-    __shared__ double sh[4][SB / 64];
-    double x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
+    double x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY, c = 0.0;
     for (int b = threadIdx.x; b < nb; b += SB) {
-        const double *p = partial + (int64_t)b * 4;
-        x0 = fmin(x0, p[0]), x1 = fmax(x1, p[1]), y0 = fmin(y0, p[2]), y1 = fmax(y1, p[3]);
+        const double *p = partial + (int64_t)b * 5;
+        x0 = fmin(x0, p[0]), x1 = fmax(x1, p[1]), y0 = fmin(y0, p[2]), y1 = fmax(y1, p[3]), c += p[4];
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        x0 = fmin(x0, __shfl_xor(x0, o, 64));
-        x1 = fmax(x1, __shfl_xor(x1, o, 64));
-        y0 = fmin(y0, __shfl_xor(y0, o, 64));
-        y1 = fmax(y1, __shfl_xor(y1, o, 64));
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) sh[0][w] = x0, sh[1][w] = x1, sh[2][w] = y0, sh[3][w] = y1;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int u = 1; u < SB / 64; u++) {
-            sh[0][0] = fmin(sh[0][0], sh[0][u]), sh[1][0] = fmax(sh[1][0], sh[1][u]);
-            sh[2][0] = fmin(sh[2][0], sh[2][u]), sh[3][0] = fmax(sh[3][0], sh[3][u]);
-        }
-        for (int u = 0; u < 4; u++) out[u] = sh[u][0];
-    }
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    sp_box_reduce(x0, x1, y0, y1, c, out);
 }
 
-// counting sort of points by grid cell, used for the indexed points and for the queries alike: histogram, scan, scatter
+// counting sort by grid cell of the points that take part, used for the indexed points and for the queries alike: histogram,
+// scan, scatter
 __global__ void __launch_bounds__(SB)
-k_sp_count(const double2 *__restrict__ xy, int64_t n, SampleGrid g, int32_t *__restrict__ count) {
+k_sp_count(const double2 *__restrict__ xy, const double *__restrict__ values, bool want_nan, int64_t n, SampleGrid g,
+           int32_t *__restrict__ count) {
     const int64_t i = (int64_t)blockIdx.x * SB + threadIdx.x;
-    if (i < n) atomicAdd(&count[sp_cell(g, xy[i])], 1);
+    if (i < n && sp_takes_part(values, want_nan, i)) atomicAdd(&count[sp_cell(g, xy[i])], 1);
 }
 
 // id_out[position] = point; xy_out (index build only): the point's coordinates beside it.  The order inside a cell is the
 // order in which the lanes arrive; no answer depends on it (the search compares ids on equal distances).
 __global__ void __launch_bounds__(SB)
-k_sp_scatter(const double2 *__restrict__ xy, int64_t n, SampleGrid g, const int32_t *__restrict__ start,
-             int32_t *__restrict__ cursor, double2 *__restrict__ xy_out, int32_t *__restrict__ id_out) {
+k_sp_scatter(const double2 *__restrict__ xy, const double *__restrict__ values, bool want_nan, int64_t n, SampleGrid g,
+             const int32_t *__restrict__ start, int32_t *__restrict__ cursor, double2 *__restrict__ xy_out,
+             int32_t *__restrict__ id_out) {
     const int64_t i = (int64_t)blockIdx.x * SB + threadIdx.x;
-    if (i >= n) return;
+    if (i >= n || !sp_takes_part(values, want_nan, i)) return;
     const double2 p = xy[i];
     const int64_t c = sp_cell(g, p);
     const int32_t pos = start[c] + atomicAdd(&cursor[c], 1);
@@ -219,16 +220,6 @@ k_sp_section(const double *__restrict__ pieces, const int64_t *__restrict__ piec
 
 } // namespace xr
 
-// Nearest-neighbour index over a fixed set of points (include/xugrid_amd.h)
-struct xr_nn {
-    int64_t n = 0;
-    xr::SampleGrid grid{};
-    xr::DevBuf<int32_t> start; // [n_cell + 1]
-    xr::DevBuf<double2> xy;    // [n] coordinates in cell order
-    xr::DevBuf<int32_t> id;    // [n] caller's id of the point stored at each position
-    int64_t n_cell() const { return (int64_t)grid.nx * grid.ny; }
-};
-
 namespace xr {
 
 static bool index_in_range(const int64_t *index_dev, int64_t count, int64_t lo, int64_t n) {
@@ -239,8 +230,7 @@ static bool index_in_range(const int64_t *index_dev, int64_t count, int64_t lo, 
     return read_scalar(flag.get()) == 0;
 }
 
-// the grid of nearest_group (xr_fill.hip): cell size for about two points per cell from the box, degenerate boxes included
-static SampleGrid size_grid(const double box[4], int64_t n) {
+SampleGrid size_grid(const double box[4], int64_t n) {
     SampleGrid g{};
     const bool finite = std::isfinite(box[0]) && std::isfinite(box[1]) && std::isfinite(box[2]) && std::isfinite(box[3]);
     const double w = finite ? std::max(box[1] - box[0], 0.0) : 0.0, ht = finite ? std::max(box[3] - box[2], 0.0) : 0.0;
@@ -258,51 +248,66 @@ static SampleGrid size_grid(const double box[4], int64_t n) {
     return g;
 }
 
-static xr_nn *nn_build(const double *xy_dev, int64_t n) {
-    XR_REQUIRE(n > 0, XR_ERR_INVALID, "xr_nn: no points to index.");
+NnExtent nn_extent(const double *xy_dev, int64_t n, const double *values_dev) {
     XR_REQUIRE(n < INT32_MAX, XR_ERR_LIMIT, "xr_nn: more than 2^31 points");
+    NnExtent ext{{INFINITY, -INFINITY, INFINITY, -INFINITY}, 0};
+    if (n <= 0) return ext;
+    const unsigned nb = div_up(n, SB);
+    DevBuf<double> partial((size_t)nb * 5), box_dev(5);
+    XR_LAUNCH("sample_bbox", k_sp_bbox, dim3(nb), dim3(SB), 0, reinterpret_cast<const double2 *>(xy_dev), values_dev, n,
+              partial.get());
+    XR_LAUNCH("sample_bbox_final", k_sp_bbox_final, dim3(1), dim3(SB), 0, partial.get(), (int)nb, box_dev.get());
+    double h[5];
+    d2h(h, box_dev.get(), sizeof(h));
+    std::copy(h, h + 4, ext.box);
+    ext.n = (int64_t)h[4];
+    return ext;
+}
+
+xr_nn *nn_build(const double *xy_dev, int64_t n, const double *values_dev, const NnExtent &extent) {
+    XR_REQUIRE(extent.n > 0, XR_ERR_INVALID, "xr_nn: no points to index.");
     const double2 *xy = reinterpret_cast<const double2 *>(xy_dev);
     Building<xr_nn> nn(OnFailure::WaitFirst);
     const unsigned nb = div_up(n, SB);
-    DevBuf<double> partial((size_t)nb * 4), box_dev(4);
-    XR_LAUNCH("sample_bbox", k_sp_bbox, dim3(nb), dim3(SB), 0, xy, n, partial.get());
-    XR_LAUNCH("sample_bbox_final", k_sp_bbox_final, dim3(1), dim3(SB), 0, partial.get(), (int)nb, box_dev.get());
-    double box[4];
-    d2h(box, box_dev.get(), sizeof(box));
-    nn->n = n;
-    nn->grid = size_grid(box, n);
+    nn->n = extent.n;
+    nn->grid = size_grid(extent.box, extent.n);
     const int64_t nc = nn->n_cell();
     DevBuf<int32_t> count_cursor(2 * (size_t)nc);
     nn->start.alloc((size_t)nc + 1);
-    nn->xy.alloc((size_t)n);
-    nn->id.alloc((size_t)n);
+    nn->xy.alloc((size_t)extent.n);
+    nn->id.alloc((size_t)extent.n);
     fill_i32(count_cursor.get(), 0, 2 * nc);
-    XR_LAUNCH("sample_count", k_sp_count, dim3(nb), dim3(SB), 0, xy, n, nn->grid, count_cursor.get());
+    XR_LAUNCH("sample_count", k_sp_count, dim3(nb), dim3(SB), 0, xy, values_dev, false, n, nn->grid, count_cursor.get());
     exclusive_scan_i32(count_cursor.get(), nn->start.get(), nc);
-    XR_LAUNCH("sample_scatter", k_sp_scatter, dim3(nb), dim3(SB), 0, xy, n, nn->grid, nn->start.get(), count_cursor.get() + nc,
-              nn->xy.get(), nn->id.get());
+    XR_LAUNCH("sample_scatter", k_sp_scatter, dim3(nb), dim3(SB), 0, xy, values_dev, false, n, nn->grid, nn->start.get(),
+              count_cursor.get() + nc, nn->xy.get(), nn->id.get());
     return nn.release();
 }
 
-static void nn_query(const xr_nn *nn, const double *query_xy_dev, int64_t n_query, double max_distance, int64_t *out_dev) {
+void nn_query(const xr_nn *nn, const double *query_xy_dev, int64_t n_query, double max_distance, int64_t *out_dev,
+              const double *values_dev, int64_t n_lookup) {
     const double2 *qxy = reinterpret_cast<const double2 *>(query_xy_dev);
     const unsigned nb = div_up(n_query, SB);
     const int64_t mode = option(OPT_NN_QUERY_SORT);
-    const bool sorted = mode > 0 || (mode < 0 && n_query >= NN_SORT_MIN_QUERIES);
+    const bool sorted = values_dev || mode > 0 || (mode < 0 && n_query >= NN_SORT_MIN_QUERIES); // (a subset is served as a list)
+    const int64_t n_search = values_dev ? n_lookup : n_query;
+    if (n_search <= 0) return;
     DevBuf<int32_t> order;
     if (sorted) {
         const int64_t nc = nn->n_cell();
         DevBuf<int32_t> count_cursor(2 * (size_t)nc), qstart((size_t)nc + 1);
-        order.alloc((size_t)n_query);
+        order.alloc((size_t)n_search);
         fill_i32(count_cursor.get(), 0, 2 * nc);
-        XR_LAUNCH("sample_query_count", k_sp_count, dim3(nb), dim3(SB), 0, qxy, n_query, nn->grid, count_cursor.get());
+        XR_LAUNCH("sample_query_count", k_sp_count, dim3(nb), dim3(SB), 0, qxy, values_dev, true, n_query, nn->grid,
+                  count_cursor.get());
         exclusive_scan_i32(count_cursor.get(), qstart.get(), nc);
-        XR_LAUNCH("sample_query_scatter", k_sp_scatter, dim3(nb), dim3(SB), 0, qxy, n_query, nn->grid, qstart.get(),
-                  count_cursor.get() + nc, (double2 *)nullptr, order.get());
+        XR_LAUNCH("sample_query_scatter", k_sp_scatter, dim3(nb), dim3(SB), 0, qxy, values_dev, true, n_query, nn->grid,
+                  qstart.get(), count_cursor.get() + nc, (double2 *)nullptr, order.get());
     }
     const double md2 = std::isinf(max_distance) ? INFINITY : max_distance * max_distance;
-    XR_LAUNCH(sorted ? "sample_search_sorted" : "sample_search", k_sp_search, dim3(nb), dim3(SB), 0, nn->xy.get(), nn->id.get(),
-              nn->start.get(), nn->grid, qxy, sorted ? order.get() : (const int32_t *)nullptr, n_query, md2, max_distance, out_dev);
+    XR_LAUNCH(sorted ? "sample_search_sorted" : "sample_search", k_sp_search, dim3(div_up(n_search, SB)), dim3(SB), 0,
+              nn->xy.get(), nn->id.get(), nn->start.get(), nn->grid, qxy, sorted ? order.get() : (const int32_t *)nullptr, n_search,
+              md2, max_distance, out_dev);
 }
 
 } // namespace xr
