@@ -516,6 +516,14 @@ int xr_topology_edge_xy_dev(const xr_topology *topology, double *xy_dev);
 /* exterior_face as uint8 [n_face] into a device buffer (the `exterior` argument of xr_graph_binary_iterate_dev) */
 int xr_topology_exterior_face_dev(const xr_topology *topology, uint8_t *flags_dev);
 int xr_topology_destroy(xr_topology *topology);
+/* node -> face and node -> edge as CSR over all n_node nodes (connectivity.invert_dense_to_sparse of face_node and of
+ * edge_node; unused nodes: empty rows), int64 outputs, any pointer may be NULL: nf_indptr [n_node+1], nf_indices
+ * [nf_indptr[n_node]] faces ascending per row, ne_indptr [n_node+1], ne_indices [node_node_nnz] edges ascending per row.
+ * node -> edge is the node_node CSR under another name: its rows have ascending neighbours, and edges are numbered
+ * lexicographically by (lower, higher) node, so its data -- the edge ids -- ascend too.  A face that names a node twice
+ * appears twice in that node's row (the host route's coo -> csr merges the two). */
+int xr_topology_download_node_tables(const xr_topology *topology, int64_t *nf_indptr, int64_t *nf_indices, int64_t *ne_indptr,
+                                     int64_t *ne_indices);
 /* The xr_graph of the faces (facet 2, XR_FACET_FACE below) or nodes (0, XR_FACET_NODE) straight from the device CSR: component labels by the
  * label kernels, weights mean(d) / d (ugridbase.py:962-970) with d the distance between the connected face centroids or
  * nodes; the mean is a fixed-order sum of block partials (the same bits on every run). */
@@ -534,6 +542,38 @@ int xr_graph_components_dev(const xr_graph *graph, int64_t *labels_dev, int64_t 
 int xr_graph_binary_iterate_dev(const xr_graph *graph, const uint8_t *in_dev, uint8_t *out_dev, int64_t K, int value,
                                 int64_t iterations, const uint8_t *mask_dev, const uint8_t *exterior_dev);
 
+/* ---- moving data between the facets of a mesh (xugrid UgridDataArray.ugrid.to_node / to_edge / to_face,
+ * core/dataarray_accessor.py:300-416) ------------------------------------------------------------------------------- */
+/* The table is {target}_{source}_connectivity, int32: dense [n_target, width] with -1 fill (face_node, face_edge, edge_node,
+ * edge_face) or CSR with `width` the widest row (node_face, node_edge).  in_dev [K, n_source] of dtype XR_F64 / XR_F32 (widened
+ * to float64 first), never modified.
+ *   XR_FACET_RAW   out_dev float64 [K, n_target, width]: out[k, t, j] = in[k, table[t, j]], NaN where the table has no entry
+ *                  (obj.isel(indexer).where(indexer != -1))
+ *   XR_FACET_MEAN / _SUM / _MIN / _MAX   out_dev float64 [K, n_target]: the reference's .mean(dim) and its kin over that new
+ *                  dimension, without the [.., width] intermediate.  NaN contributors are skipped (xarray's skipna); a target
+ *                  without a valid contributor gets NaN, 0.0 for the sum.  The sum runs over the row's entries in table order,
+ *                  sequentially, in float64, and the mean is that sum divided once by the count: the same bits on every run.
+ * Before anything is read through an index the table is checked once per call: an index >= n_source, row pointers that do
+ * not start at 0 or decrease, or a row longer than `width` is XR_ERR_INVALID.  Rows may have any length.
+ * Option "facet_tile" = 1 keeps one slice per lane instead of eight (measurement switch; no result depends on it). */
+#define XR_FACET_MEAN 0
+#define XR_FACET_SUM 1
+#define XR_FACET_MIN 2
+#define XR_FACET_MAX 3
+#define XR_FACET_RAW 4
+/* ... through the tables of a topology where they are; target / source: XR_FACET_NODE (0), XR_FACET_EDGE (1), XR_FACET_FACE
+ * (2), different from each other.  edge_face always has two columns here (the host table has one when no edge is shared). */
+int xr_topology_facet_map_dev(xr_topology *topology, int target, int source, int form, const void *in_dev, int dtype, int64_t K,
+                              double *out_dev);
+/* `width` of that table: m for the face tables, 2 for the edge tables, the widest row for the node tables (one reduction over
+ * the row pointers on first request, then kept) */
+int xr_topology_facet_width(xr_topology *topology, int target, int source, int64_t *width);
+/* ... through the caller's int32 device tables: ptr_dev NULL -> idx_dev is dense [n_target, width]; else CSR, ptr_dev
+ * [n_target+1], idx_dev [ptr[n_target]], `width` at least the widest row.  The route of host-built grids, rectilinear grids,
+ * non-manifold device grids and Ugrid1d. */
+int xr_facet_map_dev(const int32_t *ptr_dev, const int32_t *idx_dev, int64_t n_target, int64_t width, int64_t n_source, int form,
+                     const void *in_dev, int dtype, int64_t K, double *out_dev);
+
 /* ---- sampling mesh data at points and along lines (xugrid sel_points / sel / intersect_line / locate_nearest_*) ---- */
 /* Nearest-neighbour index over n fixed points xy_dev float64 [n, 2] (a device pointer): what Ugrid2d.node_kdtree /
  * edge_kdtree / face_kdtree are in the reference (scipy KDTree, xugrid/ugrid/ugridbase.py:1113-1123, ugrid2d.py:902-906).
@@ -544,6 +584,7 @@ int xr_nn_create_dev(const double *xy_dev, int64_t n, xr_nn **out);
 /* ... over the nodes or the face centroids (connectivity.centroids) of a mesh, straight from its device arrays: the index
  * of a grid made by Ugrid2d.from_device_arrays needs no host copy of the mesh. */
 #define XR_FACET_NODE 0
+#define XR_FACET_EDGE 1
 #define XR_FACET_FACE 2
 int xr_nn_create_mesh(xr_mesh *mesh, int facet, xr_nn **out);
 int xr_nn_info(const xr_nn *index, int64_t *n, int64_t *n_cell);

@@ -129,6 +129,7 @@ SIGNATURES = {
     "xr_topology_info": (c_int, [vp, p_i64, p_i64, p_i64, p_i64, p_i64]),
     "xr_topology_long_nodes": (c_int, [vp, p_i64]),
     "xr_topology_download": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "xr_topology_download_node_tables": (c_int, [vp, vp, vp, vp, vp]),
     "xr_topology_edge_xy_dev": (c_int, [vp, vp]),
     "xr_topology_exterior_face_dev": (c_int, [vp, vp]),
     "xr_topology_destroy": (c_int, [vp]),
@@ -136,6 +137,9 @@ SIGNATURES = {
     "xr_graph_label_rounds": (c_int, [vp, p_i64]),
     "xr_graph_components_dev": (c_int, [vp, vp, p_i64]),
     "xr_graph_binary_iterate_dev": (c_int, [vp, vp, vp, c_i64, c_int, c_i64, vp, vp]),
+    "xr_topology_facet_map_dev": (c_int, [vp, c_int, c_int, c_int, vp, c_int, c_i64, vp]),
+    "xr_topology_facet_width": (c_int, [vp, c_int, c_int, p_i64]),
+    "xr_facet_map_dev": (c_int, [vp, vp, c_i64, c_i64, c_i64, c_int, vp, c_int, c_i64, vp]),
     "xr_nn_create_dev": (c_int, [vp, c_i64, p_vp]),
     "xr_nn_create_mesh": (c_int, [vp, c_int, p_vp]),
     "xr_nn_info": (c_int, [vp, p_i64, p_i64]),

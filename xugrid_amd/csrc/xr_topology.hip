@@ -353,7 +353,10 @@ int xr_topology_create(xr_mesh *mesh, xr_topology **out) {
     const int32_t *faces = mesh->faces_raw.get();
 
     // 1: node -> faces
-    DevBuf<int32_t> count_cursor(2 * ((size_t)N + 1)), nf_ptr((size_t)N + 1), nf_rows((size_t)std::max<int64_t>(total, 1));
+    // (kept in the handle: node -> face is a table of its own for the facet mapping, xr_facet.hip)
+    DevBuf<int32_t> count_cursor(2 * ((size_t)N + 1));
+    DevBuf<int32_t> &nf_ptr = t->nf_ptr, &nf_rows = t->nf_idx;
+    nf_ptr.alloc((size_t)N + 1), nf_rows.alloc((size_t)std::max<int64_t>(total, 1));
     int32_t *const count = count_cursor.get(), *const cursor = count_cursor.get() + N + 1;
     fill_i32(count_cursor.get(), 0, 2 * (N + 1));
     if (total > 0) XR_LAUNCH("vor_count", k_vor_count, dim3(div_up(total, VOR_SLOTS)), dim3(256), 0, faces, total, count);
@@ -399,6 +402,7 @@ int xr_topology_create(xr_mesh *mesh, xr_topology **out) {
     if (t->n_nonmanifold > 0) { // two columns cannot hold such an edge: nothing is kept, the caller takes the host route
         t->edge_node.release(), t->edge_face.release(), t->exterior_edge.release();
         t->nn_ptr.release(), t->nn_idx.release(), t->nn_dat.release();
+        t->nf_ptr.release(), t->nf_idx.release();
         t->nn_nnz = 0;
         stream_sync();
         *out = t.release();
@@ -468,6 +472,22 @@ int xr_topology_download(const xr_topology *t, int64_t *edge_node, int64_t *face
     download_wide(t->nn_dat.get(), t->nn_nnz, nn_data, wide);
     download_wide(t->exterior_edge.get(), E, exterior_edge, wide);
     download_wide(t->exterior_face.get(), F, exterior_face, wide);
+    XR_API_END
+}
+
+int xr_topology_download_node_tables(const xr_topology *t, int64_t *nf_indptr, int64_t *nf_indices, int64_t *ne_indptr,
+                                     int64_t *ne_indices) {
+    XR_API_BEGIN
+    XR_REQUIRE(t, XR_ERR_INVALID, "xr_topology_download_node_tables: NULL handle");
+    XR_REQUIRE(t->n_nonmanifold == 0, XR_ERR_INVALID,
+               "xr_topology_download_node_tables: the mesh has %lld edges with more than two faces", (long long)t->n_nonmanifold);
+    const int64_t N = t->n_node;
+    const int64_t nf_nnz = nf_indices ? read_scalar(t->nf_ptr.get() + N) : 0; // (nobody else needs it: not read back at build time)
+    DevBuf<int64_t> wide((size_t)std::max({N + 1, nf_nnz, t->nn_nnz, (int64_t)1}));
+    download_wide(t->nf_ptr.get(), N + 1, nf_indptr, wide);
+    download_wide(t->nf_idx.get(), nf_nnz, nf_indices, wide);
+    download_wide(t->nn_ptr.get(), N + 1, ne_indptr, wide);
+    download_wide(t->nn_dat.get(), t->nn_nnz, ne_indices, wide);
     XR_API_END
 }
 

@@ -12,7 +12,7 @@ from scipy import sparse
 from . import _lib, engine
 from ._lib import check
 
-_FACET_IDS = {"node": 0, "face": 2}  # include/xugrid_amd.h: XR_FACET_NODE, XR_FACET_FACE
+_FACET_IDS = {"node": 0, "edge": 1, "face": 2}  # include/xugrid_amd.h: XR_FACET_NODE, XR_FACET_EDGE, XR_FACET_FACE
 
 # slots of xr_topology_download, in argument order
 _SLOTS = ("edge_node", "face_edge", "edge_face", "ff_indptr", "ff_indices", "ff_data", "nn_indptr", "nn_indices", "nn_data",
@@ -101,6 +101,30 @@ class DeviceTopology:
         indptr, indices, data = self._get("nn_indptr", "nn_indices", "nn_data")
         return sparse.csr_matrix((data.copy(), indices.copy(), indptr.copy()), shape=(self.n_node, self.n_node))
 
+    def _node_tables(self):
+        """node -> face and node -> edge (``xr_topology_download_node_tables``): the row pointers first, they size the rest."""
+        if "nf_indptr" not in self._host:
+            N = self.n_node
+            nf_indptr, ne_indptr = np.empty(N + 1, dtype=np.int64), np.empty(N + 1, dtype=np.int64)
+            as_vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+            check(_lib.load().xr_topology_download_node_tables(self._h, as_vp(nf_indptr), None, as_vp(ne_indptr), None))
+            nf_indices, ne_indices = np.empty(nf_indptr[-1], dtype=np.int64), np.empty(ne_indptr[-1], dtype=np.int64)
+            check(_lib.load().xr_topology_download_node_tables(self._h, None, as_vp(nf_indices), None, as_vp(ne_indices)))
+            self._host.update(nf_indptr=nf_indptr, nf_indices=nf_indices, ne_indptr=ne_indptr, ne_indices=ne_indices)
+        return [self._host[s] for s in ("nf_indptr", "nf_indices", "ne_indptr", "ne_indices")]
+
+    @property
+    def node_face_connectivity(self):
+        """scipy CSR (n_node, n_face), faces ascending per row; data = the face id, as ``invert_dense_to_sparse`` leaves it."""
+        indptr, indices, _, _ = self._node_tables()
+        return sparse.csr_matrix((indices.copy(), indices.copy(), indptr.copy()), shape=(self.n_node, self.n_face))
+
+    @property
+    def node_edge_connectivity(self):
+        """scipy CSR (n_node, n_edge), edges ascending per row: the node_node rows with the edge id as the column."""
+        _, _, indptr, indices = self._node_tables()
+        return sparse.csr_matrix((indices.copy(), indices.copy(), indptr.copy()), shape=(self.n_node, self.n_edge))
+
     @property
     def exterior_edges(self):
         return np.nonzero(self._get("exterior_edge")[0])[0]
@@ -123,6 +147,17 @@ class DeviceTopology:
         flags = engine.DeviceArray((self.n_face,), np.uint8)
         check(_lib.load().xr_topology_exterior_face_dev(self._h, ctypes.c_void_p(flags.ptr)))
         return flags
+
+    def facet_width(self, target, source):
+        """Width of ``{target}_{source}_connectivity`` in dense form: m, 2, or the widest row of a node table."""
+        w = ctypes.c_int64()
+        check(_lib.load().xr_topology_facet_width(self._h, _FACET_IDS[target], _FACET_IDS[source], ctypes.byref(w)))
+        return w.value
+
+    def facet_map(self, target, source, form, in_ptr, dtype_id, K, out_ptr):
+        """``xr_topology_facet_map_dev`` on device pointers: the tables are read where they are."""
+        check(_lib.load().xr_topology_facet_map_dev(self._h, _FACET_IDS[target], _FACET_IDS[source], form,
+                                                    ctypes.c_void_p(int(in_ptr)), dtype_id, K, ctypes.c_void_p(int(out_ptr))))
 
     def graph(self, facet):
         """The fills' ``DeviceGraph`` of the faces or nodes: structure, ``mean(d) / d`` weights and component labels, all

@@ -7,7 +7,7 @@ the regridding hot path (out of scope).
 """
 import numpy as np
 
-from . import connectivity, fill, sample
+from . import connectivity, facet, fill, sample
 from .engine import FloatDType, IntDType
 
 FILL_VALUE = -1
@@ -82,6 +82,29 @@ class Ugrid1d:
         """Nodes joined by an edge, scipy CSR; data = the edge's id."""
         return connectivity.node_node_connectivity(self.edge_node_connectivity, self.n_node)
 
+    @property
+    def node_edge_connectivity(self):
+        """node -> edge, scipy CSR over all nodes, edges ascending per row (ugridbase.py:866-878)."""
+        return facet.node_edge_connectivity(self.edge_node_connectivity, self.n_node)
+
+    # ---- moving data between nodes and edges on the device (xugrid_amd/facet.py; the Ugrid2d methods of the same name)
+    def to_node(self, data, dim=None, reduce=None):
+        """Edge data ``(..., n_edge)`` at the nodes: ``(..., n_node, w)``, or ``(..., n_node)`` with ``reduce``; see
+        ``Ugrid2d.to_node``."""
+        return facet.to_facet(self, "node", data, dim, reduce)
+
+    def to_edge(self, data, dim=None, reduce=None):
+        """Node data at the edges: ``(..., n_edge, 2)``, or ``(..., n_edge)`` with ``reduce``."""
+        return facet.to_facet(self, "edge", data, dim, reduce)
+
+    def to_face(self, data, dim=None, reduce=None):
+        """A network has no faces: raises, as the reference's ``_to_facet`` does."""
+        return facet.to_facet(self, "face", data, dim, reduce)
+
+    def facet_width(self, target, source):
+        """Width ``w`` of the ``(..., n_target, w)`` result of ``to_node`` / ``to_edge`` without ``reduce``."""
+        return facet.facet_width(self, target, source)
+
     def get_connectivity_matrix(self, dim="node", xy_weights=True):
         """ugrid1d.py:334-345: the node adjacency; with ``xy_weights`` its data are mean(d) / d of the node distances."""
         facet = fill.resolve_dim(self, dim, ("node",))
@@ -138,6 +161,7 @@ class Ugrid1d:
         from the coordinates as they were on first use)."""
         self.__dict__.pop("_fill_cache", None)
         self.__dict__.pop("_sample_cache", None)
+        self.__dict__.pop("_facet_cache", None)
 
     @property
     def bounds(self):

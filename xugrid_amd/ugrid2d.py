@@ -10,7 +10,7 @@ import numpy as np
 
 import ctypes
 
-from . import _lib, connectivity, fill, graph, sample
+from . import _lib, connectivity, facet, fill, graph, sample
 from .celltree import CellTree2d
 from .engine import FloatDType, IntDType
 
@@ -173,6 +173,7 @@ class Ugrid2d:
         self.__dict__.pop("_fill_cache", None)
         self.__dict__.pop("_sample_cache", None)
         self.__dict__.pop("_topology_cache", None)
+        self.__dict__.pop("_facet_cache", None)
 
     @property
     def device_mesh(self):
@@ -247,6 +248,11 @@ class Ugrid2d:
                 self.face_node_connectivity, n_rows=self.n_node
             )
         return self._node_face_connectivity
+
+    @property
+    def node_edge_connectivity(self):
+        """node -> edge, scipy CSR over all nodes, edges ascending per row (ugridbase.py:866-878)."""
+        return facet.node_edge_connectivity(self.edge_node_connectivity, self.n_node)
 
     @property
     def n_edge(self):
@@ -447,6 +453,25 @@ class Ugrid2d:
         """``intersect_line`` along the vertices ``xy (n_vertex, 2)`` (ugridbase.py:1412-1460; an array instead of a shapely
         geometry): ``s`` runs along the whole line."""
         return sample.intersect_linestring(self, data, xy)
+
+    # ---- moving data between facets on the device (xugrid_amd/facet.py)
+    def to_node(self, data, dim=None, reduce=None):
+        """Face or edge data ``(..., n)`` at the nodes (dataarray_accessor.py:346-368): ``(..., n_node, w)`` with NaN where a
+        node has fewer contributors, or ``(..., n_node)`` with ``reduce`` in "mean", "sum", "min", "max" (NaN skipped; the
+        sum in table order).  ``dim`` names the source facet (default: the one whose size fits).  See xugrid_amd/facet.py."""
+        return facet.to_facet(self, "node", data, dim, reduce)
+
+    def to_edge(self, data, dim=None, reduce=None):
+        """Node or face data at the edges (dataarray_accessor.py:370-392); see ``to_node``."""
+        return facet.to_facet(self, "edge", data, dim, reduce)
+
+    def to_face(self, data, dim=None, reduce=None):
+        """Node or edge data at the faces (dataarray_accessor.py:394-416); see ``to_node``."""
+        return facet.to_facet(self, "face", data, dim, reduce)
+
+    def facet_width(self, target, source):
+        """Width ``w`` of the ``(..., n_target, w)`` result ``to_{target}`` gives for ``source`` data without ``reduce``."""
+        return facet.facet_width(self, target, source)
 
     # ---- structured -> unstructured (raster cells become CCW quads)
     @staticmethod
@@ -652,6 +677,7 @@ class DeviceUgrid2d(Ugrid2d):
         self.__dict__.pop("_fill_cache", None)
         self.__dict__.pop("_sample_cache", None)
         self.__dict__.pop("_topology_cache", None)
+        self.__dict__.pop("_facet_cache", None)
         self._celltree.device_mesh.invalidate()
 
     # ---- edge connectivity from the device topology.  An edge with more than two faces does not fit its two-column tables: such
@@ -674,6 +700,8 @@ class DeviceUgrid2d(Ugrid2d):
     edge_face_connectivity = _from_topology("edge_face_connectivity")  # (always two columns; the host table has one when no edge is shared)
     face_face_connectivity = _from_topology("face_face_connectivity")
     node_node_connectivity = _from_topology("node_node_connectivity")
+    node_face_connectivity = _from_topology("node_face_connectivity")  # (from the device: the mesh is not downloaded)
+    node_edge_connectivity = _from_topology("node_edge_connectivity")
     exterior_edges = _from_topology("exterior_edges")
     exterior_faces = _from_topology("exterior_faces")
     del _from_topology
