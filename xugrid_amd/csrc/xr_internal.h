@@ -327,6 +327,7 @@ enum Option : int {
     OPT_NN_QUERY_SORT,     // -1: nearest queries are binned by index cell from NN_SORT_MIN_QUERIES on (xr_sample.hip); 0 / 1: never / always
     OPT_BURN_STRIPS,       // > 0: strips of the ring-segment index of burn_vector_geometry (xr_burn.hip; 0: from the segments; tests force 1 and very many)
     OPT_FACET_TILE,        // 1: to_node / to_edge / to_face keep one slice per lane instead of FACET_TILE (xr_facet.hip; the A/B of DESIGN section 11)
+    OPT_SCAN_FUSED_TILES,  // > 0: tiles up to which exclusive_scan_i32 runs its fused pair (xr_scan.hip; 0: SCAN_FUSED_TILES; tests force the three-kernel path with a tiny one)
     OPT_COUNT
 };
 int64_t option(Option o);

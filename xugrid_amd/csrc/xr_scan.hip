@@ -1,6 +1,8 @@
 // xr_scan.hip -- device exclusive prefix sum (int32) and fills.  wave64, 256-thread blocks.
 // Three-phase reduce / scan-of-partials / scan-with-offset; every element is read twice and
-// written once (HBM-bound, 12 B per element).
+// written once (HBM-bound, 12 B per element).  Up to SCAN_FUSED_TILES tiles the last two phases are one kernel; option
+// scan_fused_tiles (> 0) moves that limit -- read on the host only, no result depends on it (tests/test_gpu_scan.py forces the
+// three-kernel path with a tiny one).
 #include "xr_internal.h"
 
 namespace xr {
@@ -38,7 +40,9 @@ __device__ __forceinline__ int block_excl_scan(int v, int *total, int *lds /* >=
 }
 
 // a thread's SCAN_ITEMS consecutive elements as two 16-byte accesses (the tile base and every thread's offset are multiples of
-// eight elements, the arrays come from the pool: 32-byte aligned); element by element only in the one tile that holds the end
+// eight elements, the arrays come from the pool: 32-byte aligned); element by element only in the one tile that holds the end.
+// Every caller of exclusive_scan_i32 passes the base of a DevBuf (or of the zero-at-rest scratch) as `in` and as `out`, so the
+// alignment test below never fails today: it states the requirement and keeps a future caller with an offset pointer correct.
 __device__ __forceinline__ void load_items(const int32_t *__restrict__ in, int64_t base, int64_t n, int (&v)[SCAN_ITEMS]) {
     static_assert(SCAN_ITEMS == 8, "two int4 per thread");
     if (base + SCAN_ITEMS <= n && (reinterpret_cast<uintptr_t>(in) & 15) == 0) {
@@ -172,7 +176,8 @@ void exclusive_scan_i32(const int32_t *in, int32_t *out, int64_t n, int32_t *hos
     const int64_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
     DevBuf<int32_t> sums((size_t)nb);
     XR_LAUNCH("scan_reduce", k_scan_reduce, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, in, sums.get(), n);
-    if (nb <= SCAN_FUSED_TILES) {
+    const int64_t fused_tiles = option(OPT_SCAN_FUSED_TILES) > 0 ? option(OPT_SCAN_FUSED_TILES) : SCAN_FUSED_TILES; // test hook
+    if (nb <= fused_tiles) {
         XR_LAUNCH("scan_apply", k_scan_apply_fused, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, in, sums.get(), nb, out, n,
                   host_total, extra_src, extra_host);
         return;
