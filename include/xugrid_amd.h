@@ -69,6 +69,7 @@ extern "C" {
 /* Source data dtypes accepted by the apply seam (output is always float64, regridder.py:44). */
 #define XR_F64 0
 #define XR_F32 1
+#define XR_I32 2 /* int32 face data of xr_polygonize_dev only */
 
 #define XR_MAX_FACE_NODES 32 /* numba_celltree MAX_N_VERTEX */
 
@@ -638,6 +639,28 @@ int xr_burn_points_dev(xr_mesh *mesh, const double *coords_dev, int64_t n_point,
 int xr_burn_combine_dev(int64_t n_face, const int32_t *polygon_winner_dev, const double *polygon_values_dev,
                         const int32_t *line_winner_dev, const double *line_values_dev, const int32_t *point_winner_dev,
                         const double *point_values_dev, double fill, double *out_dev);
+
+/* ---- polygonizing face data (xugrid.polygonize, xugrid/ugrid/polygonize.py) ---------------------------------------------- */
+/* Regions of equal value -> polygon rings, in the layout xr_burn_polygons_dev reads (shapely.to_ragged_array).  data_dev
+ * [n_face] of dtype XR_F64 / XR_F32 / XR_I32 (a device pointer, never written).  NaN faces belong to no polygon.  A region is a
+ * maximal set of valid faces with == values joined through shared edges; regions are numbered by the rank of their smallest
+ * face, polygon p IS region p and values[p] the value of that face.  Every region is one polygon: its exterior ring (the ring
+ * of positive shoelace sum) first, then its holes ascending by leader, the half-edge of smallest (face, slot), where every
+ * ring also starts; rings are closed (first vertex == last).  A ring passes more than once through a node at which its region
+ * touches itself.  XR_ERR_INVALID: a non-manifold mesh, a face with data whose shoelace sum is zero or not finite
+ * ("degenerate face"), or rings that do not close ("internal error").  All-NaN data gives zero polygons and offsets [0]. */
+typedef struct xr_polygons xr_polygons;
+int xr_polygonize_dev(xr_topology *topology, const void *data_dev, int dtype, xr_polygons **out);
+/* n_vertex = n_halfedge + n_ring; label_rounds: hook launches of the region labelling (the last one changes nothing) */
+int xr_polygons_info(const xr_polygons *p, int64_t *n_polygon, int64_t *n_ring, int64_t *n_vertex, int64_t *n_halfedge,
+                     int64_t *label_rounds);
+/* device-to-host transfers the call waited for (label_rounds + 9; the ring table is three of them) */
+int xr_polygons_readbacks(const xr_polygons *p, int64_t *readbacks);
+/* coords float64 [n_vertex, 2], ring_offsets int64 [n_ring + 1], polygon_offsets int64 [n_polygon + 1], values float64
+ * [n_polygon], face_polygon int64 [n_face] (-1 for a NaN face) into the caller's device arrays */
+int xr_polygons_copy_dev(const xr_polygons *p, double *coords_dev, int64_t *ring_offsets_dev, int64_t *polygon_offsets_dev,
+                         double *values_dev, int64_t *face_polygon_dev);   /* any pointer may be NULL */
+int xr_polygons_destroy(xr_polygons *p);
 
 /* ---- raw HBM helpers for hosts that do not bring their own allocator -------------------- */
 int xr_dev_alloc(int64_t bytes, void **ptr_out);

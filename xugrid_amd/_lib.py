@@ -20,6 +20,7 @@ XR_ERR_LIMIT = -4
 
 XR_F64 = 0
 XR_F32 = 1
+XR_I32 = 2
 
 
 class XugridAmdError(RuntimeError):
@@ -151,6 +152,11 @@ SIGNATURES = {
     "xr_burn_lines_dev": (c_int, [vp, vp, c_i64, vp, c_i64, vp]),
     "xr_burn_points_dev": (c_int, [vp, vp, c_i64, vp]),
     "xr_burn_combine_dev": (c_int, [c_i64, vp, vp, vp, vp, vp, vp, c_f64, vp]),
+    "xr_polygonize_dev": (c_int, [vp, vp, c_int, p_vp]),
+    "xr_polygons_info": (c_int, [vp, p_i64, p_i64, p_i64, p_i64, p_i64]),
+    "xr_polygons_readbacks": (c_int, [vp, p_i64]),
+    "xr_polygons_copy_dev": (c_int, [vp, vp, vp, vp, vp, vp]),
+    "xr_polygons_destroy": (c_int, [vp]),
     "xr_dev_alloc": (c_int, [c_i64, p_vp]),
     "xr_dev_free": (c_int, [vp]),
     "xr_dev_upload": (c_int, [vp, vp, c_i64]),

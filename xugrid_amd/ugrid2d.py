@@ -473,6 +473,16 @@ class Ugrid2d:
         """Width ``w`` of the ``(..., n_target, w)`` result ``to_{target}`` gives for ``source`` data without ``reduce``."""
         return facet.facet_width(self, target, source)
 
+    # ---- face data -> polygons on the device (xugrid_amd/polygonize.py)
+    def polygonize(self, data, return_index=False):
+        """Regions of equal value of the face data ``data`` (n_face,) as polygons (xugrid.polygonize) ->
+        ``(coords, ring_offsets, polygon_offsets, values)``, the ``polygons=`` argument of ``burn_vector_geometry``; with
+        ``return_index`` also the polygon of every face (-1 for NaN).  numpy in -> numpy out, device array in -> device
+        arrays of the same kind out.  See xugrid_amd/polygonize.py."""
+        from .polygonize import polygonize  # (the package attribute of that name is this function, not the module)
+
+        return polygonize(self, data, return_index)
+
     # ---- structured -> unstructured (raster cells become CCW quads)
     @staticmethod
     def _from_intervals_helper(node_x, node_y, nx, ny, name):
