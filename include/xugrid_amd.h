@@ -416,7 +416,9 @@ int xr_apply_coo(const int64_t *row, const int64_t *col, int64_t nnz, int64_t T,
  *                      `world` stretches of equal face COUNT (owner per cell: floor(faces in front of the cell * world / S))
  *   mode 2 "balanced"  the same cut by estimated WORK, round(4096 (1 + 4 n_tgt / n_src)) per source face from a coarse raster
  *                      both meshes are counted into
- * and keeps the target faces whose box touches the 128 x 128 occupancy raster of the rank's own source faces.  Integer
+ * and keeps the target faces whose box touches the 128 x 128 occupancy raster of the rank's own source faces.  A face without
+ * a valid node (all -1) has the centroid (0, 0) and no box: it enters no bounds and the occupancy raster on neither side, but as
+ * a source face it still has a cell (its (0, 0) clamped into the other faces' bounds), work and an owner.  Integer
  * arithmetic decides every owner, so all ranks agree without communication.  Outputs: ascending global ids (device arrays of
  * capacity n_src_face / n_tgt_face), their counts, optionally the owner of every source face (int32 [n_src_face]). */
 int xr_shard_plan_dev(const double *src_xy_dev, const int64_t *src_faces_dev, int64_t n_src_face, int src_m,

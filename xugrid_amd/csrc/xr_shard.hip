@@ -7,7 +7,11 @@
 //
 // The rule (every rank evaluates it on its own device and must get the same owner for every face, so everything that decides an
 // owner is exact):
-//   * centroid of a face = sum of its valid nodes in connectivity order / their number
+//   * centroid of a face = sum of its valid nodes in connectivity order / their number.  A face without a valid node has the
+//     centroid (0, 0) and no box: it takes no part in any bounds (of centroids or of boxes) and neither occupies nor receives a
+//     cell of the occupancy raster, but it is a source face like any other -- its (0, 0) is cut against the bounds of the
+//     others (clamped into a border cell), it carries work and has an owner
+//   * cell of a value on an n-cell axis over [lo, hi] = floor((v - lo) * (n / max(hi - lo, 1e-300))), clamped to [0, n - 1]
 //   * "hash": owner = face id mod world
 //   * "morton" / "balanced": the source centroids' bounding square is cut into 1024 x 1024 cells, cells are ordered along the
 //     Morton curve, every face adds its WORK to its cell -- 1 ("morton": equal counts) or the fixed-point value
