@@ -162,6 +162,22 @@ int xr_mesh_faces(xr_mesh *mesh, int64_t *faces_out);
  * the caller's vertex order, fill -1 (either pointer may be NULL).  Mainly for meshes that were built on the
  * device (xr_voronoi_mesh). */
 int xr_mesh_download(xr_mesh *mesh, double *node_xy_out, int64_t *faces_out);
+/* ---- meshes and per-face quantities derived from a mesh, all in the caller's vertex order -----------------------------
+ * Fan triangulation (connectivity.triangulate, connectivity.py:704-788; Ugrid2d.triangulate, ugrid2d.py:1650-1662): a new
+ * device-resident mesh with the same node coordinates (copied device to device: the handle owns its arrays) whose faces are
+ * the triangles (n0, n[t + 1], n[t + 2]), t = 0 .. k - 3, of every face of k nodes, in face order.  A mesh of
+ * n_max_node == 3 gives a copy.  XR_ERR_LIMIT when 3 * n_triangle leaves the int32 range.
+ * xr_mesh_triangle_face_dev: the source face of every triangle, repeat(arange(n_face), k - 2) -> int64[n_triangle] in device
+ * memory; only for a mesh made by xr_mesh_triangulate. */
+int xr_mesh_triangulate(xr_mesh *mesh, xr_mesh **out);
+int xr_mesh_triangle_face_dev(const xr_mesh *triangles, int64_t *index_dev);
+/* Circumcenters of a triangle mesh, connectivity.circumcenters (connectivity.py:667-701), evaluated operation for operation
+ * -> float64[n_face, 2] in device memory.  XR_ERR_INVALID unless n_max_node == 3. */
+int xr_mesh_circumcenters_dev(xr_mesh *mesh, double *out_dev);
+/* connectivity.perimeter (connectivity.py:600-612), the edge lengths summed in slot order -> float64[n_face] in device memory. */
+int xr_mesh_perimeter_dev(xr_mesh *mesh, double *out_dev);
+/* Ugrid2d.face_bounds (ugrid2d.py:597-619): (min x, min y, max x, max y) over the real nodes -> float64[n_face, 4] in device memory. */
+int xr_mesh_face_bounds_dev(xr_mesh *mesh, double *out_dev);
 
 /* CellTree2d.intersect_faces (unstructured.py:124-132) + relative normalisation (:133-134)
  * + MatrixCSR.from_triplet (regridder.py:433-435): all (query face, tree face) pairs with
@@ -270,11 +286,24 @@ int xr_barycentric_csr_points(xr_mesh *voronoi, xr_mesh *source, xr_points *poin
  *   vertices = [face centroids ; extra_xy]      cells = [interior nodes ascending ; boundary_cells]. */
 typedef struct xr_voronoi xr_voronoi;
 int xr_voronoi_create(xr_mesh *mesh, xr_voronoi **out); /* `mesh` must outlive the handle */
+/* The same builder for every flag set of voronoi_topology (voronoi.py:330-458) and any generator points: generators_dev
+ * float64[n_face, 2] in device memory (copied), NULL = the face centroids.  xr_voronoi_create = (1, 1, 1, NULL).
+ *   skip_concave = 0   the true boundary node always replaces the substitute corner (no area comparison)
+ *   add_vertices = 0   no extra corner per boundary node: the tail holds projections only, the interpolation map is empty
+ *   add_exterior = 0   cells for every node with at least three faces, boundary nodes included, and no boundary part; the
+ *                      vertices are the generator points some cell uses, ascending by face (xr_voronoi_vertex_info: their
+ *                      number and the largest used face id); XR_ERR_INVALID when no node has three faces
+ * xr_voronoi_vertex_info: generator points at the head of the vertex array (n_face with the exterior) and the largest face
+ * id among them. */
+int xr_voronoi_create_flags(xr_mesh *mesh, int add_exterior, int add_vertices, int skip_concave, const double *generators_dev,
+                            xr_voronoi **out);
+int xr_voronoi_vertex_info(const xr_voronoi *v, int64_t *n_generator_vertex, int64_t *max_used_face);
 int xr_voronoi_info(const xr_voronoi *v, int64_t *n_node, int64_t *nnz, int64_t *n_exterior_edge,
                     int64_t *n_interior_cell, int64_t *max_interior_degree);
 /* node_face_connectivity as CSR (indptr int64[n_node+1], indices int64[nnz], faces ascending per node), the
  * exterior edges in lexicographic order (edge_nodes int64[n_edge, 2] = (lower, higher node id), edge_face
  * int64[n_edge]) and, optionally, the face centroids float64[n_face, 2]. */
+/* (A handle built with add_exterior = 0 keeps only the generator points its cells use: `centroids` must be NULL there.) */
 int xr_voronoi_download(const xr_voronoi *v, int64_t *indptr, int64_t *indices, int64_t *edge_nodes,
                         int64_t *edge_face, double *centroids);
 /* The same information restricted to what the O(boundary) host part reads -- nothing of size O(n) crosses PCIe:

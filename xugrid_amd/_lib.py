@@ -64,7 +64,14 @@ SIGNATURES = {
     "xr_mesh_centroids": (c_int, [vp, vp]),
     "xr_mesh_faces": (c_int, [vp, vp]),
     "xr_mesh_download": (c_int, [vp, vp, vp]),
+    "xr_mesh_triangulate": (c_int, [vp, p_vp]),
+    "xr_mesh_triangle_face_dev": (c_int, [vp, vp]),
+    "xr_mesh_circumcenters_dev": (c_int, [vp, vp]),
+    "xr_mesh_perimeter_dev": (c_int, [vp, vp]),
+    "xr_mesh_face_bounds_dev": (c_int, [vp, vp]),
     "xr_voronoi_create": (c_int, [vp, p_vp]),
+    "xr_voronoi_create_flags": (c_int, [vp, c_int, c_int, c_int, vp, p_vp]),
+    "xr_voronoi_vertex_info": (c_int, [vp, p_i64, p_i64]),
     "xr_voronoi_info": (c_int, [vp, p_i64, p_i64, p_i64, p_i64, p_i64]),
     "xr_voronoi_download": (c_int, [vp, vp, vp, vp, vp, vp]),
     "xr_voronoi_boundary_info": (c_int, [vp, vp, vp]),

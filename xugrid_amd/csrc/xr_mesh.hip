@@ -969,6 +969,103 @@ k_rect_faces(int64_t nx, int64_t n_face, bool flip_x, bool flip_y, int32_t *__re
                                                    (int)(upper * nx1 + right), (int)(upper * nx1 + left));
 }
 
+// ---------------------------------------------------------------------------------------------
+// quantities and meshes derived from a mesh: fan triangulation (connectivity.py:704-788), circumcenters (:667-701),
+// perimeter (:600-612), face bounds (ugrid2d.py:597-619).  All in the caller's vertex order (faces_raw).
+// ---------------------------------------------------------------------------------------------
+// nodes of a face in faces_raw: up to the first fill value from slot 3 on (mesh creation rejects shorter faces)
+__device__ __forceinline__ int raw_face_len(const int32_t *__restrict__ face, int m) {
+    int n = m;
+    for (int i = m - 1; i >= 3; i--)
+        if (face[i] < 0) n = i;
+    return n;
+}
+
+__global__ void __launch_bounds__(256)
+k_tri_count(const int32_t *__restrict__ faces_raw, int64_t n_face, int m, int32_t *__restrict__ count) {
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (f < n_face) count[f] = raw_face_len(faces_raw + f * m, m) - 2;
+}
+
+// One thread per slot of the PADDED output (face f, word s of its up to 3 (m - 2) triangle words): the lanes of a wave write
+// consecutive words of the triangle table, as k_vor_cells does for the cell table.  Triangle t of a face with k nodes is
+// (n0, n[t + 1], n[t + 2]); its k - 2 is read off the scan (off[f + 1] - off[f]), not counted again.  off == nullptr: every
+// face is a triangle (off[f] = f).
+__global__ void __launch_bounds__(256)
+k_tri_scatter(const int32_t *__restrict__ faces_raw, int64_t n_face, int m, const int32_t *__restrict__ off,
+              int32_t *__restrict__ triangles, int32_t *__restrict__ tri_face) {
+    const int w = 3 * (m - 2);
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_face * w) return;
+    const int64_t f = i / w;
+    const int s = (int)(i - f * w);
+    const int t = s / 3, c = s - 3 * t;
+    const int32_t *face = faces_raw + f * m;
+    const int64_t first = off ? off[f] : f;
+    if (t >= (off ? off[f + 1] - (int)first : 1)) return;
+    triangles[3 * first + s] = c == 0 ? face[0] : face[t + c];
+    if (c == 0) tri_face[first + t] = (int32_t)f;
+}
+
+// connectivity._circumcenters_triangle, operation for operation (the library is built with -ffp-contract=off)
+__global__ void __launch_bounds__(256)
+k_circumcenters(const double *__restrict__ node_xy, const int32_t *__restrict__ faces_raw, int64_t n_face,
+                double *__restrict__ out) {
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (f >= n_face) return;
+    const P2 a = load_p2(node_xy, faces_raw[3 * f]), b = load_p2(node_xy, faces_raw[3 * f + 1]),
+             c = load_p2(node_xy, faces_raw[3 * f + 2]);
+    const double a_x = a.x, a_y = a.y, b_x = b.x, b_y = b.y, c_x = c.x, c_y = c.y;
+    const double D_inv = 0.5 / (a_y * c_x + b_y * a_x - b_y * c_x - a_y * b_x - c_y * a_x + c_y * b_x);
+    const double x = ((a_x - c_x) * (a_x + c_x) + (a_y - c_y) * (a_y + c_y)) * (b_y - c_y) -
+                     ((b_x - c_x) * (b_x + c_x) + (b_y - c_y) * (b_y + c_y)) * (a_y - c_y);
+    const double y = ((b_x - c_x) * (b_x + c_x) + (b_y - c_y) * (b_y + c_y)) * (a_x - c_x) -
+                     ((a_x - c_x) * (a_x + c_x) + (a_y - c_y) * (a_y + c_y)) * (b_x - c_x);
+    reinterpret_cast<double2 *>(out)[f] = make_double2(D_inv * x, D_inv * y);
+}
+
+// connectivity.perimeter: the closed polygon relative to its first vertex (fill slots and the closing slot repeat vertex 0),
+// differences of consecutive slots, sqrt(dx * dx + dy * dy) summed in slot order
+__global__ void __launch_bounds__(256)
+k_perimeter(const double *__restrict__ node_xy, const int32_t *__restrict__ faces_raw, int64_t n_face, int m,
+            double *__restrict__ out) {
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (f >= n_face) return;
+    const int32_t *face = faces_raw + f * m;
+    const P2 p0 = load_p2(node_xy, face[0]);
+    double px = p0.x - p0.x, py = p0.y - p0.y, sum = 0.0;
+    for (int j = 1; j <= m; j++) {
+        const int v = j < m ? face[j] : -1;
+        const P2 q = v < 0 ? p0 : load_p2(node_xy, v);
+        const double qx = q.x - p0.x, qy = q.y - p0.y;
+        const double dx = qx - px, dy = qy - py;
+        sum += sqrt(dx * dx + dy * dy);
+        px = qx;
+        py = qy;
+    }
+    out[f] = sum;
+}
+
+// Ugrid2d.face_bounds: (min x, min y, max x, max y) over the real nodes
+__global__ void __launch_bounds__(256)
+k_face_bounds(const double *__restrict__ node_xy, const int32_t *__restrict__ faces_raw, int64_t n_face, int m,
+              double *__restrict__ out) {
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (f >= n_face) return;
+    const int32_t *face = faces_raw + f * m;
+    double xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY;
+    for (int j = 0; j < m; j++) {
+        const int v = face[j];
+        if (v < 0) continue;
+        const P2 p = load_p2(node_xy, v);
+        xmin = fmin(xmin, p.x);
+        xmax = fmax(xmax, p.x);
+        ymin = fmin(ymin, p.y);
+        ymax = fmax(ymax, p.y);
+    }
+    reinterpret_cast<double4 *>(out)[f] = make_double4(xmin, ymin, xmax, ymax);
+}
+
 } // namespace xr
 
 using namespace xr;
@@ -1179,7 +1276,7 @@ int xr_mesh_device_bytes(const xr_mesh *mesh, int64_t *bytes) {
                mesh->len.bytes() + mesh->bbox.bytes() + mesh->area.bytes() + mesh->stats.bytes() + mesh->q_perm.bytes() +
                mesh->q_fxy.bytes() + mesh->q_off.bytes() + mesh->q_len.bytes() + mesh->q_bbox.bytes() +
                mesh->cell_start.bytes() + mesh->rec_bb.bytes() + mesh->rec_face.bytes() + mesh->rec_fxy.bytes() +
-               mesh->rec_off.bytes() + mesh->rec_len.bytes();
+               mesh->rec_off.bytes() + mesh->rec_len.bytes() + mesh->tri_face.bytes();
     *bytes = (int64_t)b;
     XR_API_END
 }
@@ -1244,6 +1341,83 @@ int xr_mesh_centroids(xr_mesh *mesh, double *centroids_out) {
         d2h(centroids_out, c->get(), sizeof(double) * 2 * (size_t)F);
         stream_sync();
     }
+    XR_API_END
+}
+
+int xr_mesh_circumcenters_dev(xr_mesh *mesh, double *out_dev) {
+    XR_API_BEGIN
+    XR_REQUIRE(mesh && (out_dev || mesh->n_face == 0), XR_ERR_INVALID, "xr_mesh_circumcenters_dev: NULL argument");
+    XR_REQUIRE(mesh->m == 3, XR_ERR_INVALID, "Circumcenters are only supported for triangular grids");
+    if (mesh->n_face > 0)
+        XR_LAUNCH("circumcenters", k_circumcenters, dim3(div_up(mesh->n_face, 256)), dim3(256), 0, mesh->node_xy.get(),
+                  mesh->faces_raw.get(), mesh->n_face, out_dev);
+    dev_call_done();
+    XR_API_END
+}
+
+int xr_mesh_perimeter_dev(xr_mesh *mesh, double *out_dev) {
+    XR_API_BEGIN
+    XR_REQUIRE(mesh && (out_dev || mesh->n_face == 0), XR_ERR_INVALID, "xr_mesh_perimeter_dev: NULL argument");
+    if (mesh->n_face > 0)
+        XR_LAUNCH("perimeter", k_perimeter, dim3(div_up(mesh->n_face, 256)), dim3(256), 0, mesh->node_xy.get(),
+                  mesh->faces_raw.get(), mesh->n_face, mesh->m, out_dev);
+    dev_call_done();
+    XR_API_END
+}
+
+int xr_mesh_face_bounds_dev(xr_mesh *mesh, double *out_dev) {
+    XR_API_BEGIN
+    XR_REQUIRE(mesh && (out_dev || mesh->n_face == 0), XR_ERR_INVALID, "xr_mesh_face_bounds_dev: NULL argument");
+    if (mesh->n_face > 0)
+        XR_LAUNCH("face_bounds", k_face_bounds, dim3(div_up(mesh->n_face, 256)), dim3(256), 0, mesh->node_xy.get(),
+                  mesh->faces_raw.get(), mesh->n_face, mesh->m, out_dev);
+    dev_call_done();
+    XR_API_END
+}
+
+int xr_mesh_triangulate(xr_mesh *mesh, xr_mesh **out) {
+    XR_API_BEGIN
+    XR_REQUIRE(mesh && out, XR_ERR_INVALID, "xr_mesh_triangulate: NULL argument");
+    const int64_t F = mesh->n_face, N = mesh->n_node;
+    const int m = mesh->m;
+    int64_t n_triangle = F;
+    DevBuf<int32_t> off;
+    if (m != 3 && F > 0) { // count, scan, one counter read back
+        DevBuf<int32_t> count((size_t)F);
+        off.alloc((size_t)F + 1);
+        XR_LAUNCH("tri_count", k_tri_count, dim3(div_up(F, 256)), dim3(256), 0, mesh->faces_raw.get(), F, m, count.get());
+        exclusive_scan_i32(count.get(), off.get(), F);
+        n_triangle = read_scalar(off.get() + F);
+    }
+    XR_REQUIRE(n_triangle >= 0 && 3 * n_triangle < ((int64_t)1 << 31), XR_ERR_LIMIT,
+               "xr_mesh_triangulate: %lld triangles exceed the int32 index range", (long long)n_triangle);
+    Building<xr_mesh> tri;
+    tri->n_node = N;
+    tri->n_face = n_triangle;
+    tri->m = 3;
+    tri->is_triangulation = true;
+    tri->node_xy.alloc((size_t)N * 2);
+    tri->faces_raw.alloc((size_t)n_triangle * 3);
+    tri->tri_face.alloc((size_t)n_triangle); // (kept whether or not the index is asked for: 4 bytes per triangle)
+    if (N > 0) // (the handle owns its arrays)
+        XR_HIP(hipMemcpyAsync(tri->node_xy.get(), mesh->node_xy.get(), sizeof(double) * 2 * (size_t)N, hipMemcpyDeviceToDevice,
+                              launch_stream()));
+    if (n_triangle > 0)
+        XR_LAUNCH("tri_scatter", k_tri_scatter, dim3(div_up(F * 3 * (m - 2), 256)), dim3(256), 0, mesh->faces_raw.get(), F, m,
+                  m == 3 ? (const int32_t *)nullptr : off.get(), tri->faces_raw.get(), tri->tri_face.get());
+    stream_sync();
+    *out = tri.release();
+    XR_API_END
+}
+
+int xr_mesh_triangle_face_dev(const xr_mesh *triangles, int64_t *index_dev) {
+    XR_API_BEGIN
+    XR_REQUIRE(triangles && (index_dev || triangles->n_face == 0), XR_ERR_INVALID, "xr_mesh_triangle_face_dev: NULL argument");
+    XR_REQUIRE(triangles->is_triangulation, XR_ERR_INVALID, "xr_mesh_triangle_face_dev: the mesh was not made by xr_mesh_triangulate");
+    if (triangles->n_face > 0)
+        XR_LAUNCH("widen_i32", k_widen_i32_i64, dim3(div_up(triangles->n_face, 256)), dim3(256), 0, triangles->tri_face.get(),
+                  triangles->n_face, index_dev);
+    dev_call_done();
     XR_API_END
 }
 

@@ -79,6 +79,10 @@ struct xr_mesh {
 
     int64_t last_candidates = 0;
 
+    // ---- kept when this mesh is the fan triangulation of another (xr_mesh_triangulate): the source face of every triangle
+    xr::DevBuf<int32_t> tri_face; // [n_face]
+    bool is_triangulation = false;
+
     // ---- kept by the barycentric construction when this mesh is a Voronoi tessellation (xr_locate.hip:barycentric_csr): the
     // vertex -> face table with the interpolation map behind it, and the flags of the cells that hold a substitute vertex --
     // a second interpolator on a cached tessellation uploads and recomputes nothing (its first kernel then runs BESIDE the

@@ -12,8 +12,10 @@
 //     ordered counter-clockwise about the node (voronoi.py:355-372: lexsort((arctan2, node)))
 //   * the assembly of the dense, -1 padded cell table and of the vertex array into a device-resident mesh
 // The cells of nodes ON the boundary (projections on exterior edges, substitute vertices, convexity
-// choice: voronoi.py:59-327) are O(boundary) and stay host numpy (xugrid_amd/voronoi.py); they are handed
-// back in as a small table.
+// choice: voronoi.py:59-327) are O(boundary) host work on a few KB the device gathers (xr_voronoi_boundary.h); they are
+// handed back in as a small table.
+// The same builder serves the public tessellations (ugrid2d.py:1664-1732): any flag set of voronoi_topology and any
+// generator points (xr_voronoi_create_flags).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -23,16 +25,22 @@
 
 #include "xr_node_faces.h"
 #include "xr_objects.h"
+#include "xr_voronoi_boundary.h"
 
 struct xr_voronoi {
     xr_mesh *mesh = nullptr; // borrowed: the caller keeps the source mesh alive
     int64_t n_node = 0, n_face = 0, nnz = 0;
+    // what is built (voronoi.py:330-458): add_exterior closes the cells of the boundary nodes; without it every node with at
+    // least three faces gets an open-ended cell of generator points only, and the vertices are compacted to the points used
+    bool add_exterior = true, add_vertices = true, skip_concave = true;
+    xr::DevBuf<int32_t> vertex_rank; // [n_face+1] !add_exterior: exclusive scan of "some cell uses this generator point"
+    int64_t n_used = 0, max_used = -1; // !add_exterior: points used, the largest used face id
     xr::DevBuf<int32_t> indptr;    // [n_node+1]
     xr::DevBuf<int32_t> faces_asc; // [nnz] faces around each node, ascending (scipy CSR order)
     xr::DevBuf<int32_t> faces_ccw; // [nnz] interior nodes: counter-clockwise about the node
     xr::DevBuf<uint8_t> interior;  // [n_node] 1 = has faces and touches no exterior edge
     xr::DevBuf<int32_t> cell_rank; // [n_node+1] exclusive scan of `interior`
-    xr::DevBuf<double> centroids;  // [n_face*2]
+    xr::DevBuf<double> centroids;  // [n_face*2] the generator points: face centroids, or what the caller handed in
     int64_t n_interior = 0;
     int max_degree = 0, min_degree = 0; // over interior nodes
     std::vector<int64_t> edge_lo, edge_hi, edge_face; // exterior edges, lexicographic (lo, hi)
@@ -171,14 +179,15 @@ __global__ void __launch_bounds__(VOR_BLOCK)
 k_vor_interior(const double *__restrict__ node_xy, const double *__restrict__ cxy,
                const int32_t *__restrict__ indptr, const int32_t *__restrict__ rows_asc,
                const uint8_t *__restrict__ on_boundary, int64_t n_node, int32_t *__restrict__ rows_ccw,
-               uint8_t *__restrict__ interior, int32_t *__restrict__ flag32, int32_t *__restrict__ deg_minmax) {
+               uint8_t *__restrict__ interior, int32_t *__restrict__ flag32, int32_t *__restrict__ deg_minmax,
+               int all_nodes /* 1: add_exterior = False -- every node with at least three faces, boundary nodes included */) {
     __shared__ double2 sh_d[VOR_CAP][VOR_BLOCK];
     __shared__ int32_t sh_k[VOR_CAP][VOR_BLOCK];
     const int t = threadIdx.x;
     const int64_t v = (int64_t)blockIdx.x * VOR_BLOCK + t;
     const bool in_range = v < n_node;
     const int s = in_range ? indptr[v] : 0, e = in_range ? indptr[v + 1] : 0;
-    const bool ok = in_range && e > s && !on_boundary[v];
+    const bool ok = in_range && (all_nodes ? e - s >= 3 : e > s && !on_boundary[v]);
     // degree range: reduced over the wave, and an atomic only when it improves what the word already holds -- one
     // atomicMin + one atomicMax per NODE on the same two words cost 0.13 ms of the kernel's 0.23 (A/B without them: 0.097)
     {
@@ -255,14 +264,42 @@ k_vor_interior(const double *__restrict__ node_xy, const double *__restrict__ cx
 __global__ void __launch_bounds__(256)
 k_vor_cells(const int32_t *__restrict__ indptr, const int32_t *__restrict__ rows_ccw,
             const uint8_t *__restrict__ interior, const int32_t *__restrict__ cell_rank, int64_t n_node, int m,
-            int32_t *__restrict__ cells) {
+            int32_t *__restrict__ cells, const int32_t *__restrict__ vertex_rank /* nullptr: vertex id = face id */) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_node * m) return;
     const int64_t v = i / m;
     const int j = (int)(i - v * m);
     if (!interior[v]) return;
     const int s = indptr[v], n = indptr[v + 1] - s;
-    cells[(int64_t)cell_rank[v] * m + j] = j < n ? rows_ccw[s + j] : -1;
+    int c = j < n ? rows_ccw[s + j] : -1;
+    if (vertex_rank && c >= 0) c = vertex_rank[c];
+    cells[(int64_t)cell_rank[v] * m + j] = c;
+}
+
+// add_exterior = False: the generator points some cell uses (a face is used iff one of its nodes has at least three faces),
+// then -- behind the scan of the flags -- their coordinates in ascending face order and the largest used face id
+__global__ void __launch_bounds__(256)
+k_vor_used(const int32_t *__restrict__ faces, int64_t n_face, int m, const int32_t *__restrict__ indptr,
+           int32_t *__restrict__ used) {
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (f >= n_face) return;
+    int u = 0;
+    for (int j = 0; j < m; j++) {
+        const int a = faces[f * m + j];
+        if (a >= 0 && indptr[a + 1] - indptr[a] >= 3) u = 1;
+    }
+    used[f] = u;
+}
+
+__global__ void __launch_bounds__(256)
+k_vor_compact(const double *__restrict__ cxy, const int32_t *__restrict__ rank, int64_t n_face, double *__restrict__ out_xy,
+              int32_t *__restrict__ max_used) {
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (f >= n_face) return;
+    const int r = rank[f];
+    if (rank[f + 1] == r) return; // not used
+    reinterpret_cast<double2 *>(out_xy)[r] = reinterpret_cast<const double2 *>(cxy)[f];
+    if (r + 1 == rank[n_face]) *max_used = (int32_t)f;
 }
 
 __global__ void __launch_bounds__(256)
@@ -272,11 +309,6 @@ k_vor_boundary_cells(const int32_t *__restrict__ table, int64_t n_rows, int mb, 
     const int64_t r = i / m;
     const int j = (int)(i - r * m);
     cells[i] = j < mb ? table[r * mb + j] : -1;
-}
-
-__global__ void __launch_bounds__(256) k_vor_widen(const int32_t *__restrict__ in, int64_t n, int64_t *__restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = in[i];
 }
 
 // everything the host needs about the boundary except the rows themselves, in ONE launch: per boundary node its degree and
@@ -388,197 +420,42 @@ static void voronoi_boundary(xr_voronoi *v) {
 }
 
 
-// ---------------------------------------------------------------------------------------------------------------------
-// The cells of the boundary nodes (voronoi.py:59-327 for add_exterior = add_vertices = skip_concave = True): native host
-// code on the few KB voronoi_boundary() gathered -- a LOCAL problem (boundary nodes 0..nb-1, the faces around them
-// 0..nl-1, both ascending like their global ids, so every grouping and stable sort sees the order it would see globally).
-// O(boundary) items in a dozen dependent steps (sorts, a scan, a per-cell convexity choice): tens of microseconds here; as
-// device kernels each step would be a launch plus a round trip.  The arithmetic follows xugrid_amd/voronoi.py
-// (_boundary_records) operation for operation, including numpy's pairwise summation in the polygon areas: on a straight
-// boundary the two candidate areas of the convexity choice differ by rounding only.
-// ---------------------------------------------------------------------------------------------------------------------
-static double np_pairwise_sum(const double *a, int64_t n) { // numpy's DOUBLE_pairwise_sum for n <= 128
-    if (n < 8) {
-        double res = 0.0;
-        for (int64_t i = 0; i < n; i++) res += a[i];
-        return res;
-    }
-    double r[8];
-    for (int j = 0; j < 8; j++) r[j] = a[j];
-    int64_t i = 8;
-    for (; i < n - (n % 8); i += 8)
-        for (int j = 0; j < 8; j++) r[j] += a[i + j];
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; i++) res += a[i];
-    return res;
-}
-
+// The cells of the boundary nodes (voronoi.py:59-327): native host code on the few KB voronoi_boundary() gathered; the
+// computation itself is plain C++ in xr_voronoi_boundary.h (also built stand-alone under the host sanitizers).
 static void voronoi_boundary_cells(xr_voronoi *v) {
     if (v->cells_ready) return;
     voronoi_boundary(v);
     // (the boundary rows are on the host now; whatever device work is waiting for a good moment -- the source-side half of a
     // barycentric construction -- goes out here, and runs while the host builds the boundary cells below)
     flush_pending_points();
-    const auto tk0 = std::chrono::steady_clock::now();
-    const int64_t nb = (int64_t)v->b_nodes.size(), ne = (int64_t)v->edge_face.size(), n_face = v->n_face;
-    v->c_extra_xy.clear(); v->c_cells.clear(); v->c_tail.clear(); v->c_interp.clear();
-    v->c_n_cell = 0; v->c_m = 0;
-    if (ne == 0) { // closed surface: nothing to add
-        v->cells_ready = true;
-        return;
-    }
-    XR_REQUIRE(n_face + 3 * ne < ((int64_t)1 << 31), XR_ERR_LIMIT, "voronoi: vertex ids exceed the int32 range");
-    // Vertex ids are GLOBAL from the start (face centroid f -> f, kept projection r -> n_face + r, extra corner k ->
-    // n_face + n_proj + k): the local renumbering of the numpy restatement only exists to keep its arrays small; every
-    // record carries its corner's coordinates, so no vertex table is needed either.  Cell keys are local node ranks
-    // (ascending like the global node ids).
-    struct Rec {
-        int64_t key, id;
-        double x, y, angle;
-    };
-    std::vector<Rec> rec;
-    rec.reserve(v->b_faces.size() + 3 * (size_t)ne);
-    for (int64_t i = 0; i < nb; i++) // corners that are face centroids: nodes shared by several faces ...
-        if (v->b_ptr[(size_t)i + 1] - v->b_ptr[(size_t)i] > 1)
-            for (int64_t r = v->b_ptr[(size_t)i]; r < v->b_ptr[(size_t)i + 1]; r++)
-                rec.push_back({i, v->b_faces[(size_t)r], v->b_face_xy[2 * (size_t)r], v->b_face_xy[2 * (size_t)r + 1], 0.0});
-    for (int64_t i = 0; i < nb; i++) // ... then corner nodes owned by exactly one face
-        if (v->b_ptr[(size_t)i + 1] - v->b_ptr[(size_t)i] == 1) {
-            const size_t r = (size_t)v->b_ptr[(size_t)i];
-            rec.push_back({i, v->b_faces[r], v->b_face_xy[2 * r], v->b_face_xy[2 * r + 1], 0.0});
-        }
-    // projections of the adjacent face centroid on every exterior edge
-    auto local_node = [&](int64_t g) { return (int64_t)(std::lower_bound(v->b_nodes.begin(), v->b_nodes.end(), g) - v->b_nodes.begin()); };
-    const double *nxy = v->b_node_xy.data();
-    const double merge_tol = 1.0e-8 * 1.0e-8;
-    std::vector<int64_t> e_n0((size_t)ne), e_n1((size_t)ne), kept_rank((size_t)ne, -1);
-    std::vector<double> proj_all((size_t)ne * 2);
-    int64_t n_proj = 0;
-    for (int64_t e = 0; e < ne; e++) {
-        e_n0[(size_t)e] = local_node(v->edge_lo[(size_t)e]);
-        e_n1[(size_t)e] = local_node(v->edge_hi[(size_t)e]);
-        const double ax = nxy[2 * e_n0[(size_t)e]], ay = nxy[2 * e_n0[(size_t)e] + 1];
-        const double bx = nxy[2 * e_n1[(size_t)e]], by = nxy[2 * e_n1[(size_t)e] + 1];
-        const double cx = v->b_edge_face_xy[2 * (size_t)e], cy = v->b_edge_face_xy[2 * (size_t)e + 1];
-        const double vx = bx - ax, vy = by - ay, ux = cx - ax, uy = cy - ay;
-        const double sc = (ux * vx + uy * vy) / (vx * vx + vy * vy);
-        const double px = ax + sc * vx, py = ay + sc * vy;
-        proj_all[2 * (size_t)e] = px;
-        proj_all[2 * (size_t)e + 1] = py;
-        const double dx = px - cx, dy = py - cy;
-        if (std::sqrt(dx * dx + dy * dy) > merge_tol) kept_rank[(size_t)e] = n_proj++;
-    }
-    const int64_t first_new = n_face + n_proj; // id of the first extra corner
-    for (int64_t e = 0; e < ne; e++)
-        if (kept_rank[(size_t)e] >= 0) { // both end nodes use the projection
-            const int64_t id = n_face + kept_rank[(size_t)e];
-            rec.push_back({e_n0[(size_t)e], id, proj_all[2 * (size_t)e], proj_all[2 * (size_t)e + 1], 0.0});
-            rec.push_back({e_n1[(size_t)e], id, proj_all[2 * (size_t)e], proj_all[2 * (size_t)e + 1], 0.0});
-            v->c_tail.push_back(v->edge_face[(size_t)e]);
-        }
-    // one extra corner per boundary node, between the node's two projections: the (edge, end) records sorted by node id
-    // (stable), paired off two by two; the interpolation map refers to the UNFILTERED projection numbering exactly as the
-    // reference does
-    std::vector<int64_t> by_node((size_t)(2 * ne));
-    for (int64_t j = 0; j < 2 * ne; j++) by_node[(size_t)j] = j;
-    auto flat_node = [&](int64_t j) { return (j & 1) ? e_n1[(size_t)(j >> 1)] : e_n0[(size_t)(j >> 1)]; };
-    std::stable_sort(by_node.begin(), by_node.end(), [&](int64_t a, int64_t b) { return flat_node(a) < flat_node(b); });
-    const int64_t n_extra = ne; // (2 ne records, two per extra corner)
-    std::vector<double> extra_xy((size_t)n_extra * 2), true_corner((size_t)n_extra * 2);
-    v->c_interp.resize((size_t)n_extra * 2);
-    for (int64_t k = 0; k < n_extra; k++) {
-        const int64_t p0 = by_node[(size_t)(2 * k)] >> 1, p1 = by_node[(size_t)(2 * k + 1)] >> 1;
-        extra_xy[2 * (size_t)k] = 0.5 * (proj_all[2 * (size_t)p0] + proj_all[2 * (size_t)p1]);
-        extra_xy[2 * (size_t)k + 1] = 0.5 * (proj_all[2 * (size_t)p0 + 1] + proj_all[2 * (size_t)p1 + 1]);
-        const int64_t node = flat_node(by_node[(size_t)(2 * k)]);
-        rec.push_back({node, first_new + k, extra_xy[2 * (size_t)k], extra_xy[2 * (size_t)k + 1], 0.0});
-        v->c_interp[2 * (size_t)k] = p0 + n_face;
-        v->c_interp[2 * (size_t)k + 1] = p1 + n_face;
-        true_corner[2 * (size_t)k] = nxy[2 * node];
-        true_corner[2 * (size_t)k + 1] = nxy[2 * node + 1];
-    }
-    v->c_tail.insert(v->c_tail.end(), (size_t)n_extra, (int64_t)-1);
-    const auto tk1 = std::chrono::steady_clock::now();
-    // ---- counter-clockwise order about the mean of each cell's corners (sums in record order, as np.bincount)
-    const int64_t n_rec = (int64_t)rec.size();
-    std::vector<double> sx((size_t)nb, 0.0), sy((size_t)nb, 0.0), cnt((size_t)nb, 0.0);
-    for (const Rec &r : rec) {
-        sx[(size_t)r.key] += r.x;
-        sy[(size_t)r.key] += r.y;
-        cnt[(size_t)r.key] += 1.0;
-    }
-    for (Rec &r : rec) {
-        const double px = sx[(size_t)r.key] / cnt[(size_t)r.key], py = sy[(size_t)r.key] / cnt[(size_t)r.key];
-        r.angle = std::atan2(r.y - py, r.x - px);
-    }
-    std::stable_sort(rec.begin(), rec.end(), [](const Rec &a, const Rec &b) {
-        if (a.key != b.key) return a.key < b.key;
-        return a.angle < b.angle;
-    });
-    const auto tk2 = std::chrono::steady_clock::now();
-    // ---- dense table: one row per distinct key (ascending), -1 padded
-    std::vector<int64_t> row_start;
-    for (int64_t r = 0; r < n_rec; r++)
-        if (r == 0 || rec[(size_t)r].key != rec[(size_t)r - 1].key) row_start.push_back(r);
-    const int64_t n_cell = (int64_t)row_start.size();
-    row_start.push_back(n_rec);
-    int64_t m = 0;
-    for (int64_t c = 0; c < n_cell; c++) m = std::max(m, row_start[(size_t)c + 1] - row_start[(size_t)c]);
-    XR_REQUIRE(m <= 128, XR_ERR_LIMIT, "voronoi: a boundary cell has %lld corners", (long long)m);
-    std::vector<int64_t> cells((size_t)(n_cell * m), -1);
-    // ---- keep the true boundary node where it does not make the cell concave: the cell's area with the true node against
-    // its area with the midpoint substitute (closed polygon: fill slots and the closing slot repeat corner 0)
-    std::vector<double> term((size_t)m);
-    for (int64_t c = 0; c < n_cell; c++) {
-        const Rec *row = rec.data() + row_start[(size_t)c];
-        const int64_t len = row_start[(size_t)c + 1] - row_start[(size_t)c];
-        for (int64_t j = 0; j < len; j++) cells[(size_t)(c * m + j)] = row[j].id;
-        auto vertex = [&](int64_t j, bool use_true, double &x, double &y) { // corner j of the closed polygon
-            const Rec &r = row[j < len ? j : 0];
-            if (use_true && r.id >= first_new) {
-                x = true_corner[2 * (size_t)(r.id - first_new)];
-                y = true_corner[2 * (size_t)(r.id - first_new) + 1];
-            } else {
-                x = r.x;
-                y = r.y;
-            }
-        };
-        double area[2];
-        for (int t = 0; t < 2; t++) {
-            double x0, y0;
-            vertex(0, t == 1, x0, y0);
-            for (int64_t i = 0; i < m; i++) { // closed[i], closed[i + 1] with closed[m] = corner 0
-                double xa, ya, xb, yb;
-                vertex(i, t == 1, xa, ya);
-                vertex(i + 1 < m ? i + 1 : len, t == 1, xb, yb);
-                const double a0 = xa - x0, a1 = ya - y0, b0 = xb - x0, b1 = yb - y0;
-                term[(size_t)i] = a0 * b1 - a1 * b0;
-            }
-            area[t] = 0.5 * std::fabs(np_pairwise_sum(term.data(), m));
-        }
-        if (area[1] >= area[0])
-            for (int64_t j = 0; j < len; j++)
-                if (row[j].id >= first_new) {
-                    const int64_t k = row[j].id - first_new;
-                    extra_xy[2 * (size_t)k] = true_corner[2 * (size_t)k];
-                    extra_xy[2 * (size_t)k + 1] = true_corner[2 * (size_t)k + 1];
-                }
-    }
-    const auto tk3 = std::chrono::steady_clock::now();
+    VoronoiBoundaryIn in;
+    in.n_face = v->n_face;
+    in.nb = (int64_t)v->b_nodes.size();
+    in.ne = (int64_t)v->edge_face.size();
+    in.nodes = v->b_nodes.data();
+    in.row_ptr = v->b_ptr.data();
+    in.faces = v->b_faces.data();
+    in.face_xy = v->b_face_xy.data();
+    in.node_xy = v->b_node_xy.data();
+    in.edge_lo = v->edge_lo.data();
+    in.edge_hi = v->edge_hi.data();
+    in.edge_face = v->edge_face.data();
+    in.edge_face_xy = v->b_edge_face_xy.data();
+    in.add_vertices = v->add_vertices;
+    in.skip_concave = v->skip_concave;
+    VoronoiBoundaryOut out;
+    const int status = xr::voronoi_boundary_cells(in, out);
+    XR_REQUIRE(status != VORONOI_BOUNDARY_ID_RANGE, XR_ERR_LIMIT, "voronoi: vertex ids exceed the int32 range");
+    XR_REQUIRE(status != VORONOI_BOUNDARY_CELL_CORNERS, XR_ERR_LIMIT, "voronoi: a boundary cell has %lld corners", (long long)out.m);
     if (option(OPT_DEBUG) & 4)
-        fprintf(stderr, "[voronoi] records %lld: set-up %.3f, sort %.3f, cells + convexity %.3f ms\n", (long long)n_rec,
-                std::chrono::duration<double, std::milli>(tk1 - tk0).count(), std::chrono::duration<double, std::milli>(tk2 - tk1).count(),
-                std::chrono::duration<double, std::milli>(tk3 - tk2).count());
-    v->c_cells = std::move(cells);
-    v->c_n_cell = n_cell;
-    v->c_m = m;
-    v->c_extra_xy.resize((size_t)(n_proj + n_extra) * 2);
-    for (int64_t e = 0; e < ne; e++)
-        if (kept_rank[(size_t)e] >= 0) {
-            v->c_extra_xy[2 * (size_t)kept_rank[(size_t)e]] = proj_all[2 * (size_t)e];
-            v->c_extra_xy[2 * (size_t)kept_rank[(size_t)e] + 1] = proj_all[2 * (size_t)e + 1];
-        }
-    std::copy(extra_xy.begin(), extra_xy.end(), v->c_extra_xy.begin() + 2 * n_proj);
+        fprintf(stderr, "[voronoi] records %lld: set-up %.3f, sort %.3f, cells + convexity %.3f ms\n", (long long)out.n_record,
+                out.ms_setup, out.ms_sort, out.ms_cells);
+    v->c_extra_xy = std::move(out.extra_xy);
+    v->c_cells = std::move(out.cells);
+    v->c_n_cell = out.n_cell;
+    v->c_m = out.m;
+    v->c_tail = std::move(out.tail);
+    v->c_interp = std::move(out.interp);
     v->cells_ready = true;
 }
 
@@ -588,10 +465,14 @@ using namespace xr;
 
 extern "C" {
 
-int xr_voronoi_create(xr_mesh *mesh, xr_voronoi **out) {
+int xr_voronoi_create(xr_mesh *mesh, xr_voronoi **out) { return xr_voronoi_create_flags(mesh, 1, 1, 1, nullptr, out); }
+
+int xr_voronoi_create_flags(xr_mesh *mesh, int add_exterior, int add_vertices, int skip_concave, const double *generators_dev,
+                            xr_voronoi **out) {
     XR_API_BEGIN
     XR_REQUIRE(mesh && out, XR_ERR_INVALID, "xr_voronoi_create: NULL argument");
-    Building<xr_voronoi> v;
+    Building<xr_voronoi> v(generators_dev ? OnFailure::WaitFirst : OnFailure::FreeOnly);
+    v->add_exterior = add_exterior != 0; v->add_vertices = add_vertices != 0; v->skip_concave = skip_concave != 0;
     const int64_t N = mesh->n_node, F = mesh->n_face;
     const int m = mesh->m;
     const int64_t total = F * m;
@@ -620,14 +501,21 @@ int xr_voronoi_create(xr_mesh *mesh, xr_voronoi **out) {
                   v->indptr.get(), cursor, v->faces_asc.get());
         XR_LAUNCH("vor_sort_rows", k_vor_sort_rows, dim3(div_up(N, 256)), dim3(256), 0, v->indptr.get(), N,
                   v->faces_asc.get());
-        XR_LAUNCH("vor_exterior", k_vor_exterior, dim3(div_up(total, 256)), dim3(256), 0, mesh->faces_raw.get(), F, m,
-                  v->indptr.get(), v->faces_asc.get(), on_boundary.get(), counters.get(), e_all.get());
+        if (v->add_exterior) // (without it no cell is closed along the boundary: nothing reads the exterior edges)
+            XR_LAUNCH("vor_exterior", k_vor_exterior, dim3(div_up(total, 256)), dim3(256), 0, mesh->faces_raw.get(), F, m,
+                      v->indptr.get(), v->faces_asc.get(), on_boundary.get(), counters.get(), e_all.get());
     }
-    mesh_centroids_dev(mesh, v->centroids.get());
+    if (generators_dev) {
+        if (F > 0)
+            XR_HIP(hipMemcpyAsync(v->centroids.get(), generators_dev, sizeof(double) * 2 * (size_t)F, hipMemcpyDeviceToDevice,
+                                  launch_stream()));
+    } else {
+        mesh_centroids_dev(mesh, v->centroids.get());
+    }
     if (N > 0)
         XR_LAUNCH("vor_interior", k_vor_interior, dim3(div_up(N, VOR_BLOCK)), dim3(VOR_BLOCK), 0, mesh->node_xy.get(),
                   v->centroids.get(), v->indptr.get(), v->faces_asc.get(), on_boundary.get(), N, v->faces_ccw.get(),
-                  v->interior.get(), flag32.get(), counters.get() + 1);
+                  v->interior.get(), flag32.get(), counters.get() + 1, v->add_exterior ? 0 : 1);
     exclusive_scan_i32(flag32.get(), v->cell_rank.get(), N);
     XR_LAUNCH("vor_totals", k_vor_totals, dim3(1), dim3(64), 0, v->cell_rank.get() + N, v->indptr.get() + N, counters.get());
     // (every kernel of the O(n) part is enqueued; from here on the host reads counters and lists back -- the device idles for
@@ -663,7 +551,29 @@ int xr_voronoi_create(xr_mesh *mesh, xr_voronoi **out) {
         v->edge_hi[(size_t)i] = hi[(size_t)order[(size_t)i]];
         v->edge_face[(size_t)i] = fc[(size_t)order[(size_t)i]];
     }
+    if (!v->add_exterior) {
+        XR_REQUIRE(v->n_interior > 0, XR_ERR_INVALID, "voronoi: no node is shared by at least three faces, nothing to tessellate");
+        DevBuf<int32_t> used((size_t)F), max_used(1);
+        v->vertex_rank.alloc((size_t)F + 1);
+        XR_LAUNCH("vor_used", k_vor_used, dim3(div_up(F, 256)), dim3(256), 0, mesh->faces_raw.get(), F, m, v->indptr.get(), used.get());
+        exclusive_scan_i32(used.get(), v->vertex_rank.get(), F);
+        DevBuf<double> packed((size_t)F * 2);
+        fill_i32(max_used.get(), -1, 1);
+        XR_LAUNCH("vor_compact", k_vor_compact, dim3(div_up(F, 256)), dim3(256), 0, v->centroids.get(), v->vertex_rank.get(), F,
+                  packed.get(), max_used.get());
+        v->n_used = read_scalar(v->vertex_rank.get() + F);
+        v->max_used = read_scalar(max_used.get());
+        v->centroids = std::move(packed); // (the first n_used entries: the vertices of the tessellation)
+    }
     *out = v.release();
+    XR_API_END
+}
+
+int xr_voronoi_vertex_info(const xr_voronoi *v, int64_t *n_generator_vertex, int64_t *max_used_face) {
+    XR_API_BEGIN
+    XR_REQUIRE(v && n_generator_vertex && max_used_face, XR_ERR_INVALID, "xr_voronoi_vertex_info: NULL argument");
+    *n_generator_vertex = v->add_exterior ? v->n_face : v->n_used;
+    *max_used_face = v->add_exterior ? v->n_face - 1 : v->max_used;
     XR_API_END
 }
 
@@ -683,13 +593,15 @@ int xr_voronoi_download(const xr_voronoi *v, int64_t *indptr, int64_t *indices, 
                         double *centroids) {
     XR_API_BEGIN
     XR_REQUIRE(v && indptr && (v->nnz == 0 || indices), XR_ERR_INVALID, "xr_voronoi_download: NULL argument");
+    XR_REQUIRE(v->add_exterior || !centroids, XR_ERR_INVALID,
+               "xr_voronoi_download: a handle built without exterior keeps only the generator points its cells use");
     {
         DevBuf<int64_t> wide((size_t)std::max<int64_t>(v->n_node + 1, v->nnz));
-        XR_LAUNCH("vor_widen", k_vor_widen, dim3(div_up(v->n_node + 1, 256)), dim3(256), 0, v->indptr.get(), v->n_node + 1,
+        XR_LAUNCH("vor_widen", k_widen_i32_i64, dim3(div_up(v->n_node + 1, 256)), dim3(256), 0, v->indptr.get(), v->n_node + 1,
                   wide.get());
         d2h(indptr, wide.get(), sizeof(int64_t) * (size_t)(v->n_node + 1));
         if (v->nnz > 0) {
-            XR_LAUNCH("vor_widen", k_vor_widen, dim3(div_up(v->nnz, 256)), dim3(256), 0, v->faces_asc.get(), v->nnz,
+            XR_LAUNCH("vor_widen", k_widen_i32_i64, dim3(div_up(v->nnz, 256)), dim3(256), 0, v->faces_asc.get(), v->nnz,
                       wide.get());
             d2h(indices, wide.get(), sizeof(int64_t) * (size_t)v->nnz);
         }
@@ -747,7 +659,10 @@ int xr_voronoi_mesh(const xr_voronoi *v, const double *extra_xy, int64_t n_extra
                "xr_voronoi_mesh: NULL arrays");
     XR_REQUIRE(v->n_interior == 0 || v->min_degree >= 3, XR_ERR_INVALID,
                "xr_voronoi_mesh: an interior node is surrounded by only %d faces (non-manifold mesh)", v->min_degree);
-    const int64_t n_vertex = v->n_face + n_extra_vertex;
+    const int64_t n_generator = v->add_exterior ? v->n_face : v->n_used; // (without the exterior: the points some cell uses)
+    XR_REQUIRE(v->add_exterior || (n_extra_vertex == 0 && n_boundary_cell == 0), XR_ERR_INVALID,
+               "xr_voronoi_mesh: a tessellation without exterior has no boundary cells");
+    const int64_t n_vertex = n_generator + n_extra_vertex;
     const int64_t n_cell = v->n_interior + n_boundary_cell;
     const int64_t m64 = std::max<int64_t>(std::max<int64_t>(v->max_degree, n_boundary_cell > 0 ? n_max_boundary : 0), 3);
     XR_REQUIRE(m64 <= XR_MAX_FACE_NODES, XR_ERR_LIMIT, "xr_voronoi_mesh: a Voronoi cell has %lld corners (limit %d)",
@@ -756,6 +671,7 @@ int xr_voronoi_mesh(const xr_voronoi *v, const double *extra_xy, int64_t n_extra
                "xr_voronoi_mesh: mesh exceeds the int32 index range");
     const int m = (int)m64;
     const int mb = (int)n_max_boundary;
+    XR_REQUIRE(n_boundary_cell == 0 || mb >= 3, XR_ERR_INVALID, "xr_voronoi_mesh: every boundary cell has fewer than 3 corners (n_max_boundary = %d)", mb);
     std::vector<int32_t> table((size_t)(n_boundary_cell * mb) + 1);
     for (int64_t r = 0; r < n_boundary_cell; r++) {
         for (int j = 0; j < mb; j++) {
@@ -773,14 +689,15 @@ int xr_voronoi_mesh(const xr_voronoi *v, const double *extra_xy, int64_t n_extra
     mesh->m = m;
     mesh->node_xy.alloc((size_t)n_vertex * 2);
     mesh->faces_raw.alloc((size_t)(n_cell * m));
-    if (v->n_face > 0)
-        XR_HIP(hipMemcpyAsync(mesh->node_xy.get(), v->centroids.get(), sizeof(double) * 2 * (size_t)v->n_face,
+    if (n_generator > 0)
+        XR_HIP(hipMemcpyAsync(mesh->node_xy.get(), v->centroids.get(), sizeof(double) * 2 * (size_t)n_generator,
                               hipMemcpyDeviceToDevice, launch_stream()));
     if (n_extra_vertex > 0)
-        h2d(mesh->node_xy.get() + 2 * v->n_face, extra_xy, sizeof(double) * 2 * (size_t)n_extra_vertex);
+        h2d(mesh->node_xy.get() + 2 * n_generator, extra_xy, sizeof(double) * 2 * (size_t)n_extra_vertex);
     if (v->n_node > 0 && v->n_interior > 0)
         XR_LAUNCH("vor_cells", k_vor_cells, dim3(div_up(v->n_node * m, 256)), dim3(256), 0, v->indptr.get(),
-                  v->faces_ccw.get(), v->interior.get(), v->cell_rank.get(), v->n_node, m, mesh->faces_raw.get());
+                  v->faces_ccw.get(), v->interior.get(), v->cell_rank.get(), v->n_node, m, mesh->faces_raw.get(),
+                  v->add_exterior ? (const int32_t *)nullptr : v->vertex_rank.get());
     if (n_boundary_cell > 0) {
         DevBuf<int32_t> dtable((size_t)(n_boundary_cell * mb));
         h2d(dtable.get(), table.data(), sizeof(int32_t) * (size_t)(n_boundary_cell * mb));

@@ -321,6 +321,35 @@ class DeviceMesh:
         check(_lib.load().xr_mesh_faces(self._h, _ptr(out)))
         return out
 
+    # ---- meshes and per-face quantities derived on the device (include/xugrid_amd.h: xr_mesh_triangulate ...)
+    def triangulate(self) -> "DeviceMesh":
+        """The fan triangulation as a new device-resident mesh; ``triangle_face_dev`` of the result gives the index."""
+        handle = ctypes.c_void_p()
+        check(_lib.load().xr_mesh_triangulate(self._h, ctypes.byref(handle)))
+        return DeviceMesh._from_handle(handle)
+
+    def triangle_face_dev(self, like=None):
+        """Source face of every triangle of a mesh made by ``triangulate``: an int64 device array of the kind of ``like``."""
+        out, ptr = empty_like_device(like, (self.n_face,), np.int64)
+        check(_lib.load().xr_mesh_triangle_face_dev(self._h, ctypes.c_void_p(ptr)))
+        return out
+
+    def _derived_dev(self, name, shape):
+        out = DeviceArray(shape, np.float64)
+        check(getattr(_lib.load(), name)(self._h, ctypes.c_void_p(out.ptr)))
+        return out
+
+    def circumcenters_dev(self) -> "DeviceArray":
+        if self.n_max_node != 3:  # (connectivity.py:697-700; before anything touches the device)
+            raise NotImplementedError("Circumcenters are only supported for triangular grids")
+        return self._derived_dev("xr_mesh_circumcenters_dev", (self.n_face, 2))
+
+    def perimeter_dev(self) -> "DeviceArray":
+        return self._derived_dev("xr_mesh_perimeter_dev", (self.n_face,))
+
+    def face_bounds_dev(self) -> "DeviceArray":
+        return self._derived_dev("xr_mesh_face_bounds_dev", (self.n_face, 4))
+
     def overlap(self, query: "DeviceMesh", relative=False) -> "DeviceCSR":
         """All (query face, self face) pairs with positive intersection area, as CSR rows=query."""
         handle = ctypes.c_void_p()
@@ -388,11 +417,22 @@ class DeviceMesh:
 class DeviceVoronoi:
     """Device part of the centroidal Voronoi pre-step of a mesh (see include/xugrid_amd.h, xr_voronoi_*)."""
 
-    def __init__(self, mesh: DeviceMesh):
+    def __init__(self, mesh: DeviceMesh, add_exterior=True, add_vertices=True, skip_concave=True, generators=None):
+        """``generators``: the points the cells are made of, a float64 ``(n_face, 2)`` device array (copied); None: the face
+        centroids.  The flags are those of ``voronoi.voronoi_topology``."""
         handle = ctypes.c_void_p()
-        check(_lib.load().xr_voronoi_create(mesh._h, ctypes.byref(handle)))
+        ptr = None
+        if generators is not None:
+            info = device_array_info(generators)
+            if info is None or info[1] != (mesh.n_face, 2) or info[2] != np.float64:
+                raise ValueError("generators must be a float64 (n_face, 2) device array")
+            sync_producer(generators)
+            ptr = info[0]
+        check(_lib.load().xr_voronoi_create_flags(mesh._h, int(bool(add_exterior)), int(bool(add_vertices)),
+                                                  int(bool(skip_concave)), ctypes.c_void_p(ptr), ctypes.byref(handle)))
         self._h = handle
         self._mesh = mesh  # keep the source alive
+        self.add_exterior, self.add_vertices = bool(add_exterior), bool(add_vertices)
         vals = [ctypes.c_int64() for _ in range(5)]
         check(_lib.load().xr_voronoi_info(handle, *[ctypes.byref(v) for v in vals]))
         self.n_node, self.nnz, self.n_exterior_edge, self.n_interior_cell, self.max_interior_degree = (v.value for v in vals)
@@ -406,16 +446,23 @@ class DeviceVoronoi:
                 pass
             self._h = None
 
+    def vertex_info(self):
+        """-> (generator points at the head of the tessellation's vertices, the largest face id among them)."""
+        n, hi = ctypes.c_int64(), ctypes.c_int64()
+        check(_lib.load().xr_voronoi_vertex_info(self._h, ctypes.byref(n), ctypes.byref(hi)))
+        return n.value, hi.value
+
     def download(self):
-        """-> (indptr, indices) of node_face_connectivity, exterior edge_nodes (n, 2), edge_face (n,), centroids."""
+        """-> (indptr, indices) of node_face_connectivity, exterior edge_nodes (n, 2), edge_face (n,), centroids (None for a
+        builder without exterior: it keeps only the generator points its cells use)."""
         indptr = np.empty(self.n_node + 1, dtype=np.int64)
         indices = np.empty(self.nnz, dtype=np.int64)
         edge_nodes = np.empty((self.n_exterior_edge, 2), dtype=np.int64)
         edge_face = np.empty(self.n_exterior_edge, dtype=np.int64)
-        centroids = np.empty((self._mesh.n_face, 2), dtype=np.float64)
+        centroids = np.empty((self._mesh.n_face, 2), dtype=np.float64) if self.add_exterior else None
         check(
             _lib.load().xr_voronoi_download(
-                self._h, _ptr(indptr), _ptr(indices), _ptr(edge_nodes), _ptr(edge_face), _ptr(centroids)
+                self._h, _ptr(indptr), _ptr(indices), _ptr(edge_nodes), _ptr(edge_face), _ptr(centroids) if self.add_exterior else None
             )
         )
         return indptr, indices, edge_nodes, edge_face, centroids

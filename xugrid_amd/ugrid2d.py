@@ -174,6 +174,7 @@ class Ugrid2d:
         self.__dict__.pop("_sample_cache", None)
         self.__dict__.pop("_topology_cache", None)
         self.__dict__.pop("_facet_cache", None)
+        self.__dict__.pop("_derive_cache", None)
 
     @property
     def device_mesh(self):
@@ -483,6 +484,113 @@ class Ugrid2d:
 
         return polygonize(self, data, return_index)
 
+    # ---- meshes and per-face geometry derived on the device (csrc/xr_mesh.hip: triangulation, circumcenters, perimeter,
+    # face bounds; csrc/xr_voronoi.hip: the tessellations)
+    _device_resident = False  # True: the mesh exists in HBM only; derived grids stay there and indices are device arrays
+
+    def _derived(self, key, make):
+        cache = self.__dict__.setdefault("_derive_cache", {})
+        if key not in cache:
+            cache[key] = make()
+        return cache[key]
+
+    def _grid_from_mesh(self, mesh):
+        """A grid of this grid's kind around a mesh that was built on the device."""
+        if self._device_resident:
+            return DeviceUgrid2d.from_device_mesh(mesh, name=self.name)
+        xy, faces = mesh.download()
+        grid = Ugrid2d(xy[:, 0], xy[:, 1], FILL_VALUE, faces, name=self.name)
+        grid._celltree = CellTree2d.from_device_mesh(mesh)  # (the mesh is in HBM already: no second upload)
+        return grid
+
+    def triangulate(self, return_index=False):
+        """The fan triangulation of the grid (ugrid2d.py:1650-1662): every face of k nodes becomes the triangles
+        ``(n0, n[t + 1], n[t + 2])``, in the caller's vertex order -> a grid of this grid's kind with the same nodes.
+        ``return_index`` (not in the reference): also ``triangle_face_connectivity``, the face of every triangle -- numpy for
+        a host grid, an int64 device array for a grid whose mesh lives in HBM."""
+        triangles = self.device_mesh.triangulate()
+        grid = self._grid_from_mesh(triangles)
+        if not return_index:
+            return grid
+        index = triangles.triangle_face_dev()
+        return grid, (index if self._device_resident else index.download().astype(IntDType, copy=False))
+
+    @property
+    def triangulation(self):
+        """``((node_x, node_y, triangles), triangle_face_connectivity)`` as numpy (ugrid2d.py:857-875)."""
+
+        def make():
+            triangles = self.device_mesh.triangulate()
+            faces = triangles.download()[1].astype(IntDType, copy=False)
+            index = triangles.triangle_face_dev().download().astype(IntDType, copy=False)
+            return (self.node_x, self.node_y, faces), index
+
+        return self._derived("triangulation", make)
+
+    def _tesselate_voronoi(self, generators, add_exterior, add_vertices, skip_concave):
+        from .voronoi import voronoi_topology_device
+
+        mesh, face_index, _ = voronoi_topology_device(self, add_exterior=add_exterior, add_vertices=add_vertices,
+                                                      skip_concave=skip_concave, generators=generators)
+        return mesh, face_index
+
+    def tesselate_centroidal_voronoi(self, add_exterior=True, add_vertices=True, skip_concave=False):
+        """The centroidal Voronoi tessellation of the grid (ugrid2d.py:1686-1708) -> a grid of this grid's kind.  Raises
+        ``ValueError`` where the reference crashes (no node with three faces and ``add_exterior=False``) or yields cells of
+        two corners."""
+        return self._grid_from_mesh(self._tesselate_voronoi(None, add_exterior, add_vertices, skip_concave)[0])
+
+    def tesselate_circumcenter_voronoi(self, add_exterior=True, add_vertices=True, skip_concave=False):
+        """... with the circumcenters of the faces as generator points (ugrid2d.py:1710-1732); triangular grids only."""
+        if self.n_max_node_per_face != 3:  # (before anything touches the device)
+            raise NotImplementedError("Circumcenters are only supported for triangular grids")
+        generators = self.device_mesh.circumcenters_dev()
+        return self._grid_from_mesh(self._tesselate_voronoi(generators, add_exterior, add_vertices, skip_concave)[0])
+
+    def _voronoi_topology_mesh(self):
+        return self._derived("voronoi_mesh", lambda: self._tesselate_voronoi(None, True, False, False))
+
+    @property
+    def voronoi_topology(self):
+        """``(vertices, faces, face_index)`` of the centroidal tessellation with ``add_exterior=True, add_vertices=False``
+        as numpy (ugrid2d.py:810-833)."""
+
+        def make():
+            mesh, face_index = self._voronoi_topology_mesh()
+            vertices, faces = mesh.download()
+            return vertices, faces.astype(IntDType, copy=False), face_index
+
+        return self._derived("voronoi_topology", make)
+
+    @property
+    def centroid_triangulation(self):
+        """``((x, y, triangles), face_index)``: the triangle mesh over the face centroids (ugrid2d.py:835-855), the
+        triangulation kernel run on the tessellation of ``voronoi_topology``."""
+
+        def make():
+            mesh, face_index = self._voronoi_topology_mesh()
+            vertices, triangles = mesh.triangulate().download()
+            return (vertices[:, 0].copy(), vertices[:, 1].copy(), triangles.astype(IntDType, copy=False)), face_index
+
+        return self._derived("centroid_triangulation", make)
+
+    @property
+    def circumcenters(self):
+        """(n_face, 2) circumcenter of every face; triangular grids only (ugrid2d.py:561-573)."""
+        if self.n_max_node_per_face != 3:  # (before anything touches the device)
+            raise NotImplementedError("Circumcenters are only supported for triangular grids")
+        return self._derived("circumcenters", lambda: self.device_mesh.circumcenters_dev().download())
+
+    @property
+    def perimeter(self):
+        """(n_face,) perimeter length of every face (ugrid2d.py:586-595)."""
+        return self._derived("perimeter", lambda: self.device_mesh.perimeter_dev().download())
+
+    @property
+    def face_bounds(self):
+        """(n_face, 4) ``minx, miny, maxx, maxy`` of every face (ugrid2d.py:597-619)."""
+        return self._derived("face_bounds", lambda: self.device_mesh.face_bounds_dev().download())
+
     # ---- structured -> unstructured (raster cells become CCW quads)
     @staticmethod
     def _from_intervals_helper(node_x, node_y, nx, ny, name):
@@ -584,6 +692,8 @@ class RectilinearUgrid2d(Ugrid2d):
         self._edge_face_connectivity = None
         self._node_face_connectivity = None
 
+    _device_resident = True
+
     def _materialise(self):
         if self._host is None:
             node_y, node_x = (a.ravel() for a in np.meshgrid(self._yv, self._xv, indexing="ij"))
@@ -644,7 +754,10 @@ class DeviceUgrid2d(Ugrid2d):
         engine.sync_producer(node_coordinates)
         engine.sync_producer(face_node_connectivity)
         mesh = engine.DeviceMesh.from_device(xy_ptr, xy_shape[0], f_ptr, f_dtype.itemsize, f_shape[0], f_shape[1], fill_value)
-        self._n_node, self._n_face, self._m = xy_shape[0], f_shape[0], f_shape[1]
+        self._init_from_mesh(mesh, name)
+
+    def _init_from_mesh(self, mesh, name):
+        self._n_node, self._n_face, self._m = mesh.n_node, mesh.n_face, mesh.n_max_node
         self._host = None
         self.fill_value = FILL_VALUE
         self.start_index = 0
@@ -657,6 +770,15 @@ class DeviceUgrid2d(Ugrid2d):
         self._face_edge_connectivity = None
         self._edge_face_connectivity = None
         self._node_face_connectivity = None
+
+    _device_resident = True
+
+    @classmethod
+    def from_device_mesh(cls, mesh, name="mesh2d"):
+        """A grid around an existing ``engine.DeviceMesh`` (one built on the device: a triangulation, a tessellation)."""
+        self = cls.__new__(cls)
+        self._init_from_mesh(mesh, name)
+        return self
 
     def _materialise(self):
         if self._host is None:
@@ -688,6 +810,7 @@ class DeviceUgrid2d(Ugrid2d):
         self.__dict__.pop("_sample_cache", None)
         self.__dict__.pop("_topology_cache", None)
         self.__dict__.pop("_facet_cache", None)
+        self.__dict__.pop("_derive_cache", None)
         self._celltree.device_mesh.invalidate()
 
     # ---- edge connectivity from the device topology.  An edge with more than two faces does not fit its two-column tables: such

@@ -199,7 +199,8 @@ def voronoi_topology(
     return table, cells, face_index, interp_map
 
 
-def voronoi_topology_device(grid, compact=False, host_boundary=False):
+def voronoi_topology_device(grid, compact=False, host_boundary=False, *, add_exterior=True, add_vertices=True,
+                            skip_concave=True, generators=None):
     """
     ``voronoi_topology(..., add_exterior=True, add_vertices=True, skip_concave=True)`` of a Ugrid2d with the
     O(n) part on the device (node -> face inversion, exterior edges, counter-clockwise interior cells, assembly;
@@ -214,15 +215,26 @@ def voronoi_topology_device(grid, compact=False, host_boundary=False):
     The cells of the boundary nodes are computed by the library itself (native code, ``xr_voronoi_mesh_auto``);
     ``host_boundary=True`` uses the numpy restatement below instead (kept as the readable cross-check: both give the
     same vertices, cells, face index and interpolation map bit for bit).
+
+    Keyword only: the three flags of ``voronoi_topology`` (the defaults here are those of the barycentric pre-step, the
+    public ``Ugrid2d.tesselate_*`` methods default to ``skip_concave=False``) and ``generators``, a float64 ``(n_face, 2)``
+    device array of the points the cells are made of instead of the face centroids (the circumcenters, say).  The
+    interpolation map is None where the host function returns None (no extra corners); without exterior the vertices are
+    the generator points some cell uses and ``face_index`` is ``arange(largest used face + 1)``, as on the host.
     """
     from . import engine
 
-    builder = engine.DeviceVoronoi(grid.device_mesh)
+    builder = engine.DeviceVoronoi(grid.device_mesh, add_exterior, add_vertices, skip_concave, generators)
     n_face = grid.n_face
+    if not add_exterior:
+        if host_boundary or compact:
+            raise ValueError("a tessellation without exterior has no boundary part: host_boundary and compact do not apply")
+        mesh, _, _ = builder.assemble_auto()
+        return mesh, np.arange(builder.vertex_info()[1] + 1, dtype=IntDType), None
     if not host_boundary:
         mesh, tail, interp_map = builder.assemble_auto()
         tail = tail.astype(IntDType, copy=False)
-        interp_map = interp_map.astype(IntDType, copy=False)
+        interp_map = interp_map.astype(IntDType, copy=False) if add_vertices else None
         if compact:
             return mesh, tail, interp_map
         return mesh, np.concatenate([np.arange(n_face, dtype=IntDType), tail]), interp_map
@@ -240,7 +252,7 @@ def voronoi_topology_device(grid, compact=False, host_boundary=False):
         )
         node_xy = grid.node_coordinates_of(nodes)
         table, bkeys, bids, findex, interp_map = _boundary_records(
-            nfc, node_xy, cen, np.searchsorted(nodes, edge_nodes), inverse[faces.size:], True, True
+            nfc, node_xy, cen, np.searchsorted(nodes, edge_nodes), inverse[faces.size:], add_vertices, skip_concave
         )
         shift = n_face - nl  # local id of an added vertex -> its global id
         bids = np.where(bids < nl, needed[np.minimum(bids, nl - 1)], bids + shift)
@@ -248,11 +260,11 @@ def voronoi_topology_device(grid, compact=False, host_boundary=False):
         extra = table[nl:]
         tail = findex[nl:]
         tail = np.where(tail >= 0, needed[np.maximum(tail, 0)], -1).astype(IntDType)
-        interp_map = interp_map + shift
+        interp_map = interp_map + shift if interp_map is not None else None
     else:  # closed surface: nothing to add
         cells = np.zeros((0, 3), dtype=IntDType)
         extra = np.zeros((0, 2))
-        tail, interp_map = np.zeros(0, dtype=IntDType), np.zeros((0, 2), dtype=IntDType)
+        tail, interp_map = np.zeros(0, dtype=IntDType), (np.zeros((0, 2), dtype=IntDType) if add_vertices else None)
     mesh = builder.assemble(extra, cells)
     if compact:
         return mesh, tail, interp_map
