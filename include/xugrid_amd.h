@@ -693,6 +693,50 @@ int xr_polygons_copy_dev(const xr_polygons *p, double *coords_dev, int64_t *ring
                          double *values_dev, int64_t *face_polygon_dev);   /* any pointer may be NULL */
 int xr_polygons_destroy(xr_polygons *p);
 
+/* ---- sub-meshes (Ugrid2d.topology_subset, ugrid2d.py:1138-1216; clip_box :1218-1226; isel :1228-1288) ----------------------
+ * xr_mesh_subset_dev: a NEW device-resident mesh of the faces face_index_dev int64[n] (device memory; ids unique, any order):
+ *   - its faces are faces[index] in the order given; the table keeps its width n_max_node, the caller's vertex order and -1
+ *     in the unused slots, even when every kept face is shorter;
+ *   - its nodes are the distinct nodes of those faces in ascending old id, renumbered by their dense rank (np.unique, then
+ *     connectivity.renumber); the coordinates are copied, so they are bit-identical to the source's.
+ * problems[0]: ids outside [0, n_face) (negative ones included: nothing wraps), problems[1]: ids that repeat an earlier one.
+ * If either is non-zero *out is NULL and the call still returns XR_OK: the caller words the exception.  Nothing is read
+ * through an id before it has been compared with its range.  *is_identity = 1 (and *out NULL) when the selection is every
+ * face in order: the caller keeps the mesh it has.  n == 0 gives the empty mesh (0 faces, 0 nodes) without a launch.
+ * XR_ERR_INVALID: n > n_face; XR_ERR_LIMIT: n * n_max_node leaves the int32 range.  One synchronising read-back per call (the
+ * number of kept nodes and the three status words in one copy).
+ * xr_mesh_subset_node_index_dev: the old id of every node of such a mesh, ascending -> int64[n_node] in device memory;
+ * XR_ERR_INVALID for a mesh that xr_mesh_subset_dev did not make. */
+int xr_mesh_subset_dev(xr_mesh *mesh, const int64_t *face_index_dev, int64_t n, xr_mesh **out, int *is_identity, int64_t *problems);
+int xr_mesh_subset_node_index_dev(const xr_mesh *subset, int64_t *index_dev);
+/* The same two counts for any index int64[n] into a dimension of `size` entries (the node and edge indexers of isel), and the
+ * number of i with a[i] != b[i] (isel's pre- and post-check, pandas Index.equals on arrays of one length). */
+int xr_index_check_dev(const int64_t *index_dev, int64_t n, int64_t size, int64_t *problems);
+int xr_index_mismatch_dev(const int64_t *a_dev, const int64_t *b_dev, int64_t n, int64_t *count);
+/* An ascending index made on the device: flags int32[n] -> exclusive scan -> compaction, one read-back (its length).  The
+ * handle owns int32 ids; xr_index_copy_dev widens them into the caller's int64[n] device array.
+ *   xr_index_from_mask_dev          nonzero of a one-byte mask uint8[n]
+ *   xr_mesh_box_faces_dev           Ugrid2d.locate_bounding_box (ugrid2d.py:1029-1052) on the mesh's device centroids: the faces
+ *                                   with xmin <= x < xmax and ymin <= y < ymax, exactly these four comparisons (a NaN centroid
+ *                                   is outside)
+ *   xr_mesh_faces_of_nodes_dev      the faces with at least one of the nodes node_index_dev[n] (unique of
+ *                                   node_face_connectivity[node_index].data); ids out of range select nothing
+ *   xr_topology_faces_of_edges_dev  the faces in either column of edge_face_connectivity[edge_index], without the fill
+ *   xr_topology_subset_edges_dev    the distinct ids of face_edge_connectivity[face_index], without the fill: since edges are
+ *                                   numbered lexicographically by (lower, higher) node and the node renumbering is monotone,
+ *                                   edge k of the sub-mesh IS old edge index[k]
+ * The two topology calls return XR_ERR_INVALID for a non-manifold topology (it keeps no tables: the caller takes the host
+ * route). */
+typedef struct xr_index xr_index;
+int xr_index_from_mask_dev(const uint8_t *mask_dev, int64_t n, xr_index **out);
+int xr_mesh_box_faces_dev(xr_mesh *mesh, double xmin, double ymin, double xmax, double ymax, xr_index **out);
+int xr_mesh_faces_of_nodes_dev(xr_mesh *mesh, const int64_t *node_index_dev, int64_t n, xr_index **out);
+int xr_topology_faces_of_edges_dev(const xr_topology *topology, const int64_t *edge_index_dev, int64_t n, xr_index **out);
+int xr_topology_subset_edges_dev(const xr_topology *topology, const int64_t *face_index_dev, int64_t n, xr_index **out);
+int xr_index_info(const xr_index *index, int64_t *n);
+int xr_index_copy_dev(const xr_index *index, int64_t *out_dev);
+int xr_index_destroy(xr_index *index);
+
 /* ---- raw HBM helpers for hosts that do not bring their own allocator -------------------- */
 int xr_dev_alloc(int64_t bytes, void **ptr_out);
 int xr_dev_free(void *ptr);

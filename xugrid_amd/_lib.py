@@ -164,6 +164,18 @@ SIGNATURES = {
     "xr_polygons_readbacks": (c_int, [vp, p_i64]),
     "xr_polygons_copy_dev": (c_int, [vp, vp, vp, vp, vp, vp]),
     "xr_polygons_destroy": (c_int, [vp]),
+    "xr_mesh_subset_dev": (c_int, [vp, vp, c_i64, p_vp, p_int, p_i64]),
+    "xr_mesh_subset_node_index_dev": (c_int, [vp, vp]),
+    "xr_index_check_dev": (c_int, [vp, c_i64, c_i64, p_i64]),
+    "xr_index_mismatch_dev": (c_int, [vp, vp, c_i64, p_i64]),
+    "xr_index_from_mask_dev": (c_int, [vp, c_i64, p_vp]),
+    "xr_mesh_box_faces_dev": (c_int, [vp, c_f64, c_f64, c_f64, c_f64, p_vp]),
+    "xr_mesh_faces_of_nodes_dev": (c_int, [vp, vp, c_i64, p_vp]),
+    "xr_topology_faces_of_edges_dev": (c_int, [vp, vp, c_i64, p_vp]),
+    "xr_topology_subset_edges_dev": (c_int, [vp, vp, c_i64, p_vp]),
+    "xr_index_info": (c_int, [vp, p_i64]),
+    "xr_index_copy_dev": (c_int, [vp, vp]),
+    "xr_index_destroy": (c_int, [vp]),
     "xr_dev_alloc": (c_int, [c_i64, p_vp]),
     "xr_dev_free": (c_int, [vp]),
     "xr_dev_upload": (c_int, [vp, vp, c_i64]),

@@ -1276,7 +1276,7 @@ int xr_mesh_device_bytes(const xr_mesh *mesh, int64_t *bytes) {
                mesh->len.bytes() + mesh->bbox.bytes() + mesh->area.bytes() + mesh->stats.bytes() + mesh->q_perm.bytes() +
                mesh->q_fxy.bytes() + mesh->q_off.bytes() + mesh->q_len.bytes() + mesh->q_bbox.bytes() +
                mesh->cell_start.bytes() + mesh->rec_bb.bytes() + mesh->rec_face.bytes() + mesh->rec_fxy.bytes() +
-               mesh->rec_off.bytes() + mesh->rec_len.bytes() + mesh->tri_face.bytes();
+               mesh->rec_off.bytes() + mesh->rec_len.bytes() + mesh->tri_face.bytes() + mesh->sub_node.bytes();
     *bytes = (int64_t)b;
     XR_API_END
 }

@@ -83,6 +83,10 @@ struct xr_mesh {
     xr::DevBuf<int32_t> tri_face; // [n_face]
     bool is_triangulation = false;
 
+    // ---- kept when this mesh was cut out of another (xr_mesh_subset_dev, xr_subset.hip): the source node of every node, ascending
+    xr::DevBuf<int32_t> sub_node; // [n_node]
+    bool is_subset = false;
+
     // ---- kept by the barycentric construction when this mesh is a Voronoi tessellation (xr_locate.hip:barycentric_csr): the
     // vertex -> face table with the interpolation map behind it, and the flags of the cells that hold a substitute vertex --
     // a second interpolator on a cached tessellation uploads and recomputes nothing (its first kernel then runs BESIDE the

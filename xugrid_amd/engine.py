@@ -350,6 +350,35 @@ class DeviceMesh:
     def face_bounds_dev(self) -> "DeviceArray":
         return self._derived_dev("xr_mesh_face_bounds_dev", (self.n_face, 4))
 
+    # ---- sub-meshes cut on the device (include/xugrid_amd.h: xr_mesh_subset_dev ...; xugrid_amd/subset.py)
+    def subset(self, face_index_ptr, n):
+        """The sub-mesh of the faces ``face_index`` (an int64 device pointer, ``n`` ids) -> ``(mesh, is_identity, (ids out of
+        range, repeated ids))``; ``mesh`` is None when the selection is every face in order or when one of the counts is
+        not zero."""
+        handle, identity, problems = ctypes.c_void_p(), ctypes.c_int(), (ctypes.c_int64 * 2)()
+        check(_lib.load().xr_mesh_subset_dev(self._h, ctypes.c_void_p(int(face_index_ptr)), int(n), ctypes.byref(handle),
+                                             ctypes.byref(identity), problems))
+        mesh = DeviceMesh._from_handle(handle) if handle.value else None
+        return mesh, bool(identity.value), (int(problems[0]), int(problems[1]))
+
+    def subset_node_index_dev(self, like=None):
+        """Old id of every node of a mesh made by ``subset``, ascending: an int64 device array of the kind of ``like``."""
+        out, ptr = empty_like_device(like, (self.n_node,), np.int64)
+        check(_lib.load().xr_mesh_subset_node_index_dev(self._h, ctypes.c_void_p(ptr)))
+        return out
+
+    def box_faces(self, xmin, ymin, xmax, ymax) -> "DeviceIndex":
+        """``locate_bounding_box`` on the mesh's device centroids."""
+        handle = ctypes.c_void_p()
+        check(_lib.load().xr_mesh_box_faces_dev(self._h, float(xmin), float(ymin), float(xmax), float(ymax), ctypes.byref(handle)))
+        return DeviceIndex(handle)
+
+    def faces_of_nodes(self, node_index_ptr, n) -> "DeviceIndex":
+        """The faces that touch one of the nodes ``node_index`` (an int64 device pointer, ``n`` ids)."""
+        handle = ctypes.c_void_p()
+        check(_lib.load().xr_mesh_faces_of_nodes_dev(self._h, ctypes.c_void_p(int(node_index_ptr)), int(n), ctypes.byref(handle)))
+        return DeviceIndex(handle)
+
     def overlap(self, query: "DeviceMesh", relative=False) -> "DeviceCSR":
         """All (query face, self face) pairs with positive intersection area, as CSR rows=query."""
         handle = ctypes.c_void_p()
@@ -412,6 +441,53 @@ class DeviceMesh:
             raise ValueError("tolerance must be non-negative")
         check(_lib.load().xr_barycentric(self._h, _ptr(pts), pts.shape[0], tol, _ptr(face), _ptr(w)))
         return face.astype(IntDType, copy=False), w
+
+
+class DeviceIndex:
+    """An ascending index made on the device (include/xugrid_amd.h: xr_index): ``n`` ids in HBM; ``to_dev`` copies them
+    into an int64 device array."""
+
+    def __init__(self, handle):
+        self._h = handle
+        n = ctypes.c_int64()
+        check(_lib.load().xr_index_info(handle, ctypes.byref(n)))
+        self.n = n.value
+
+    @classmethod
+    def from_mask(cls, mask_ptr, n):
+        """``nonzero`` of a one-byte mask of ``n`` entries in device memory."""
+        handle = ctypes.c_void_p()
+        check(_lib.load().xr_index_from_mask_dev(ctypes.c_void_p(int(mask_ptr)), int(n), ctypes.byref(handle)))
+        return cls(handle)
+
+    def to_dev(self, like=None):
+        """-> an int64 ``(n,)`` device array of the kind of ``like`` (None: a ``DeviceArray``)."""
+        out, ptr = empty_like_device(like, (self.n,), np.int64)
+        check(_lib.load().xr_index_copy_dev(self._h, ctypes.c_void_p(ptr)))
+        return out
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                _lib.load().xr_index_destroy(h)
+            except Exception:  # noqa: BLE001
+                pass
+            self._h = None
+
+
+def index_check(index_ptr, n, size):
+    """-> (ids outside ``[0, size)``, ids that repeat an earlier one) of an int64 index of ``n`` ids in device memory."""
+    problems = (ctypes.c_int64 * 2)()
+    check(_lib.load().xr_index_check_dev(ctypes.c_void_p(int(index_ptr)), int(n), int(size), problems))
+    return int(problems[0]), int(problems[1])
+
+
+def index_mismatch(a_ptr, b_ptr, n):
+    """Number of positions at which two int64 device arrays of ``n`` entries differ."""
+    count = ctypes.c_int64()
+    check(_lib.load().xr_index_mismatch_dev(ctypes.c_void_p(int(a_ptr)), ctypes.c_void_p(int(b_ptr)), int(n), ctypes.byref(count)))
+    return count.value
 
 
 class DeviceVoronoi:

@@ -24,6 +24,7 @@ from .fill import resolve_dim
 PointSelection = namedtuple("PointSelection", ["values", "index", "x", "y"])
 LineSelection = namedtuple("LineSelection", ["values", "face_index", "x", "y", "s"])
 BoxSelection = namedtuple("BoxSelection", ["values", "face_index"])
+BoxGridSelection = namedtuple("BoxGridSelection", ["values", "face_index", "grid"])
 
 FACETS = ("node", "edge", "face")
 _MESH_FACET_IDS = {"node": 0, "face": 2}  # include/xugrid_amd.h: XR_FACET_NODE, XR_FACET_FACE
@@ -320,11 +321,13 @@ def _bound(value, default):
     return default if value is None else value
 
 
-def sel(grid, data, x=None, y=None, dim=None):
+def sel(grid, data, x=None, y=None, dim=None, return_grid=False):
     """ugridbase.py:1462-1506 on arrays: see ``Ugrid2d.sel``."""
     x = validate_indexer(slice(None, None) if x is None else x)
     y = validate_indexer(slice(None, None) if y is None else y)
     kind = sel_kind(x, y)
+    if return_grid and kind != "box":
+        raise ValueError("return_grid needs a box selection (two slices without step): points and lines select no sub-grid")
     if kind == "points":
         yy, xx = (a.ravel() for a in np.meshgrid(y, x, indexing="ij"))
         return sel_points(grid, data, xx, yy, dim=dim)
@@ -343,4 +346,7 @@ def sel(grid, data, x=None, y=None, dim=None):
     xmin, ymin, xmax, ymax = grid.bounds
     face_index = grid.locate_bounding_box(_bound(x.start, xmin), _bound(y.start, ymin), _bound(x.stop, xmax),
                                           _bound(y.stop, ymax))
-    return BoxSelection(gather_points(data, grid.n_face, face_index), face_index)
+    values = gather_points(data, grid.n_face, face_index)
+    if return_grid:  # (the face index alone: no edge topology is built for it)
+        return BoxGridSelection(values, face_index, grid.topology_subset(face_index))
+    return BoxSelection(values, face_index)

@@ -159,6 +159,19 @@ class DeviceTopology:
         check(_lib.load().xr_topology_facet_map_dev(self._h, _FACET_IDS[target], _FACET_IDS[source], form,
                                                     ctypes.c_void_p(int(in_ptr)), dtype_id, K, ctypes.c_void_p(int(out_ptr))))
 
+    # ---- index arithmetic of sub-meshes (xugrid_amd/subset.py); manifold topologies only
+    def faces_of_edges(self, edge_index_ptr, n):
+        """The faces beside the edges ``edge_index`` (an int64 device pointer, ``n`` ids), ascending -> ``engine.DeviceIndex``."""
+        handle = ctypes.c_void_p()
+        check(_lib.load().xr_topology_faces_of_edges_dev(self._h, ctypes.c_void_p(int(edge_index_ptr)), int(n), ctypes.byref(handle)))
+        return engine.DeviceIndex(handle)
+
+    def subset_edges(self, face_index_ptr, n):
+        """The edges of the faces ``face_index`` (an int64 device pointer, ``n`` ids), ascending -> ``engine.DeviceIndex``."""
+        handle = ctypes.c_void_p()
+        check(_lib.load().xr_topology_subset_edges_dev(self._h, ctypes.c_void_p(int(face_index_ptr)), int(n), ctypes.byref(handle)))
+        return engine.DeviceIndex(handle)
+
     def graph(self, facet):
         """The fills' ``DeviceGraph`` of the faces or nodes: structure, ``mean(d) / d`` weights and component labels, all
         made on the device."""

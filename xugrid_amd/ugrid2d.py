@@ -3,8 +3,8 @@ Minimal ``Ugrid2d``: exactly the slice of xugrid/ugrid/ugrid2d.py the regridding
 (SURVEY.md 2 row 11): the constructor's connectivity handling (:72-115), ``node_coordinates``
 (ugridbase.py:576-579), ``area`` (:575-584), ``centroids`` (:544-559), ``celltree`` (:908-921),
 ``locate_points`` (ugridbase.py:1305-1323), ``compute_barycentric_weights`` (:1054-1078) and
-``from_structured_bounds`` (:1894-1912, :1973-2034).  Everything else of the 2.2 kLoC class
-(IO, plotting, selection, partitioning ...) is out of scope.
+``from_structured_bounds`` (:1894-1912, :1973-2034), and what later sections of DESIGN.md added (fills, sampling, facets,
+derived meshes, sub-meshes: ``topology_subset`` / ``clip_box`` / ``isel``).  IO, plotting and partitioning are out of scope.
 """
 import numpy as np
 
@@ -436,13 +436,13 @@ class Ugrid2d:
         out, device array in -> float64 device array out; the gather runs on the device."""
         return sample.sel_points(self, data, x, y, dim, method, out_of_bounds, fill_value, tolerance)
 
-    def sel(self, data, x=None, y=None, dim=None):
+    def sel(self, data, x=None, y=None, dim=None, return_grid=False):
         """Selection in x and y (ugridbase.py:1462-1506): scalars, lists, arrays or slices with a step give orthogonal points
         through ``sel_points``; a slice without step paired with one value gives a line across the grid's bounds
         (``intersect_line``); two slices give the faces whose centroid lies in the box, open ends taken from the grid's
-        bounds -> ``(values (..., n_sel), face_index)``.  (The reference also returns the sub-grid of a box; this package
-        has no ``topology_subset`` and stops at the index.)"""
-        return sample.sel(self, data, x, y, dim)
+        bounds -> ``(values (..., n_sel), face_index)``.  ``return_grid``: a box selection also returns the sub-grid of those
+        faces, ``(values, face_index, grid)``, as the reference does; points and lines have none and raise ``ValueError``."""
+        return sample.sel(self, data, x, y, dim, return_grid)
 
     def intersect_line(self, data, start, end):
         """Values of face data (..., n_face) in the faces the line from ``start`` to ``end`` crosses (ugridbase.py:1345-1378)
@@ -483,6 +483,37 @@ class Ugrid2d:
         from .polygonize import polygonize  # (the package attribute of that name is this function, not the module)
 
         return polygonize(self, data, return_index)
+
+    # ---- sub-meshes cut on the device (xugrid_amd/subset.py, csrc/xr_subset.hip)
+    def topology_subset(self, face_index, return_index=False):
+        """The grid of the faces ``face_index`` (ugrid2d.py:1138-1216): 1-D integer ids, unique and in any order, or a bool mask
+        of length ``n_face``.  The faces keep the order given, the connectivity its width and the caller's vertex order; the
+        nodes are the distinct nodes of those faces in ascending old id; coordinates are copied -> a grid of this grid's kind,
+        or this grid itself when the selection is every face in order.  ``return_index``: also ``{node_dimension: node_index,
+        edge_dimension: edge_index, face_dimension: face_index}``, int64 -- edge ``k`` of the sub-grid is edge
+        ``edge_index[k]`` of this one.  Repeated ids raise ``ValueError``, ids outside ``[0, n_face)`` ``IndexError`` (negative
+        ids too).  See xugrid_amd/subset.py for the kinds of the results."""
+        from . import subset
+
+        return subset.topology_subset(self, face_index, return_index)
+
+    def clip_box(self, xmin, ymin, xmax, ymax):
+        """``topology_subset`` of the faces whose centroid lies in the half-open box ``xmin <= x < xmax``, ``ymin <= y < ymax``
+        (ugrid2d.py:1218-1226)."""
+        from . import subset
+
+        return subset.clip_box(self, xmin, ymin, xmax, ymax)
+
+    def isel(self, indexers=None, return_index=False, data=None, **indexers_kwargs):
+        """Selection by node, edge or face ids or masks, keyed by dimension name (ugrid2d.py:1228-1288).  A node selection
+        stands for the faces touching any selected node, an edge selection for the faces beside any selected edge; several
+        dimensions must stand for the same faces, and a node or edge selection must be exactly the nodes or edges of those
+        faces, else ``ValueError``.  -> the sub-grid; with ``return_index`` also the three indexes; with ``data`` ``(..., n)``,
+        ``n`` the size of exactly one dimension, also ``data`` gathered along that dimension's index (numpy in -> numpy out,
+        device array in -> float64 device array out)."""
+        from . import subset
+
+        return subset.isel(self, indexers, return_index, data, **indexers_kwargs)
 
     # ---- meshes and per-face geometry derived on the device (csrc/xr_mesh.hip: triangulation, circumcenters, perimeter,
     # face bounds; csrc/xr_voronoi.hip: the tessellations)
