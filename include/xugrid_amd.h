@@ -737,6 +737,56 @@ int xr_index_info(const xr_index *index, int64_t *n);
 int xr_index_copy_dev(const xr_index *index, int64_t *out_dev);
 int xr_index_destroy(xr_index *index);
 
+/* ---- joining meshes (Ugrid2d.merge_partitions, partitioning.py:81-148), matching point sets (connectivity.index_like,
+ * connectivity.py:38-61), splitting by label (partitioning.py:16-27); xr_merge.hip, DESIGN section 15 -------------------------
+ * All of it rests on one primitive, an open-addressing key table in HBM that finds the FIRST row of every set of equal rows
+ * (insert with atomicCAS / atomicMin, look-up in a second launch; option merge_table_slack = 1 gives it the smallest legal
+ * capacity).  No sort.
+ *
+ * xr_merge_meshes_dev: the meshes parts[0 .. n_part) joined into one.
+ *   nodes  the partitions' node_xy concatenated in the order given; two nodes are one when both coordinates compare equal as
+ *          doubles (-0.0 == 0.0; a row holding NaN equals nothing, not even itself); the first occurrence is kept, bit for
+ *          bit, and kept nodes keep their concatenation order.
+ *   faces  every table widened to m = max n_max_node with -1, real slots mapped to merged node ids; two faces are one when
+ *          their rows are equal after sorting each row, the -1 taking part; the first occurrence is kept with its slot order.
+ * The handle owns the merged mesh (xr_merge_take_mesh hands it out once; the caller destroys it with xr_mesh_destroy), the
+ * merged id of every concatenated node (xr_merge_node_inverse_copy_dev, int64[sum n_node]) and the kept rows per partition.
+ * One synchronising read-back per call: both scans at the 2 (n_part + 1) partition boundaries in one copy.
+ * XR_ERR_LIMIT: the concatenated nodes or face slots leave the int32 range.
+ *
+ * xr_merge_edges_dev: the same question for the partitions' DERIVED edges (their xr_topology, all manifold): an edge is kept
+ * when its merged (lower, higher) node pair occurs at no earlier edge of the concatenation; `merged` is the topology of the
+ * merged mesh, in whose node -> node CSR (data = edge id) every kept edge's own id there is looked up.  One read-back.
+ *
+ * xr_merge_index_info / xr_merge_index_copy_dev: facet 0 nodes, 1 edges (after xr_merge_edges_dev), 2 faces.  part >= 0: the
+ * ascending LOCAL ids of that partition's kept rows; part == -1: all kept rows as ids into the concatenation.  position != 0
+ * (edges only): instead the merged mesh's own edge id of each of those kept edges. */
+typedef struct xr_merge xr_merge;
+int xr_merge_meshes_dev(xr_mesh *const *parts, int64_t n_part, xr_merge **out);
+int xr_merge_edges_dev(xr_merge *merge, const xr_topology *const *parts, int64_t n_part, const xr_topology *merged);
+int xr_merge_info(const xr_merge *merge, int64_t *n_part, int64_t *n_node_all, int64_t *n_face_all);
+int xr_merge_take_mesh(xr_merge *merge, xr_mesh **mesh);
+int xr_merge_index_info(const xr_merge *merge, int facet, int64_t part, int64_t *n);
+int xr_merge_index_copy_dev(const xr_merge *merge, int facet, int64_t part, int position, int64_t *out_dev);
+int xr_merge_node_inverse_copy_dev(const xr_merge *merge, int64_t *out_dev);
+int xr_merge_destroy(xr_merge *merge);
+/* index_out_dev[i] = the row j of a float64[n, 2] whose key equals the key of row i of b (-1: none, or the pair differs by
+ * more than `tolerance` on an axis).  Key: the coordinate pair (tolerance == 0) or rint(xy / tolerance).  problems[0]: keys
+ * that repeat inside a or inside b; problems[1]: rows of b without a partner.  The caller words the errors; one read-back. */
+int xr_index_like_dev(const double *a_dev, const double *b_dev, int64_t n, double tolerance, int64_t *index_out_dev, int64_t *problems);
+/* labels int64[n] in device memory: their range (clamped to [-1, INT32_MAX]; n == 0: 0, -1), then the ids grouped by label
+ * 0 .. n_label - 1 and ascending inside a label -- flags per label laid out label-major, ONE exclusive scan, a placement
+ * without atomics; bounds[n_label + 1] (host): where each label's ids start.  One read-back each.  XR_ERR_LIMIT: n * n_label
+ * leaves the int32 range. */
+typedef struct xr_label_order xr_label_order;
+int xr_labels_range_dev(const int64_t *labels_dev, int64_t n, int64_t *min_label, int64_t *max_label);
+int xr_labels_order_dev(const int64_t *labels_dev, int64_t n, int64_t n_label, xr_label_order **out, int64_t *bounds);
+int xr_label_order_copy_dev(const xr_label_order *order, int64_t first, int64_t count, int64_t *out_dev);
+int xr_label_order_destroy(xr_label_order *order);
+/* `rows` rows of src_row_bytes each into rows of dst_row_bytes (>= src_row_bytes), device to device: a column block of a wider
+ * array (the concatenation of the partitions' data along the last axis) */
+int xr_dev_copy_columns(void *dst_dev, int64_t dst_row_bytes, const void *src_dev, int64_t src_row_bytes, int64_t rows);
+
 /* ---- raw HBM helpers for hosts that do not bring their own allocator -------------------- */
 int xr_dev_alloc(int64_t bytes, void **ptr_out);
 int xr_dev_free(void *ptr);

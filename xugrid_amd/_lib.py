@@ -176,6 +176,20 @@ SIGNATURES = {
     "xr_index_info": (c_int, [vp, p_i64]),
     "xr_index_copy_dev": (c_int, [vp, vp]),
     "xr_index_destroy": (c_int, [vp]),
+    "xr_merge_meshes_dev": (c_int, [vp, c_i64, p_vp]),
+    "xr_merge_edges_dev": (c_int, [vp, vp, c_i64, vp]),
+    "xr_merge_info": (c_int, [vp, p_i64, p_i64, p_i64]),
+    "xr_merge_take_mesh": (c_int, [vp, p_vp]),
+    "xr_merge_index_info": (c_int, [vp, c_int, c_i64, p_i64]),
+    "xr_merge_index_copy_dev": (c_int, [vp, c_int, c_i64, c_int, vp]),
+    "xr_merge_node_inverse_copy_dev": (c_int, [vp, vp]),
+    "xr_merge_destroy": (c_int, [vp]),
+    "xr_index_like_dev": (c_int, [vp, vp, c_i64, c_f64, vp, p_i64]),
+    "xr_labels_range_dev": (c_int, [vp, c_i64, p_i64, p_i64]),
+    "xr_labels_order_dev": (c_int, [vp, c_i64, c_i64, p_vp, p_i64]),
+    "xr_label_order_copy_dev": (c_int, [vp, c_i64, c_i64, vp]),
+    "xr_label_order_destroy": (c_int, [vp]),
+    "xr_dev_copy_columns": (c_int, [vp, c_i64, vp, c_i64, c_i64]),
     "xr_dev_alloc": (c_int, [c_i64, p_vp]),
     "xr_dev_free": (c_int, [vp]),
     "xr_dev_upload": (c_int, [vp, vp, c_i64]),

@@ -116,3 +116,11 @@ def node_node_connectivity(edge_node_connectivity, n_node):
     """Nodes joined by an edge; data = the edge's id."""
     edge = np.arange(len(edge_node_connectivity), dtype=IntDType)
     return _symmetric_csr(edge_node_connectivity[:, 0], edge_node_connectivity[:, 1], edge, n_node)
+
+
+def index_like_device(xy_a, xy_b, tolerance=0.0):
+    """``index_like`` (xugrid/ugrid/connectivity.py:38-61) through the device key table: the index that turns ``xy_a`` into
+    ``xy_b``.  See ``xugrid_amd.partition.index_like_device`` (imported on use: that module needs the engine)."""
+    from .partition import index_like_device as run
+
+    return run(xy_a, xy_b, tolerance)

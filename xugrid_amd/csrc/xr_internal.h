@@ -328,6 +328,7 @@ enum Option : int {
     OPT_BURN_STRIPS,       // > 0: strips of the ring-segment index of burn_vector_geometry (xr_burn.hip; 0: from the segments; tests force 1 and very many)
     OPT_FACET_TILE,        // 1: to_node / to_edge / to_face keep one slice per lane instead of FACET_TILE (xr_facet.hip; the A/B of DESIGN section 11)
     OPT_SCAN_FUSED_TILES,  // > 0: tiles up to which exclusive_scan_i32 runs its fused pair (xr_scan.hip; 0: SCAN_FUSED_TILES; tests force the three-kernel path with a tiny one)
+    OPT_MERGE_TABLE_SLACK, // 1: the key table of xr_merge.hip takes the smallest legal capacity (long chains, wrap-around on small inputs); 0: >= 2 n
     OPT_COUNT
 };
 int64_t option(Option o);

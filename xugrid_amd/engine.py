@@ -490,6 +490,102 @@ def index_mismatch(a_ptr, b_ptr, n):
     return count.value
 
 
+class DeviceMerge:
+    """Meshes joined on the device (include/xugrid_amd.h: xr_merge): the merged mesh, the merged id of every concatenated
+    node and, per partition, the ascending local ids of its kept nodes, faces and (after ``add_edges``) edges."""
+
+    FACETS = {"node": 0, "edge": 1, "face": 2}
+
+    def __init__(self, meshes):
+        self._meshes = list(meshes)  # (kept alive for the call)
+        parts = (ctypes.c_void_p * len(self._meshes))(*[m._h for m in self._meshes])
+        handle = ctypes.c_void_p()
+        check(_lib.load().xr_merge_meshes_dev(parts, len(self._meshes), ctypes.byref(handle)))
+        self._h = handle
+        self.n_part = len(self._meshes)
+        self.n_node_all = sum(m.n_node for m in self._meshes)
+
+    def take_mesh(self) -> "DeviceMesh":
+        handle = ctypes.c_void_p()
+        check(_lib.load().xr_merge_take_mesh(self._h, ctypes.byref(handle)))
+        return DeviceMesh._from_handle(handle)
+
+    def add_edges(self, topologies, merged_topology):
+        """The kept edges of the partitions' device topologies and their ids in ``merged_topology`` (all manifold)."""
+        parts = (ctypes.c_void_p * len(topologies))(*[t._h for t in topologies])
+        check(_lib.load().xr_merge_edges_dev(self._h, parts, len(topologies), merged_topology._h))
+
+    def index(self, facet, part, like=None, position=False):
+        """int64 device array of the kind of ``like``: the local ids of partition ``part``'s kept rows (``part=-1``: all
+        kept rows as ids into the concatenation); ``position``: the merged grid's own id of each kept edge instead."""
+        n = ctypes.c_int64()
+        check(_lib.load().xr_merge_index_info(self._h, self.FACETS[facet], int(part), ctypes.byref(n)))
+        out, ptr = empty_like_device(like, (n.value,), np.int64)
+        check(_lib.load().xr_merge_index_copy_dev(self._h, self.FACETS[facet], int(part), int(bool(position)), ctypes.c_void_p(ptr)))
+        return out
+
+    def node_inverse(self, like=None):
+        out, ptr = empty_like_device(like, (self.n_node_all,), np.int64)
+        check(_lib.load().xr_merge_node_inverse_copy_dev(self._h, ctypes.c_void_p(ptr)))
+        return out
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                _lib.load().xr_merge_destroy(h)
+            except Exception:  # noqa: BLE001
+                pass
+            self._h = None
+
+
+def index_like_dev(a_ptr, b_ptr, n, tolerance, like=None):
+    """include/xugrid_amd.h: xr_index_like_dev on two float64 ``(n, 2)`` device pointers -> (int64 ``(n,)`` device array of the
+    kind of ``like``, keys that repeat, rows of b without a partner)."""
+    out, ptr = empty_like_device(like, (int(n),), np.int64)
+    problems = (ctypes.c_int64 * 2)()
+    check(_lib.load().xr_index_like_dev(ctypes.c_void_p(int(a_ptr)), ctypes.c_void_p(int(b_ptr)), int(n), float(tolerance),
+                                        ctypes.c_void_p(ptr), problems))
+    return out, int(problems[0]), int(problems[1])
+
+
+def labels_range(labels_ptr, n):
+    """-> (smallest, largest) of ``n`` int64 labels in device memory, clamped to [-1, 2**31 - 1]; (0, -1) for none."""
+    lo, hi = ctypes.c_int64(), ctypes.c_int64()
+    check(_lib.load().xr_labels_range_dev(ctypes.c_void_p(int(labels_ptr)), int(n), ctypes.byref(lo), ctypes.byref(hi)))
+    return lo.value, hi.value
+
+
+def labels_order(labels_ptr, n, n_label, like=None):
+    """-> ``n_label`` int64 device arrays of the kind of ``like``: the ascending ids of every label (xr_labels_order_dev)."""
+    handle, bounds = ctypes.c_void_p(), (ctypes.c_int64 * (int(n_label) + 1))()
+    lib = _lib.load()
+    check(lib.xr_labels_order_dev(ctypes.c_void_p(int(labels_ptr)), int(n), int(n_label), ctypes.byref(handle), bounds))
+    try:
+        out = []
+        for l in range(int(n_label)):
+            ids, ptr = empty_like_device(like, (bounds[l + 1] - bounds[l],), np.int64)
+            check(lib.xr_label_order_copy_dev(handle, bounds[l], bounds[l + 1] - bounds[l], ctypes.c_void_p(ptr)))
+            out.append(ids)
+        return out
+    finally:
+        lib.xr_label_order_destroy(handle)
+
+
+def concat_last_axis_dev(arrays, like=None):
+    """Device arrays ``(K, n_p)`` of one dtype side by side -> ``(K, sum n_p)`` of the kind of ``like`` (xr_dev_copy_columns)."""
+    infos = [device_array_info(a) for a in arrays]
+    K, dtype = infos[0][1][0], infos[0][2]
+    total = sum(info[1][1] for info in infos)
+    out, ptr = empty_like_device(like, (K, total), dtype)
+    at = 0
+    for info in infos:
+        width = info[1][1] * dtype.itemsize
+        check(_lib.load().xr_dev_copy_columns(ctypes.c_void_p(ptr + at), total * dtype.itemsize, ctypes.c_void_p(info[0]), width, K))
+        at += width
+    return out
+
+
 class DeviceVoronoi:
     """Device part of the centroidal Voronoi pre-step of a mesh (see include/xugrid_amd.h, xr_voronoi_*)."""
 

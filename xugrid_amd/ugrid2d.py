@@ -515,6 +515,35 @@ class Ugrid2d:
 
         return subset.isel(self, indexers, return_index, data, **indexers_kwargs)
 
+    # ---- joining and matching grids on the device (xugrid_amd/partition.py, csrc/xr_merge.hip)
+    @staticmethod
+    def merge_partitions(grids, return_index=False, data=None, dim=None):
+        """The grids joined into one (ugrid2d.py ``merge_partitions``, partitioning.py:81-148): nodes whose coordinates compare
+        equal as doubles become one node, faces with the same node set one face; of each the first occurrence is kept, in the
+        order of the list -> the merged grid (one grid: that grid itself; none: ``ValueError``).  ``return_index``: also
+        ``{node_dimension: [...], edge_dimension: [...], face_dimension: [...]}``, per partition the ascending local ids of
+        the nodes, edges and faces it contributes.  ``data``: one array ``(..., n_p)`` per partition on one facet (found by
+        its size, or named by ``dim``) -> also the merged ``(..., n_merged)`` float64 array.  See xugrid_amd/partition.py for
+        the kinds of the results."""
+        from . import partition
+
+        return partition.merge_partitions(grids, return_index, data, dim)
+
+    def partition_by_label(self, labels, data=None):
+        """One ``topology_subset(index, return_index=True)`` result per label ``0 .. max(labels)`` of the 1-D integer face
+        ``labels`` (partitioning.py:71-76); with ``data`` each entry also carries its selection of ``data``."""
+        from . import partition
+
+        return partition.partition_by_label(self, labels, data)
+
+    def reindex_like(self, other, data, dim=None, tolerance=0.0):
+        """``data`` of this grid in the order of ``other`` (ugrid2d.py:1574-1617): the two grids hold the same nodes, edge
+        midpoints or centroids -- those of ``data``'s facet, found by its size or named by ``dim`` -- in another order,
+        equal, or within ``tolerance`` on both axes.  Raises ``ValueError`` when they do not match one to one."""
+        from . import partition
+
+        return partition.reindex_like(self, other, data, dim, tolerance)
+
     # ---- meshes and per-face geometry derived on the device (csrc/xr_mesh.hip: triangulation, circumcenters, perimeter,
     # face bounds; csrc/xr_voronoi.hip: the tessellations)
     _device_resident = False  # True: the mesh exists in HBM only; derived grids stay there and indices are device arrays
