@@ -8,12 +8,13 @@
 //                             vertices per cell) keep the blocks FLAT with offsets instead: f64 [sum len][2] +
 //                             off i32 [n_face + 1] (fxy_off / q_off / rec_off); face_vertex_base() hides the difference
 //   len   u8  [n_face]        number of valid vertices (polygon_length)
-//   bbox  f64 [n_face][4]     xmin, xmax, ymin, ymax
+//   bbox  f64 [n_face][4]     xmin, xmax, ymin, ymax -- polygon meshes only (the index build reads it); for dense meshes
+//                             a face's box is taken from its vertices where it is needed (query_face_box below)
 //   area  f64 [n_face]        connectivity.area on the caller's vertex order
 // The raw upload (node_xy f64[N][2], faces_raw i32[F][M], the CSR-style flat connectivity with the
 // implicit offset f*M) is only read once, by the prepare kernel.
 // Two spatially sorted copies exist (counting sort, xr_mesh.hip):
-//   query order  q_perm/q_fxy/q_len/q_bbox: faces grouped by the Morton code of a coarse cell, so a
+//   query order  q_perm/q_fxy/q_len (+ q_bbox, polygon meshes): faces grouped by the Morton code of a coarse cell, so a
 //                256-face block is a compact 2-D patch (search/clip/row kernels walk this order)
 //   tree index   hierarchical uniform grid, one insertion per face: level l has square cells of
 //                size h0 * 2^l; a face lives on the lowest level whose cell size exceeds its bbox
@@ -80,6 +81,38 @@ __device__ __forceinline__ int64_t face_vertex_base(const int32_t *__restrict__ 
 __device__ __forceinline__ P2 load_p2(const double *__restrict__ xy, int i) {
     const double2 v = reinterpret_cast<const double2 *>(xy)[i];
     return P2{v.x, v.y};
+}
+
+// float64 box (xmin, xmax, ymin, ymax) of face t of a query-order (or caller-order) vertex block.  Dense meshes (MC = 3, 4)
+// store no box: it is the fmin / fmax over the face's `len` vertices -- the values k_prepare_faces reduces, so cell coordinates
+// and float boxes derived from it are the ones a stored box gave; a fill slot is never read.  Polygon meshes (MC = 0) keep
+// a stored box (the index build reads it, xr_mesh.hip).
+template <int MC>
+__device__ __forceinline__ double4 query_face_box(const double *__restrict__ q_bbox, const double *__restrict__ q_fxy,
+                                                  const uint8_t *__restrict__ q_len, int64_t t) {
+    if (MC == 0) return reinterpret_cast<const double4 *>(q_bbox)[t];
+    constexpr int MA = MC > 0 ? MC : 1;
+    const double2 *__restrict__ fx = reinterpret_cast<const double2 *>(q_fxy) + t * MA;
+    const int n = MC == 3 ? 3 : (int)q_len[t];
+    double xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < MA; j++) {
+        if (j < n) {
+            const double2 p = fx[j];
+            xmin = fmin(xmin, p.x);
+            xmax = fmax(xmax, p.x);
+            ymin = fmin(ymin, p.y);
+            ymax = fmax(ymax, p.y);
+        }
+    }
+    return make_double4(xmin, xmax, ymin, ymax);
+}
+// ... with the node count at run time (q_m: 3, 4, or anything else for a stored box)
+__device__ __forceinline__ double4 query_face_box_rt(const double *__restrict__ q_bbox, const double *__restrict__ q_fxy,
+                                                     const uint8_t *__restrict__ q_len, int q_m, int64_t t) {
+    if (q_m == 3) return query_face_box<3>(q_bbox, q_fxy, q_len, t);
+    if (q_m == 4) return query_face_box<4>(q_bbox, q_fxy, q_len, t);
+    return query_face_box<0>(q_bbox, q_fxy, q_len, t);
 }
 
 // f32 box test as ONE float.  b = (xmin, xmax, ymin, ymax) of a record, q = the query box: the value is negative iff all

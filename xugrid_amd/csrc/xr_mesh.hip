@@ -188,7 +188,7 @@ k_prepare_faces(const double *__restrict__ node_xy, const int32_t *__restrict__ 
                 if (!LIGHT && fxy) fx[flip ? n - 1 - j : j] = make_double2(p.x, p.y);
             }
         }
-        if (!LIGHT) reinterpret_cast<double4 *>(bbox)[f] = make_double4(xmin, xmax, ymin, ymax);
+        if (!LIGHT && bbox) reinterpret_cast<double4 *>(bbox)[f] = make_double4(xmin, xmax, ymin, ymax); // (polygon meshes only)
         ext = fmax(xmax - xmin, ymax - ymin);
         const double dx = xmax - xmin, dy = ymax - ymin;
         diag = sqrt(dx * dx + dy * dy);
@@ -515,7 +515,9 @@ void mesh_prepare(xr_mesh *mesh, bool want_fxy, bool stats_on_side, bool allow_s
     if (want_fxy) {
         if (dense_fxy) mesh->fxy.alloc((size_t)F * m * 2);
         mesh->len.alloc((size_t)F);
-        mesh->bbox.alloc((size_t)F * 4);
+        // (dense meshes keep no box array: whoever needs a face's box takes it from the vertices, query_face_box in xr_geom.h --
+        // 32 of this kernel's 81 bytes per triangle, and the overlap kernels were the only readers)
+        if (mesh->ragged()) mesh->bbox.alloc((size_t)F * 4);
     }
     mesh->fxy_valid = dense_fxy;
     mesh->has_attrs = want_fxy;
@@ -734,7 +736,7 @@ k_spatial_scatter(const int32_t *__restrict__ key, int64_t n, int m_rt, const in
     if (INDEX) {
         reinterpret_cast<float4 *>(o_recbb)[r] =
             make_float4(f32_below(xmin - x0), f32_above(xmax - x0), f32_below(ymin - y0), f32_above(ymax - y0));
-    } else {
+    } else if (o_bbox) {
         reinterpret_cast<double4 *>(o_bbox)[r] = make_double4(xmin, xmax, ymin, ymax);
     }
 }
@@ -797,7 +799,7 @@ void mesh_query_order(xr_mesh *mesh) {
     mesh->q_perm.alloc((size_t)F);
     if (!mesh->ragged()) mesh->q_fxy.alloc((size_t)F * m * 2);
     mesh->q_len.alloc((size_t)F);
-    mesh->q_bbox.alloc((size_t)F * 4);
+    if (mesh->ragged()) mesh->q_bbox.alloc((size_t)F * 4); // (dense meshes: query_face_box)
     if (F > 0) {
         const double xmin = mesh->h_stats[0], xmax = mesh->h_stats[1], ymin = mesh->h_stats[2], ymax = mesh->h_stats[3];
         double span = std::max(xmax - xmin, ymax - ymin);

@@ -29,7 +29,7 @@ struct xr_mesh {
     bool fxy_valid = false;
     xr::DevBuf<int32_t> fxy_off; // [n_face+1] only for ragged() meshes: fxy is flat, face f starts at vertex fxy_off[f]
     xr::DevBuf<uint8_t> len;  // [n_face]
-    xr::DevBuf<double> bbox;  // [n_face*4] xmin,xmax,ymin,ymax
+    xr::DevBuf<double> bbox;  // [n_face*4] xmin,xmax,ymin,ymax; ragged() meshes only (dense ones: query_face_box, xr_geom.h)
     xr::DevBuf<double> area;  // [n_face]   connectivity.area on the caller's vertex order (mesh_area, on demand)
     hipEvent_t centroids_event = nullptr;   // recorded behind the kernel that filled centroids_dev, on centroids_stream: a user on
     hipStream_t centroids_stream = nullptr; // another stream (the handles' kernels run on the side stream) waits for it
@@ -65,7 +65,7 @@ struct xr_mesh {
     xr::DevBuf<double> q_fxy;   // [n_face*m*2], ragged(): [sum len * 2]
     xr::DevBuf<int32_t> q_off;  // [n_face+1] ragged() only
     xr::DevBuf<uint8_t> q_len;  // [n_face]
-    xr::DevBuf<double> q_bbox;  // [n_face*4]
+    xr::DevBuf<double> q_bbox;  // [n_face*4] ragged() only
 
     // ---- tree index (records in grid-cell order)
     bool indexed = false;
@@ -104,7 +104,7 @@ struct xr_mesh {
     const int32_t *qo_off() const { return !ragged() ? nullptr : query_identity ? fxy_off.get() : q_off.get(); }
     const double *qo_fxy() const { return query_identity ? fxy.get() : q_fxy.get(); }
     const uint8_t *qo_len() const { return query_identity ? len.get() : q_len.get(); }
-    const double *qo_bbox() const { return query_identity ? bbox.get() : q_bbox.get(); }
+    const double *qo_bbox() const { return query_identity ? bbox.get() : q_bbox.get(); } // nullptr for dense meshes
     const int32_t *qo_perm() const { return query_identity ? nullptr : q_perm.get(); } // nullptr = identity
 };
 

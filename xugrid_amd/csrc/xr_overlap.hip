@@ -77,9 +77,11 @@ static constexpr int BIGREC_BLOCK = 64;  // ... of which at most this many may t
 // (The f32 box test of a step through subtract / max, 62 vector instructions per step of four records.  Two cheaper forms --
 // compares combined on the scalar unit: 37 + 28 scalar; packed adds: 47 + 10 -- were measured in round 5 and changed nothing:
 // the kernel waits on memory.  They are gone.)
-template <bool PACK>
+// MC: nodes per query face (3, 4: the face's box comes from its vertices, query_face_box; 0: a polygon mesh's stored box).
+template <bool PACK, int MC>
 __global__ void __launch_bounds__(256)
-k_search(const double *__restrict__ q_bbox, int64_t n_query, GridParams g, int64_t n_tree,
+k_search(const double *__restrict__ q_bbox, const double *__restrict__ q_fxy, const uint8_t *__restrict__ q_len,
+         int64_t n_query, GridParams g, int64_t n_tree,
          const int32_t *__restrict__ cell_start,
          const float *__restrict__ rec_bb, int32_t *__restrict__ cand_count, int32_t *__restrict__ cand_off,
          int32_t *__restrict__ cand_tgt, int32_t *__restrict__ cand_src, int32_t *__restrict__ queue_cursor,
@@ -116,7 +118,7 @@ k_search(const double *__restrict__ q_bbox, int64_t n_query, GridParams g, int64
     double4 bb = make_double4(0, 0, 0, 0);
     float qx0 = INFINITY, qx1 = -INFINITY, qy0 = INFINITY, qy1 = -INFINITY;
     if (t < n_query) {
-        bb = reinterpret_cast<const double4 *>(q_bbox)[t];
+        bb = query_face_box<MC>(q_bbox, q_fxy, q_len, t);
         qx0 = f32_below(bb.x - g.x0), qx1 = f32_above(bb.y - g.x0);
         qy0 = f32_below(bb.z - g.y0), qy1 = f32_above(bb.w - g.y0);
     }
@@ -211,7 +213,7 @@ k_search(const double *__restrict__ q_bbox, int64_t n_query, GridParams g, int64
             // row tiling hint for the many-variable apply: all rows of a run of TILE_RUN consecutive ids share the
             // key of the run's middle row, so runs stay contiguous (long output stores) and neighbouring runs meet
             const int64_t mid = (t & ~(int64_t)(tile.n_run - 1)) + tile.n_run / 2;
-            tile_key[t] = morton_key(tile, reinterpret_cast<const double4 *>(q_bbox)[mid < n_query ? mid : n_query - 1]);
+            tile_key[t] = morton_key(tile, query_face_box<MC>(q_bbox, q_fxy, q_len, mid < n_query ? mid : n_query - 1));
         }
         // Level-0 cells of the bbox corners, once; the level-l cell of x is (level-0 cell) >> l exactly (cell
         // sizes are power-of-two multiples and the clamped ranges nest), and the cell of x - h_l is that minus one:
@@ -394,6 +396,7 @@ k_search_big(const double *__restrict__ q_bbox, const double *__restrict__ q_fxy
     // appended through a per-face cursor in LDS (their order inside the row is irrelevant: rows are
     // ranked by tree face id afterwards)
     __shared__ double2 sh_poly[XR_MAX_FACE_NODES];
+    __shared__ double4 sh_bb;
     extern __shared__ int32_t sh_stage[]; // [big_stage] (FUSED) / [1]
     __shared__ int sh_cursor;
     __shared__ int sh_out0;
@@ -419,10 +422,13 @@ k_search_big(const double *__restrict__ q_bbox, const double *__restrict__ q_fxy
         if (slot_face && threadIdx.x == 0)
             slot_face[nb <= BIG_RANK_MAX ? sh_rankw[0] + sh_rankw[1] + sh_rankw[2] + sh_rankw[3] : bi] = t;
         if (threadIdx.x < np) sh_poly[threadIdx.x] = reinterpret_cast<const double2 *>(q_fxy)[face_vertex_base(q_off, t, q_m) + threadIdx.x];
-        if (threadIdx.x == 0) sh_cursor = 0;
+        if (threadIdx.x == 0) {
+            sh_cursor = 0;
+            sh_bb = query_face_box_rt(q_bbox, q_fxy, q_len, q_m, t); // (dense meshes store no box)
+        }
         __syncthreads();
         const double2 *poly = sh_poly;
-        const double4 bb = reinterpret_cast<const double4 *>(q_bbox)[t];
+        const double4 bb = sh_bb;
         const float qx0 = f32_below(bb.x - g.x0), qx1 = f32_above(bb.y - g.x0);
         const float qy0 = f32_below(bb.z - g.y0), qy1 = f32_above(bb.w - g.y0);
         for (int pass = FUSED ? 0 : 1; pass < 2; pass++) {
@@ -1465,10 +1471,12 @@ static void launch_search(const xr_mesh *tree, const xr_mesh *query, const Searc
     const int64_t T = query->n_face;
     const dim3 grid(xcd_grid(div_up(T, 256), REMAP_SEARCH));
     auto launch = [&](auto packed) {
-        XR_LAUNCH("search", (k_search<decltype(packed)::value>), grid, dim3(256), 0, query->qo_bbox(), T, tree->grid, tree->n_face,
-                  tree->cell_start.get(), tree->rec_bb.get(), l.cand_count.get(), l.cand_off.get(), q.tgt, q.src, q.cursor,
-                  l.block_seg.get(), l.is_big.get(), l.big_list.get(), n_big, tile, tile_key, l.nnz_row.get(), REMAP_SEARCH,
-                  blk_rows, blk_surv, blk_rows ? (int)q.capacity : 0);
+        with_nodes_per_face(query->m, [&](auto mc) {
+            XR_LAUNCH("search", (k_search<decltype(packed)::value, mc()>), grid, dim3(256), 0, query->qo_bbox(), query->qo_fxy(),
+                      query->qo_len(), T, tree->grid, tree->n_face, tree->cell_start.get(), tree->rec_bb.get(), l.cand_count.get(),
+                      l.cand_off.get(), q.tgt, q.src, q.cursor, l.block_seg.get(), l.is_big.get(), l.big_list.get(), n_big, tile,
+                      tile_key, l.nnz_row.get(), REMAP_SEARCH, blk_rows, blk_surv, blk_rows ? (int)q.capacity : 0);
+        });
     };
     if (tree->n_face <= ((int64_t)1 << 24)) launch(std::true_type());
     else launch(std::false_type());
@@ -1630,8 +1638,8 @@ static bool overlap_tri(xr_mesh *tree, xr_mesh *query, const double *tree_area, 
         if (scan_mode == 1)
             XR_LAUNCH("assemble_scan", k_assemble_scan, dim3(1), dim3(1024), 0, blk_rows, blk_surv, (int64_t)n_blocks, (int)grid,
                       remap, blk_base.get(), blk_base.get() + grid, fc, csr->indptr.get());
-        XR_LAUNCH("assemble", k_assemble, dim3(grid), dim3(FB), 0, query->qo_bbox(), query->qo_perm(), T, cand_tgt.get(),
-                  l.cand_off.get(), l.cand_count.get(), l.block_seg.get(), l.is_big.get(), cand_area.get(), cand_sid.get(),
+        XR_LAUNCH("assemble", k_assemble, dim3(grid), dim3(FB), 0, query->qo_bbox(), query->qo_fxy(), query->qo_len(), query->m,
+                  query->qo_perm(), T, cand_tgt.get(), l.cand_off.get(), l.cand_count.get(), l.block_seg.get(), l.is_big.get(), cand_area.get(), cand_sid.get(),
                   tree_area, relative, tile, tile_key, fc,
                   csr->indptr.get(), csr->indices.get(), csr->data.get(), csr->row_order.get(),
                   csr->long_rows.get(), cap, remap, scan_mode == 1 ? blk_base.get() : (const int32_t *)nullptr,
@@ -1639,8 +1647,8 @@ static bool overlap_tri(xr_mesh *tree, xr_mesh *query, const double *tree_area, 
                   scan_mode == 2 ? blk_rows : (const int32_t *)nullptr, scan_mode == 2 ? blk_surv : (const int32_t *)nullptr);
         side_join();
         XR_LAUNCH("place_big", k_place_big, dim3(64), dim3(256), 0, n_big_dev, slot_face.get(), big_indptr.get(),
-                  big_indices.get(), big_data.get(), T, query->qo_perm(), query->qo_bbox(), tile,
-                  tile_key, fc, csr->indptr.get(), csr->indices.get(),
+                  big_indices.get(), big_data.get(), T, query->qo_perm(), query->qo_bbox(), query->qo_fxy(), query->qo_len(),
+                  query->m, tile, tile_key, fc, csr->indptr.get(), csr->indices.get(),
                   csr->data.get(), csr->row_order.get(), csr->long_rows.get(), cap, n_pending_dev);
         host_stamp(5);
         const int32_t seq = mailbox_next_seq();

@@ -344,7 +344,8 @@ k_assemble_scan(const int32_t *__restrict__ blk_rows, const int32_t *__restrict_
 // stretch of the pair queue in LDS ("dead" for area <= 0), counts the survivors per face (LDS atomics), reserves its
 // rows and entries with ONE atomic, ranks every survivor among its row and writes it to its final CSR position.
 __global__ void __launch_bounds__(FB, 2)
-k_assemble(const double *__restrict__ q_bbox, const int32_t *__restrict__ q_perm, int64_t n_query,
+k_assemble(const double *__restrict__ q_bbox, const double *__restrict__ q_fxy, const uint8_t *__restrict__ q_len, int q_m,
+           const int32_t *__restrict__ q_perm, int64_t n_query,
            const int32_t *__restrict__ cand_tgt, const int32_t *__restrict__ cand_off,
            const int32_t *__restrict__ cand_count, const int2 *__restrict__ block_seg,
            const uint8_t *__restrict__ is_big, const double *__restrict__ cand_area,
@@ -448,7 +449,7 @@ k_assemble(const double *__restrict__ q_bbox, const int32_t *__restrict__ q_perm
         row_order[r] = q_perm ? q_perm[t] : (int32_t)t;
         if (tile_key) {
             const int64_t mid = (t & ~(int64_t)(tile.n_run - 1)) + tile.n_run / 2;
-            tile_key[r] = morton_key(tile, reinterpret_cast<const double4 *>(q_bbox)[mid < n_query ? mid : n_query - 1]);
+            tile_key[r] = morton_key(tile, query_face_box_rt(q_bbox, q_fxy, q_len, q_m, mid < n_query ? mid : n_query - 1));
         }
         if (my_nnz > XR_APPLY_LONG_ROW) {
             apply_long_rows[atomicAdd(&counters->n_apply_long, 1)] = (int32_t)r;
@@ -497,7 +498,8 @@ __global__ void __launch_bounds__(256)
 k_place_big(const int32_t *__restrict__ n_big_dev, const int32_t *__restrict__ slot_face,
             const int32_t *__restrict__ big_indptr, const int32_t *__restrict__ big_indices,
             const double *__restrict__ big_data, int64_t n_query, const int32_t *__restrict__ q_perm,
-            const double *__restrict__ q_bbox, MortonParams tile, int32_t *__restrict__ tile_key,
+            const double *__restrict__ q_bbox, const double *__restrict__ q_fxy, const uint8_t *__restrict__ q_len, int q_m,
+            MortonParams tile, int32_t *__restrict__ tile_key,
             FusedCounters *counters, int32_t *__restrict__ indptr, int32_t *__restrict__ indices,
             double *__restrict__ data, int32_t *__restrict__ row_order, int32_t *__restrict__ apply_long_rows,
             int64_t csr_capacity, const int32_t *__restrict__ skip_if) {
@@ -518,7 +520,7 @@ k_place_big(const int32_t *__restrict__ n_big_dev, const int32_t *__restrict__ s
         row_order[r] = q_perm ? q_perm[f] : f;
         if (tile_key) {
             const int64_t mid = ((int64_t)f & ~(int64_t)(tile.n_run - 1)) + tile.n_run / 2;
-            tile_key[r] = morton_key(tile, reinterpret_cast<const double4 *>(q_bbox)[mid < n_query ? mid : n_query - 1]);
+            tile_key[r] = morton_key(tile, query_face_box_rt(q_bbox, q_fxy, q_len, q_m, mid < n_query ? mid : n_query - 1));
         }
         if (n > XR_APPLY_LONG_ROW) {
             apply_long_rows[atomicAdd(&counters->n_apply_long, 1)] = (int32_t)r;
