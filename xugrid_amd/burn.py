@@ -21,20 +21,11 @@ Semantics: a face is in a polygon iff its centroid passes the
 ``all_touched`` adds the faces in which a ring segment has a piece of positive length.  Polygons, then lines, then points;
 within a kind the highest index wins, as in the reference's sequential loop.  A point outside the mesh burns nothing.
 """
-import ctypes
-
 import numpy as np
 
 from . import _lib, engine
 from ._lib import check
-
-
-def _vp(ptr):
-    return ctypes.c_void_p(int(ptr)) if ptr else None
-
-
-def _is_torch(obj):
-    return (type(obj).__module__ or "").startswith("torch")
+from .engine import vp
 
 
 class _Arg:
@@ -47,7 +38,7 @@ class _Arg:
         if info is not None:
             ptr, shape, got = info
             if got != np.dtype(dtype):
-                if not _is_torch(array):
+                if not engine.is_torch(array):
                     raise TypeError(f"{what} on the device must be {np.dtype(dtype).name}, received {got}")
                 import torch
 
@@ -128,9 +119,9 @@ def _polygon_args(polygons):
 
 
 def _polygon_winner(mesh, coords, ring_offsets, polygon_offsets, all_touched, winner_ptr):
-    check(_lib.load().xr_burn_polygons_dev(mesh._h, _vp(coords.ptr), coords.n, _vp(ring_offsets.ptr), ring_offsets.n - 1,
-                                           _vp(polygon_offsets.ptr), polygon_offsets.n - 1, int(bool(all_touched)),
-                                           _vp(winner_ptr)))
+    check(_lib.load().xr_burn_polygons_dev(mesh._h, vp(coords.ptr), coords.n, vp(ring_offsets.ptr), ring_offsets.n - 1,
+                                           vp(polygon_offsets.ptr), polygon_offsets.n - 1, int(bool(all_touched)),
+                                           vp(winner_ptr)))
 
 
 def polygon_winner(like, coords, ring_offsets, polygon_offsets, all_touched=False):
@@ -189,18 +180,18 @@ def burn_vector_geometry(like, *, polygons=None, lines=None, points=None, fill=n
         _polygon_winner(mesh, polygon_xy, ring_offsets, polygon_offsets, all_touched, w_polygon.ptr)
     if lines is not None and line_offsets.n - 1 > 0 and n_face > 0:
         w_line = engine.DeviceArray((n_face,), np.int32)
-        check(lib.xr_burn_lines_dev(mesh._h, _vp(line_xy.ptr), line_xy.n, _vp(line_offsets.ptr), line_offsets.n - 1,
-                                    _vp(w_line.ptr)))
+        check(lib.xr_burn_lines_dev(mesh._h, vp(line_xy.ptr), line_xy.n, vp(line_offsets.ptr), line_offsets.n - 1,
+                                    vp(w_line.ptr)))
     if points is not None and point_xy.n > 0 and n_face > 0:
         w_point = engine.DeviceArray((n_face,), np.int32)
-        check(lib.xr_burn_points_dev(mesh._h, _vp(point_xy.ptr), point_xy.n, _vp(w_point.ptr)))
+        check(lib.xr_burn_points_dev(mesh._h, vp(point_xy.ptr), point_xy.n, vp(w_point.ptr)))
 
     def ptr(arg):
-        return _vp(arg.ptr) if arg is not None else None
+        return vp(arg.ptr) if arg is not None else None
 
     def combine(out_ptr):
         check(lib.xr_burn_combine_dev(n_face, ptr(w_polygon), ptr(v_polygon), ptr(w_line), ptr(v_line), ptr(w_point),
-                                      ptr(v_point), fill, _vp(out_ptr)))
+                                      ptr(v_point), fill, vp(out_ptr)))
 
     if device_like is not None:
         out, out_ptr = engine.empty_like_device(device_like, (n_face,))

@@ -19,6 +19,7 @@
 #include <memory>
 
 #include "xr_objects.h"
+#include "xr_prims.h"
 
 namespace xr {
 
@@ -2224,10 +2225,6 @@ __global__ void k_narrow_i64(const int64_t *__restrict__ in, int32_t *__restrict
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) out[i] = (int32_t)in[i];
 }
-__global__ void k_widen_i32(const int32_t *__restrict__ in, int64_t *__restrict__ out, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = in[i];
-}
 __global__ void k_bincount(const int32_t *__restrict__ row, int64_t nnz, int32_t *__restrict__ count) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < nnz) atomicAdd(&count[row[i]], 1);
@@ -2442,13 +2439,6 @@ static void upload_narrow(const int64_t *host, int64_t n, int32_t *dev) {
     XR_LAUNCH("narrow_i64", k_narrow_i64, dim3(div_up(n, 256)), dim3(256), 0, wide.get(), dev, n);
 }
 
-static void download_widen(const int32_t *dev, int64_t n, int64_t *host) {
-    if (n <= 0) return;
-    DevBuf<int64_t> wide((size_t)n);
-    XR_LAUNCH("widen_i32", k_widen_i32, dim3(div_up(n, 256)), dim3(256), 0, dev, wide.get(), n);
-    d2h(host, wide.get(), sizeof(int64_t) * (size_t)n);
-}
-
 } // namespace xr
 
 using namespace xr;
@@ -2614,6 +2604,8 @@ int xr_csr_download(const xr_csr *csr, double *data, int64_t *indices, int64_t *
     if (data && csr->nnz > 0) {
         d2h(data, d_data, sizeof(double) * (size_t)csr->nnz);
     }
+    DevBuf<int64_t> wide;
+    if (indices || indptr) wide.alloc((size_t)std::max(csr->nnz, csr->n + 1));
     if (indices) {
         DevBuf<int32_t> caller_ids;
         if (csr->has_col_perm && csr->nnz > 0) { // stored column ids -> the caller's
@@ -2622,9 +2614,9 @@ int xr_csr_download(const xr_csr *csr, double *data, int64_t *indices, int64_t *
                       csr->nnz, caller_ids.get());
             d_indices = caller_ids.get();
         }
-        download_widen(d_indices, csr->nnz, indices);
+        download_wide(d_indices, csr->nnz, indices, wide);
     }
-    if (indptr) download_widen(d_indptr, csr->n + 1, indptr);
+    download_wide(d_indptr, csr->n + 1, indptr, wide);
     stream_sync();
     XR_API_END
 }
@@ -2840,7 +2832,8 @@ int xr_csr_col_order(const xr_csr *csr, int64_t *order_out) {
     XR_API_BEGIN
     XR_REQUIRE(csr && (order_out || csr->m == 0), XR_ERR_INVALID, "xr_csr_col_order: NULL argument");
     if (csr->has_col_perm) {
-        download_widen(csr->col_of.get(), csr->m, order_out);
+        DevBuf<int64_t> wide((size_t)csr->m);
+        download_wide(csr->col_of.get(), csr->m, order_out, wide);
         stream_sync();
     } else {
         for (int64_t i = 0; i < csr->m; i++) order_out[i] = i;
@@ -2882,7 +2875,8 @@ int xr_csr_row_order(const xr_csr *csr, int64_t K_hint, int64_t *order_out) {
     XR_REQUIRE(csr && (order_out || csr->n == 0), XR_ERR_INVALID, "xr_csr_row_order: NULL argument");
     settle_row_layout(csr);
     if (csr->has_row_order) {
-        download_widen(csr->row_order.get(), csr->n, order_out);
+        DevBuf<int64_t> wide((size_t)csr->n);
+        download_wide(csr->row_order.get(), csr->n, order_out, wide);
         stream_sync();
     } else {
         for (int64_t i = 0; i < csr->n; i++) order_out[i] = i;

@@ -24,6 +24,7 @@
 
 #include "xr_objects.h"
 #include "xr_point_in_face.h"
+#include "xr_prims.h"
 
 namespace xr {
 
@@ -52,7 +53,7 @@ k_burn_check_offsets(const int64_t *__restrict__ off, int64_t n_off, int64_t tot
         const int64_t v = off[i];
         bad = (i == 0 && v != 0) || (i == n_off - 1 && v != total) || (i > 0 && v < off[i - 1]);
     }
-    if (__ballot(bad) && (threadIdx.x & 63) == 0) *flag = 1;
+    wave_flag(bad, flag);
 }
 
 // the last r in [0, n) with off[r] <= i (off ascending, off[0] <= i)
@@ -84,46 +85,9 @@ k_burn_segments(const double2 *__restrict__ xy, int64_t n_vertex, const int64_t 
     key[i] = (int32_t)(group_off ? offset_owner(group_off, n_group, r) : r);
 }
 
-// per block: ymin, ymax, the largest |coordinate| and the summed |dy| of the segments that count (len2 > 0)
-__global__ void __launch_bounds__(BB) k_burn_extent(const double4 *__restrict__ seg, int64_t n, double *__restrict__ partial) {
+// block reduction of (min, max, max, sum) over the BB lanes -> out[0..3], written by thread 0
+__device__ __forceinline__ void burn_extent_reduce(double y0, double y1, double am, double dy, double *__restrict__ out) {
     __shared__ double sh[4][BB / 64];
-    const int64_t i = (int64_t)blockIdx.x * BB + threadIdx.x;
-    double y0 = INFINITY, y1 = -INFINITY, am = 0.0, dy = 0.0;
-    if (i < n) {
-        const double4 s = seg[i];
-        const double wx = s.z - s.x, wy = s.w - s.y;
-        if (wx * wx + wy * wy > 0) {
-            y0 = fmin(s.y, s.w), y1 = fmax(s.y, s.w);
-            am = fmax(fmax(fabs(s.x), fabs(s.z)), fmax(fabs(s.y), fabs(s.w)));
-            dy = fabs(wy);
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        y0 = fmin(y0, __shfl_xor(y0, o, 64));
-        y1 = fmax(y1, __shfl_xor(y1, o, 64));
-        am = fmax(am, __shfl_xor(am, o, 64));
-        dy += __shfl_xor(dy, o, 64);
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) sh[0][w] = y0, sh[1][w] = y1, sh[2][w] = am, sh[3][w] = dy;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int u = 1; u < BB / 64; u++) {
-            sh[0][0] = fmin(sh[0][0], sh[0][u]), sh[1][0] = fmax(sh[1][0], sh[1][u]);
-            sh[2][0] = fmax(sh[2][0], sh[2][u]), sh[3][0] += sh[3][u];
-        }
-        for (int u = 0; u < 4; u++) partial[(int64_t)blockIdx.x * 4 + u] = sh[u][0];
-    }
-}
-
-__global__ void __launch_bounds__(BB) k_burn_extent_final(const double *__restrict__ partial, int nb, double *__restrict__ out) {
-    __shared__ double sh[4][BB / 64];
-    double y0 = INFINITY, y1 = -INFINITY, am = 0.0, dy = 0.0;
-    for (int b = threadIdx.x; b < nb; b += BB) {
-        const double *p = partial + (int64_t)b * 4;
-        y0 = fmin(y0, p[0]), y1 = fmax(y1, p[1]), am = fmax(am, p[2]), dy += p[3];
-    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         y0 = fmin(y0, __shfl_xor(y0, o, 64));
@@ -141,6 +105,31 @@ __global__ void __launch_bounds__(BB) k_burn_extent_final(const double *__restri
         }
         for (int u = 0; u < 4; u++) out[u] = sh[u][0];
     }
+}
+
+// per block: ymin, ymax, the largest |coordinate| and the summed |dy| of the segments that count (len2 > 0)
+__global__ void __launch_bounds__(BB) k_burn_extent(const double4 *__restrict__ seg, int64_t n, double *__restrict__ partial) {
+    const int64_t i = (int64_t)blockIdx.x * BB + threadIdx.x;
+    double y0 = INFINITY, y1 = -INFINITY, am = 0.0, dy = 0.0;
+    if (i < n) {
+        const double4 s = seg[i];
+        const double wx = s.z - s.x, wy = s.w - s.y;
+        if (wx * wx + wy * wy > 0) {
+            y0 = fmin(s.y, s.w), y1 = fmax(s.y, s.w);
+            am = fmax(fmax(fabs(s.x), fabs(s.z)), fmax(fabs(s.y), fabs(s.w)));
+            dy = fabs(wy);
+        }
+    }
+    burn_extent_reduce(y0, y1, am, dy, partial + (int64_t)blockIdx.x * 4);
+}
+
+__global__ void __launch_bounds__(BB) k_burn_extent_final(const double *__restrict__ partial, int nb, double *__restrict__ out) {
+    double y0 = INFINITY, y1 = -INFINITY, am = 0.0, dy = 0.0;
+    for (int b = threadIdx.x; b < nb; b += BB) {
+        const double *p = partial + (int64_t)b * 4;
+        y0 = fmin(y0, p[0]), y1 = fmax(y1, p[1]), am = fmax(am, p[2]), dy += p[3];
+    }
+    burn_extent_reduce(y0, y1, am, dy, out);
 }
 
 // span[i] = (first, last) strip of segment i, (1, 0) for a segment no rule reads; count[strip * n_chunk + chunk] += 1 for

@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "xr_prims.h"
 #include "xr_topology.h"
 
 namespace xr {
@@ -45,7 +46,7 @@ __global__ void __launch_bounds__(FB) k_facet_check(FacetTable tb, int32_t *__re
     } else if (i < tb.n_target * tb.width) {
         bad = tb.idx[i] >= tb.n_source;
     }
-    if (__ballot(bad) && (threadIdx.x & 63) == 0) *flag = 1;
+    wave_flag(bad, flag);
 }
 
 // widest row of a CSR: one block, any number of rows -> out[0]

@@ -398,11 +398,4 @@ void exclusive_scan_i32(const int32_t *in, int32_t *out, int64_t n, int32_t *hos
 void fill_i32(int32_t *p, int32_t v, int64_t n);
 void fill_f64(double *p, double v, int64_t n);
 
-// int32 -> int64 on the way out of the library (indices are int32 in HBM, int64 in the C ABI): shared by the units that hand
-// out index arrays (`static`: one copy per unit that uses it)
-static __global__ void __launch_bounds__(256) k_widen_i32_i64(const int32_t *__restrict__ in, int64_t n, int64_t *__restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = in[i];
-}
-
 } // namespace xr

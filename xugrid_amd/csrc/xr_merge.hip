@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "xr_objects.h"
+#include "xr_prims.h"
 #include "xr_topology.h"
 
 #include "xr_merge_keys.h"
@@ -63,11 +64,6 @@ struct xr_label_order {
 namespace xr {
 
 static constexpr int MERGE_SORT_REGS = 8; // rows up to this width are sorted in registers
-
-__device__ __forceinline__ void merge_wave_count(bool pred, int32_t *counter) {
-    const unsigned long long ballot = __ballot(pred);
-    if ((threadIdx.x & 63) == 0 && ballot) atomicAdd(counter, __popcll(ballot));
-}
 
 // ---- the two kinds of rows
 struct XYRows {
@@ -229,12 +225,6 @@ k_merge_compact_edges(const int32_t *__restrict__ flag, const int32_t *__restric
     position[j] = id;
 }
 
-__global__ void __launch_bounds__(256)
-k_merge_widen(const int32_t *__restrict__ in, int64_t n, int64_t subtract, int64_t *__restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = (int64_t)in[i] - subtract;
-}
-
 // ---- index_like
 __global__ void __launch_bounds__(256) k_like_keys(const double *__restrict__ xy, int64_t n2, double tolerance, double *__restrict__ keys) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -243,7 +233,7 @@ __global__ void __launch_bounds__(256) k_like_keys(const double *__restrict__ xy
 
 __global__ void __launch_bounds__(256) k_like_repeats(const int32_t *__restrict__ flag, int64_t n, int32_t *__restrict__ count) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    merge_wave_count(i < n && !flag[i], count);
+    wave_count(i < n && !flag[i], count);
 }
 
 enum LikeStatus : int { LS_REPEAT = 0, LS_MISS = 1, LS_COUNT = 2 };
@@ -277,8 +267,8 @@ k_like_lookup(const double2 *__restrict__ key_a, const double2 *__restrict__ key
         if (!miss) repeat = atomicExch(hit + j, 1) != 0;
         index[i] = j;
     }
-    merge_wave_count(repeat, status + LS_REPEAT);
-    merge_wave_count(miss, status + LS_MISS);
+    wave_count(repeat, status + LS_REPEAT);
+    wave_count(miss, status + LS_MISS);
 }
 
 // ---- labels
@@ -526,8 +516,7 @@ int xr_merge_index_copy_dev(const xr_merge *merge, int facet, int64_t part, int 
     const int64_t first = part < 0 ? 0 : rows.bound[part], n = (part < 0 ? rows.bound.back() : rows.bound[part + 1]) - first;
     XR_REQUIRE(out_dev || n == 0, XR_ERR_INVALID, "xr_merge_index_copy_dev: NULL argument");
     const int32_t *src = (position ? merge->edge_position.get() : rows.keep.get()) + first;
-    if (n > 0)
-        XR_LAUNCH("merge_widen", k_merge_widen, dim3(div_up(n, 256)), dim3(256), 0, src, n, position || part < 0 ? 0 : rows.off[part], out_dev);
+    widen_dev(src, n, out_dev, position || part < 0 ? 0 : rows.off[part]);
     dev_call_done();
     XR_API_END
 }
@@ -537,7 +526,7 @@ int xr_merge_node_inverse_copy_dev(const xr_merge *merge, int64_t *out_dev) {
     XR_REQUIRE(merge, XR_ERR_INVALID, "xr_merge_node_inverse_copy_dev: NULL argument");
     const int64_t n = merge->rows[0].off.back();
     XR_REQUIRE(out_dev || n == 0, XR_ERR_INVALID, "xr_merge_node_inverse_copy_dev: NULL argument");
-    if (n > 0) XR_LAUNCH("merge_widen", k_merge_widen, dim3(div_up(n, 256)), dim3(256), 0, merge->node_inverse.get(), n, (int64_t)0, out_dev);
+    widen_dev(merge->node_inverse.get(), n, out_dev);
     dev_call_done();
     XR_API_END
 }
@@ -633,8 +622,7 @@ int xr_label_order_copy_dev(const xr_label_order *order, int64_t first, int64_t 
     XR_API_BEGIN
     XR_REQUIRE(order && first >= 0 && count >= 0 && first + count <= order->n && (out_dev || count == 0), XR_ERR_INVALID,
                "xr_label_order_copy_dev: bad argument");
-    if (count > 0)
-        XR_LAUNCH("merge_widen", k_merge_widen, dim3(div_up(count, 256)), dim3(256), 0, order->ids.get() + first, count, (int64_t)0, out_dev);
+    widen_dev(order->ids.get() + first, count, out_dev);
     dev_call_done();
     XR_API_END
 }

@@ -19,6 +19,7 @@
 
 #include "xr_objects.h"
 #include "xr_agg.h"
+#include "xr_prims.h"
 
 namespace xr {
 
@@ -1416,9 +1417,7 @@ int xr_mesh_triangle_face_dev(const xr_mesh *triangles, int64_t *index_dev) {
     XR_API_BEGIN
     XR_REQUIRE(triangles && (index_dev || triangles->n_face == 0), XR_ERR_INVALID, "xr_mesh_triangle_face_dev: NULL argument");
     XR_REQUIRE(triangles->is_triangulation, XR_ERR_INVALID, "xr_mesh_triangle_face_dev: the mesh was not made by xr_mesh_triangulate");
-    if (triangles->n_face > 0)
-        XR_LAUNCH("widen_i32", k_widen_i32_i64, dim3(div_up(triangles->n_face, 256)), dim3(256), 0, triangles->tri_face.get(),
-                  triangles->n_face, index_dev);
+    widen_dev(triangles->tri_face.get(), triangles->n_face, index_dev);
     dev_call_done();
     XR_API_END
 }

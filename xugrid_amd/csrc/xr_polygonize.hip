@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "xr_polygonize_order.h"
+#include "xr_prims.h"
 #include "xr_topology.h"
 
 struct xr_polygons {
@@ -157,11 +158,6 @@ k_pg_halfedge_flag(const int32_t *__restrict__ faces, int64_t n_face, int m, con
         }
     }
     hflag[i] = flag;
-}
-__global__ void __launch_bounds__(PB)
-k_pg_compact(const int32_t *__restrict__ hflag, const int32_t *__restrict__ hpos, int64_t n_slot, int32_t *__restrict__ he_slot) {
-    const int64_t i = (int64_t)blockIdx.x * PB + threadIdx.x;
-    if (i < n_slot && hflag[i]) he_slot[hpos[i]] = (int32_t)i;
 }
 
 // 5: successor of half-edge h = a -> b of face f: in f the slot that leaves b; a boundary half-edge is the answer, else across it
@@ -413,7 +409,7 @@ static void polygonize(xr_topology *t, const void *data_dev, int dtype, xr_polyg
     p->n_halfedge = H;
     const unsigned hb = div_up(H, PB);
     DevBuf<int32_t> he_slot((size_t)H), succ((size_t)H);
-    XR_LAUNCH("pg_compact", k_pg_compact, dim3(div_up(n_slot, PB)), dim3(PB), 0, flag.get(), hpos.get(), n_slot, he_slot.get());
+    XR_LAUNCH("pg_compact", k_compact_ids<int32_t>, dim3(div_up(n_slot, PB)), dim3(PB), 0, flag.get(), hpos.get(), n_slot, he_slot.get());
 
     // 5
     XR_LAUNCH("pg_successor", k_pg_successor, dim3(hb), dim3(PB), 0, he_slot.get(), H, faces, m, t->face_edge.get(),

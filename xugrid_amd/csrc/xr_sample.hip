@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "xr_nn.h"
+#include "xr_prims.h"
 
 namespace xr {
 
@@ -188,7 +189,7 @@ __global__ void __launch_bounds__(SB)
 k_sp_index_check(const int64_t *__restrict__ index, int64_t count, int64_t lo, int64_t n, int32_t *__restrict__ flag) {
     const int64_t i = (int64_t)blockIdx.x * SB + threadIdx.x;
     const bool bad = i < count && (index[i] >= n || index[i] < lo);
-    if (__ballot(bad) && (threadIdx.x & 63) == 0) *flag = 1;
+    wave_flag(bad, flag);
 }
 
 // out[k, p] = index[p] >= 0 ? in[k, index[p]] : fill; slice k = blockIdx.y of this tile

@@ -23,6 +23,7 @@
 //     (difference array + two prefix sums + integral image, all int32; conservative at cell granularity, not spoiled by a few
 //     long hull slivers the way one box per shard would be).
 #include "xr_internal.h"
+#include "xr_prims.h"
 
 namespace xr {
 
@@ -267,12 +268,6 @@ k_shard_owner(int64_t S, const int32_t *__restrict__ mcell, const unsigned long 
     if (owner_out) owner_out[i] = o;
 }
 
-__global__ void __launch_bounds__(256)
-k_shard_compact(const int32_t *__restrict__ flag, const int32_t *__restrict__ pos, int64_t n, int64_t *__restrict__ ids) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n && flag[i]) ids[pos[i]] = i;
-}
-
 // pass 5: bounds of the boxes of MY source faces and of all target faces
 __global__ void __launch_bounds__(256)
 k_shard_box_bounds(const double *__restrict__ sxy, const int64_t *__restrict__ sf, int64_t S, int ms, const int32_t *__restrict__ mine,
@@ -421,7 +416,7 @@ int xr_shard_plan_dev(const double *src_xy_dev, const int64_t *src_faces_dev, in
     XR_LAUNCH("shard_owner", k_shard_owner, dim3(div_up(S, 256)), dim3(256), 0, S, mcell.get(), cell_work.get(),
               part.get() + SHARD_CELLS / S64_TILE, world, rank, hash, sflag.get(), owner_dev);
     exclusive_scan_i32(sflag.get(), spos.get(), S);
-    XR_LAUNCH("shard_compact", k_shard_compact, dim3(div_up(S, 256)), dim3(256), 0, sflag.get(), spos.get(), S, local_faces_dev);
+    XR_LAUNCH("shard_compact", k_compact_ids<int64_t>, dim3(div_up(S, 256)), dim3(256), 0, sflag.get(), spos.get(), S, local_faces_dev);
     if (T > 0) {
         XR_LAUNCH("shard_box_bounds", k_shard_box_bounds, dim3(nb_all), dim3(256), 0, src_xy_dev, src_faces_dev, S, src_m,
                   sflag.get(), tgt_xy_dev, tgt_faces_dev, T, tgt_m, partial.get());
@@ -433,7 +428,7 @@ int xr_shard_plan_dev(const double *src_xy_dev, const int64_t *src_faces_dev, in
         XR_LAUNCH("shard_targets", k_shard_targets, dim3(div_up(T, 256)), dim3(256), 0, tgt_xy_dev, tgt_faces_dev, T, tgt_m, bounds.get(),
                   integral.get(), tflag.get());
         exclusive_scan_i32(tflag.get(), tpos.get(), T);
-        XR_LAUNCH("shard_compact", k_shard_compact, dim3(div_up(T, 256)), dim3(256), 0, tflag.get(), tpos.get(), T, local_targets_dev);
+        XR_LAUNCH("shard_compact", k_compact_ids<int64_t>, dim3(div_up(T, 256)), dim3(256), 0, tflag.get(), tpos.get(), T, local_targets_dev);
     }
     int32_t n_s = 0, n_t = 0;
     d2h(&n_s, spos.get() + S, sizeof(int32_t));

@@ -13,6 +13,7 @@
 #include <algorithm>
 
 #include "xr_objects.h"
+#include "xr_prims.h"
 #include "xr_topology.h"
 
 // ascending int32 ids in HBM; what xr_index_from_mask_dev and its relatives return
@@ -24,12 +25,6 @@ struct xr_index {
 namespace xr {
 
 enum SubsetStatus : int { SS_RANGE = 0, SS_REPEAT = 1, SS_MOVED = 2, SS_COUNT = 3 };
-
-// one integer add per wave in which `pred` holds for some lane (every lane of the wave must get here)
-__device__ __forceinline__ void wave_count(bool pred, int32_t *counter) {
-    const unsigned long long ballot = __ballot(pred);
-    if ((threadIdx.x & 63) == 0 && ballot) atomicAdd(counter, __popcll(ballot));
-}
 
 // 1: one thread per i.  pos[index[i]] = i + 1 (pos is zero at the start: 0 = not selected; of a repeated id one writer wins,
 // the others find out in the next pass); ids outside [0, size) are counted, never used; status[SS_MOVED] = 1 when some
@@ -168,12 +163,6 @@ k_faces_of_edges(const int64_t *__restrict__ index, int64_t n, int64_t n_edge, c
 }
 
 __global__ void __launch_bounds__(256)
-k_compact_flags(const int32_t *__restrict__ flags, const int32_t *__restrict__ off, int64_t n, int32_t *__restrict__ ids) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n && flags[i]) ids[off[i]] = (int32_t)i;
-}
-
-__global__ void __launch_bounds__(256)
 k_index_mismatch(const int64_t *__restrict__ a, const int64_t *__restrict__ b, int64_t n, int32_t *__restrict__ count) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     wave_count(i < n && a[i] != b[i], count);
@@ -188,7 +177,7 @@ static xr_index *index_from_flags(const int32_t *flags, int64_t n) {
         exclusive_scan_i32(flags, off.get(), n);
         out->n = read_scalar(off.get() + n);
         out->ids.alloc((size_t)out->n);
-        if (out->n > 0) XR_LAUNCH("subset_compact", k_compact_flags, dim3(div_up(n, 256)), dim3(256), 0, flags, off.get(), n, out->ids.get());
+        if (out->n > 0) XR_LAUNCH("subset_compact", k_compact_ids<int32_t>, dim3(div_up(n, 256)), dim3(256), 0, flags, off.get(), n, out->ids.get());
         stream_sync(); // (the scan's scratch goes back to the pool behind its readers)
     }
     return out.release();
@@ -259,9 +248,7 @@ int xr_mesh_subset_node_index_dev(const xr_mesh *subset, int64_t *index_dev) {
     XR_API_BEGIN
     XR_REQUIRE(subset && (index_dev || subset->n_node == 0), XR_ERR_INVALID, "xr_mesh_subset_node_index_dev: NULL argument");
     XR_REQUIRE(subset->is_subset, XR_ERR_INVALID, "xr_mesh_subset_node_index_dev: the mesh was not made by xr_mesh_subset_dev");
-    if (subset->n_node > 0)
-        XR_LAUNCH("widen_i32", k_widen_i32_i64, dim3(div_up(subset->n_node, 256)), dim3(256), 0, subset->sub_node.get(),
-                  subset->n_node, index_dev);
+    widen_dev(subset->sub_node.get(), subset->n_node, index_dev);
     dev_call_done();
     XR_API_END
 }
@@ -375,8 +362,7 @@ int xr_index_info(const xr_index *index, int64_t *n) {
 int xr_index_copy_dev(const xr_index *index, int64_t *out_dev) {
     XR_API_BEGIN
     XR_REQUIRE(index && (out_dev || index->n == 0), XR_ERR_INVALID, "xr_index_copy_dev: NULL argument");
-    if (index->n > 0)
-        XR_LAUNCH("widen_i32", k_widen_i32_i64, dim3(div_up(index->n, 256)), dim3(256), 0, index->ids.get(), index->n, out_dev);
+    widen_dev(index->ids.get(), index->n, out_dev);
     dev_call_done();
     XR_API_END
 }

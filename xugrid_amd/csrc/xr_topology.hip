@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "xr_node_faces.h"
+#include "xr_prims.h"
 #include "xr_topology.h"
 
 namespace xr {
@@ -320,17 +321,6 @@ k_topo_edge_xy(const double *__restrict__ node_xy, const int32_t *__restrict__ e
     const int64_t e = i >> 1;
     const int c = (int)(i & 1);
     out[i] = 0.5 * (node_xy[2 * (int64_t)edge_node[2 * e] + c] + node_xy[2 * (int64_t)edge_node[2 * e + 1] + c]);
-}
-
-template <typename T> __global__ void __launch_bounds__(256) k_topo_widen(const T *__restrict__ in, int64_t n, int64_t *__restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = (int64_t)in[i];
-}
-
-template <typename T> static void download_wide(const T *dev, int64_t n, int64_t *host, DevBuf<int64_t> &wide) {
-    if (!host || n <= 0) return;
-    XR_LAUNCH("topo_widen", k_topo_widen<T>, dim3(div_up(n, 256)), dim3(256), 0, dev, n, wide.get());
-    d2h(host, wide.get(), sizeof(int64_t) * (size_t)n);
 }
 
 } // namespace xr

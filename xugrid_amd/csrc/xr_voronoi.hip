@@ -25,6 +25,7 @@
 
 #include "xr_node_faces.h"
 #include "xr_objects.h"
+#include "xr_prims.h"
 #include "xr_voronoi_boundary.h"
 
 struct xr_voronoi {
@@ -597,14 +598,8 @@ int xr_voronoi_download(const xr_voronoi *v, int64_t *indptr, int64_t *indices, 
                "xr_voronoi_download: a handle built without exterior keeps only the generator points its cells use");
     {
         DevBuf<int64_t> wide((size_t)std::max<int64_t>(v->n_node + 1, v->nnz));
-        XR_LAUNCH("vor_widen", k_widen_i32_i64, dim3(div_up(v->n_node + 1, 256)), dim3(256), 0, v->indptr.get(), v->n_node + 1,
-                  wide.get());
-        d2h(indptr, wide.get(), sizeof(int64_t) * (size_t)(v->n_node + 1));
-        if (v->nnz > 0) {
-            XR_LAUNCH("vor_widen", k_widen_i32_i64, dim3(div_up(v->nnz, 256)), dim3(256), 0, v->faces_asc.get(), v->nnz,
-                      wide.get());
-            d2h(indices, wide.get(), sizeof(int64_t) * (size_t)v->nnz);
-        }
+        download_wide(v->indptr.get(), v->n_node + 1, indptr, wide);
+        download_wide(v->faces_asc.get(), v->nnz, indices, wide);
     }
     const size_t ne = v->edge_lo.size();
     XR_REQUIRE(ne == 0 || (edge_nodes && edge_face), XR_ERR_INVALID, "xr_voronoi_download: NULL edge arrays");

@@ -87,6 +87,15 @@ class option:
         return False
 
 
+def is_torch(obj):
+    return (type(obj).__module__ or "").startswith("torch")
+
+
+def vp(ptr):
+    """A device pointer held as an integer -> the ctypes argument (0 / None: NULL)."""
+    return ctypes.c_void_p(int(ptr)) if ptr else None
+
+
 # ---- arrays that already live in HBM -----------------------------------------------------------------------------------------
 _DEV_TYPESTR = {"<f8": np.float64, "<f4": np.float32, "<i8": np.int64, "<i4": np.int32}
 
@@ -97,7 +106,7 @@ def device_array_info(obj):
     else None.  Device arrays that are not contiguous, or of another dtype than float64 / float32 / int64 / int32, raise."""
     if isinstance(obj, np.ndarray):
         return None
-    if (type(obj).__module__ or "").startswith("torch"):
+    if is_torch(obj):
         if not getattr(obj, "is_cuda", False):
             return None
         if not obj.is_contiguous():
@@ -129,10 +138,48 @@ def device_array_info(obj):
     return int(cai["data"][0]), shape, dtype
 
 
-class DeviceArray:
+def byte_array_info(obj):
+    """-> (device pointer, shape, 'bool' | 'uint8') if ``obj`` is a C-contiguous one-byte array in device memory (a mask: torch
+    ``bool`` / ``uint8``, typestr ``|b1`` / ``|u1``), else None.  One-byte device arrays that are not contiguous raise."""
+    if isinstance(obj, np.ndarray):
+        return None
+    if is_torch(obj):
+        name = str(obj.dtype).replace("torch.", "")
+        if not getattr(obj, "is_cuda", False) or name not in ("bool", "uint8"):
+            return None
+        if not obj.is_contiguous():
+            raise ValueError("device arrays must be C-contiguous")
+        return int(obj.data_ptr()), tuple(int(n) for n in obj.shape), name
+    cai = getattr(obj, "__cuda_array_interface__", None)
+    if not isinstance(cai, dict) or cai["typestr"] not in ("|b1", "|u1"):
+        return None
+    if cai.get("strides") is not None:
+        raise ValueError("device arrays must be C-contiguous")
+    return int(cai["data"][0]), tuple(int(n) for n in cai["shape"]), "bool" if cai["typestr"] == "|b1" else "uint8"
+
+
+class Handle:
+    """Owner of one handle of the C ABI in ``_h``: destroyed with the object by the function ``_destroy`` names.  ``__del__``
+    also runs on half-built objects and at interpreter shutdown: a missing ``_h`` is fine and nothing is raised."""
+
+    _destroy = None
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                getattr(_lib.load(), self._destroy)(h)
+            except Exception:  # noqa: BLE001
+                pass
+            self._h = None
+
+
+class DeviceArray(Handle):
     """An array in the engine's HBM (xr_dev_alloc): what ``Regridder.regrid`` returns for device input that is not a torch
     tensor, and a way to put host arrays there once.  Exposes ``__cuda_array_interface__`` (version 3), so torch / cupy can wrap
     it without a copy; ``download()`` -> numpy."""
+
+    _destroy = "xr_dev_free"
 
     def __init__(self, shape, dtype=np.float64):
         self.shape = tuple(int(n) for n in (shape if isinstance(shape, (tuple, list)) else (shape,)))
@@ -169,20 +216,11 @@ class DeviceArray:
             check(_lib.load().xr_dev_download(out.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(self.ptr), self.nbytes))
         return out
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                _lib.load().xr_dev_free(h)
-            except Exception:  # noqa: BLE001
-                pass
-            self._h = None
-
 
 def empty_like_device(like, shape, dtype=np.float64):
     """A fresh device array of ``shape`` of the same KIND as ``like``: a torch tensor on ``like``'s device for a torch tensor,
     a ``DeviceArray`` otherwise.  -> (array, device pointer)"""
-    if (type(like).__module__ or "").startswith("torch"):
+    if is_torch(like):
         import torch
 
         out = torch.empty(tuple(shape), dtype=getattr(torch, np.dtype(dtype).name), device=like.device)
@@ -194,10 +232,28 @@ def empty_like_device(like, shape, dtype=np.float64):
 def sync_producer(obj):
     """Device input handed over by another library was written on ITS stream; the engine reads it on its own.  For torch
     tensors the current torch stream is drained first (a no-op when the engine runs on that very stream, xr_set_stream)."""
-    if (type(obj).__module__ or "").startswith("torch"):
+    if is_torch(obj):
         import torch
 
         torch.cuda.current_stream(obj.device).synchronize()
+
+
+def upload_like(a, like):
+    """A host int64 array as a device array of the kind of ``like`` (None: a ``DeviceArray``)."""
+    a = np.ascontiguousarray(a, dtype=np.int64)
+    if like is not None and is_torch(like):
+        import torch
+
+        return torch.as_tensor(a).to(like.device)
+    return DeviceArray.from_host(a)
+
+
+def download(dev):
+    """A device array (``DeviceArray`` or torch tensor) -> numpy."""
+    if isinstance(dev, DeviceArray):
+        return dev.download()
+    sync_producer(dev)
+    return dev.cpu().numpy()
 
 
 def _as_xy(vertices):
@@ -218,8 +274,10 @@ def _as_faces(faces):
     return np.ascontiguousarray(f)
 
 
-class DeviceMesh:
+class DeviceMesh(Handle):
     """Face topology resident in HBM (+ lazily built derived data and spatial index)."""
+
+    _destroy = "xr_mesh_destroy"
 
     @classmethod
     def _from_handle(cls, handle):
@@ -281,15 +339,6 @@ class DeviceMesh:
             )
         )
         self._h = handle
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                _lib.load().xr_mesh_destroy(h)
-            except Exception:
-                pass
-            self._h = None
 
     def prepare(self):
         check(_lib.load().xr_mesh_prepare(self._h))
@@ -443,9 +492,11 @@ class DeviceMesh:
         return face.astype(IntDType, copy=False), w
 
 
-class DeviceIndex:
+class DeviceIndex(Handle):
     """An ascending index made on the device (include/xugrid_amd.h: xr_index): ``n`` ids in HBM; ``to_dev`` copies them
     into an int64 device array."""
+
+    _destroy = "xr_index_destroy"
 
     def __init__(self, handle):
         self._h = handle
@@ -466,15 +517,6 @@ class DeviceIndex:
         check(_lib.load().xr_index_copy_dev(self._h, ctypes.c_void_p(ptr)))
         return out
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                _lib.load().xr_index_destroy(h)
-            except Exception:  # noqa: BLE001
-                pass
-            self._h = None
-
 
 def index_check(index_ptr, n, size):
     """-> (ids outside ``[0, size)``, ids that repeat an earlier one) of an int64 index of ``n`` ids in device memory."""
@@ -490,9 +532,11 @@ def index_mismatch(a_ptr, b_ptr, n):
     return count.value
 
 
-class DeviceMerge:
+class DeviceMerge(Handle):
     """Meshes joined on the device (include/xugrid_amd.h: xr_merge): the merged mesh, the merged id of every concatenated
     node and, per partition, the ascending local ids of its kept nodes, faces and (after ``add_edges``) edges."""
+
+    _destroy = "xr_merge_destroy"
 
     FACETS = {"node": 0, "edge": 1, "face": 2}
 
@@ -528,15 +572,6 @@ class DeviceMerge:
         out, ptr = empty_like_device(like, (self.n_node_all,), np.int64)
         check(_lib.load().xr_merge_node_inverse_copy_dev(self._h, ctypes.c_void_p(ptr)))
         return out
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                _lib.load().xr_merge_destroy(h)
-            except Exception:  # noqa: BLE001
-                pass
-            self._h = None
 
 
 def index_like_dev(a_ptr, b_ptr, n, tolerance, like=None):
@@ -586,8 +621,10 @@ def concat_last_axis_dev(arrays, like=None):
     return out
 
 
-class DeviceVoronoi:
+class DeviceVoronoi(Handle):
     """Device part of the centroidal Voronoi pre-step of a mesh (see include/xugrid_amd.h, xr_voronoi_*)."""
+
+    _destroy = "xr_voronoi_destroy"
 
     def __init__(self, mesh: DeviceMesh, add_exterior=True, add_vertices=True, skip_concave=True, generators=None):
         """``generators``: the points the cells are made of, a float64 ``(n_face, 2)`` device array (copied); None: the face
@@ -608,15 +645,6 @@ class DeviceVoronoi:
         vals = [ctypes.c_int64() for _ in range(5)]
         check(_lib.load().xr_voronoi_info(handle, *[ctypes.byref(v) for v in vals]))
         self.n_node, self.nnz, self.n_exterior_edge, self.n_interior_cell, self.max_interior_degree = (v.value for v in vals)
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                _lib.load().xr_voronoi_destroy(h)
-            except Exception:
-                pass
-            self._h = None
 
     def vertex_info(self):
         """-> (generator points at the head of the tessellation's vertices, the largest face id among them)."""
@@ -783,11 +811,13 @@ def replace_interpolated_weights(vertices, faces, face_index, weights, node_to_n
     return weights
 
 
-class DevicePoints:
+class DevicePoints(Handle):
     """Query points of a barycentric construction and their "inside the source grid" flags, in HBM
     (include/xugrid_amd.h: xr_locate_flags_begin).  The source-side kernels are deferred: the engine enqueues them when the
     Voronoi pre-step or the construction that consumes the handle next has the device to spare.  The handle keeps BOTH
     meshes alive until then."""
+
+    _destroy = "xr_points_destroy"
 
     def __init__(self, source: DeviceMesh, query: DeviceMesh = None, points=None):
         if (query is None) == (points is None):
@@ -803,15 +833,6 @@ class DevicePoints:
         self._h = handle
         self._source = source  # (the deferred kernels read both meshes: they live as long as the handle)
         self._query = query
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                _lib.load().xr_points_destroy(h)
-            except Exception:
-                pass
-            self._h = None
 
 
 def barycentric_csr(voronoi: DeviceMesh, source: DeviceMesh, vertex_face, node_to_node_map, query: DeviceMesh = None,
@@ -915,8 +936,10 @@ def _apply_dev(fn, weights, source_ptr, dtype, K, out_ptr, method_id, percentile
              ctypes.c_void_p(out_ptr)))
 
 
-class DeviceCSR:
+class DeviceCSR(Handle):
     """MatrixCSR resident in HBM: rows = target faces, columns = source faces."""
+
+    _destroy = "xr_csr_destroy"
 
     def __init__(self, handle, owner=None):
         self._h = handle
@@ -926,13 +949,8 @@ class DeviceCSR:
         self.n, self.m, self.nnz = n.value, m.value, nnz.value
 
     def __del__(self):
-        h = getattr(self, "_h", None)
-        if h and getattr(self, "_owner", None) is None:
-            try:
-                _lib.load().xr_csr_destroy(h)
-            except Exception:
-                pass
-            self._h = None
+        if getattr(self, "_owner", None) is None:  # (a matrix that belongs to a DeviceOuter goes with it)
+            super().__del__()
 
     @classmethod
     def from_arrays(cls, data, indices, indptr, n, m):
@@ -1058,10 +1076,12 @@ class DeviceCSR:
         )
 
 
-class DeviceOuter:
+class DeviceOuter(Handle):
     """Separable (rectilinear x rectilinear) weights kept as their two per-axis factors in HBM
     (include/xugrid_amd.h: xr_outer_create).  Same interface as DeviceCSR; the product matrix is only
     materialised for ``download`` / ``csr`` and for the mode / percentile reducers."""
+
+    _destroy = "xr_outer_destroy"
 
     def __init__(self, axis_y, n_source_y, axis_x, n_source_x):
         (ipy, sy, wy), (ipx, sx, wx) = _axis_arrays(axis_y, axis_x)
@@ -1076,15 +1096,6 @@ class DeviceOuter:
         n, m, nnz = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         check(_lib.load().xr_outer_info(handle, ctypes.byref(n), ctypes.byref(m), ctypes.byref(nnz)))
         self.n, self.m, self.nnz = n.value, m.value, nnz.value
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                _lib.load().xr_outer_destroy(h)
-            except Exception:
-                pass
-            self._h = None
 
     def csr(self) -> "DeviceCSR":
         """The materialised product (built once, owned by this object)."""

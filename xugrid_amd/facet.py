@@ -25,8 +25,9 @@ import numpy as np
 
 from . import _lib, connectivity, engine
 from ._lib import check
+from .engine import vp
 from .fill import resolve_dim
-from .sample import _as_data, _vp
+from .sample import _as_data
 
 FORM_IDS = {"mean": 0, "sum": 1, "min": 2, "max": 3, None: 4}  # include/xugrid_amd.h: XR_FACET_MEAN, _SUM, _MIN, _MAX, _RAW
 REDUCERS = ("mean", "sum", "min", "max")
@@ -152,9 +153,9 @@ def to_facet(grid, target, data, dim=None, reduce=None):
         width = table.width
 
         def run(in_ptr, out_ptr):
-            check(_lib.load().xr_facet_map_dev(_vp(table.ptr.ptr) if table.ptr is not None else None, _vp(table.idx.ptr),
-                                               table.n_target, table.width, table.n_source, form, _vp(in_ptr), dtype_id, K,
-                                               _vp(out_ptr)))
+            check(_lib.load().xr_facet_map_dev(vp(table.ptr.ptr) if table.ptr is not None else None,
+                                               vp(table.idx.ptr), table.n_target, table.width, table.n_source, form,
+                                               vp(in_ptr), dtype_id, K, vp(out_ptr)))
     out_shape = shape[:-1] + ((n_target, width) if reduce is None else (n_target,))
     if kind == "device":
         engine.sync_producer(a)

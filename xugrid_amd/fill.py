@@ -30,8 +30,10 @@ _STATUS_MAXITER, _STATUS_BREAKDOWN, _STATUS_NODATA = 1, 2, 3
 last_iterations = None
 
 
-class DeviceGraph:
+class DeviceGraph(engine.Handle):
     """A symmetric adjacency in HBM (include/xugrid_amd.h: xr_graph): CSR structure, the weights, component labels."""
+
+    _destroy = "xr_graph_destroy"
 
     def __init__(self, connectivity, labels=None, weights=None):
         lib = _lib.load()
@@ -76,15 +78,6 @@ class DeviceGraph:
         out = np.empty(self.n, dtype=np.int64)
         check(_lib.load().xr_graph_download(self._h, None, None, None, out.ctypes.data_as(ctypes.c_void_p)))
         return out
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                _lib.load().xr_graph_destroy(h)
-            except Exception:  # noqa: BLE001
-                pass
-            self._h = None
 
 
 def _check_square(connectivity):

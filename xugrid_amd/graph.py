@@ -23,38 +23,24 @@ from ._lib import check
 from .fill import MAX_SLICES, DeviceGraph, _check_square
 
 
-def _is_torch(obj):
-    return (type(obj).__module__ or "").startswith("torch")
-
-
-def _byte_array_info(obj):
-    """-> (device pointer, shape, 'bool' | 'uint8') for a C-contiguous one-byte device array, None for host data."""
-    if isinstance(obj, np.ndarray):
-        return None
-    if _is_torch(obj):
-        if not getattr(obj, "is_cuda", False):
-            return None
-        name = str(obj.dtype).replace("torch.", "")
-        if name not in ("bool", "uint8"):
+def _bool_info(obj):
+    """``engine.byte_array_info``; a device array of any other dtype raises."""
+    info = engine.byte_array_info(obj)
+    if info is None:
+        try:
+            other = engine.device_array_info(obj) is not None
+        except (TypeError, ValueError):  # (a device array the engine takes nowhere)
+            other = True
+        if other:
             raise TypeError("input dtype should be bool")
-        if not obj.is_contiguous():
-            raise ValueError("device arrays must be C-contiguous")
-        return int(obj.data_ptr()), tuple(int(n) for n in obj.shape), name
-    cai = getattr(obj, "__cuda_array_interface__", None)
-    if not isinstance(cai, dict):
-        return None
-    if cai["typestr"] not in ("|b1", "|u1"):
-        raise TypeError("input dtype should be bool")
-    if cai.get("strides") is not None:
-        raise ValueError("device arrays must be C-contiguous")
-    return int(cai["data"][0]), tuple(int(n) for n in cai["shape"]), "bool" if cai["typestr"] == "|b1" else "uint8"
+    return info
 
 
 def _flags(flags, n, what):
     """mask / exterior -> a uint8 (n,) device array (or None): bool arrays, index arrays (``exterior``) or device bytes."""
     if flags is None:
         return None
-    info = _byte_array_info(flags)
+    info = _bool_info(flags)
     if info is not None:
         if info[1] != (n,):
             raise ValueError(f"expected {what} of shape ({n},), received: {info[1]}")
@@ -77,7 +63,7 @@ def binary_iterate(graph: DeviceGraph, input, value, iterations=1, mask=None, ex
     if iterations < 1:
         raise ValueError(f"iterations must be at least 1, received: {iterations}")
     n = graph.n
-    info = _byte_array_info(input)
+    info = _bool_info(input)
     if info is None:
         a = np.asarray(input)
         if a.dtype != np.bool_:
@@ -99,7 +85,7 @@ def binary_iterate(graph: DeviceGraph, input, value, iterations=1, mask=None, ex
     else:
         engine.sync_producer(input)
         in_ptr = info[0]
-        if _is_torch(input):
+        if engine.is_torch(input):
             import torch
 
             out = torch.empty(shape, dtype=input.dtype, device=input.device)

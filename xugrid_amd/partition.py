@@ -16,18 +16,18 @@ the device when every grid in the list is device-resident with a manifold topolo
 import numpy as np
 
 from . import engine, sample, subset
-from .subset import FACETS, _download, _is_torch, _upload
+from .subset import FACETS
 
 ZERO = "Cannot merge partitions: zero partitions provided."
 NOT_IDENTICAL = "coordinates are not identical after sorting"
 
 
 def _first_torch(items):
-    return next((x for x in items if x is not None and _is_torch(x)), None)
+    return next((x for x in items if x is not None and engine.is_torch(x)), None)
 
 
 def _emit(dev, to_numpy):
-    return _download(dev).astype(np.int64, copy=False) if to_numpy else dev
+    return engine.download(dev).astype(np.int64, copy=False) if to_numpy else dev
 
 
 # ---- labels ---------------------------------------------------------------------------------------------------------------
@@ -40,7 +40,7 @@ def _labels_dev(labels, n=None):
             raise TypeError("labels must have integer dtype")
         dev = labels
         if dtype != np.int64:
-            if not _is_torch(labels):
+            if not engine.is_torch(labels):
                 raise TypeError("integer device labels must be int64")
             dev = labels.long()
         engine.sync_producer(labels)
@@ -88,9 +88,9 @@ def partition_by_label(grid, labels, data=None):
             continue
         by = indexes[dims[facet]]
         if engine.device_array_info(data) is None:
-            by = by if isinstance(by, np.ndarray) else _download(by)
+            by = by if isinstance(by, np.ndarray) else engine.download(by)
         elif isinstance(by, np.ndarray):
-            by = _upload(by, data)
+            by = engine.upload_like(by, data)
         out.append((sub, indexes, sample.gather_points(data, getattr(grid, f"n_{facet}"), by)))
     return out
 
@@ -217,7 +217,7 @@ def merge_partitions(grids, return_index=False, data=None, dim=None):
     if return_index:
         def emit(a):
             if isinstance(a, np.ndarray):
-                return a if to_numpy else _upload(a, like)
+                return a if to_numpy else engine.upload_like(a, like)
             return _emit(a, to_numpy)
 
         out.append({dims[f]: [emit(a) for a in indexes[f]] for f in FACETS})
@@ -227,16 +227,16 @@ def merge_partitions(grids, return_index=False, data=None, dim=None):
         if facet == "edge":
             source = np.full(merged.n_edge, -1, dtype=np.int64)
             for p, (idx, pos) in enumerate(zip(indexes["edge"], positions)):
-                idx, pos = (a if isinstance(a, np.ndarray) else _download(a) for a in (idx, pos))
+                idx, pos = (a if isinstance(a, np.ndarray) else engine.download(a) for a in (idx, pos))
                 source[pos] = idx + edge_slices[p]
         elif merge is None:
             source = indexes[facet][0]
         else:
             source = merge.index(facet, -1, like)
         if engine.device_array_info(cat) is None:
-            source = source if isinstance(source, np.ndarray) else _download(source)
+            source = source if isinstance(source, np.ndarray) else engine.download(source)
         elif isinstance(source, np.ndarray):
-            source = _upload(source, cat)
+            source = engine.upload_like(source, cat)
         out.append(sample.gather_points(cat, total, source))
     return out[0] if len(out) == 1 else tuple(out)
 
@@ -272,7 +272,7 @@ def index_like_device(xy_a, xy_b, tolerance=0.0):
     if repeats or misses:
         raise ValueError(NOT_IDENTICAL)
     host = engine.device_array_info(xy_a) is None and engine.device_array_info(xy_b) is None
-    return _download(index).astype(np.int64, copy=False) if host else index
+    return engine.download(index).astype(np.int64, copy=False) if host else index
 
 
 def _facet_coordinates(grid, facet):
@@ -294,7 +294,7 @@ def reindex_like(grid, other, data, dim=None, tolerance=0.0):
         facet = subset._data_facet(grid, data)
     index = index_like_device(_facet_coordinates(grid, facet), _facet_coordinates(other, facet), tolerance)
     if engine.device_array_info(data) is None:
-        index = index if isinstance(index, np.ndarray) else _download(index)
+        index = index if isinstance(index, np.ndarray) else engine.download(index)
     elif isinstance(index, np.ndarray):
-        index = _upload(index, data)
+        index = engine.upload_like(index, data)
     return sample.gather_points(data, getattr(grid, f"n_{facet}"), index)

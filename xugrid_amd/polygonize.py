@@ -28,12 +28,9 @@ import numpy as np
 
 from . import _lib, engine
 from ._lib import check
+from .engine import vp
 
 _DTYPE_IDS = {np.dtype(np.float64): _lib.XR_F64, np.dtype(np.float32): _lib.XR_F32, np.dtype(np.int32): _lib.XR_I32}
-
-
-def _vp(ptr):
-    return ctypes.c_void_p(int(ptr)) if ptr else None
 
 
 def _check_shape(shape, n_face):
@@ -56,12 +53,14 @@ def host_data(data, n_face):
     return out
 
 
-class DevicePolygons:
+class DevicePolygons(engine.Handle):
     """``xr_polygons``: the result of one call in HBM, with its counts."""
+
+    _destroy = "xr_polygons_destroy"
 
     def __init__(self, topology, data_ptr, dtype_id):
         handle = ctypes.c_void_p()
-        check(_lib.load().xr_polygonize_dev(topology._h, _vp(data_ptr), dtype_id, ctypes.byref(handle)))
+        check(_lib.load().xr_polygonize_dev(topology._h, vp(data_ptr), dtype_id, ctypes.byref(handle)))
         self._h = handle
         v = [ctypes.c_int64() for _ in range(6)]
         check(_lib.load().xr_polygons_info(handle, *(ctypes.byref(x) for x in v[:5])))
@@ -69,21 +68,12 @@ class DevicePolygons:
         self.n_polygon, self.n_ring, self.n_vertex, self.n_halfedge, self.label_rounds, self.readbacks = (x.value for x in v)
         self.n_face = topology.n_face
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                _lib.load().xr_polygons_destroy(h)
-            except Exception:  # noqa: BLE001
-                pass
-            self._h = None
-
     def shapes(self):
         return (((self.n_vertex, 2), np.float64), ((self.n_ring + 1,), np.int64), ((self.n_polygon + 1,), np.int64),
                 ((self.n_polygon,), np.float64), ((self.n_face,), np.int64))
 
     def copy_to(self, pointers):
-        check(_lib.load().xr_polygons_copy_dev(self._h, *(_vp(p) for p in pointers)))
+        check(_lib.load().xr_polygons_copy_dev(self._h, *(vp(p) for p in pointers)))
 
 
 def polygonize_device(like, data):

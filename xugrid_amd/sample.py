@@ -19,6 +19,7 @@ import numpy as np
 
 from . import _lib, engine
 from ._lib import XR_F32, XR_F64, check
+from .engine import vp
 from .fill import resolve_dim
 
 PointSelection = namedtuple("PointSelection", ["values", "index", "x", "y"])
@@ -30,17 +31,11 @@ FACETS = ("node", "edge", "face")
 _MESH_FACET_IDS = {"node": 0, "face": 2}  # include/xugrid_amd.h: XR_FACET_NODE, XR_FACET_FACE
 
 
-def _is_torch(obj):
-    return (type(obj).__module__ or "").startswith("torch")
-
-
-def _vp(ptr):
-    return ctypes.c_void_p(int(ptr))
-
-
-class NearestIndex:
+class NearestIndex(engine.Handle):
     """Nearest-neighbour index over a fixed set of points in HBM (include/xugrid_amd.h: xr_nn): the device counterpart
     of the reference's ``scipy.spatial.KDTree`` per facet.  The handle keeps its own copy of the coordinates."""
+
+    _destroy = "xr_nn_destroy"
 
     def __init__(self, handle):
         self._h = handle
@@ -61,7 +56,7 @@ class NearestIndex:
         if len(shape) != 2 or shape[1] != 2 or dtype != np.float64:
             raise ValueError("expected a float64 (n, 2) array of coordinates")
         handle = ctypes.c_void_p()
-        check(_lib.load().xr_nn_create_dev(_vp(ptr), shape[0], ctypes.byref(handle)))
+        check(_lib.load().xr_nn_create_dev(vp(ptr), shape[0], ctypes.byref(handle)))
         return cls(handle)
 
     @classmethod
@@ -85,22 +80,13 @@ class NearestIndex:
                 raise ValueError("expected a float64 (n_point, 2) array of points")
             engine.sync_producer(points)
             out, out_ptr = engine.empty_like_device(points, (shape[0],), np.int64)
-            check(_lib.load().xr_nn_query_dev(self._h, _vp(ptr), shape[0], max_distance, _vp(out_ptr)))
+            check(_lib.load().xr_nn_query_dev(self._h, vp(ptr), shape[0], max_distance, vp(out_ptr)))
             return out
         pts = engine._as_xy(points)
         src = engine.DeviceArray.from_host(pts)
         dst = engine.DeviceArray((pts.shape[0],), np.int64)
-        check(_lib.load().xr_nn_query_dev(self._h, _vp(src.ptr), pts.shape[0], max_distance, _vp(dst.ptr)))
+        check(_lib.load().xr_nn_query_dev(self._h, vp(src.ptr), pts.shape[0], max_distance, vp(dst.ptr)))
         return dst.download().astype(engine.IntDType, copy=False)
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                _lib.load().xr_nn_destroy(h)
-            except Exception:  # noqa: BLE001
-                pass
-            self._h = None
 
 
 class GridSample:
@@ -121,7 +107,7 @@ def _as_data(data, n):
     if info is not None:
         ptr, shape, dtype = info
         if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
-            if not _is_torch(data):
+            if not engine.is_torch(data):
                 raise TypeError(f"device data must be float64 or float32, received {dtype}")
             data = data.double()
             ptr, shape, dtype = engine.device_array_info(data)
@@ -158,12 +144,12 @@ def gather_points(data, n, index, fill_value=np.nan):
     if kind == "device":
         engine.sync_producer(a)
         out, out_ptr = engine.empty_like_device(a, out_shape)
-        check(_lib.load().xr_gather_points_dev(_vp(engine.device_array_info(a)[0]), dtype_id, K, n, _vp(idx_ptr), n_point,
-                                               fill_value, _vp(out_ptr)))
+        check(_lib.load().xr_gather_points_dev(vp(engine.device_array_info(a)[0]), dtype_id, K, n, vp(idx_ptr), n_point,
+                                               fill_value, vp(out_ptr)))
         return out
     src = engine.DeviceArray.from_host(a)
     dst = engine.DeviceArray(out_shape)
-    check(_lib.load().xr_gather_points_dev(_vp(src.ptr), dtype_id, K, n, _vp(idx_ptr), n_point, fill_value, _vp(dst.ptr)))
+    check(_lib.load().xr_gather_points_dev(vp(src.ptr), dtype_id, K, n, vp(idx_ptr), n_point, fill_value, vp(dst.ptr)))
     return dst.download()
 
 
@@ -178,14 +164,14 @@ def section_arrays(pieces, piece_segment, segments, like=None):
     if seg_of.shape[0] != n:
         raise ValueError("one segment id per piece expected")
     d_pieces, d_seg_of, d_segments = (engine.DeviceArray.from_host(a) for a in (pieces, seg_of, segments))
-    if like is not None and _is_torch(like):
+    if like is not None and engine.is_torch(like):
         mid, mid_ptr = engine.empty_like_device(like, (n, 2))
         s, s_ptr = engine.empty_like_device(like, (n,))
     else:
         mid, s = engine.DeviceArray((n, 2)), engine.DeviceArray((n,))
         mid_ptr, s_ptr = mid.ptr, s.ptr
-    check(_lib.load().xr_section_coords_dev(_vp(d_pieces.ptr), _vp(d_seg_of.ptr), n, _vp(d_segments.ptr), segments.shape[0],
-                                            _vp(mid_ptr), _vp(s_ptr)))
+    check(_lib.load().xr_section_coords_dev(vp(d_pieces.ptr), vp(d_seg_of.ptr), n, vp(d_segments.ptr), segments.shape[0],
+                                            vp(mid_ptr), vp(s_ptr)))
     if isinstance(mid, engine.DeviceArray):
         return mid.download(), s.download()
     return mid, s

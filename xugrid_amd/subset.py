@@ -23,45 +23,6 @@ REPEATED = "index contains repeated values; only subsets will result in valid UG
 FACETS = ("node", "edge", "face")
 
 
-def _is_torch(obj):
-    return (type(obj).__module__ or "").startswith("torch")
-
-
-def _upload(a, like):
-    """A host int64 array as a device array of the kind of ``like`` (None: a ``DeviceArray``)."""
-    a = np.ascontiguousarray(a, dtype=np.int64)
-    if like is not None and _is_torch(like):
-        import torch
-
-        return torch.as_tensor(a).to(like.device)
-    return engine.DeviceArray.from_host(a)
-
-
-def _download(dev):
-    if isinstance(dev, engine.DeviceArray):
-        return dev.download()
-    engine.sync_producer(dev)
-    return dev.cpu().numpy()
-
-
-def _byte_mask_info(obj):
-    """-> (device pointer, shape) when ``obj`` is a one-byte device array (a mask), else None."""
-    if _is_torch(obj):
-        if not getattr(obj, "is_cuda", False) or str(obj.dtype) not in ("torch.bool", "torch.uint8"):
-            return None
-        if not obj.is_contiguous():
-            raise ValueError("device arrays must be C-contiguous")
-        import torch
-
-        return int(obj.view(torch.uint8).data_ptr()), tuple(int(n) for n in obj.shape)
-    cai = getattr(obj, "__cuda_array_interface__", None) if not isinstance(obj, np.ndarray) else None
-    if not isinstance(cai, dict) or cai["typestr"] not in ("|b1", "|u1"):
-        return None
-    if cai.get("strides") is not None:
-        raise ValueError("device arrays must be C-contiguous")
-    return int(cai["data"][0]), tuple(int(n) for n in cai["shape"])
-
-
 def _raise_problems(problems, n):
     out_of_range, repeated = problems
     if out_of_range:
@@ -80,12 +41,12 @@ class Index:
 
     def numpy(self):
         if self.host is None:
-            self.host = _download(self.dev).astype(np.int64, copy=False)
+            self.host = engine.download(self.dev).astype(np.int64, copy=False)
         return self.host
 
     def device(self, like=None):
         if self.dev is None:
-            self.dev = _upload(self.host, like if like is not None else self.like)
+            self.dev = engine.upload_like(self.host, like if like is not None else self.like)
         return self.dev
 
     def ptr(self):
@@ -95,9 +56,9 @@ class Index:
         """The index as the caller gets it: numpy, or a device array of the kind of ``like``."""
         if to_numpy:
             return self.numpy()
-        if self.dev is not None and _is_torch(self.dev) == (like is not None and _is_torch(like)):
+        if self.dev is not None and engine.is_torch(self.dev) == (like is not None and engine.is_torch(like)):
             return self.dev
-        return _upload(self.numpy(), like)
+        return engine.upload_like(self.numpy(), like)
 
 
 def as_index(index, n, checked=True):
@@ -105,9 +66,9 @@ def as_index(index, n, checked=True):
     checked on the device (``checked``: now; else the caller's next kernel does it, ``DeviceMesh.subset``)."""
     if isinstance(index, Index):
         return index
-    mask = _byte_mask_info(index)
+    mask = engine.byte_array_info(index)
     if mask is not None:
-        ptr, shape = mask
+        ptr, shape, _ = mask
         if len(shape) != 1:
             raise ValueError("index should be 1d")
         if shape[0] != n:
@@ -125,7 +86,7 @@ def as_index(index, n, checked=True):
             raise TypeError(f"index should be bool or integer. Received: {dtype}")
         dev = index
         if dtype != np.int64:
-            if not _is_torch(index):
+            if not engine.is_torch(index):
                 raise TypeError("an integer device index must be int64")
             dev = index.long()
         engine.sync_producer(index)

@@ -19,7 +19,7 @@ _SLOTS = ("edge_node", "face_edge", "edge_face", "ff_indptr", "ff_indices", "ff_
           "exterior_edge", "exterior_face")
 
 
-class DeviceTopology:
+class DeviceTopology(engine.Handle):
     """``xr_topology`` of a ``DeviceMesh`` (which it keeps alive).  ``n_nonmanifold`` > 0 -- an edge with more than two faces
     does not fit the two columns of ``edge_face_connectivity`` -- means the handle holds nothing: the caller takes the host
     route.  Arrays are downloaded lazily as int64 numpy and kept.
@@ -29,6 +29,8 @@ class DeviceTopology:
     derives (centroids, areas, index), never ``faces_raw`` or the node coordinates.  A topology still held by the caller
     after that keeps answering: ``graph("face")`` has the mesh rebuild its centroids, at the cost of that rebuild.  The grid
     itself makes a new topology on next use."""
+
+    _destroy = "xr_topology_destroy"
 
     def __init__(self, device_mesh):
         self._mesh = device_mesh
@@ -50,15 +52,6 @@ class DeviceTopology:
     @property
     def manifold(self):
         return self.n_nonmanifold == 0
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                _lib.load().xr_topology_destroy(h)
-            except Exception:  # noqa: BLE001
-                pass
-            self._h = None
 
     # ---- lazy int64 downloads
     def _shape(self, slot):
