@@ -787,6 +787,43 @@ int xr_label_order_destroy(xr_label_order *order);
  * array (the concatenation of the partitions' data along the last axis) */
 int xr_dev_copy_columns(void *dst_dev, int64_t dst_row_bytes, const void *src_dev, int64_t src_row_bytes, int64_t rows);
 
+/* ---- periodic meshes (Ugrid2d.to_periodic, ugrid2d.py:1392-1462; to_nonperiodic, :1464-1572); xr_periodic.hip, DESIGN section
+ * 16.  Both make a NEW device mesh and keep, per UGRID dimension, the GATHER index that aligns data of the old mesh with the
+ * new one (data_new = data[..., index]).  The input mesh is only read.  XR_ERR_INVALID: a mesh without nodes.
+ *
+ * xr_periodic_wrap_dev: the right column folded onto the left one.
+ *   xmin / xmax   smallest / largest node x (every node counts, used by a face or not)
+ *   boundary      |x - xmax| <= 1e-8 + 1e-5 |xmax| is a right node, the same with xmin a left node (np.isclose).  The y of both
+ *                 sets are read back and sorted on the host; they must have one length and agree pair by pair within
+ *                 |l - r| <= 1e-8 + 1e-5 |r| (np.allclose).  Otherwise *out is NULL, problems[0] = 1 for different lengths,
+ *                 problems[1] = pairs apart, and the call still returns XR_OK: the caller words the exception.
+ *   nodes         in a working copy every right node has x = xmin; rows of it that compare equal as doubles are one node (the
+ *                 key table of xr_merge_meshes_dev).  The first occurrence is kept, kept nodes keep their order and their
+ *                 ORIGINAL coordinates, bit for bit: a right node that comes before its left twin keeps x = xmax.
+ *   faces         every real slot through the old -> new node map; a fill slot stays -1.
+ * Read-backs: the bounds, the two boundary counts, the boundary y, the number of kept nodes.
+ *
+ * xr_periodic_unwrap_dev: the seam cut open again.  half = 0.5 (xright - xleft) of the node bounds; slot (f, k) is periodic when
+ * (max x over the real slots of f) - x > half; the distinct nodes of periodic slots, ascending, are appended as (xmax, y) and
+ * the periodic slots name the copies.  Old nodes keep their ids and coordinates.  Read-backs: the bounds, the number of new nodes.
+ *
+ * xr_periodic_edges_dev: the edge index, for the DERIVED edges of both meshes (their xr_topology, both manifold).  After a wrap
+ * index[e] is the lowest old edge whose node pair, through the node map, is new edge e; after an unwrap the old edge of the pair
+ * (map(a), map(b)) of new edge e.  *misses: new edges without an old one (the index is then not handed out).  One read-back.
+ *
+ * xr_periodic_info: n_index[3], the length of the node / edge / face index (edge: -1 before xr_periodic_edges_dev).
+ * xr_periodic_index_copy_dev: facet 0 nodes, 1 edges, 2 faces (0 .. n_face - 1) -> int64 in device memory.
+ * xr_periodic_node_inverse_copy_dev (after a wrap only): the new id of every old node, int64[n_node of the old mesh]. */
+typedef struct xr_periodic xr_periodic;
+int xr_periodic_wrap_dev(xr_mesh *mesh, xr_periodic **out, int64_t *problems);
+int xr_periodic_unwrap_dev(xr_mesh *mesh, double xmax, xr_periodic **out);
+int xr_periodic_edges_dev(xr_periodic *periodic, const xr_topology *old_topology, const xr_topology *new_topology, int64_t *misses);
+int xr_periodic_info(const xr_periodic *periodic, int64_t *n_index);
+int xr_periodic_take_mesh(xr_periodic *periodic, xr_mesh **mesh);
+int xr_periodic_index_copy_dev(const xr_periodic *periodic, int facet, int64_t *out_dev);
+int xr_periodic_node_inverse_copy_dev(const xr_periodic *periodic, int64_t *out_dev);
+int xr_periodic_destroy(xr_periodic *periodic);
+
 /* ---- raw HBM helpers for hosts that do not bring their own allocator -------------------- */
 int xr_dev_alloc(int64_t bytes, void **ptr_out);
 int xr_dev_free(void *ptr);

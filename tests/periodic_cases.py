@@ -1,0 +1,226 @@
+"""
+Yardsticks and cases of the periodic tests (tests/test_periodic_cpu.py, tests/test_gpu_periodic.py): numpy restatements of
+``to_periodic`` and ``to_nonperiodic``, written from the rule with ``np.isclose``, ``np.allclose``,
+``np.unique(axis=0, return_index=True, return_inverse=True)`` and ``np.searchsorted``, and pinned to what the reference's own
+methods return in tests/golden/periodic_known.json; the meshes the tests run on.
+"""
+import hashlib
+import json
+import os
+import warnings
+
+import numpy as np
+
+import subset_cases as sc
+from xugrid_amd import connectivity, meshgen
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+Y_MISMATCH = "y-coordinates of the left and right boundaries do not match"
+NO_COUNTERPART = "Cannot map edge-associated data onto the non-periodic grid"
+
+
+def known():
+    with open(os.path.join(HERE, "golden", "periodic_known.json")) as f:
+        return json.load(f)
+
+
+def equals_known(got, want):
+    """``got`` is the recorded array ``want``, bit for bit: the values themselves, or for the large case their shape, dtype and
+    the SHA-256 of their bytes (tests/golden/gen_periodic.py)."""
+    if isinstance(want, dict):
+        got = np.ascontiguousarray(got, dtype=want["dtype"])
+        return list(got.shape) == want["shape"] and hashlib.sha256(got.tobytes()).hexdigest() == want["sha256"]
+    got = np.asarray(got)
+    want = np.array(want, dtype=np.float64 if got.dtype.kind == "f" else np.int64).reshape(got.shape if np.size(want) == got.size else -1)
+    return got.shape == want.shape and (same_bits(got, want) if got.dtype.kind == "f" else bool(np.array_equal(got, want)))
+
+
+# ---- restatements ---------------------------------------------------------------------------------------------------------
+def host_edges(faces):
+    if len(faces) == 0:
+        return np.zeros((0, 2), dtype=np.int64)
+    return connectivity.edge_connectivity(np.asarray(faces, dtype=np.intp))[0].astype(np.int64)
+
+
+def _keys(rows, width):
+    return rows[:, 0] * width + rows[:, 1]
+
+
+def to_periodic(xy, faces, edges=True):
+    """-> dict(xy, faces, node_index, node_inverse, face_index, edge_index, edges) of the periodic grid (``edges=False``: without
+    the last two)."""
+    xy, faces = np.asarray(xy, dtype=np.float64).reshape(-1, 2), np.asarray(faces, dtype=np.int64)
+    xmin, xmax = xy[:, 0].min(), xy[:, 0].max()
+    is_right, is_left = np.isclose(xy[:, 0], xmax), np.isclose(xy[:, 0], xmin)
+    left, right = np.sort(xy[is_left, 1]), np.sort(xy[is_right, 1])
+    if left.shape != right.shape or not np.allclose(left, right):
+        raise ValueError(Y_MISMATCH)
+    work = xy.copy()
+    work[is_right, 0] = xmin
+    _, first, inverse = np.unique(work, axis=0, return_index=True, return_inverse=True)
+    node_index = np.sort(first)  # the kept nodes keep their order
+    node_inverse = np.searchsorted(node_index, first[inverse.ravel()]).astype(np.int64)
+    new_faces = np.where(faces == -1, -1, node_inverse[faces])  # a fill slot stays -1
+    out = dict(xy=xy[node_index], faces=new_faces, node_index=node_index.astype(np.int64), node_inverse=node_inverse,
+               face_index=np.arange(len(faces), dtype=np.int64))
+    if not edges:
+        return out
+    # edges: both grids derive their own; index[e] = the lowest old edge whose pair, through the node map, is new edge e
+    old_edges, new_edges = host_edges(faces), host_edges(new_faces)
+    width = max(len(xy), 1)
+    mapped, lowest = np.unique(_keys(np.sort(node_inverse[old_edges], axis=1), width), return_index=True)
+    assert np.array_equal(mapped, _keys(new_edges, width))  # the mapped old edges ARE the new grid's edges
+    return dict(out, edge_index=lowest.astype(np.int64), edges=new_edges)
+
+
+def to_nonperiodic(xy, faces, xmax, edges=True):
+    """-> dict(xy, faces, node_index, face_index, edge_index, edges) of the non-periodic grid (``edges=False``: without the last
+    two)."""
+    xy, faces = np.asarray(xy, dtype=np.float64).reshape(-1, 2), np.asarray(faces, dtype=np.int64)
+    n = len(xy)
+    half = 0.5 * (xy[:, 0].max() - xy[:, 0].min())
+    x = np.where(faces == -1, np.nan, xy[faces, 0])
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        top = np.nanmax(x, axis=1)
+    is_periodic = (top[:, np.newaxis] - x) > half
+    uniques, rank = np.unique(faces[is_periodic], return_inverse=True)
+    new_xy = np.concatenate([xy, np.column_stack([np.full(uniques.size, float(xmax)), xy[uniques, 1]])])
+    new_faces = faces.copy()
+    new_faces[is_periodic] = rank.ravel() + n
+    node_index = np.concatenate([np.arange(n), uniques]).astype(np.int64)
+    out = dict(xy=new_xy, faces=new_faces, node_index=node_index, face_index=np.arange(len(faces), dtype=np.int64))
+    if not edges:
+        return out
+    old_edges, new_edges = host_edges(faces), host_edges(new_faces)
+    width = max(len(new_xy), 1)
+    old_keys, wanted = _keys(old_edges, width), _keys(np.sort(node_index[new_edges], axis=1), width)
+    position = np.clip(np.searchsorted(old_keys, wanted), 0, max(len(old_keys) - 1, 0))
+    if not np.array_equal(old_keys[position], wanted):
+        raise ValueError(NO_COUNTERPART)
+    return dict(out, edge_index=position.astype(np.int64), edges=new_edges)
+
+
+# ---- meshes: name -> (node_xy, faces, xmax of to_nonperiodic) -----------------------------------------------------------------
+def quads(nx, ny):
+    return meshgen.quad_mesh(np.arange(nx + 1.0), np.arange(ny + 1.0))
+
+
+def quads32():
+    return quads(3, 2) + (3.0,)
+
+
+def quads32_reversed():
+    """The node numbering reversed: every right node comes before its left twin, so the kept nodes keep x = xmax."""
+    xy, faces = quads(3, 2)
+    return xy[::-1].copy(), len(xy) - 1 - faces, 3.0
+
+
+def tri43():
+    xy, faces = quads(4, 3)
+    return xy, np.concatenate([faces[:, [0, 1, 2]], faces[:, [0, 2, 3]]], axis=1).reshape(-1, 3), 4.0
+
+
+def shuffled():
+    xy, faces, xmax = tri43()
+    rng = np.random.default_rng(41)
+    order = rng.permutation(len(xy))  # new node k is old node order[k]
+    return xy[order], np.argsort(order)[faces][rng.permutation(len(faces))], xmax
+
+
+def lon():
+    """Longitudes -180 .. 180 with the right column at 180 - 1e-4: close to the largest x, and merged because it is SET to xmin."""
+    xy, faces = meshgen.quad_mesh(np.linspace(-180.0, 180.0, 7), np.linspace(-60.0, 60.0, 4))
+    xy[xy[:, 0] == 180.0, 0] = 180.0 - 1e-4
+    return xy, faces, 180.0
+
+
+def near_y():
+    """One right y is off by 1e-9: np.allclose passes, the rows differ, nothing is merged there."""
+    xy, faces = quads(3, 2)
+    xy[7, 1] += 1e-9  # node 7 = (3, 1)
+    return xy, faces, 3.0
+
+
+def dup():
+    """The interior node (1, 1) is stored twice (ids 5 and 12): np.unique merges the pair too."""
+    xy, faces = quads(3, 2)
+    xy = np.concatenate([xy, xy[5:6]])
+    faces = faces.copy()
+    faces[4][faces[4] == 5] = 12
+    return xy, faces, 3.0
+
+
+def big():
+    """64 x 40 quads: 2665 nodes, 2560 faces -- past one 2048-element scan tile, ten blocks."""
+    return quads(64, 40) + (64.0,)
+
+
+def mixed():
+    """Quads and triangles in a 4-wide table: faces 0 and 7 (the one at the seam) of 4 x 2 quads split in two."""
+    xy, faces = quads(4, 2)
+    rows = []
+    for f, (a, b, c, d) in enumerate(faces.tolist()):
+        rows += [[a, b, c, -1], [a, c, d, -1]] if f in (0, 7) else [[a, b, c, d]]
+    return xy, np.array(rows, dtype=np.int64), 4.0
+
+
+MESHES = {"quads32": quads32, "quads32_reversed": quads32_reversed, "tri43": tri43, "shuffled": shuffled, "lon": lon, "near_y": near_y,
+          "dup": dup, "big": big, "mixed": mixed}
+DENSE_CASES = tuple(n for n in MESHES if n != "mixed")  # (recorded from the reference; fill slots never go there)
+# the round trip gives the mesh back where every left node comes before its right twin (not in "shuffled": a right node that
+# comes first keeps x = xmax in the periodic grid, the reproduced quirk of DESIGN section 7)
+CLEAN_CASES = ("quads32", "tri43", "lon", "big")
+SLACK_CASES = ("quads32", "shuffled", "dup", "big")
+_MADE, _EXPECTED = {}, {}
+
+
+def symmetric():
+    """The two triangles of the reference's comment (ugrid2d.py:1515-1529): a periodic grid of three nodes whose faces share
+    all three edges.  Both faces reach node 0 across more than half the domain, so both name its copy."""
+    return np.array([[0.0, 0.0], [1.0, 0.0], [1.0, 1.0]]), np.array([[0, 1, 2], [1, 0, 2]], dtype=np.int64), 2.0
+
+
+def mesh(name):
+    if name not in _MADE:
+        xy, faces, xmax = MESHES[name]()
+        _MADE[name] = (np.ascontiguousarray(xy, dtype=np.float64), np.ascontiguousarray(faces, dtype=np.int64), float(xmax))
+    return _MADE[name]
+
+
+def expected(name):
+    """-> (the periodic grid of the mesh, the non-periodic grid of THAT grid): both directions of every case."""
+    if name not in _EXPECTED:
+        xy, faces, xmax = mesh(name)
+        wrapped = to_periodic(xy, faces)
+        _EXPECTED[name] = wrapped, to_nonperiodic(wrapped["xy"], wrapped["faces"], xmax)
+    return _EXPECTED[name]
+
+
+# ---- assertions shared by tests/test_gpu_periodic.py and tests/periodic_worker_gpu.py ----------------------------------------
+def to_numpy(a):
+    return sc.to_numpy(a)
+
+
+def same_bits(a, b):
+    """Equal bit for bit: -0.0 does not equal 0.0."""
+    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
+    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
+
+
+def assert_grid(grid, e):
+    assert grid.n_node == len(e["xy"]) and grid.n_face == len(e["faces"])
+    assert grid.n_max_node_per_face == e["faces"].shape[1]
+    assert np.array_equal(grid.face_node_connectivity, e["faces"])
+    assert same_bits(grid.node_coordinates, e["xy"])
+    assert np.array_equal(grid.edge_node_connectivity, e["edges"])
+
+
+def assert_indexes(grid, indexes, e, kind_of=None):
+    assert set(indexes) == {grid.node_dimension, grid.edge_dimension, grid.face_dimension}
+    for dim, key in ((grid.node_dimension, "node_index"), (grid.edge_dimension, "edge_index"), (grid.face_dimension, "face_index")):
+        got = indexes[dim]
+        if kind_of is not None:
+            assert isinstance(got, kind_of), (dim, type(got))
+        got = to_numpy(got)
+        assert got.dtype == np.int64 and np.array_equal(got, e[key]), (dim, got, e[key])

@@ -190,6 +190,14 @@ SIGNATURES = {
     "xr_label_order_copy_dev": (c_int, [vp, c_i64, c_i64, vp]),
     "xr_label_order_destroy": (c_int, [vp]),
     "xr_dev_copy_columns": (c_int, [vp, c_i64, vp, c_i64, c_i64]),
+    "xr_periodic_wrap_dev": (c_int, [vp, p_vp, p_i64]),
+    "xr_periodic_unwrap_dev": (c_int, [vp, c_f64, p_vp]),
+    "xr_periodic_edges_dev": (c_int, [vp, vp, vp, p_i64]),
+    "xr_periodic_info": (c_int, [vp, p_i64]),
+    "xr_periodic_take_mesh": (c_int, [vp, p_vp]),
+    "xr_periodic_index_copy_dev": (c_int, [vp, c_int, vp]),
+    "xr_periodic_node_inverse_copy_dev": (c_int, [vp, vp]),
+    "xr_periodic_destroy": (c_int, [vp]),
     "xr_dev_alloc": (c_int, [c_i64, p_vp]),
     "xr_dev_free": (c_int, [vp]),
     "xr_dev_upload": (c_int, [vp, vp, c_i64]),

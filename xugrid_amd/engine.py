@@ -574,6 +574,58 @@ class DeviceMerge(Handle):
         return out
 
 
+class DevicePeriodic(Handle):
+    """A mesh converted to or from its periodic form on the device (include/xugrid_amd.h: xr_periodic): the new mesh and, per
+    UGRID dimension, the gather index that aligns data of the old mesh with it.  ``wrap`` returns ``(None, problems)`` when the
+    left and right boundaries do not match: ``problems = (the counts differ, pairs of y apart)``."""
+
+    _destroy = "xr_periodic_destroy"
+
+    FACETS = {"node": 0, "edge": 1, "face": 2}
+
+    def __init__(self, handle, mesh, wrapped):
+        self._h, self._mesh, self.wrapped = handle, mesh, wrapped  # (the source mesh is kept alive for the edges)
+
+    @classmethod
+    def wrap(cls, mesh):
+        handle, problems = ctypes.c_void_p(), (ctypes.c_int64 * 2)()
+        check(_lib.load().xr_periodic_wrap_dev(mesh._h, ctypes.byref(handle), problems))
+        if not handle:
+            return None, (int(problems[0]), int(problems[1]))
+        return cls(handle, mesh, True), (0, 0)
+
+    @classmethod
+    def unwrap(cls, mesh, xmax):
+        handle = ctypes.c_void_p()
+        check(_lib.load().xr_periodic_unwrap_dev(mesh._h, float(xmax), ctypes.byref(handle)))
+        return cls(handle, mesh, False)
+
+    def take_mesh(self) -> "DeviceMesh":
+        handle = ctypes.c_void_p()
+        check(_lib.load().xr_periodic_take_mesh(self._h, ctypes.byref(handle)))
+        return DeviceMesh._from_handle(handle)
+
+    def add_edges(self, old_topology, new_topology):
+        """The edge index from the two device topologies (both manifold) -> new edges without an old one (0: the index exists)."""
+        misses = ctypes.c_int64()
+        check(_lib.load().xr_periodic_edges_dev(self._h, old_topology._h, new_topology._h, ctypes.byref(misses)))
+        return misses.value
+
+    def index(self, facet, like=None):
+        """int64 device array of the kind of ``like``: for every node, edge or face of the new mesh the one of the old mesh."""
+        sizes = (ctypes.c_int64 * 3)()
+        check(_lib.load().xr_periodic_info(self._h, sizes))
+        out, ptr = empty_like_device(like, (max(int(sizes[self.FACETS[facet]]), 0),), np.int64)
+        check(_lib.load().xr_periodic_index_copy_dev(self._h, self.FACETS[facet], ctypes.c_void_p(ptr)))
+        return out
+
+    def node_inverse(self, like=None):
+        """After ``wrap``: the new id of every old node."""
+        out, ptr = empty_like_device(like, (self._mesh.n_node,), np.int64)
+        check(_lib.load().xr_periodic_node_inverse_copy_dev(self._h, ctypes.c_void_p(ptr)))
+        return out
+
+
 def index_like_dev(a_ptr, b_ptr, n, tolerance, like=None):
     """include/xugrid_amd.h: xr_index_like_dev on two float64 ``(n, 2)`` device pointers -> (int64 ``(n,)`` device array of the
     kind of ``like``, keys that repeat, rows of b without a partner)."""

@@ -544,6 +544,29 @@ class Ugrid2d:
 
         return partition.reindex_like(self, other, data, dim, tolerance)
 
+    # ---- periodic grids converted on the device (xugrid_amd/periodic.py, csrc/xr_periodic.hip)
+    def to_periodic(self, data=None, dim=None, return_index=False):
+        """The grid with its rightmost nodes folded onto its leftmost ones (ugrid2d.py:1392-1462): nodes with ``x`` close to
+        the grid's largest ``x`` (``np.isclose``) count as ``x = xmin``, nodes that then coincide become one, the first of them
+        is kept with the coordinates it HAS (a right node that comes before its left twin keeps ``x = xmax``, as in the
+        reference), faces are renumbered with their fill slots left at ``-1``.  The sorted ``y`` of the left and the right
+        boundary must be ``np.allclose``, else ``ValueError``.  -> the periodic grid, of this grid's kind; ``return_index``:
+        also ``{node_dimension: ..., edge_dimension: ..., face_dimension: ...}``, int64 gather indexes with
+        ``data_new = data[..., index]``; ``data`` ``(..., n)`` on one facet (found by its size, or named by ``dim``): also that
+        selection.  See xugrid_amd/periodic.py for the kinds of the results."""
+        from . import periodic
+
+        return periodic.to_periodic(self, data, dim, return_index)
+
+    def to_nonperiodic(self, xmax, data=None, dim=None, return_index=False):
+        """The periodic grid cut open at its seam (ugrid2d.py:1464-1572): a node that a face reaches across more than half the
+        width of the grid is copied to ``(xmax, y)``, the copies are appended behind the grid's nodes in ascending order of
+        their originals, and those face slots name the copies.  Returns as ``to_periodic``; edge data of an edge on the seam is
+        repeated on both sides."""
+        from . import periodic
+
+        return periodic.to_nonperiodic(self, xmax, data, dim, return_index)
+
     # ---- meshes and per-face geometry derived on the device (csrc/xr_mesh.hip: triangulation, circumcenters, perimeter,
     # face bounds; csrc/xr_voronoi.hip: the tessellations)
     _device_resident = False  # True: the mesh exists in HBM only; derived grids stay there and indices are device arrays
