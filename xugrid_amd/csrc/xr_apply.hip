@@ -3074,11 +3074,11 @@ int xr_reduce_partial_rows_dev(int method, const double *rows_dev, const int64_t
         XR_REQUIRE(indptr_dev && out_dev, XR_ERR_INVALID, "xr_reduce_partial_rows_dev: NULL argument");
         if (K == 1 && (reinterpret_cast<uintptr_t>(rows_dev) & 15) == 0) {
             with_decomposable(method, [&](auto m) {
-                XR_LAUNCH("reduce_partial_rows", k_reduce_partial_rows_k1<decltype(m)::value>, dim3(div_up(n_targets, 256)),
+                XR_LAUNCH("reduce_partial_rows_k1", k_reduce_partial_rows_k1<decltype(m)::value>, dim3(div_up(n_targets, 256)),
                           dim3(256), 0, rows_dev, indptr_dev, order_dev, n_targets, out_dev);
             });
         } else if (K >= 8)
-            XR_LAUNCH("reduce_partial_rows", k_reduce_partial_rows_t, dim3(div_up(n_targets, 64), (unsigned)std::min<int64_t>(div_up(K, 32), 64)),
+            XR_LAUNCH("reduce_partial_rows_t", k_reduce_partial_rows_t, dim3(div_up(n_targets, 64), (unsigned)std::min<int64_t>(div_up(K, 32), 64)),
                       dim3(256), 0, method, rows_dev, indptr_dev, order_dev, n_targets, K, out_dev);
         else
             XR_LAUNCH("reduce_partial_rows", k_reduce_partial_rows, dim3(div_up(n_targets * K, 256)), dim3(256), 0, method,
