@@ -574,6 +574,39 @@ int xr_graph_components_dev(const xr_graph *graph, int64_t *labels_dev, int64_t 
 int xr_graph_binary_iterate_dev(const xr_graph *graph, const uint8_t *in_dev, uint8_t *out_dev, int64_t K, int value,
                                 int64_t iterations, const uint8_t *mask_dev, const uint8_t *exterior_dev);
 
+/* ---- filling NaN entries of a network along its edges (xugrid Ugrid1d._nearest_interpolate: multi-source dijkstra) ---- */
+/* The graph of a network (node_xy_dev float64 [n_node, 2], edges_dev int64 [n_edge, 2], device pointers) for the nearest calls below.
+ * facet XR_FACET_NODE: the reference's node_node_connectivity over ALL n_node nodes (unused nodes: empty rows), columns ascending,
+ *   data = length of the joining edge.
+ * facet XR_FACET_EDGE: the reference's edge_edge_connectivity (every OTHER edge sharing a node, each once, columns ascending),
+ *   data = 0.5 * (length[i] + length[j]).
+ * length = sqrt(dx*dx + dy*dy), uncontracted (the unit is compiled with the Makefile's -ffp-contract=off like the rest).
+ * problems[0] = self-loops (a == b), problems[1] = edges repeating an earlier edge's node pair in either orientation.
+ * With any problem *out is NULL and the call is still XR_OK.  nnz >= 2^31 is XR_ERR_LIMIT.  Labels by the existing label kernels.
+ * An edge that names a node outside [0, n_node) is XR_ERR_INVALID.  (XR_FACET_* are defined further down.) */
+int xr_network_graph_dev(const double *node_xy_dev, int64_t n_node, const int64_t *edges_dev, int64_t n_edge, int facet,
+                         xr_graph **out, int64_t *problems);
+/* Per slice k and vertex v the state is (d, s).  Sources start at (0.0, v); every other vertex starts at (inf, none).
+ * The result is the fixed point of
+ *     (d_v, s_v) = lexicographic min of the start value and, over the CSR entries (v, u, w), of (fl(d_u + w), s_u),
+ *                  keeping only candidates with fl(d_u + w) <= limit.
+ * limit is inclusive, as scipy's; INFINITY means none.
+ * is_source_dev uint8 [K,n]; distance_dev float64 [K,n] (inf where unreached), source_dev int64 [K,n] (-1 where unreached); either
+ * may be NULL.
+ * The host reads one "changed" word per `chunk` rounds (<= 0: default), as the CG does.  rounds_out gets the rounds run (the one that
+ * found nothing to change included).
+ * The graph must carry weights, all finite and >= 0.  Zero weights are allowed.
+ * The rounds are pulls whose results go to a second buffer, a block sweeping its own vertices several times within a round (DESIGN
+ * section 17): no state is read while it is written, the same bits on every run.  A vertex takes the minimum of its previous state
+ * and the candidates, so states only decrease and the rounds end; the distances are Dijkstra's bits, the source is the lowest id
+ * among equidistant ones. */
+int xr_graph_nearest_dev(const xr_graph *graph, const uint8_t *is_source_dev, int64_t K, double limit, int64_t chunk,
+                         double *distance_dev, int64_t *source_dev, int64_t *rounds_out);
+/* Sources are the non-NaN entries of in_dev [K,n].  out = in where valid, in[s_v] where reached, NaN elsewhere.
+ * A slice without NaN is copied.  A slice without any value is XR_ERR_INVALID "All values are NA.", as xr_nearest_fill_dev. */
+int xr_graph_nearest_fill_dev(const xr_graph *graph, const double *in_dev, double *out_dev, int64_t K, double limit,
+                              int64_t chunk, int64_t *rounds_out);
+
 /* ---- moving data between the facets of a mesh (xugrid UgridDataArray.ugrid.to_node / to_edge / to_face,
  * core/dataarray_accessor.py:300-416) ------------------------------------------------------------------------------- */
 /* The table is {target}_{source}_connectivity, int32: dense [n_target, width] with -1 fill (face_node, face_edge, edge_node,

@@ -133,6 +133,9 @@ SIGNATURES = {
     "xr_graph_destroy": (c_int, [vp]),
     "xr_graph_laplace_fill_dev": (c_int, [vp, vp, vp, c_i64, c_int, c_f64, c_f64, c_i64, c_i64, vp, vp]),
     "xr_nearest_fill_dev": (c_int, [vp, c_i64, vp, vp, c_i64, c_f64]),
+    "xr_network_graph_dev": (c_int, [vp, c_i64, vp, c_i64, c_int, p_vp, p_i64]),
+    "xr_graph_nearest_dev": (c_int, [vp, vp, c_i64, c_f64, c_i64, vp, vp, p_i64]),
+    "xr_graph_nearest_fill_dev": (c_int, [vp, vp, vp, c_i64, c_f64, c_i64, p_i64]),
     "xr_topology_create": (c_int, [vp, p_vp]),
     "xr_topology_info": (c_int, [vp, p_i64, p_i64, p_i64, p_i64, p_i64]),
     "xr_topology_long_nodes": (c_int, [vp, p_i64]),

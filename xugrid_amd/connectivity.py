@@ -118,6 +118,22 @@ def node_node_connectivity(edge_node_connectivity, n_node):
     return _symmetric_csr(edge_node_connectivity[:, 0], edge_node_connectivity[:, 1], edge, n_node)
 
 
+def edge_edge_connectivity(edge_node_connectivity, node_edge_connectivity):
+    """Edges that share a node (xugrid/ugrid/connectivity.py:534-551): row i holds every OTHER edge at either node of edge i,
+    columns ascending; data = the shared node (coo -> csr sums the nodes where two edges share both)."""
+    n_edge = len(edge_node_connectivity)
+    node = np.asarray(edge_node_connectivity).ravel()  # the two nodes of edge 0, of edge 1, ...
+    ptr = node_edge_connectivity.indptr
+    count = (ptr[1:] - ptr[:-1])[node]  # edges at each of them
+    # ... and which: the node -> edge rows ptr[node] .. ptr[node] + count, one after the other
+    at = np.repeat(ptr[node] - (np.cumsum(count) - count), count) + np.arange(count.sum())
+    other = node_edge_connectivity.indices[at]
+    own = np.repeat(np.arange(n_edge, dtype=IntDType), count.reshape(-1, 2).sum(axis=1))
+    shared = np.repeat(node, count)
+    keep = own != other
+    return sparse.coo_matrix((shared[keep], (own[keep], other[keep])), shape=(n_edge, n_edge)).tocsr()
+
+
 def index_like_device(xy_a, xy_b, tolerance=0.0):
     """``index_like`` (xugrid/ugrid/connectivity.py:38-61) through the device key table: the index that turns ``xy_a`` into
     ``xy_b``.  See ``xugrid_amd.partition.index_like_device`` (imported on use: that module needs the engine)."""

@@ -20,16 +20,6 @@
 #include "xr_objects.h"
 #include "xr_topology.h"
 
-struct xr_graph {
-    int64_t n = 0, nnz = 0;
-    xr::DevBuf<int32_t> indptr;  // [n+1]
-    xr::DevBuf<int32_t> indices; // [nnz] ascending per row
-    xr::DevBuf<double> data;     // [nnz] weights (1.0 when the caller gave none)
-    xr::DevBuf<int32_t> labels;  // [n] connected component: the smallest node id of the component
-    bool has_data = false;
-    int64_t label_rounds = 0; // rounds of k_label_round the labelling took (0: labels given by the caller)
-};
-
 namespace xr {
 
 enum FillStatus : int { FILL_CONVERGED = 0, FILL_MAXITER = 1, FILL_BREAKDOWN = 2, FILL_NODATA = 3 };
@@ -328,7 +318,7 @@ static void nearest_group(const double *xy, int64_t n, const double *in, double 
 }
 
 // labels = the smallest member id of every component: rounds of k_label_round until none lowers a label
-static void label_components(xr_graph *g) {
+void label_components(xr_graph *g) {
     const int64_t n = g->n;
     if (n <= 0) return;
     DevBuf<int32_t> changed(1);

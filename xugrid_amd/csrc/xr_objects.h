@@ -1,4 +1,4 @@
-// xr_objects.h -- the two device-resident handle types behind the C ABI.
+// xr_objects.h -- the device-resident handle types behind the C ABI that more than one unit reads.
 #pragma once
 #include <memory>
 #include <vector>
@@ -168,7 +168,20 @@ struct xr_outer {
     ~xr_outer() { delete csr; }
 };
 
+// A symmetric adjacency in HBM (xr_fill.hip: the Laplace fill and the graph operations; xr_netfill.hip: the network graphs and
+// the shortest-path nearest).
+struct xr_graph {
+    int64_t n = 0, nnz = 0;
+    xr::DevBuf<int32_t> indptr;  // [n+1]
+    xr::DevBuf<int32_t> indices; // [nnz] ascending per row
+    xr::DevBuf<double> data;     // [nnz] weights (1.0 when the caller gave none)
+    xr::DevBuf<int32_t> labels;  // [n] connected component: the smallest node id of the component
+    bool has_data = false;
+    int64_t label_rounds = 0; // rounds of k_label_round the labelling took (0: labels given by the caller)
+};
+
 namespace xr {
+void label_components(xr_graph *g); // labels = the smallest member id of every component (xr_fill.hip)
 void mesh_prepare(xr_mesh *mesh, bool want_fxy = true, bool stats_on_side = false, bool allow_sampled = false); // stats_on_side: the reduction of the
     // statistics (only the HOST reads them) leaves the main stream: kernels queued behind the prepare pass do not wait for it
 const double *mesh_area(xr_mesh *mesh); // connectivity.area in the caller's face order (computed on first use)

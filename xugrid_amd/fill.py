@@ -1,7 +1,8 @@
 """
 Filling the NaN entries of mesh data on the device: ``laplace_interpolate`` (xugrid/ugrid/interpolate.py:207-330) and the
 nearest fill of ``UgridDataArrayAccessor.interpolate_na`` (xugrid/core/dataarray_accessor.py:761-886).  Kernels in
-``csrc/xr_fill.hip``.
+``csrc/xr_fill.hip``.  The nearest fill of a network along its edges (xugrid/ugrid/ugrid1d.py ``_nearest_interpolate``: a
+multi-source dijkstra) is ``network_graph`` / ``network_fill`` / ``network_nearest``, kernels in ``csrc/xr_netfill.hip``.
 
 Arrays in, arrays out, like ``Regridder.regrid``: ``data`` is ``(..., n)``; the leading dims are K slices filled
 independently (the reference's ``apply_ufunc(vectorize=True)``).  K is unbounded: the kernels take at most 65 535 slices
@@ -28,6 +29,10 @@ _STATUS_MAXITER, _STATUS_BREAKDOWN, _STATUS_NODATA = 1, 2, 3
 
 # what the last fill reported per slice (tests and profiles read it: iteration counts of the device CG)
 last_iterations = None
+NET_CHUNK = 32  # rounds of the network nearest enqueued between two reads of the "changed" words
+_NETWORK_FACET_IDS = {"node": 0, "edge": 1}  # include/xugrid_amd.h: XR_FACET_NODE, XR_FACET_EDGE
+# rounds the last network fill / network nearest ran (the largest count of its tiles of slices; None: nothing ran)
+last_rounds = None
 
 
 class DeviceGraph(engine.Handle):
@@ -59,6 +64,22 @@ class DeviceGraph(engine.Handle):
         self._h = handle
         self.n, self.nnz, self.has_weights = n.value, nnz.value, has_weights
         return self
+
+    @classmethod
+    def network(cls, node_xy, edges, facet):
+        """The node graph (weights: the edge lengths) or the edge graph (half of the two edge lengths) of a network, built on
+        the device from ``node_xy`` (n_node, 2) and ``edges`` (n_edge, 2) (include/xugrid_amd.h: xr_network_graph_dev)."""
+        xy = engine.DeviceArray.from_host(np.ascontiguousarray(node_xy, dtype=np.float64).reshape(-1, 2))
+        ed = engine.DeviceArray.from_host(np.ascontiguousarray(edges, dtype=np.int64).reshape(-1, 2))
+        handle, problems = ctypes.c_void_p(), (ctypes.c_int64 * 2)()
+        check(_lib.load().xr_network_graph_dev(engine.vp(xy.ptr), xy.shape[0], engine.vp(ed.ptr), ed.shape[0],
+                                               _NETWORK_FACET_IDS[facet], ctypes.byref(handle), problems))
+        if problems[0] or problems[1]:
+            raise ValueError(
+                f"the network has {problems[0]} self-loops (edges from a node to itself) and {problems[1]} edges that repeat "
+                "the node pair of an earlier edge; distances along the network need every node pair at most once"
+            )
+        return cls.from_handle(handle, True)
 
     def label_rounds(self):
         """Rounds of minimum-label propagation the component labelling took (0: the labels were given)."""
@@ -190,6 +211,76 @@ def nearest_fill(xy_dev: "engine.DeviceArray", data, max_distance=None):
     return _run(data, n, launch)
 
 
+def _limit(max_distance):
+    limit = np.inf if max_distance is None else float(max_distance)
+    if not limit >= 0.0:
+        raise ValueError("max_distance must be non-negative")
+    return limit
+
+
+def network_graph(grid, facet):
+    """The device graph of ``grid`` (a ``Ugrid1d``) for ``facet`` "node" or "edge", built on first use and kept with the grid's
+    other device caches (``DeviceGraph.network``)."""
+    return grid._fill().network_graph(grid, facet)
+
+
+def network_fill(graph: DeviceGraph, data, max_distance=None, chunk=None):
+    """Nearest fill of ``data`` (..., n) along ``graph``: a NaN takes the value of the valid entry with the shortest path to
+    it, of the lowest id among equidistant ones; entries farther than ``max_distance`` (inclusive, scipy's ``limit``) from
+    every value, or in a component without one, stay NaN.  ``chunk``: rounds between two reads of the device's "changed"
+    words (None: NET_CHUNK; no result depends on it)."""
+    global last_rounds
+    limit = _limit(max_distance)
+    chunk = NET_CHUNK if chunk is None else int(chunk)
+    rounds = []
+
+    def launch(in_ptr, out_ptr, K):
+        r = ctypes.c_int64()
+        check(_lib.load().xr_graph_nearest_fill_dev(graph._h, engine.vp(in_ptr), engine.vp(out_ptr), K, limit, chunk,
+                                                    ctypes.byref(r)))
+        rounds.append(r.value)
+
+    out = _run(data, graph.n, launch)
+    last_rounds = max(rounds) if rounds else None
+    return out
+
+
+def network_nearest(graph: DeviceGraph, is_source, max_distance=None, chunk=None):
+    """Per entry the distance along ``graph`` to the nearest source and that source's id: ``(distance (..., n) float64,
+    source (..., n) int64)``, ``inf`` / ``-1`` where no source is within ``max_distance`` (inclusive).  ``is_source`` is a
+    mask (..., n): a host array (anything non-zero is a source; numpy out) or a one-byte device array (torch ``bool`` /
+    ``uint8`` -> torch tensors, another device array -> ``DeviceArray``).  The leading dims are slices, as in ``network_fill``."""
+    global last_rounds
+    limit = _limit(max_distance)
+    chunk = NET_CHUNK if chunk is None else int(chunk)
+    n = graph.n
+    info = engine.byte_array_info(is_source)
+    if info is not None:
+        ptr, shape, _ = info
+        like = is_source
+        engine.sync_producer(is_source)
+    else:
+        mask = np.ascontiguousarray(np.asarray(is_source) != 0, dtype=np.uint8)
+        shape = mask.shape
+        uploaded = engine.DeviceArray.from_host(mask)  # (alive until the calls below have returned)
+        ptr, like = uploaded.ptr, None
+    if len(shape) == 0 or shape[-1] != n:
+        raise ValueError(f"expected a mask of shape (..., {n}), received: {tuple(shape)}")
+    K = int(np.prod(shape[:-1], dtype=np.int64))
+    distance, d_ptr = engine.empty_like_device(like, shape)
+    source, s_ptr = engine.empty_like_device(like, shape, np.int64)
+    rounds = []
+    for k0 in range(0, K, MAX_SLICES):
+        r = ctypes.c_int64()
+        check(_lib.load().xr_graph_nearest_dev(graph._h, engine.vp(ptr + k0 * n), min(MAX_SLICES, K - k0), limit, chunk,
+                                               engine.vp(d_ptr + k0 * n * 8), engine.vp(s_ptr + k0 * n * 8), ctypes.byref(r)))
+        rounds.append(r.value)
+    last_rounds = max(rounds) if rounds else None
+    if info is None:
+        return distance.download(), source.download()
+    return distance, source
+
+
 def laplace_interpolate(data, connectivity, components_labels, use_weights, direct_solve=False, delta=0.0, relax=0.0,
                         atol=1e-4, rtol=0.0, maxiter=500):
     """xugrid.ugrid.interpolate.laplace_interpolate on the device: 1-D ``data`` (n,), scipy CSR ``connectivity`` (n, n)
@@ -229,6 +320,14 @@ class GridFill:
             else:
                 conn = make_connectivity()
                 self.graphs[key] = DeviceGraph(conn, weights=connectivity_weights(conn, coordinates()))
+        return self.graphs[key]
+
+    def network_graph(self, grid, facet):
+        """The shortest-path graph of a ``Ugrid1d`` (weights: lengths along the edges), under a key of its own: the Laplace
+        graph of the same facet carries other weights."""
+        key = ("network", facet)
+        if key not in self.graphs:
+            self.graphs[key] = DeviceGraph.network(grid.node_coordinates, grid.edge_node_connectivity, facet)
         return self.graphs[key]
 
     def xy(self, key, coordinates):

@@ -7,7 +7,7 @@ the regridding hot path (out of scope).
 """
 import numpy as np
 
-from . import connectivity, facet, fill, sample
+from . import connectivity, engine, facet, fill, sample
 from .engine import FloatDType, IntDType
 
 FILL_VALUE = -1
@@ -87,6 +87,12 @@ class Ugrid1d:
         """node -> edge, scipy CSR over all nodes, edges ascending per row (ugridbase.py:866-878)."""
         return facet.node_edge_connectivity(self.edge_node_connectivity, self.n_node)
 
+    @property
+    def edge_edge_connectivity(self):
+        """Edges that share a node, scipy CSR (n_edge, n_edge), columns ascending; data = the shared node
+        (connectivity.py:534-551)."""
+        return connectivity.edge_edge_connectivity(self.edge_node_connectivity, self.node_edge_connectivity)
+
     # ---- moving data between nodes and edges on the device (xugrid_amd/facet.py; the Ugrid2d methods of the same name)
     def to_node(self, data, dim=None, reduce=None):
         """Edge data ``(..., n_edge)`` at the nodes: ``(..., n_node, w)``, or ``(..., n_node)`` with ``reduce``; see
@@ -130,14 +136,73 @@ class Ugrid1d:
         graph = self._fill().graph("node", lambda: self.node_node_connectivity, lambda: self.node_coordinates)
         return fill.laplace_fill(graph, data, xy_weights, direct_solve, delta, relax, atol, rtol, maxiter)
 
-    def interpolate_na(self, data, dim=None, method="nearest", max_distance=None):
-        """Nearest fill of node or edge data (default: edges) at the nodes or edge midpoints, Euclidean distance; see
-        ``Ugrid2d.interpolate_na``."""
+    def interpolate_na(self, data, dim=None, method="nearest", max_distance=None, metric="euclidean"):
+        """Nearest fill of node or edge data (default: edges).
+
+        ``metric="euclidean"`` (the default): the nearest node or edge midpoint in the plane, strictly closer than
+        ``max_distance``; see ``Ugrid2d.interpolate_na``.
+
+        ``metric="network"``: the reference's rule for a ``Ugrid1d`` (ugrid1d.py ``_nearest_interpolate``) -- the nearest value
+        measured ALONG the edges: between nodes the edge lengths, between edges half of the two edge lengths (midpoint to
+        midpoint through the shared node).  Across a meander or between two parallel branches that is another reach than the
+        Euclidean neighbour.  ``max_distance`` is INCLUSIVE here (scipy's dijkstra ``limit``): an entry at exactly that distance
+        is filled.  Among equidistant values the one with the lowest id is taken.  Entries in a part of the network without any
+        value stay NaN.  A network with self-loops or repeated edges raises ``ValueError``.
+
+        ``max_distance=None`` is no limit; a negative one, or an unknown ``metric``, raises ``ValueError`` before the device is
+        touched."""
         if method != "nearest":
             raise ValueError(f'"{method}" is not a valid interpolator.')
+        if metric not in ("euclidean", "network"):
+            raise ValueError(f'metric must be "euclidean" or "network", received: {metric!r}')
+        fill._limit(max_distance)
         facet = fill.resolve_dim(self, dim, ("node", "edge"))
+        if metric == "network":
+            return fill.network_fill(fill.network_graph(self, facet), data, max_distance)
         coords = (lambda: self.node_coordinates) if facet == "node" else (lambda: self.edge_coordinates)
         return fill.nearest_fill(self._fill().xy(facet, coords), data, max_distance)
+
+    def network_distance(self, sources, dim=None, max_distance=None):
+        """Distance along the network to the nearest of ``sources`` (gauges, outlets) and which one it is:
+        ``(distance (n,) float64, source_index (n,) int64)`` over the nodes or edges of ``dim`` (default: edges), ``inf`` / ``-1``
+        where none is within ``max_distance`` (inclusive; None: no limit).  ``sources``: unique ids, or a bool mask of the
+        dimension's length.  Host arrays in -> numpy out; torch tensors on the GPU in -> torch tensors out.  The metric and the
+        tie rule are those of ``interpolate_na(metric="network")``."""
+        fill._limit(max_distance)
+        facet = fill.resolve_dim(self, dim, ("node", "edge"))
+        n = self.n_node if facet == "node" else self.n_edge
+        if engine.is_torch(sources) and getattr(sources, "is_cuda", False):
+            import torch
+
+            if sources.dtype == torch.bool:
+                if tuple(sources.shape) != (n,):
+                    raise ValueError(f"expected a mask of shape ({n},), received: {tuple(sources.shape)}")
+                mask = sources.to(torch.uint8).contiguous()
+            else:
+                ids = sources.reshape(-1).long()
+                if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= n):
+                    raise ValueError(f"sources must be ids in [0, {n})")
+                if torch.unique(ids).numel() != ids.numel():
+                    raise ValueError("sources must be unique ids")
+                mask = torch.zeros(n, dtype=torch.uint8, device=sources.device)
+                mask[ids] = 1
+        else:
+            a = np.asarray(sources.cpu() if engine.is_torch(sources) else sources)
+            if a.dtype == np.bool_:
+                if a.shape != (n,):
+                    raise ValueError(f"expected a mask of shape ({n},), received: {a.shape}")
+                mask = a
+            else:
+                if not np.issubdtype(a.dtype, np.integer):
+                    raise TypeError("sources must be integer ids or a bool mask")
+                ids = a.reshape(-1)
+                if ids.size and (ids.min() < 0 or ids.max() >= n):
+                    raise ValueError(f"sources must be ids in [0, {n})")
+                if np.unique(ids).size != ids.size:
+                    raise ValueError("sources must be unique ids")
+                mask = np.zeros(n, dtype=np.bool_)
+                mask[ids] = True
+        return fill.network_nearest(fill.network_graph(self, facet), mask, max_distance)
 
     # ---- nearest node / edge on the device (xugrid_amd/sample.py; the Ugrid2d methods of the same name)
     def _nearest_index(self, facet):
@@ -157,8 +222,8 @@ class Ugrid1d:
         return self._nearest_index("edge").query(points, max_distance)
 
     def drop_device_caches(self):
-        """Release what this grid keeps in HBM: the fills' graphs and point arrays and the nearest-neighbour indices (built
-        from the coordinates as they were on first use)."""
+        """Release what this grid keeps in HBM: the fills' graphs (the network graphs of ``metric="network"`` among them) and
+        point arrays and the nearest-neighbour indices (built from the coordinates as they were on first use)."""
         self.__dict__.pop("_fill_cache", None)
         self.__dict__.pop("_sample_cache", None)
         self.__dict__.pop("_facet_cache", None)
