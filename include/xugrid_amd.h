@@ -857,6 +857,82 @@ int xr_periodic_index_copy_dev(const xr_periodic *periodic, int facet, int64_t *
 int xr_periodic_node_inverse_copy_dev(const xr_periodic *periodic, int64_t *out_dev);
 int xr_periodic_destroy(xr_periodic *periodic);
 
+/* ---- editing networks (Ugrid1d.topology_subset, ugrid1d.py:603-663; sel / clip_box :574-601, :665-672; remove_self_loops
+ * :714-738; merge_partitions, partitioning.py:81-116, :137-148; refine_by_vertices, ugrid1d.py:770-876); xr_netedit.hip, DESIGN
+ * section 18.  A network is two arrays of the caller in DEVICE memory, node_xy float64[n_node, 2] and edges int64[n_edge, 2];
+ * every pointer argument below is device memory except the per-partition arrays of xr_network_merge_dev, which are host arrays
+ * (of device pointers and of sizes).  The inputs are only read.  Ids are int32 inside the library: XR_ERR_LIMIT when a count
+ * leaves that range.  Nothing is read through an id before it has been compared with its range; an edge that names a node
+ * outside [0, n_node) is never followed and fails the call with XR_ERR_INVALID.  Every call makes an xr_netedit handle that
+ * owns its results in HBM; xr_netedit_info / xr_netedit_copy_dev read them.
+ *
+ * xr_network_subset_dev: the network of the edges edge_index_dev int64[n] (ids unique, any order):
+ *   - its edges are edges[index] in the order given, with their orientation;
+ *   - its nodes are the distinct end nodes of those edges in ascending old id, renumbered by their dense rank (np.unique, then
+ *     connectivity.renumber); the coordinates are copied bit for bit.  XR_NET_NODE_INDEX: that ascending node index.
+ * problems[0]: ids outside [0, n_edge) (negative ones included: nothing wraps), problems[1]: ids that repeat an earlier one.
+ * If either is non-zero *out is NULL and the call still returns XR_OK: the caller words the exception.  *is_identity = 1 (and
+ * *out NULL) when the selection is every edge in order; with is_identity == NULL that selection is cut like any other (its unused
+ * nodes go: remove_self_loops).  n == 0 gives the empty network without a launch.  XR_ERR_INVALID:
+ * n > n_edge.  One synchronising read-back (the number of kept nodes and the four status words in one copy).
+ *
+ * Ascending edge indexes (xr_index: flags -> exclusive scan -> compaction, one read-back each, its length):
+ *   xr_network_edges_of_nodes_dev  the edges with at least one end among node_index_dev[n] (np.unique of
+ *                                  node_edge_connectivity[node_index].data); ids out of range select nothing
+ *   xr_network_box_edges_dev       the edges whose midpoint 0.5 * (a + b), per coordinate, satisfies xmin <= x < xmax and
+ *                                  ymin <= y < ymax: exactly these four comparisons, so a NaN midpoint is outside
+ *   xr_network_nonloop_edges_dev   the edges with a != b (compared as ids, in range or not)
+ *
+ * xr_network_merge_dev: the networks 0 .. n_part - 1 joined into one.
+ *   nodes  the rule of xr_merge_meshes_dev: the partitions' node_xy concatenated in the order given; two nodes are one when both
+ *          coordinates compare equal as doubles (-0.0 == 0.0; a row holding NaN equals nothing, not even itself); the first
+ *          occurrence is kept, bit for bit, and kept nodes keep their concatenation order.
+ *   edges  the partitions' GIVEN edges mapped to merged node ids; two edges are one when their (lower, higher) pairs are equal;
+ *          the first occurrence is kept with its own orientation, kept edges keep their concatenation order.
+ * XR_NET_NODE_INVERSE: the merged id of every concatenated node; xr_netedit_part_*: per partition the ascending LOCAL ids of its
+ * kept nodes (facet 0) and kept edges (facet 1).  One synchronising read-back: both scans at the 2 (n_part + 1) partition
+ * boundaries and the count of bad edges in one copy.
+ *
+ * xr_network_refine_dev: every vertex float64[n_vertex, 2] becomes a node of the edge it lies on.
+ *   locate  vertex p lies on edge (a, b) when its distance to the closed segment is <= tolerance (>= 0): with u = b - a and
+ *           v = p - a, the distance is |v| when u.v <= 0 (a zero-length edge is its point), |p - b| when u.v >= u.u, else
+ *           |u x v| / |u| -- the projection clamped to the segment, in uncontracted double arithmetic.  Among several such edges
+ *           the LOWEST edge id wins (atomicMin, read in the next launch).  A NaN coordinate is on no edge.  The search is not
+ *           all-pairs: the vertices are binned in the cell grid of xr_nn and every edge visits the cells its tolerance-inflated
+ *           segment passes.  If some vertex is on no edge, *n_off_edge is their number, the handle holds ONLY the mask
+ *           (XR_NET_OFF_EDGE, uint8[n_vertex]) and the call returns XR_OK: the caller words the exception.
+ *   drop    a vertex is kept iff the first row of [nodes; vertices] with its coordinates (the key table's equality, as above) is a
+ *           vertex: vertices that equal a node are dropped, vertices that equal one another are all kept.
+ *   order   kept vertices by edge, then by sqrt(dx * dx + dy * dy) from the edge's FIRST node, then by their position among the
+ *           kept vertices (np.lexsort((distance, edge_index)), stable).
+ *   emit    node_xy = [nodes; kept vertices in the order given], copied bit for bit (never projected onto the edge); old edge e
+ *           becomes 1 + count[e] consecutive edges first -> v1 -> v2 .. -> last.  XR_NET_NODE_INDEX: int64[kept] the new ids in
+ *           that order; XR_NET_PARENT_EDGE: int64[n_edge of the result] the old edge of every new edge.
+ * Read-backs: the extent of the vertices (the cell grid), the count of vertices on no edge, the numbers of kept vertices and of
+ * long rows in one copy;  without vertices only the last, and the count of edges with a node out of range.
+ *
+ * xr_netedit_info: sizes[7] = n_node, n_edge of the result (-1, -1 without one), the lengths of XR_NET_NODE_INDEX,
+ * XR_NET_PARENT_EDGE, XR_NET_NODE_INVERSE, the number of partitions, the length of XR_NET_OFF_EDGE.
+ * xr_netedit_copy_dev: `what` into the caller's device array: float64[n_node, 2], int64[n_edge, 2], int64[..] or the uint8 mask. */
+typedef struct xr_netedit xr_netedit;
+enum { XR_NET_NODE_XY = 0, XR_NET_EDGES = 1, XR_NET_NODE_INDEX = 2, XR_NET_PARENT_EDGE = 3, XR_NET_NODE_INVERSE = 4, XR_NET_OFF_EDGE = 5 };
+int xr_network_subset_dev(const double *node_xy_dev, int64_t n_node, const int64_t *edges_dev, int64_t n_edge, const int64_t *edge_index_dev,
+                          int64_t n, xr_netedit **out, int *is_identity, int64_t *problems);
+int xr_network_edges_of_nodes_dev(const int64_t *edges_dev, int64_t n_edge, int64_t n_node, const int64_t *node_index_dev, int64_t n,
+                                  xr_index **out);
+int xr_network_box_edges_dev(const double *node_xy_dev, int64_t n_node, const int64_t *edges_dev, int64_t n_edge, double xmin, double ymin,
+                             double xmax, double ymax, xr_index **out);
+int xr_network_nonloop_edges_dev(const int64_t *edges_dev, int64_t n_edge, xr_index **out);
+int xr_network_merge_dev(const double *const *node_xy_dev, const int64_t *n_node, const int64_t *const *edges_dev, const int64_t *n_edge,
+                         int64_t n_part, xr_netedit **out);
+int xr_network_refine_dev(const double *node_xy_dev, int64_t n_node, const int64_t *edges_dev, int64_t n_edge, const double *vertices_dev,
+                          int64_t n_vertex, double tolerance, xr_netedit **out, int64_t *n_off_edge);
+int xr_netedit_info(const xr_netedit *net, int64_t *sizes);
+int xr_netedit_copy_dev(const xr_netedit *net, int what, void *out_dev);
+int xr_netedit_part_info(const xr_netedit *net, int facet, int64_t part, int64_t *n);
+int xr_netedit_part_copy_dev(const xr_netedit *net, int facet, int64_t part, int64_t *out_dev);
+int xr_netedit_destroy(xr_netedit *net);
+
 /* ---- raw HBM helpers for hosts that do not bring their own allocator -------------------- */
 int xr_dev_alloc(int64_t bytes, void **ptr_out);
 int xr_dev_free(void *ptr);

@@ -201,6 +201,17 @@ SIGNATURES = {
     "xr_periodic_index_copy_dev": (c_int, [vp, c_int, vp]),
     "xr_periodic_node_inverse_copy_dev": (c_int, [vp, vp]),
     "xr_periodic_destroy": (c_int, [vp]),
+    "xr_network_subset_dev": (c_int, [vp, c_i64, vp, c_i64, vp, c_i64, p_vp, p_int, p_i64]),
+    "xr_network_edges_of_nodes_dev": (c_int, [vp, c_i64, c_i64, vp, c_i64, p_vp]),
+    "xr_network_box_edges_dev": (c_int, [vp, c_i64, vp, c_i64, c_f64, c_f64, c_f64, c_f64, p_vp]),
+    "xr_network_nonloop_edges_dev": (c_int, [vp, c_i64, p_vp]),
+    "xr_network_merge_dev": (c_int, [p_vp, p_i64, p_vp, p_i64, c_i64, p_vp]),
+    "xr_network_refine_dev": (c_int, [vp, c_i64, vp, c_i64, vp, c_i64, c_f64, p_vp, p_i64]),
+    "xr_netedit_info": (c_int, [vp, p_i64]),
+    "xr_netedit_copy_dev": (c_int, [vp, c_int, vp]),
+    "xr_netedit_part_info": (c_int, [vp, c_int, c_i64, p_i64]),
+    "xr_netedit_part_copy_dev": (c_int, [vp, c_int, c_i64, vp]),
+    "xr_netedit_destroy": (c_int, [vp]),
     "xr_dev_alloc": (c_int, [c_i64, p_vp]),
     "xr_dev_free": (c_int, [vp]),
     "xr_dev_upload": (c_int, [vp, vp, c_i64]),

@@ -103,6 +103,14 @@ k_merge_compact_xy(const int32_t *__restrict__ flag, const int32_t *__restrict__
     out_xy[j] = xy[i]; // (16 bytes copied: bit for bit, a kept zero keeps its sign)
 }
 
+// out[k] = rank[at[k]]: the scan's values at the segment boundaries, gathered for one read-back
+static __global__ void k_merge_bounds(const int32_t *__restrict__ rank_a, const int32_t *__restrict__ rank_b, const int32_t *__restrict__ at,
+                                      int n_a, int n_b, int32_t *__restrict__ out) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n_a) out[k] = rank_a[at[k]];
+    else if (k < n_a + n_b) out[k] = rank_b[at[k]];
+}
+
 struct KeyTable {
     DevBuf<int32_t> slots;
     uint32_t mask = 0;

@@ -96,14 +96,6 @@ k_merge_edge_rows(const int32_t *__restrict__ edge_node, int64_t n_edge, int64_t
     rows[2 * e + 1] = u < v ? v : u;
 }
 
-// out[k] = rank[at[k]]: the scan's values at the segment boundaries, gathered for one read-back
-__global__ void k_merge_bounds(const int32_t *__restrict__ rank_a, const int32_t *__restrict__ rank_b, const int32_t *__restrict__ at,
-                               int n_a, int n_b, int32_t *__restrict__ out) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < n_a) out[k] = rank_a[at[k]];
-    else if (k < n_a + n_b) out[k] = rank_b[at[k]];
-}
-
 // one thread per (row, slot) of the concatenation: consecutive lanes read consecutive words
 __global__ void __launch_bounds__(256)
 k_merge_compact_rows(const int32_t *__restrict__ flag, const int32_t *__restrict__ rank, int64_t n, int m,

@@ -22,6 +22,22 @@ struct xr_nn {
 
 namespace xr {
 
+#if defined(__HIPCC__)
+// the cell of a coordinate: the one rule behind the index's build, its queries and every kernel that walks its cells
+// (comparisons written so that a NaN coordinate lands in cell 0)
+__device__ __forceinline__ int sp_cell_x(const SampleGrid &g, double x) {
+    const double t = (x - g.x0) * g.inv_h;
+    return !(t >= 0.0) ? 0 : t >= (double)(g.nx - 1) ? g.nx - 1 : (int)t;
+}
+__device__ __forceinline__ int sp_cell_y(const SampleGrid &g, double y) {
+    const double t = (y - g.y0) * g.inv_h;
+    return !(t >= 0.0) ? 0 : t >= (double)(g.ny - 1) ? g.ny - 1 : (int)t;
+}
+__device__ __forceinline__ int64_t sp_cell(const SampleGrid &g, double2 p) {
+    return (int64_t)sp_cell_y(g, p.y) * g.nx + sp_cell_x(g, p.x);
+}
+#endif
+
 // What a build indexes: the bounding box (xmin, xmax, ymin, ymax) and the number of the points that take part
 struct NnExtent {
     double box[4];

@@ -30,19 +30,6 @@ static constexpr int SB = 256; // threads per block
 // about 384 000 queries on (even there, a fifth faster at 512 000), so the constant sits at the first size the sort clearly wins.
 static constexpr int64_t NN_SORT_MIN_QUERIES = 1 << 19;
 
-// (comparisons written so that a NaN coordinate lands in cell 0)
-__device__ __forceinline__ int sp_cell_x(const SampleGrid &g, double x) {
-    const double t = (x - g.x0) * g.inv_h;
-    return !(t >= 0.0) ? 0 : t >= (double)(g.nx - 1) ? g.nx - 1 : (int)t;
-}
-__device__ __forceinline__ int sp_cell_y(const SampleGrid &g, double y) {
-    const double t = (y - g.y0) * g.inv_h;
-    return !(t >= 0.0) ? 0 : t >= (double)(g.ny - 1) ? g.ny - 1 : (int)t;
-}
-__device__ __forceinline__ int64_t sp_cell(const SampleGrid &g, double2 p) {
-    return (int64_t)sp_cell_y(g, p.y) * g.nx + sp_cell_x(g, p.x);
-}
-
 // the subset a pass works on: every point without `values`, else the points whose value is NaN (want_nan) or is not
 __device__ __forceinline__ bool sp_takes_part(const double *__restrict__ values, bool want_nan, int64_t i) {
     return !values || (values[i] != values[i]) == want_nan;

@@ -626,6 +626,87 @@ class DevicePeriodic(Handle):
         return out
 
 
+class DeviceNetEdit(Handle):
+    """The result of one network edit on the device (include/xugrid_amd.h: xr_netedit): the new network and the indexes that came
+    with it.  A network goes in as two device pointers, ``node_xy`` float64 ``(n_node, 2)`` and ``edges`` int64 ``(n_edge, 2)``."""
+
+    _destroy = "xr_netedit_destroy"
+
+    NODE_XY, EDGES, NODE_INDEX, PARENT_EDGE, NODE_INVERSE, OFF_EDGE = range(6)
+
+    def __init__(self, handle):
+        self._h = handle
+        sizes = (ctypes.c_int64 * 7)()
+        check(_lib.load().xr_netedit_info(handle, sizes))
+        self.n_node, self.n_edge, self.n_node_index, self.n_parent, self.n_node_all, self.n_part, self.n_vertex = (int(s) for s in sizes)
+
+    @classmethod
+    def subset(cls, xy_ptr, n_node, edges_ptr, n_edge, index_ptr, n, keep_identity=True):
+        """-> ``(result or None, is_identity, (ids out of range, repeated ids))``; without ``keep_identity`` the selection of
+        every edge in order is cut like any other (its unused nodes go)."""
+        handle, identity, problems = ctypes.c_void_p(), ctypes.c_int(), (ctypes.c_int64 * 2)()
+        check(_lib.load().xr_network_subset_dev(vp(xy_ptr), int(n_node), vp(edges_ptr), int(n_edge), vp(index_ptr), int(n),
+                                                ctypes.byref(handle), ctypes.byref(identity) if keep_identity else None, problems))
+        return (cls(handle) if handle.value else None), bool(identity.value), (int(problems[0]), int(problems[1]))
+
+    @classmethod
+    def merge(cls, xy_ptrs, n_nodes, edges_ptrs, n_edges):
+        P = len(xy_ptrs)
+        handle = ctypes.c_void_p()
+        check(_lib.load().xr_network_merge_dev((ctypes.c_void_p * P)(*xy_ptrs), (ctypes.c_int64 * P)(*n_nodes),
+                                               (ctypes.c_void_p * P)(*edges_ptrs), (ctypes.c_int64 * P)(*n_edges), P, ctypes.byref(handle)))
+        return cls(handle)
+
+    @classmethod
+    def refine(cls, xy_ptr, n_node, edges_ptr, n_edge, vertices_ptr, n_vertex, tolerance):
+        """-> ``(result, vertices on no edge)``; with such vertices the result holds only their mask (``off_edge``)."""
+        handle, off = ctypes.c_void_p(), ctypes.c_int64()
+        check(_lib.load().xr_network_refine_dev(vp(xy_ptr), int(n_node), vp(edges_ptr), int(n_edge), vp(vertices_ptr), int(n_vertex),
+                                                float(tolerance), ctypes.byref(handle), ctypes.byref(off)))
+        return cls(handle), off.value
+
+    def _copy(self, what, shape, dtype, like=None):
+        out, ptr = empty_like_device(like, shape, dtype)
+        check(_lib.load().xr_netedit_copy_dev(self._h, what, vp(ptr)))
+        return out
+
+    def node_xy(self):
+        return self._copy(self.NODE_XY, (self.n_node, 2), np.float64)
+
+    def edges(self):
+        return self._copy(self.EDGES, (self.n_edge, 2), np.int64)
+
+    def node_index(self, like=None):
+        return self._copy(self.NODE_INDEX, (self.n_node_index,), np.int64, like)
+
+    def parent_edge(self, like=None):
+        return self._copy(self.PARENT_EDGE, (self.n_parent,), np.int64, like)
+
+    def node_inverse(self, like=None):
+        return self._copy(self.NODE_INVERSE, (self.n_node_all,), np.int64, like)
+
+    def off_edge(self):
+        """bool ``(n_vertex,)`` on the host: the vertices on no edge."""
+        keep = DeviceArray((max(self.n_vertex, 1),), np.uint8)
+        check(_lib.load().xr_netedit_copy_dev(self._h, self.OFF_EDGE, vp(keep.ptr)))
+        return keep.download()[: self.n_vertex].astype(np.bool_)
+
+    def part_index(self, facet, part, like=None):
+        """int64 device array: the ascending local ids of partition ``part``'s kept nodes (``facet`` 0) or edges (1)."""
+        n = ctypes.c_int64()
+        check(_lib.load().xr_netedit_part_info(self._h, int(facet), int(part), ctypes.byref(n)))
+        out, ptr = empty_like_device(like, (n.value,), np.int64)
+        check(_lib.load().xr_netedit_part_copy_dev(self._h, int(facet), int(part), vp(ptr)))
+        return out
+
+
+def network_index(name, *args):
+    """One of the ascending edge indexes of include/xugrid_amd.h (``xr_network_<name>_dev``) -> ``DeviceIndex``."""
+    handle = ctypes.c_void_p()
+    check(getattr(_lib.load(), f"xr_network_{name}_dev")(*args, ctypes.byref(handle)))
+    return DeviceIndex(handle)
+
+
 def index_like_dev(a_ptr, b_ptr, n, tolerance, like=None):
     """include/xugrid_amd.h: xr_index_like_dev on two float64 ``(n, 2)`` device pointers -> (int64 ``(n,)`` device array of the
     kind of ``like``, keys that repeat, rows of b without a partner)."""

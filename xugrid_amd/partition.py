@@ -15,8 +15,9 @@ the device when every grid in the list is device-resident with a manifold topolo
 """
 import numpy as np
 
-from . import engine, sample, subset
+from . import engine, netedit, sample, subset
 from .subset import FACETS
+from .ugrid1d import Ugrid1d
 
 ZERO = "Cannot merge partitions: zero partitions provided."
 NOT_IDENTICAL = "coordinates are not identical after sorting"
@@ -175,8 +176,11 @@ def _concat(data, sizes):
 
 
 def merge_partitions(grids, return_index=False, data=None, dim=None):
-    """See ``Ugrid2d.merge_partitions``."""
+    """See ``Ugrid2d.merge_partitions``; a list of ``Ugrid1d`` goes to ``netedit.merge_partitions``, a mixed one raises
+    ``TypeError`` (partitioning.py:151-158)."""
     grids = list(grids)
+    if any(isinstance(g, Ugrid1d) for g in grids):
+        return netedit.merge_partitions(grids, return_index, data, dim)
     if len(grids) == 0:
         raise ValueError(ZERO)
     if data is not None:
@@ -284,7 +288,9 @@ def _facet_coordinates(grid, facet):
 
 
 def reindex_like(grid, other, data, dim=None, tolerance=0.0):
-    """See ``Ugrid2d.reindex_like``."""
+    """See ``Ugrid2d.reindex_like`` / ``Ugrid1d.reindex_like``."""
+    if isinstance(grid, Ugrid1d):
+        return netedit.reindex_like(grid, other, data, dim, tolerance)
     if dim is not None:
         names = {grid.node_dimension: "node", grid.edge_dimension: "edge", grid.face_dimension: "face"}
         if dim not in names:

@@ -2,12 +2,12 @@
 ``Ugrid1d``: a network of line segments -- the part of xugrid/ugrid/ugrid1d.py:65-111 and ugridbase.py the
 NetworkGridder path reads: the constructor arguments ``(node_x, node_y, fill_value, edge_node_connectivity)``,
 ``n_node`` / ``n_edge``, ``node_coordinates``, ``edge_node_coordinates`` (ugridbase.py:611-614) and ``edge_length``
-(:955-959).  UGRID IO, CRS handling, the edge kd-tree and the topology editing of the reference class are outside
-the regridding hot path (out of scope).
+(:955-959), and the topology editing of xugrid_amd/netedit.py.  UGRID IO, CRS handling and the depth-first graph walks of the
+reference class are outside (out of scope).
 """
 import numpy as np
 
-from . import connectivity, engine, facet, fill, sample
+from . import connectivity, engine, facet, fill, netedit, sample
 from .engine import FloatDType, IntDType
 
 FILL_VALUE = -1
@@ -221,9 +221,67 @@ class Ugrid1d:
         """Index of the nearest edge midpoint per point, -1 for none (ugridbase.py:1283-1303)."""
         return self._nearest_index("edge").query(points, max_distance)
 
+    # ---- editing the network on the device (xugrid_amd/netedit.py, csrc/xr_netedit.hip; DESIGN section 18)
+    def topology_subset(self, edge_index, return_index=False):
+        """ugrid1d.py:603-663: the network of the edges ``edge_index`` (unique ids in any order, or a bool mask of length
+        ``n_edge``; host or device) in the order given; its nodes are the end nodes of those edges in ascending old id.  Every
+        edge in order gives the grid itself.  ``return_index``: also ``{node_dimension: .., edge_dimension: ..}``, int64 (numpy,
+        or device arrays of the indexer's kind).  Ids outside ``[0, n_edge)`` raise ``IndexError`` (negative ones too),
+        repeated ids ``ValueError``."""
+        return netedit.topology_subset(self, edge_index, return_index)
+
+    def isel(self, indexers=None, return_index=False, data=None, dim=None, **indexers_kwargs):
+        """ugridbase.py:703-720: the sub-network of an indexer per UGRID dimension (node and / or edge).  A node indexer stands
+        for the edges with at least one end in it; all indexers must stand for the same edges ("UGRID dimensions do not align")
+        and a node indexer must be exactly the ascending nodes of the result ("results in an invalid topology").  ``data``
+        ``(..., n)`` on one dimension comes back indexed alongside; ``dim`` names that dimension where ``n_node == n_edge`` (a
+        ring) leaves it open.  -> grid [, indexes] [, data]."""
+        return netedit.isel(self, indexers, return_index, data, dim, **indexers_kwargs)
+
+    def sel(self, x=None, y=None, data=None, return_index=False, dim=None):
+        """ugrid1d.py:574-601: the edges whose midpoint lies in the half-open box of two slices (no steps).  A ``None`` slice or
+        bound is unbounded on that side (an addition).  -> grid [, indexes] [, data]."""
+        return netedit.sel(self, x, y, data, return_index, dim)
+
+    def clip_box(self, xmin, ymin, xmax, ymax):
+        """ugrid1d.py:665-672: ``sel(x=slice(xmin, xmax), y=slice(ymin, ymax))``."""
+        return netedit.clip_box(self, xmin, ymin, xmax, ymax)
+
+    def remove_self_loops(self, return_index=False):
+        """ugrid1d.py:714-738: the network without the edges that join a node to itself.  Always a NEW grid, whose nodes are
+        exactly those the kept edges use.  ``return_index``: also the node and edge index."""
+        return netedit.remove_self_loops(self, return_index)
+
+    @staticmethod
+    def merge_partitions(grids, return_index=False, data=None, dim=None):
+        """partitioning.py:81-116, :137-148: the networks joined into one.  Nodes whose coordinates compare equal as doubles are
+        one node (first occurrence kept, bit for bit, in concatenation order); edges with the same (lower, higher) node pair are
+        one edge (first occurrence kept with its orientation).  One grid gives that grid itself.  ``return_index``: per
+        dimension a list with every partition's ascending local ids of its kept nodes / edges; ``data``: one array
+        ``(..., n_p)`` per partition on one dimension -> the merged data.  -> grid [, indexes] [, data]."""
+        return netedit.merge_partitions(grids, return_index, data, dim)
+
+    def reindex_like(self, other, data, dim=None, tolerance=0.0):
+        """``data`` ``(..., n)`` of this grid in the node or edge order of ``other``, the same network numbered differently:
+        nodes are matched by their coordinates, edges by their midpoints (``partition.index_like_device``); a mismatch raises
+        ``ValueError``."""
+        return netedit.reindex_like(self, other, data, dim, tolerance)
+
+    def refine_by_vertices(self, vertices, return_index=False, tolerance=None, data=None):
+        """ugrid1d.py:770-876: every vertex ``(n, 2)`` (host or float64 device array) becomes a node of the edge it lies on, the
+        edge is split there.  A vertex lies on an edge when its distance to the closed segment is ``<= tolerance`` (None:
+        ``1e-9`` times the larger side of the node bounding box; the lowest edge id wins); a vertex on no edge raises
+        ``ValueError`` listing those vertices.  Vertices that equal an existing node are dropped, vertices that equal one
+        another are all inserted.  New nodes follow the old ones in the order given, unprojected.  ``return_index``: the new
+        ids ordered by edge, then distance from the edge's first node.  ``data``: edge data ``(..., n_edge)`` repeated onto the
+        new edges (an addition; node data raises ``ValueError``).  -> grid [, node_index] [, data]."""
+        return netedit.refine_by_vertices(self, vertices, return_index, tolerance, data)
+
     def drop_device_caches(self):
         """Release what this grid keeps in HBM: the fills' graphs (the network graphs of ``metric="network"`` among them) and
-        point arrays and the nearest-neighbour indices (built from the coordinates as they were on first use)."""
+        point arrays, the nearest-neighbour indices (built from the coordinates as they were on first use) and the copy of the
+        nodes and edges the edits read."""
+        self.__dict__.pop("_netedit_cache", None)
         self.__dict__.pop("_fill_cache", None)
         self.__dict__.pop("_sample_cache", None)
         self.__dict__.pop("_facet_cache", None)
