@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the partial-state kernels of the source-sharded apply (xr_apply.hip: k_apply_partial*, k_reduce_partial_rows*,
+"""GPU (-m gpu): the partial-state kernels of the source-sharded apply (xr_partial.hip: k_apply_partial*, k_reduce_partial_rows*,
 k_partial_identity, k_finalize_partial) called in process through their entry points, against the numpy yardstick of
 tests/partial_cases.py: the STATES themselves, every kernel form (K = 1 wave windows, K = 2..7 thread per row, K >= 8 tiles of
 eight variables in both layouts, the long-row kernel), the combine / finalize kernels on given tables, the whole route over

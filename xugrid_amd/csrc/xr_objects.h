@@ -133,7 +133,7 @@ struct xr_csr {
     bool has_long = false;
     // Coarse Morton key per STORED row (tile of ~12 target extents).  Set by xr_overlap when the rows are kept
     // in the caller's order, or by xr_csr_set_row_keys; consumed once by the many-variable apply, which regroups
-    // the stored rows into compact 2-D tiles (xr_apply.hip: ensure_tiled) and then drops the keys.
+    // the stored rows into compact 2-D tiles (xr_csr.hip: ensure_tiled) and then drops the keys.
     xr::DevBuf<int32_t> tile_key; // [n]
     bool has_tile_key = false;
     int64_t tile_key_range = 0;   // keys are in [0, tile_key_range)
@@ -143,7 +143,7 @@ struct xr_csr {
     bool has_col_perm = false;
     bool source_permuted = false;
     bool output_stored = false; // applies write row r of the STORED order to out[k, r] (xr_csr_output_stored_order)
-    // "apply plan" for many source variables (built lazily, xr_apply.hip): per block of 256 stored
+    // "apply plan" for many source variables (built lazily, xr_apply.hip: ensure_plan): per block of 256 stored
     // rows the sorted list of DISTINCT column ids and, per entry, its 16-bit position in that list
     bool plan_ready = false;
     bool plan_merged = false;           // the lists are per GROUP of row blocks (k_plan_build_group), not per block
@@ -191,7 +191,8 @@ void mesh_build_index(xr_mesh *mesh);
 void flush_pending_points(); // launch the deferred source-side kernels of pending xr_points handles (xr_locate.hip)
 void flush_pending_points_of(const xr_mesh *mesh); // ... if one of them reads `mesh`, before its arrays are released
 void mesh_read_stats(xr_mesh *mesh, bool need_exact = false); // need_exact: statistics over ALL faces (sampled ones are redone)
-// the apply of a finished (or, K = 1, of a just-enqueued) matrix on the calling thread's launch stream (xr_apply.hip)
+// the apply of a finished (or, K = 1, of a just-enqueued) matrix on the calling thread's launch stream (xr_apply.hip), and its
+// partial states for the source-sharded apply (xr_partial.hip)
 void csr_apply_dev(const xr_csr *csr, int method, double percentile, const void *src_dev, int dtype, int64_t K, double *out_dev);
 void csr_partial_dev(const xr_csr *csr, int method, const void *src_dev, int dtype, int64_t K, double *out_dev, int rows_layout);
 void mesh_centroids_dev(xr_mesh *mesh, double *cxy_dev);    // connectivity.centroids into device memory [n_face*2]

@@ -1,6 +1,6 @@
 """
 Reduction methods of the regridders: the names of xugrid/regrid/reduce.py:254-272 mapped onto
-the reducer ids of the HIP apply kernels (include/xugrid_amd.h, xugrid_amd/csrc/xr_apply.hip).
+the reducer ids of the HIP apply kernels (include/xugrid_amd.h, xugrid_amd/csrc/xr_reduce.h).
 
 The reference hands Python functions ``f(values, weights, workspace)`` to numba; here a method
 is a small descriptor ``Method(name, method_id, percentile)`` that selects a kernel
