@@ -933,6 +933,49 @@ int xr_netedit_part_info(const xr_netedit *net, int facet, int64_t part, int64_t
 int xr_netedit_part_copy_dev(const xr_netedit *net, int facet, int64_t part, int64_t *out_dev);
 int xr_netedit_destroy(xr_netedit *net);
 
+/* ---- snapping points (xugrid.snap_nodes, xugrid/ugrid/snapping.py:46-143; snap_to_nodes, :146-219); xr_snap.hip, DESIGN section
+ * 19.  Every pointer argument is device memory and the inputs are only read.  Coordinates come as two pointers and one stride in
+ * elements: stride 1 for separate x and y arrays, (xy, xy + 1, 2) for an interleaved float64[n, 2] array.  "Within the distance"
+ * is dx * dx + dy * dy <= max_distance * max_distance in uncontracted float64, INCLUSIVE (the test of the KD-tree's
+ * sparse_distance_matrix), so max_distance = 0 still pairs coincident points.  A NaN or infinite coordinate is XR_ERR_INVALID
+ * ("data must be finite", as cKDTree raises); a negative or NaN max_distance is XR_ERR_INVALID.
+ *
+ * xr_snap_nodes_dev: nodes within the distance of each other are merged (snapping.py:86-143).
+ *   adjacency  every point's neighbours within the distance, itself excluded, as CSR, with the ROUNDED square root of each squared
+ *              distance (what the reference's distance matrix holds).  More than 2^31 - 1 entries is XR_ERR_INVALID.
+ *   targets    point i is a target iff no lower-numbered target lies within the distance (the greedy loop of :66-81 taken as what
+ *              it computes: the lexicographically first maximal independent set).  Decided in rounds: undecided -> snapped when a
+ *              lower-numbered neighbour is a target, -> target when every lower-numbered neighbour is snapped; XR_SNAP_SWEEPS
+ *              bounded passes over a point's row per launch; the host reads one pair of status words every few launches.
+ *   assign     a point that is not a target goes to the target among its neighbours with the smallest stored distance, the lowest
+ *              id on equal distances (:77: overwritten only when strictly closer, targets met in ascending order).
+ *   result     np.unique(visited, return_inverse=True) of :140: XR_SNAP_INDEX the kept points ascending, XR_SNAP_INVERSE the rank
+ *              of the kept point every point went to, the kept coordinates copied bit for bit.
+ * xr_snap_info: n_kept; n_pair, the number of adjacency entries -- 0 means nothing lies within the distance (the reference then
+ * returns None and copies), the handle holds no arrays and xr_snap_copy_dev / xr_snap_relabel_dev are XR_ERR_INVALID; rounds, the
+ * number of the last launch that decided a point.  n = 0 gives n_pair = 0 without a launch.
+ * xr_snap_copy_dev: XR_SNAP_INVERSE int64[n], XR_SNAP_INDEX int64[n_kept], XR_SNAP_XY float64[n_kept, 2], XR_SNAP_X / XR_SNAP_Y
+ * float64[n_kept].  xr_snap_relabel_dev: out[k] = inverse[ids[k]] for int64 ids[count] (a connectivity); an id outside [0, n) is
+ * XR_ERR_INVALID, checked before anything is read through it.
+ *
+ * xr_nn_snap_dev: points move onto the nearest point of an xr_nn index within the distance (snapping.py:146-219); to_index NULL
+ * stands for an empty set.  Per point: the indexed points within the distance are counted; with at least one, the output
+ * coordinates are those of the one with the smallest squared distance, the LOWEST id on equal squares (the reference's choice
+ * between distinct equidistant points follows its tree and is arbitrary), and index_out_dev (optional, int64[n]) is its id; with
+ * none the point is copied and the id is -1.  *n_tied: points with more than one indexed point within the distance (the
+ * reference raises for them without a tiebreaker; with "nearest" it takes what is computed here).  The indexed points are
+ * checked for NaN / infinity on every call. */
+typedef struct xr_snap xr_snap;
+#define XR_SNAP_SWEEPS 4
+enum { XR_SNAP_INVERSE = 0, XR_SNAP_INDEX = 1, XR_SNAP_XY = 2, XR_SNAP_X = 3, XR_SNAP_Y = 4 };
+int xr_snap_nodes_dev(const double *x_dev, const double *y_dev, int64_t stride, int64_t n, double max_distance, xr_snap **out);
+int xr_snap_info(const xr_snap *snap, int64_t *n_kept, int64_t *n_pair, int64_t *rounds);
+int xr_snap_copy_dev(const xr_snap *snap, int what, void *out_dev);
+int xr_snap_relabel_dev(const xr_snap *snap, const int64_t *ids_dev, int64_t count, int64_t *out_dev);
+int xr_snap_destroy(xr_snap *snap);
+int xr_nn_snap_dev(const xr_nn *to_index, const double *x_dev, const double *y_dev, int64_t stride, int64_t n, double max_distance,
+                   double *x_out_dev, double *y_out_dev, int64_t out_stride, int64_t *index_out_dev, int64_t *n_tied);
+
 /* ---- raw HBM helpers for hosts that do not bring their own allocator -------------------- */
 int xr_dev_alloc(int64_t bytes, void **ptr_out);
 int xr_dev_free(void *ptr);

@@ -700,6 +700,50 @@ class DeviceNetEdit(Handle):
         return out
 
 
+class DeviceSnap(Handle):
+    """The result of one ``snap_nodes`` on the device (include/xugrid_amd.h: xr_snap).  ``n_pair == 0``: nothing lay within the
+    distance and the handle holds no arrays."""
+
+    _destroy = "xr_snap_destroy"
+
+    INVERSE, INDEX, XY, X, Y = range(5)
+    SWEEPS = 4  # include/xugrid_amd.h: XR_SNAP_SWEEPS, the passes over a point's row per launch of a decision round
+
+    def __init__(self, x_ptr, y_ptr, stride, n, max_distance):
+        handle = ctypes.c_void_p()
+        check(_lib.load().xr_snap_nodes_dev(vp(x_ptr), vp(y_ptr), int(stride), int(n), float(max_distance), ctypes.byref(handle)))
+        self._h = handle
+        n_kept, n_pair, rounds = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        check(_lib.load().xr_snap_info(handle, ctypes.byref(n_kept), ctypes.byref(n_pair), ctypes.byref(rounds)))
+        self.n, self.n_kept, self.n_pair, self.rounds = int(n), n_kept.value, n_pair.value, rounds.value
+
+    def _copy(self, what, shape, dtype, like=None):
+        out, ptr = empty_like_device(like, shape, dtype)
+        check(_lib.load().xr_snap_copy_dev(self._h, what, vp(ptr)))
+        return out
+
+    def inverse(self, like=None):
+        return self._copy(self.INVERSE, (self.n,), np.int64, like)
+
+    def index(self, like=None):
+        return self._copy(self.INDEX, (self.n_kept,), np.int64, like)
+
+    def xy(self, like=None):
+        return self._copy(self.XY, (self.n_kept, 2), np.float64, like)
+
+    def x(self, like=None):
+        return self._copy(self.X, (self.n_kept,), np.float64, like)
+
+    def y(self, like=None):
+        return self._copy(self.Y, (self.n_kept,), np.float64, like)
+
+    def relabel(self, ids_ptr, shape, like=None):
+        """``inverse[ids]`` for an int64 device array of ids (a connectivity) -> an int64 device array of ``shape``."""
+        out, ptr = empty_like_device(like, shape, np.int64)
+        check(_lib.load().xr_snap_relabel_dev(self._h, vp(ids_ptr), int(np.prod(shape, dtype=np.int64)), vp(ptr)))
+        return out
+
+
 def network_index(name, *args):
     """One of the ascending edge indexes of include/xugrid_amd.h (``xr_network_<name>_dev``) -> ``DeviceIndex``."""
     handle = ctypes.c_void_p()

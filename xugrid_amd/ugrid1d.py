@@ -7,7 +7,7 @@ reference class are outside (out of scope).
 """
 import numpy as np
 
-from . import connectivity, engine, facet, fill, netedit, sample
+from . import connectivity, engine, facet, fill, netedit, sample, snap
 from .engine import FloatDType, IntDType
 
 FILL_VALUE = -1
@@ -276,6 +276,20 @@ class Ugrid1d:
         ids ordered by edge, then distance from the edge's first node.  ``data``: edge data ``(..., n_edge)`` repeated onto the
         new edges (an addition; node data raises ``ValueError``).  -> grid [, node_index] [, data]."""
         return netedit.refine_by_vertices(self, vertices, return_index, tolerance, data)
+
+    # ---- snapping (xugrid_amd/snap.py, csrc/xr_snap.hip; DESIGN section 19)
+    def snap_to_nodes(self, x, y, max_distance, tiebreaker=None, return_index=False):
+        """``xugrid_amd.snap_to_nodes`` (snapping.py:146-219) with this network's nodes as the targets, through its cached
+        node index; see ``Ugrid2d.snap_to_nodes``."""
+        return snap.grid_snap_to_nodes(self, x, y, max_distance, tiebreaker, return_index)
+
+    def snap_nodes(self, max_snap_distance, return_index=False):
+        """``xugrid_amd.snap_nodes`` (snapping.py:86-143) on this network's nodes: nodes within ``max_snap_distance`` of each
+        other become one node and ``edge_node_connectivity`` is ``inverse[edges]``, gathered on the device.  Every edge is
+        kept, so edges may become self-loops (``remove_self_loops`` drops them) or repeat one another.  The grid itself comes
+        back when no two nodes lie within the distance.  ``return_index``: also ``{node_dimension: inverse}``, int64
+        ``(n_node,)`` the new id of every old node, None for the identity."""
+        return snap.network_snap_nodes(self, max_snap_distance, return_index)
 
     def drop_device_caches(self):
         """Release what this grid keeps in HBM: the fills' graphs (the network graphs of ``metric="network"`` among them) and

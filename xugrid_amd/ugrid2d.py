@@ -10,7 +10,7 @@ import numpy as np
 
 import ctypes
 
-from . import _lib, connectivity, facet, fill, graph, sample
+from . import _lib, connectivity, facet, fill, graph, sample, snap
 from .celltree import CellTree2d
 from .engine import FloatDType, IntDType
 
@@ -417,6 +417,12 @@ class Ugrid2d:
     def locate_nearest_face(self, points, max_distance=np.inf):
         """... the nearest face centroid (ugrid2d.py:1007-1027)."""
         return self._locate_nearest("face", points, max_distance)
+
+    def snap_to_nodes(self, x, y, max_distance, tiebreaker=None, return_index=False):
+        """``xugrid_amd.snap_to_nodes`` (snapping.py:146-219) with this grid's nodes as the targets, through its cached node
+        index: the points ``(x, y)`` within ``max_distance`` of a node move onto the nearest one.  -> ``(x_snapped,
+        y_snapped[, index])``; host arrays in -> numpy out, device arrays in -> device arrays out."""
+        return snap.grid_snap_to_nodes(self, x, y, max_distance, tiebreaker, return_index)
 
     def intersect_edges(self, edges):
         """ugridbase.py:1325-1343: ``(edge_index, face_index, intersections (n, 2, 2))`` of segments ``(n_edge, 2, 2)``."""
