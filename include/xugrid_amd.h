@@ -574,6 +574,28 @@ int xr_graph_components_dev(const xr_graph *graph, int64_t *labels_dev, int64_t 
 int xr_graph_binary_iterate_dev(const xr_graph *graph, const uint8_t *in_dev, uint8_t *out_dev, int64_t K, int value,
                                 int64_t iterations, const uint8_t *mask_dev, const uint8_t *exterior_dev);
 
+/* ---- renumbering (scipy.sparse.csgraph.reverse_cuthill_mckee, symmetric_mode=True; xugrid Ugrid2d.reverse_cuthill_mckee) ---- */
+/* order_dev int64 [n] (a device pointer): the permutation in scipy's reversed order, new row i = old row order_dev[i].
+ * The graph must be symmetric with ascending columns; an entry that repeats a column of its row counts in the degree (as in scipy)
+ * and is otherwise ignored.
+ * degree = entries of the row, plus one where the row holds its diagonal entry (scipy's count; the diagonal is never visited).
+ * scipy's routine is a sequential breadth-first search: the seed is the first unvisited vertex in the order of ascending
+ * degree; each visited row appends its unvisited neighbours in stored column order; the new entries of that one row are then
+ * insertion-sorted by degree (stable); a new seed follows whenever a component is exhausted; the order is reversed at the end.
+ * The engine runs it level by level: each unvisited neighbour j of level L takes as parent the smallest position in the order
+ * among its neighbours in level L, and level L + 1 is the claimed vertices sorted by (parent position, degree[j], j) -- equal to
+ * the sequential search element for element.  The claim is an integer minimum: the result is the same on every run.
+ * The engine's rule: seeds are taken in (degree, id) order, which is the stable sort.  Everything else follows scipy.  scipy
+ * takes its seeds from numpy's default, unstable argsort of the degrees: which of several unvisited vertices of equal least
+ * degree it picks depends on numpy's sort kernel.  Where scipy's answer does not depend on its tie order, the engine equals
+ * scipy exactly.  Elsewhere it equals the restatement (the same loop with a stable argsort).
+ * levels_out (or NULL): the breadth-first levels run, every seed being a level of one.  The host reads one word per chunk of
+ * levels, not per level; no kernel waits for another block. */
+int xr_graph_rcm_dev(const xr_graph *graph, int64_t *order_dev, int64_t *levels_out);
+/* A new mesh with the nodes of `mesh` (all of them, used or not, coordinates copied) and the face table
+ * faces[order_dev[i], :] (order_dev int64 [n_face], a device pointer; an id outside [0, n_face) is XR_ERR_INVALID). */
+int xr_mesh_reorder_faces_dev(const xr_mesh *mesh, const int64_t *order_dev, xr_mesh **out);
+
 /* ---- filling NaN entries of a network along its edges (xugrid Ugrid1d._nearest_interpolate: multi-source dijkstra) ---- */
 /* The graph of a network (node_xy_dev float64 [n_node, 2], edges_dev int64 [n_edge, 2], device pointers) for the nearest calls below.
  * facet XR_FACET_NODE: the reference's node_node_connectivity over ALL n_node nodes (unused nodes: empty rows), columns ascending,

@@ -148,6 +148,8 @@ SIGNATURES = {
     "xr_graph_label_rounds": (c_int, [vp, p_i64]),
     "xr_graph_components_dev": (c_int, [vp, vp, p_i64]),
     "xr_graph_binary_iterate_dev": (c_int, [vp, vp, vp, c_i64, c_int, c_i64, vp, vp]),
+    "xr_graph_rcm_dev": (c_int, [vp, vp, p_i64]),
+    "xr_mesh_reorder_faces_dev": (c_int, [vp, vp, p_vp]),
     "xr_topology_facet_map_dev": (c_int, [vp, c_int, c_int, c_int, vp, c_int, c_i64, vp]),
     "xr_topology_facet_width": (c_int, [vp, c_int, c_int, p_i64]),
     "xr_facet_map_dev": (c_int, [vp, vp, c_i64, c_i64, c_i64, c_int, vp, c_int, c_i64, vp]),

@@ -107,6 +107,8 @@ def _symmetric_csr(a, b, edge, n):
 
 def face_face_connectivity(edge_face_connectivity, n_face):
     """Faces that share an edge; data = the shared edge's id."""
+    if edge_face_connectivity.shape[1] < 2:  # (the table is as wide as the busiest edge: no edge is shared)
+        return sparse.csr_matrix((n_face, n_face), dtype=IntDType)
     inner = edge_face_connectivity[:, 1] != FILL_VALUE
     edge = np.nonzero(inner)[0].astype(IntDType)
     return _symmetric_csr(edge_face_connectivity[inner, 0], edge_face_connectivity[inner, 1], edge, n_face)

@@ -85,41 +85,12 @@ k_net_sort_short(const int32_t *__restrict__ ptr, int64_t n, T *key, int32_t *__
     }
 }
 
-template <typename T> __device__ __forceinline__ void net_order(T *row, int64_t l, int64_t p) {
-    const T a = row[l], b = row[p];
-    if (a > b) {
-        row[l] = b;
-        row[p] = a;
-    }
-}
-
-// one block per long row, any length: a bitonic network in which every comparison puts the smaller key first (the first step
-// of a merge pairs l with its mirror image in the run, the others pair l with l + j).  The row is thought padded with +inf to
-// a power of two; a pair whose upper element is padding changes nothing and is skipped, so padding never moves.
+// one block per long row, any length (block_sort_ascending, xr_prims.h)
 template <typename T>
 __global__ void __launch_bounds__(NB)
 k_net_sort_long(const int32_t *__restrict__ ptr, const int32_t *__restrict__ rows, T *key) {
     const int32_t r = rows[blockIdx.x];
-    const int64_t L = ptr[r + 1] - ptr[r];
-    T *row = key + ptr[r];
-    int64_t P = 1;
-    while (P < L) P <<= 1;
-    for (int64_t k = 2; k <= P; k <<= 1) {
-        const int64_t half = k >> 1;
-        for (int64_t t = threadIdx.x; t < (P >> 1); t += NB) {
-            const int64_t base = (t / half) * k, off = t & (half - 1);
-            const int64_t l = base + off, p = base + k - 1 - off;
-            if (p < L) net_order(row, l, p);
-        }
-        __syncthreads();
-        for (int64_t j = half >> 1; j > 0; j >>= 1) {
-            for (int64_t t = threadIdx.x; t < (P >> 1); t += NB) {
-                const int64_t l = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = l + j;
-                if (p < L) net_order(row, l, p);
-            }
-            __syncthreads();
-        }
-    }
+    block_sort_ascending<NB>(key + ptr[r], (int64_t)ptr[r + 1] - ptr[r]);
 }
 
 // sorted node rows -> indices (the neighbour), data (the edge's length); counters[2] counts the repeated node pairs, each at the

@@ -4,40 +4,13 @@
 // scan_fused_tiles (> 0) moves that limit -- read on the host only, no result depends on it (tests/test_gpu_scan.py forces the
 // three-kernel path with a tiny one).
 #include "xr_internal.h"
+#include "xr_prims.h"
 
 namespace xr {
 
 static constexpr int SCAN_BLOCK = 256;
 static constexpr int SCAN_ITEMS = 8; // per thread
 static constexpr int SCAN_TILE = SCAN_BLOCK * SCAN_ITEMS;
-
-__device__ __forceinline__ int wave_incl_scan(int v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        int t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-
-// block-wide exclusive scan of one value per thread; returns exclusive prefix, total via *total
-__device__ __forceinline__ int block_excl_scan(int v, int *total, int *lds /* >= 4 ints */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = wave_incl_scan(v);
-    if (lane == 63) lds[wave] = incl;
-    __syncthreads();
-    int woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < SCAN_BLOCK / 64; w++) {
-        int s = lds[w];
-        if (w < wave) woff += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return woff + incl - v;
-}
 
 // a thread's SCAN_ITEMS consecutive elements as two 16-byte accesses (the tile base and every thread's offset are multiples of
 // eight elements, the arrays come from the pool: 32-byte aligned); element by element only in the one tile that holds the end.

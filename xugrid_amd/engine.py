@@ -416,6 +416,12 @@ class DeviceMesh(Handle):
         check(_lib.load().xr_mesh_subset_node_index_dev(self._h, ctypes.c_void_p(ptr)))
         return out
 
+    def reorder_faces(self, order_ptr) -> "DeviceMesh":
+        """A mesh with this mesh's nodes (all of them) and the faces ``faces[order]`` (an int64 device pointer, ``n_face`` ids)."""
+        handle = ctypes.c_void_p()
+        check(_lib.load().xr_mesh_reorder_faces_dev(self._h, vp(order_ptr), ctypes.byref(handle)))
+        return DeviceMesh._from_handle(handle)
+
     def box_faces(self, xmin, ymin, xmax, ymax) -> "DeviceIndex":
         """``locate_bounding_box`` on the mesh's device centroids."""
         handle = ctypes.c_void_p()

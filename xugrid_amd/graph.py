@@ -2,7 +2,10 @@
 Graph operations on a symmetric adjacency on the device: ``connected_components`` (scipy.sparse.csgraph's numbering) and the
 binary morphology of xugrid/ugrid/connectivity.py:791-877 (``binary_dilation`` / ``binary_erosion``).  Kernels in
 ``csrc/xr_fill.hip`` (k_comp_*, k_binary_step); the functions here take a scipy CSR like ``fill.laplace_interpolate``, the
-``Ugrid2d`` methods hand in the grid's device graph.
+``Ugrid2d`` methods hand in the grid's device graph.  ``reverse_cuthill_mckee`` (kernels in ``csrc/xr_rcm.hip``) renumbers the
+rows as ``scipy.sparse.csgraph.reverse_cuthill_mckee(..., symmetric_mode=True)`` does, with one stated difference: seeds are
+taken in ``(degree, id)`` order, the stable sort, where scipy's unstable argsort picks among equal degrees as numpy's sort
+kernel happens to (include/xugrid_amd.h: xr_graph_rcm_dev).
 
 Binary iteration, restated: one iteration is a Jacobi step on a snapshot -- an entry becomes ``value`` (True for dilation,
 False for erosion) iff a neighbour's old state differs from its own.  After every step the entries of ``mask`` are set to
@@ -113,6 +116,26 @@ def components(graph: DeviceGraph):
     return out.download()
 
 
+RCM_BLOCK = 256  # RB, csrc/xr_rcm.hip: positions of a level one block of the level kernels takes per turn
+RCM_GRID = 1024  # RCM_GRID, csrc/xr_rcm.hip: blocks of a level kernel at most (a wider level takes several turns)
+last_levels = None  # breadth-first levels the last renumbering ran (tests and profiles read it)
+
+
+def rcm_dev(graph: DeviceGraph):
+    """The reverse Cuthill-McKee order of ``graph`` as an int64 ``DeviceArray`` ``(n,)``: new row ``i`` is old row ``order[i]``."""
+    global last_levels
+    levels = ctypes.c_int64()
+    out = engine.DeviceArray((graph.n,), np.int64)
+    check(_lib.load().xr_graph_rcm_dev(graph._h, ctypes.c_void_p(out.ptr), ctypes.byref(levels)))
+    last_levels = levels.value
+    return out
+
+
+def rcm(graph: DeviceGraph):
+    """``rcm_dev`` as int64 numpy ``(n,)``."""
+    return rcm_dev(graph).download()
+
+
 def _graph_of(connectivity):
     _check_square(connectivity)
     csr = connectivity.tocsr()
@@ -123,6 +146,15 @@ def _graph_of(connectivity):
 def connected_components(connectivity):
     """Component number per row of the symmetric scipy CSR ``connectivity``, as ``scipy.sparse.csgraph.connected_components``."""
     return components(_graph_of(connectivity))
+
+
+def reverse_cuthill_mckee(connectivity):
+    """The permutation ``scipy.sparse.csgraph.reverse_cuthill_mckee(connectivity, symmetric_mode=True)`` gives for the symmetric
+    scipy CSR ``connectivity``, its seeds taken in ``(degree, id)`` order (see the module docstring)."""
+    _check_square(connectivity)
+    csr = connectivity.tocsr().copy()  # (the caller's matrix keeps its repeated entries)
+    csr.sum_duplicates()
+    return rcm(_graph_of(csr))
 
 
 def binary_dilation(connectivity, input, iterations=1, mask=None, exterior=None, border_value=False):

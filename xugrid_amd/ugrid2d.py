@@ -10,7 +10,7 @@ import numpy as np
 
 import ctypes
 
-from . import _lib, connectivity, facet, fill, graph, sample, snap
+from . import _lib, connectivity, engine, facet, fill, graph, sample, snap
 from .celltree import CellTree2d
 from .engine import FloatDType, IntDType
 
@@ -347,6 +347,30 @@ class Ugrid2d:
         ``scipy.sparse.csgraph.connected_components`` on the adjacency (dataarray_accessor.py:691-708); labelled on the device."""
         facet = fill.resolve_dim(self, dim, ("node", "face"))
         return graph.components(self._graph(facet))
+
+    def reverse_cuthill_mckee(self, dimension=None, data=None, return_device=False):
+        """The grid with its faces renumbered to reduce the bandwidth of ``face_face_connectivity`` (ugrid2d.py:1734-1756) ->
+        ``(reordered_grid, reordering)``: a grid of this grid's kind with the same nodes (unused ones included) and the faces
+        ``face_node_connectivity[reordering]``.  The order is ``scipy.sparse.csgraph.reverse_cuthill_mckee``'s with seeds taken
+        in ``(degree, id)`` order (``graph.reverse_cuthill_mckee``), computed on the device; for a grid whose mesh lives in HBM
+        the face table is gathered there too.  ``reordering``: int64 numpy, or with ``return_device`` on such a grid an int64
+        device array (of ``data``'s kind when ``data`` is a device array).  ``dimension``: ``None`` or the face dimension
+        (nodes are not renumbered), else ``ValueError``.  ``data`` ``(..., n_face)``: also returned, gathered along its last
+        axis (numpy in -> numpy out, device array in -> float64 device array out)."""
+        from . import subset
+
+        if dimension is not None and dimension != self.face_dimension:
+            raise ValueError(f"reverse_cuthill_mckee renumbers {self.face_dimension} only, received: {dimension}")
+        index = subset.Index(dev=graph.rcm_dev(self._graph("face")))
+        data_on_device = data is not None and engine.device_array_info(data) is not None
+        if self._device_resident:
+            grid = self._grid_from_mesh(self.device_mesh.reorder_faces(index.ptr()))
+        else:
+            grid = Ugrid2d(self.node_x, self.node_y, FILL_VALUE, self.face_node_connectivity[index.numpy()], name=self.name)
+        out = [grid, index.emit(data if data_on_device else None, not (return_device and self._device_resident))]
+        if data is not None:
+            out.append(sample.gather_points(data, self.n_face, index.device() if data_on_device else index.numpy()))
+        return tuple(out)
 
     def _binary(self, data, value, iterations, mask, border_value):
         exterior = self._exterior_face_flags() if bool(border_value) == bool(value) else None
