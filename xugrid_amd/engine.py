@@ -174,6 +174,17 @@ class Handle:
             self._h = None
 
 
+class CopyHandle(Handle):
+    """A handle whose arrays are copied out by number: ``_copy_dev`` names the C function ``(handle, what, destination)``."""
+
+    _copy_dev = None
+
+    def _copy(self, what, shape, dtype, like=None):
+        out, ptr = empty_like_device(like, shape, dtype)
+        check(getattr(_lib.load(), self._copy_dev)(self._h, what, vp(ptr)))
+        return out
+
+
 class DeviceArray(Handle):
     """An array in the engine's HBM (xr_dev_alloc): what ``Regridder.regrid`` returns for device input that is not a torch
     tensor, and a way to put host arrays there once.  Exposes ``__cuda_array_interface__`` (version 3), so torch / cupy can wrap
@@ -538,13 +549,14 @@ def index_mismatch(a_ptr, b_ptr, n):
     return count.value
 
 
+FACET_IDS = {"node": 0, "edge": 1, "face": 2}  # include/xugrid_amd.h: XR_FACET_NODE, _EDGE, _FACE
+
+
 class DeviceMerge(Handle):
     """Meshes joined on the device (include/xugrid_amd.h: xr_merge): the merged mesh, the merged id of every concatenated
     node and, per partition, the ascending local ids of its kept nodes, faces and (after ``add_edges``) edges."""
 
     _destroy = "xr_merge_destroy"
-
-    FACETS = {"node": 0, "edge": 1, "face": 2}
 
     def __init__(self, meshes):
         self._meshes = list(meshes)  # (kept alive for the call)
@@ -569,9 +581,9 @@ class DeviceMerge(Handle):
         """int64 device array of the kind of ``like``: the local ids of partition ``part``'s kept rows (``part=-1``: all
         kept rows as ids into the concatenation); ``position``: the merged grid's own id of each kept edge instead."""
         n = ctypes.c_int64()
-        check(_lib.load().xr_merge_index_info(self._h, self.FACETS[facet], int(part), ctypes.byref(n)))
+        check(_lib.load().xr_merge_index_info(self._h, FACET_IDS[facet], int(part), ctypes.byref(n)))
         out, ptr = empty_like_device(like, (n.value,), np.int64)
-        check(_lib.load().xr_merge_index_copy_dev(self._h, self.FACETS[facet], int(part), int(bool(position)), ctypes.c_void_p(ptr)))
+        check(_lib.load().xr_merge_index_copy_dev(self._h, FACET_IDS[facet], int(part), int(bool(position)), ctypes.c_void_p(ptr)))
         return out
 
     def node_inverse(self, like=None):
@@ -586,8 +598,6 @@ class DevicePeriodic(Handle):
     left and right boundaries do not match: ``problems = (the counts differ, pairs of y apart)``."""
 
     _destroy = "xr_periodic_destroy"
-
-    FACETS = {"node": 0, "edge": 1, "face": 2}
 
     def __init__(self, handle, mesh, wrapped):
         self._h, self._mesh, self.wrapped = handle, mesh, wrapped  # (the source mesh is kept alive for the edges)
@@ -621,8 +631,8 @@ class DevicePeriodic(Handle):
         """int64 device array of the kind of ``like``: for every node, edge or face of the new mesh the one of the old mesh."""
         sizes = (ctypes.c_int64 * 3)()
         check(_lib.load().xr_periodic_info(self._h, sizes))
-        out, ptr = empty_like_device(like, (max(int(sizes[self.FACETS[facet]]), 0),), np.int64)
-        check(_lib.load().xr_periodic_index_copy_dev(self._h, self.FACETS[facet], ctypes.c_void_p(ptr)))
+        out, ptr = empty_like_device(like, (max(int(sizes[FACET_IDS[facet]]), 0),), np.int64)
+        check(_lib.load().xr_periodic_index_copy_dev(self._h, FACET_IDS[facet], ctypes.c_void_p(ptr)))
         return out
 
     def node_inverse(self, like=None):
@@ -632,11 +642,12 @@ class DevicePeriodic(Handle):
         return out
 
 
-class DeviceNetEdit(Handle):
+class DeviceNetEdit(CopyHandle):
     """The result of one network edit on the device (include/xugrid_amd.h: xr_netedit): the new network and the indexes that came
     with it.  A network goes in as two device pointers, ``node_xy`` float64 ``(n_node, 2)`` and ``edges`` int64 ``(n_edge, 2)``."""
 
     _destroy = "xr_netedit_destroy"
+    _copy_dev = "xr_netedit_copy_dev"
 
     NODE_XY, EDGES, NODE_INDEX, PARENT_EDGE, NODE_INVERSE, OFF_EDGE = range(6)
 
@@ -671,11 +682,6 @@ class DeviceNetEdit(Handle):
                                                 float(tolerance), ctypes.byref(handle), ctypes.byref(off)))
         return cls(handle), off.value
 
-    def _copy(self, what, shape, dtype, like=None):
-        out, ptr = empty_like_device(like, shape, dtype)
-        check(_lib.load().xr_netedit_copy_dev(self._h, what, vp(ptr)))
-        return out
-
     def node_xy(self):
         return self._copy(self.NODE_XY, (self.n_node, 2), np.float64)
 
@@ -706,11 +712,12 @@ class DeviceNetEdit(Handle):
         return out
 
 
-class DeviceSnap(Handle):
+class DeviceSnap(CopyHandle):
     """The result of one ``snap_nodes`` on the device (include/xugrid_amd.h: xr_snap).  ``n_pair == 0``: nothing lay within the
     distance and the handle holds no arrays."""
 
     _destroy = "xr_snap_destroy"
+    _copy_dev = "xr_snap_copy_dev"
 
     INVERSE, INDEX, XY, X, Y = range(5)
     SWEEPS = 4  # include/xugrid_amd.h: XR_SNAP_SWEEPS, the passes over a point's row per launch of a decision round
@@ -722,11 +729,6 @@ class DeviceSnap(Handle):
         n_kept, n_pair, rounds = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         check(_lib.load().xr_snap_info(handle, ctypes.byref(n_kept), ctypes.byref(n_pair), ctypes.byref(rounds)))
         self.n, self.n_kept, self.n_pair, self.rounds = int(n), n_kept.value, n_pair.value, rounds.value
-
-    def _copy(self, what, shape, dtype, like=None):
-        out, ptr = empty_like_device(like, shape, dtype)
-        check(_lib.load().xr_snap_copy_dev(self._h, what, vp(ptr)))
-        return out
 
     def inverse(self, like=None):
         return self._copy(self.INVERSE, (self.n,), np.int64, like)

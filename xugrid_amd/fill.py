@@ -122,7 +122,7 @@ def _as_slices(data, n):
     if info is not None:
         ptr, shape, dtype = info
         if dtype != np.float64:
-            if (type(data).__module__ or "").startswith("torch"):
+            if engine.is_torch(data):
                 data = data.double()
                 ptr, shape, dtype = engine.device_array_info(data)
             else:

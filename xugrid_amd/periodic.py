@@ -20,8 +20,10 @@ over the host tables otherwise.
 """
 import numpy as np
 
-from . import engine, partition, sample
-from .subset import FACETS
+from . import engine
+from .inkind import Index, data_facet, device_topologies, host_edge_node, result_kind
+
+FACETS = ("node", "edge", "face")
 
 Y_MISMATCH = "y-coordinates of the left and right boundaries do not match"
 NO_COUNTERPART = ("Cannot map edge-associated data onto the non-periodic grid:\n"
@@ -32,7 +34,7 @@ NO_COUNTERPART = ("Cannot map edge-associated data onto the non-periodic grid:\n
 
 def _edges_numpy(grid, new, handle):
     """The edge index over the host tables (both grids' derived edges are (lower, higher) rows in lexicographic order)."""
-    old_edges, new_edges = partition._host_edge_node(grid), partition._host_edge_node(new)
+    old_edges, new_edges = host_edge_node(grid), host_edge_node(new)
     if len(new_edges) == 0:
         return np.zeros(0, dtype=np.int64)
     width = max(grid.n_node, new.n_node, 1)
@@ -51,48 +53,31 @@ def _edges_numpy(grid, new, handle):
 
 
 def _edge_index(grid, new, handle, like):
-    """-> the edge index: a device array from the device topologies, or numpy from the host route."""
-    topologies = partition._device_topologies([grid], new)
+    """-> the edge ``Index``: from the device topologies, or from the host route."""
+    topologies = device_topologies([grid], new)
     if topologies is None:
-        return _edges_numpy(grid, new, handle)
+        return Index(host=_edges_numpy(grid, new, handle))
     if handle.add_edges(topologies[0], topologies[1]):
         raise ValueError(NO_COUNTERPART)
-    return handle.index("edge", like)
+    return Index(dev=handle.index("edge", like))
 
 
 def _convert(grid, handle, data, facet, return_index):
-    like = data if data is not None and engine.is_torch(data) else None
-    to_numpy = like is None and not grid._device_resident
+    like, to_numpy = result_kind(grid, data if data is not None and engine.is_torch(data) else None)
     new = grid._grid_from_mesh(handle.take_mesh())
     out = [new]
     need = set(FACETS) if return_index else ({facet} if facet else set())
-    indexes = {f: (_edge_index(grid, new, handle, like) if f == "edge" else handle.index(f, like)) for f in need}
+    indexes = {f: (_edge_index(grid, new, handle, like) if f == "edge" else Index(dev=handle.index(f, like))) for f in need}
     if return_index:
-        def emit(a):
-            if isinstance(a, np.ndarray):
-                return a if to_numpy else engine.upload_like(a, like)
-            return partition._emit(a, to_numpy)
-
-        dims = {"node": grid.node_dimension, "edge": grid.edge_dimension, "face": grid.face_dimension}
-        out.append({dims[f]: emit(indexes[f]) for f in FACETS})
+        out.append({getattr(grid, f"{f}_dimension"): indexes[f].emit(like, to_numpy) for f in FACETS})
     if data is not None:
-        by = indexes[facet]
-        if engine.device_array_info(data) is None:
-            by = by if isinstance(by, np.ndarray) else engine.download(by)
-        elif isinstance(by, np.ndarray):
-            by = engine.upload_like(by, data)
-        out.append(sample.gather_points(data, getattr(grid, f"n_{facet}"), by))
+        out.append(indexes[facet].gather(data, getattr(grid, f"n_{facet}")))
     return out[0] if len(out) == 1 else tuple(out)
-
-
-def _facet(grid, data, dim):
-    """The facet ``data`` lives on, before any work is done (None without data)."""
-    return partition._merge_facet([grid], [data], dim) if data is not None else None
 
 
 def to_periodic(grid, data=None, dim=None, return_index=False):
     """See ``Ugrid2d.to_periodic``."""
-    facet = _facet(grid, data, dim)
+    facet = data_facet(grid, data, dim) if data is not None else None  # (before any work is done)
     handle, _ = engine.DevicePeriodic.wrap(grid.device_mesh)
     if handle is None:
         raise ValueError(Y_MISMATCH)
@@ -101,5 +86,5 @@ def to_periodic(grid, data=None, dim=None, return_index=False):
 
 def to_nonperiodic(grid, xmax, data=None, dim=None, return_index=False):
     """See ``Ugrid2d.to_nonperiodic``."""
-    facet = _facet(grid, data, dim)
+    facet = data_facet(grid, data, dim) if data is not None else None
     return _convert(grid, engine.DevicePeriodic.unwrap(grid.device_mesh, float(xmax)), data, facet, return_index)

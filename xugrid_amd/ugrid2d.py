@@ -357,11 +357,11 @@ class Ugrid2d:
         device array (of ``data``'s kind when ``data`` is a device array).  ``dimension``: ``None`` or the face dimension
         (nodes are not renumbered), else ``ValueError``.  ``data`` ``(..., n_face)``: also returned, gathered along its last
         axis (numpy in -> numpy out, device array in -> float64 device array out)."""
-        from . import subset
+        from .inkind import Index
 
         if dimension is not None and dimension != self.face_dimension:
             raise ValueError(f"reverse_cuthill_mckee renumbers {self.face_dimension} only, received: {dimension}")
-        index = subset.Index(dev=graph.rcm_dev(self._graph("face")))
+        index = Index(dev=graph.rcm_dev(self._graph("face")))
         data_on_device = data is not None and engine.device_array_info(data) is not None
         if self._device_resident:
             grid = self._grid_from_mesh(self.device_mesh.reorder_faces(index.ptr()))
@@ -369,7 +369,7 @@ class Ugrid2d:
             grid = Ugrid2d(self.node_x, self.node_y, FILL_VALUE, self.face_node_connectivity[index.numpy()], name=self.name)
         out = [grid, index.emit(data if data_on_device else None, not (return_device and self._device_resident))]
         if data is not None:
-            out.append(sample.gather_points(data, self.n_face, index.device() if data_on_device else index.numpy()))
+            out.append(index.gather(data, self.n_face))
         return tuple(out)
 
     def _binary(self, data, value, iterations, mask, border_value):
