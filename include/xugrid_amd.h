@@ -998,6 +998,39 @@ int xr_snap_destroy(xr_snap *snap);
 int xr_nn_snap_dev(const xr_nn *to_index, const double *x_dev, const double *y_dev, int64_t stride, int64_t n, double max_distance,
                    double *x_out_dev, double *y_out_dev, int64_t out_stride, int64_t *index_out_dev, int64_t *n_tied);
 
+/* ---- snapping lines to mesh edges (xugrid.create_snap_to_grid_dataframe and snap_to_grid, xugrid/ugrid/snapping.py:255-552);
+ * xr_snapgrid.hip, DESIGN section 21.  Every pointer argument is device memory and the inputs are only read.
+ *
+ * xr_snapgrid_create_dev: coords_dev float64[n_vertex, 2] and line_offsets_dev int64[n_line + 1] (start at 0, end at n_vertex,
+ * never decrease: checked on the device, XR_ERR_INVALID otherwise) are the vertices of n_line lines; `topology` is the
+ * xr_topology of `mesh` (manifold), `node_index` the xr_nn over the mesh's nodes.
+ *   snap      every vertex moves onto the nearest node within max_snap_distance (xr_nn_snap_dev, lowest id among equidistant ones)
+ *   segments  segment i joins vertex i to the next vertex of its line, the last vertex of a line to itself (no piece)
+ *   pieces    the entries of xr_edge_length_csr_dev, their end points recomputed with the arithmetic of xr_edge_pieces
+ *   rows      snap_to_edges (:289-325) per piece: widened by tolerance * max(|Ux|, |Uy|) along sign(U), strict left_of, exterior
+ *             edges skipped, a face's edges in ascending id; one row per (piece, edge) that passes
+ *   order     rows by segment, then face, then edge (within a segment the reference's order is that of its tree traversal)
+ *   reduce    (reduce != 0) per edge the row of greatest length, the first in row order among equal ones
+ * A NaN or infinite coordinate is XR_ERR_INVALID ("data must be finite"); n_vertex, the number of pieces or of rows >= 2^30 is
+ * XR_ERR_LIMIT.
+ * xr_snapgrid_copy_dev: the frame's columns XR_SNAPGRID_LINE / _EDGE int64[n_row], _X0 / _Y0 / _X1 / _Y1 / _LENGTH float64[n_row]
+ * (the un-widened piece and its SQUARED length, :491); of a reduced handle also XR_SNAPGRID_LINE_INDEX float64[n_edge] (the
+ * winning line, NaN for none), XR_SNAPGRID_EDGES int64[n_snapped] (the edges with a line, ascending) and XR_SNAPGRID_EDGE_LINES
+ * int64[n_snapped] (their lines).  xr_snapgrid_values_dev: out_dev float64[K, n_edge] = values_dev[K, n_line] of every edge's
+ * winning line, NaN for none. */
+typedef struct xr_snapgrid xr_snapgrid;
+enum {
+    XR_SNAPGRID_LINE = 0, XR_SNAPGRID_EDGE = 1, XR_SNAPGRID_X0 = 2, XR_SNAPGRID_Y0 = 3, XR_SNAPGRID_X1 = 4, XR_SNAPGRID_Y1 = 5,
+    XR_SNAPGRID_LENGTH = 6, XR_SNAPGRID_LINE_INDEX = 7, XR_SNAPGRID_EDGES = 8, XR_SNAPGRID_EDGE_LINES = 9
+};
+int xr_snapgrid_create_dev(xr_mesh *mesh, const xr_topology *topology, const xr_nn *node_index, const double *coords_dev,
+                           int64_t n_vertex, const int64_t *line_offsets_dev, int64_t n_line, double max_snap_distance,
+                           double tolerance, int reduce, xr_snapgrid **out);
+int xr_snapgrid_info(const xr_snapgrid *snapgrid, int64_t *n_piece, int64_t *n_row, int64_t *n_snapped);
+int xr_snapgrid_copy_dev(const xr_snapgrid *snapgrid, int what, void *out_dev);
+int xr_snapgrid_values_dev(const xr_snapgrid *snapgrid, const double *values_dev, int64_t K, double *out_dev);
+int xr_snapgrid_destroy(xr_snapgrid *snapgrid);
+
 /* ---- raw HBM helpers for hosts that do not bring their own allocator -------------------- */
 int xr_dev_alloc(int64_t bytes, void **ptr_out);
 int xr_dev_free(void *ptr);

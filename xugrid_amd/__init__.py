@@ -24,6 +24,7 @@ from .regrid import (  # noqa: F401
     RelativeOverlapRegridder,
 )
 from .snap import snap_nodes, snap_to_nodes  # noqa: F401
+from .snapgrid import create_snap_to_grid_dataframe, snap_to_grid  # noqa: F401
 from .sparse import MatrixCOO, MatrixCSR  # noqa: F401
 from .topology import DeviceTopology  # noqa: F401
 from .ugrid1d import Ugrid1d  # noqa: F401

@@ -220,6 +220,11 @@ SIGNATURES = {
     "xr_snap_relabel_dev": (c_int, [vp, vp, c_i64, vp]),
     "xr_snap_destroy": (c_int, [vp]),
     "xr_nn_snap_dev": (c_int, [vp, vp, vp, c_i64, c_i64, c_f64, vp, vp, c_i64, vp, p_i64]),
+    "xr_snapgrid_create_dev": (c_int, [vp, vp, vp, vp, c_i64, vp, c_i64, c_f64, c_f64, c_int, p_vp]),
+    "xr_snapgrid_info": (c_int, [vp, p_i64, p_i64, p_i64]),
+    "xr_snapgrid_copy_dev": (c_int, [vp, c_int, vp]),
+    "xr_snapgrid_values_dev": (c_int, [vp, vp, c_i64, vp]),
+    "xr_snapgrid_destroy": (c_int, [vp]),
     "xr_dev_alloc": (c_int, [c_i64, p_vp]),
     "xr_dev_free": (c_int, [vp]),
     "xr_dev_upload": (c_int, [vp, vp, c_i64]),

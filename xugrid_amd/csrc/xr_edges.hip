@@ -16,6 +16,7 @@
 
 #include "xr_objects.h"
 #include "xr_agg.h"
+#include "xr_edge_clip.h"
 
 namespace xr {
 
@@ -23,44 +24,6 @@ static constexpr int EDGE_WALK_PAD = 8;    // records of padding behind rec_bb (
 static constexpr int EDGE_BIG_CELLS = 64;  // edges whose box covers more grid cells (all levels) get a wave of their own
 static constexpr int ROW_SORT_SMALL = 16;  // rows up to this length are insertion-sorted by one thread (k_edge_rows_sort)
 static constexpr int ROW_SORT_LDS = 4096;  // rows up to this length are sorted in LDS by one block
-
-// a + t (b - a), t in [0, 1], against every half-plane of the CCW polygon.  -> length of the clipped piece, or -1;
-// its end points in c / d when asked for
-__device__ __forceinline__ double cyrus_beck_length(const double *__restrict__ poly, int n, P2 a, P2 b,
-                                                    P2 *c = nullptr, P2 *d = nullptr) {
-    const double sx = b.x - a.x, sy = b.y - a.y;
-    double t0 = 0.0, t1 = 1.0;
-    P2 v0 = load_p2(poly, 0);
-    for (int i = 0; i < n; i++) {
-        const P2 v1 = load_p2(poly, (i + 1 < n) ? i + 1 : 0);
-        const double wx = v1.x - v0.x, wy = v1.y - v0.y;
-        if (wx != 0.0 || wy != 0.0) {
-            const double nx = -wy, ny = wx; // inward normal of a CCW polygon
-            const double den = nx * sx + ny * sy;
-            const double num = nx * (v0.x - a.x) + ny * (v0.y - a.y);
-            if (den == 0.0) {
-                if (num > 0.0) return -1.0; // parallel and outside
-            } else {
-                const double t = num / den;
-                if (den > 0.0) {
-                    if (t > t0) t0 = t;
-                } else {
-                    if (t < t1) t1 = t;
-                }
-            }
-        }
-        v0 = v1;
-    }
-    if (!(t0 < t1)) return -1.0;
-    const double cx = a.x + t0 * sx, cy = a.y + t0 * sy;
-    const double dx = a.x + t1 * sx, dy = a.y + t1 * sy;
-    if (c) {
-        *c = P2{cx, cy};
-        *d = P2{dx, dy};
-    }
-    const double ex = dx - cx, ey = dy - cy;
-    return sqrt(ex * ex + ey * ey);
-}
 
 // the same clip on a polygon held in registers (MP slots, n <= MP corners; static indices): every operation of
 // cyrus_beck_length in the same order -- only the vertex loads have moved in front of the loop

@@ -752,6 +752,45 @@ class DeviceSnap(CopyHandle):
         return out
 
 
+class DeviceSnapGrid(CopyHandle):
+    """The frame of one ``create_snap_to_grid_dataframe`` on the device and, with ``reduce``, the winner per edge (include/
+    xugrid_amd.h: xr_snapgrid).  ``mesh``, ``topology`` and ``node_index`` are the grid's handles; the rest are device pointers."""
+
+    _destroy = "xr_snapgrid_destroy"
+    _copy_dev = "xr_snapgrid_copy_dev"
+
+    LINE, EDGE, X0, Y0, X1, Y1, LENGTH, LINE_INDEX, EDGES, EDGE_LINES = range(10)
+
+    def __init__(self, mesh, topology, node_index, coords_ptr, n_vertex, offsets_ptr, n_line, max_snap_distance, tolerance, reduce):
+        handle = ctypes.c_void_p()
+        check(_lib.load().xr_snapgrid_create_dev(mesh._h, topology._h, node_index._h if node_index is not None else None,
+                                                 vp(coords_ptr), int(n_vertex), vp(offsets_ptr), int(n_line),
+                                                 float(max_snap_distance), float(tolerance), int(bool(reduce)), ctypes.byref(handle)))
+        self._h = handle
+        n_piece, n_row, n_snapped = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        check(_lib.load().xr_snapgrid_info(handle, ctypes.byref(n_piece), ctypes.byref(n_row), ctypes.byref(n_snapped)))
+        self.n_edge, self.n_piece, self.n_row, self.n_snapped = topology.n_edge, n_piece.value, n_row.value, n_snapped.value
+
+    def column(self, what, like=None):
+        """One column of the frame: int64 for ``LINE`` / ``EDGE``, float64 for the others."""
+        return self._copy(what, (self.n_row,), np.int64 if what <= self.EDGE else np.float64, like)
+
+    def line_index(self, like=None):
+        return self._copy(self.LINE_INDEX, (self.n_edge,), np.float64, like)
+
+    def edges(self, like=None):
+        return self._copy(self.EDGES, (self.n_snapped,), np.int64, like)
+
+    def edge_lines(self, like=None):
+        return self._copy(self.EDGE_LINES, (self.n_snapped,), np.int64, like)
+
+    def values(self, values_ptr, K, like=None):
+        """``values[K, n_line]`` (a device pointer) of every edge's winning line -> float64 ``(K, n_edge)``, NaN for none."""
+        out, ptr = empty_like_device(like, (K, self.n_edge))
+        check(_lib.load().xr_snapgrid_values_dev(self._h, vp(values_ptr), int(K), vp(ptr)))
+        return out
+
+
 def network_index(name, *args):
     """One of the ascending edge indexes of include/xugrid_amd.h (``xr_network_<name>_dev``) -> ``DeviceIndex``."""
     handle = ctypes.c_void_p()

@@ -1,6 +1,7 @@
 """
 Snapping points: ``snap_nodes`` (xugrid/ugrid/snapping.py:46-143) and ``snap_to_nodes`` (:146-219) on arrays, and the grid
-methods built on them.  Kernels in ``csrc/xr_snap.hip``; DESIGN section 19.  ``snap_to_grid`` and its frame are not here.
+methods built on them.  Kernels in ``csrc/xr_snap.hip``; DESIGN section 19.  ``snap_to_grid`` and its frame are in ``snapgrid.py``, which snaps the line
+vertices through ``grid_snap_to_nodes``'s index.
 
 ``x`` and ``y`` (and ``to_x``, ``to_y``) are 1-D coordinate arrays of one length, both on the host or both on the device.  numpy in
 -> numpy out; device arrays in (``DeviceArray``, torch tensors on the GPU, ``__cuda_array_interface__``, float64) -> device
