@@ -91,18 +91,19 @@ struct StatsTail {
     double seq;
 };
 
-__device__ __forceinline__ void stats_tail(const StatsTail &t, const double (&a)[8], double (*lds)[PREP_BLOCK / 64]) {
+// (bid / nb: the block's index among the nb blocks that share the tail -- the whole grid, or one part of the paired k_prepare_faces')
+__device__ __forceinline__ void stats_tail(const StatsTail &t, const double (&a)[8], double (*lds)[PREP_BLOCK / 64], int64_t bid,
+                                           int64_t nb) {
     __shared__ int s_last;
-    const int64_t nb = gridDim.x;
     if (threadIdx.x == 0) {
-        double *p = t.partials + (int64_t)blockIdx.x * 8;
+        double *p = t.partials + bid * 8;
 #pragma unroll
         for (int i = 0; i < 8; i++) __hip_atomic_store(&p[i], a[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         // Two-level arrival count: thousands of returning atomics on ONE address serialise (~10 ns each: 3900 blocks that
         // finish together = 40 us, measured); STATS_SHARDS counters on lines of their own take 1/STATS_SHARDS of the blocks
         // each, and only the last arrival of a shard goes on to the second-level word.
-        const int shard = (int)(blockIdx.x % STATS_SHARDS);
+        const int shard = (int)(bid % STATS_SHARDS);
         const unsigned in_shard = (unsigned)((nb - shard + STATS_SHARDS - 1) / STATS_SHARDS);
         unsigned *first = t.done + 16 * (1 + shard);
         bool last = false;
@@ -157,14 +158,15 @@ __device__ __forceinline__ void stats_tail(const StatsTail &t, const double (&a)
 
 // LIGHT: statistics only (a mesh that is only ever the TREE: its records are built from the raw mesh by
 // k_spatial_scatter, nothing reads caller-order per-face arrays)
+// (block bid of nb: the body of k_prepare_faces, which its paired form runs too)
 template <int MC, bool LIGHT>
-__global__ void __launch_bounds__(PREP_BLOCK)
-k_prepare_faces(const double *__restrict__ node_xy, const int32_t *__restrict__ faces_raw, int64_t n_face,
-                int m_rt, double *__restrict__ fxy, uint8_t *__restrict__ len_out, double *__restrict__ bbox,
-                double *__restrict__ partials, StatsTail tail) {
+__device__ __forceinline__ void prepare_faces_block(int64_t bid, int64_t nb, const double *__restrict__ node_xy,
+                                                    const int32_t *__restrict__ faces_raw, int64_t n_face, int m_rt,
+                                                    double *__restrict__ fxy, uint8_t *__restrict__ len_out,
+                                                    double *__restrict__ bbox, double *__restrict__ partials, const StatsTail &tail) {
     constexpr int MA = MC > 0 ? MC : XR_MAX_FACE_NODES;
     const int m = MC > 0 ? MC : m_rt;
-    const int64_t f = (int64_t)blockIdx.x * PREP_BLOCK + threadIdx.x;
+    const int64_t f = bid * PREP_BLOCK + threadIdx.x;
 
     double xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY, ext = 0.0, diag = 0.0, jump = 0.0;
     if (f < n_face) {
@@ -219,12 +221,20 @@ k_prepare_faces(const double *__restrict__ node_xy, const int32_t *__restrict__ 
             a3 = fmax(a3, lds[3][w]); a4 += lds[4][w]; a5 = fmax(a5, lds[5][w]); a6 = fmax(a6, lds[6][w]); a7 += lds[7][w];
         }
         if (tail.done == nullptr) { // (separate reduction kernel behind this one)
-            double *p = partials + (int64_t)blockIdx.x * 8;
+            double *p = partials + bid * 8;
             p[0] = a0; p[1] = a1; p[2] = a2; p[3] = a3; p[4] = a4; p[5] = a5; p[6] = a6; p[7] = a7;
         }
         a[0] = a0; a[1] = a1; a[2] = a2; a[3] = a3; a[4] = a4; a[5] = a5; a[6] = a6; a[7] = a7;
     }
-    if (tail.done != nullptr) stats_tail(tail, a, lds);
+    if (tail.done != nullptr) stats_tail(tail, a, lds, bid, nb);
+}
+
+template <int MC, bool LIGHT>
+__global__ void __launch_bounds__(PREP_BLOCK)
+k_prepare_faces(const double *__restrict__ node_xy, const int32_t *__restrict__ faces_raw, int64_t n_face,
+                int m_rt, double *__restrict__ fxy, uint8_t *__restrict__ len_out, double *__restrict__ bbox,
+                double *__restrict__ partials, StatsTail tail) {
+    prepare_faces_block<MC, LIGHT>(blockIdx.x, gridDim.x, node_xy, faces_raw, n_face, m_rt, fxy, len_out, bbox, partials, tail);
 }
 
 // Statistics of a mesh that is only ever the TREE, from a SAMPLE of its faces: the index only needs the bounds (exact:
@@ -235,12 +245,12 @@ k_prepare_faces(const double *__restrict__ node_xy, const int32_t *__restrict__ 
 // statistic with a meaning outside the index -- the largest bbox diagonal behind the default tolerance -- is recomputed over
 // all faces when somebody asks for it (mesh_read_stats(need_exact)).
 template <int MC>
-__global__ void __launch_bounds__(PREP_BLOCK)
-k_sample_stats(const double *__restrict__ node_xy, int64_t n_node, const int32_t *__restrict__ faces_raw, int64_t n_face,
-               int m_rt, int stride, double *__restrict__ partials, StatsTail tail) {
+__device__ __forceinline__ void sample_stats_block(int64_t bid, int64_t nb, const double *__restrict__ node_xy, int64_t n_node,
+                                                   const int32_t *__restrict__ faces_raw, int64_t n_face, int m_rt, int stride,
+                                                   double *__restrict__ partials, const StatsTail &tail) {
     constexpr int MA = MC > 0 ? MC : XR_MAX_FACE_NODES;
     const int m = MC > 0 ? MC : m_rt;
-    const int64_t f = ((int64_t)blockIdx.x * stride) * PREP_BLOCK + threadIdx.x;
+    const int64_t f = (bid * stride) * PREP_BLOCK + threadIdx.x;
     double ext = 0.0, diag = 0.0, cnt = 0.0;
     if (f < n_face) {
         double xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY;
@@ -266,8 +276,8 @@ k_sample_stats(const double *__restrict__ node_xy, int64_t n_node, const int32_t
     }
     // this block's slice of the node array
     double nx0 = INFINITY, nx1 = -INFINITY, ny0 = INFINITY, ny1 = -INFINITY;
-    const int64_t per = (n_node + gridDim.x - 1) / gridDim.x;
-    const int64_t i0 = (int64_t)blockIdx.x * per, i1 = i0 + per < n_node ? i0 + per : n_node;
+    const int64_t per = (n_node + nb - 1) / nb;
+    const int64_t i0 = bid * per, i1 = i0 + per < n_node ? i0 + per : n_node;
     const double2 *nodes = reinterpret_cast<const double2 *>(node_xy);
     for (int64_t i = i0 + threadIdx.x; i < i1; i += PREP_BLOCK) {
         const double2 p = nodes[i];
@@ -293,12 +303,48 @@ k_sample_stats(const double *__restrict__ node_xy, int64_t n_node, const int32_t
             a3 = fmax(a3, lds[3][w]); a4 += lds[4][w]; a5 = fmax(a5, lds[5][w]); a6 = fmax(a6, lds[6][w]); a7 += lds[7][w];
         }
         if (tail.done == nullptr) { // (separate reduction kernel behind this one)
-            double *p = partials + (int64_t)blockIdx.x * 8;
+            double *p = partials + bid * 8;
             p[0] = a0; p[1] = a1; p[2] = a2; p[3] = a3; p[4] = a4; p[5] = a5; p[6] = a6; p[7] = a7;
         }
         a[0] = a0; a[1] = a1; a[2] = a2; a[3] = a3; a[4] = a4; a[5] = a5; a[6] = a6; a[7] = a7;
     }
-    if (tail.done != nullptr) stats_tail(tail, a, lds);
+    if (tail.done != nullptr) stats_tail(tail, a, lds, bid, nb);
+}
+
+template <int MC>
+__global__ void __launch_bounds__(PREP_BLOCK)
+k_sample_stats(const double *__restrict__ node_xy, int64_t n_node, const int32_t *__restrict__ faces_raw, int64_t n_face,
+               int m_rt, int stride, double *__restrict__ partials, StatsTail tail) {
+    sample_stats_block<MC>(blockIdx.x, gridDim.x, node_xy, n_node, faces_raw, n_face, m_rt, stride, partials, tail);
+}
+
+// One front launch for a weight build (mesh_prepare_pair): the first nb_sample blocks are k_sample_stats of the TREE with its
+// tail -- dispatched first, they run BESIDE the blocks behind them, which are k_prepare_faces of the QUERY.  The sampled pass is
+// latency (a tenth of the bytes of the query's pass, on a grid that fills two of every three CUs once): alone it costs a launch of
+// its own at the head of the chain, 17.5 + 30.6 us against 33.5 us for this kernel (1M x 1M step).  Beside
+// the first generation of the query's blocks the sampling blocks take longer than alone: the host has the tree's statistics near
+// the end of the launch (it waits ~12 us where it waited for nothing) and still reaches the index build earlier than before.
+// The two parts share nothing: partials, counters and sequence words are each mesh's own.
+struct SampleArgs {
+    const double *node_xy;
+    int64_t n_node;
+    const int32_t *faces_raw;
+    int64_t n_face;
+    int stride;
+    double *partials;
+    StatsTail tail;
+};
+// (An overload of k_prepare_faces, told apart by its third template argument MT, the tree's nodes per face: the kernel tables
+// of the profiles know the query's preparation by that name, and this is the form it takes in a weight build.)
+template <int MC, bool LIGHT, int MT>
+__global__ void __launch_bounds__(PREP_BLOCK)
+k_prepare_faces(int nb_sample, SampleArgs t, const double *__restrict__ node_xy, const int32_t *__restrict__ faces_raw,
+                int64_t n_face, double *__restrict__ fxy, uint8_t *__restrict__ len_out, double *__restrict__ partials, StatsTail tail) {
+    if ((int)blockIdx.x < nb_sample) // (block-uniform)
+        sample_stats_block<MT>(blockIdx.x, nb_sample, t.node_xy, t.n_node, t.faces_raw, t.n_face, MT, t.stride, t.partials, t.tail);
+    else
+        prepare_faces_block<MC, LIGHT>((int64_t)blockIdx.x - nb_sample, (int64_t)gridDim.x - nb_sample, node_xy, faces_raw, n_face, MC,
+                                       fxy, len_out, nullptr, partials, tail);
 }
 
 // ingest of the caller's connectivity (xr_mesh_create): fill -> -1, narrow to int32, validate
@@ -476,6 +522,20 @@ static StatsTail stats_tail_for(xr_mesh *mesh, double *partials, int64_t nb) {
     return StatsTail{partials, mesh->stats_done.get(), mesh->stats.get(), mesh->stats_host, mesh->stats_seq};
 }
 
+// behind the statistics kernel of a preparation: the reduction of its partials where the kernel's last block does not do it
+static void prepare_done(xr_mesh *mesh, const double *partials, int64_t nb, const StatsTail &tail, bool stats_on_side) {
+    if (!tail.done) {
+        // (a one-block kernel that ends with writes to pinned host memory: ~10 us, which only the host waits for)
+        std::unique_ptr<SideScope> side;
+        if (stats_on_side) side.reset(new SideScope);
+        XR_LAUNCH("reduce_stats", k_reduce_stats, dim3(1), dim3(256), 0, partials, nb, mesh->stats.get(), mesh->stats_host, tail.seq);
+        XR_HIP(hipEventRecord(mesh->stats_event, launch_stream()));
+    }
+    mesh->stats_event_pending = !tail.done;
+    mesh->prepared = true;
+    mesh->stats_valid = false;
+}
+
 void mesh_prepare(xr_mesh *mesh, bool want_fxy, bool stats_on_side, bool allow_sampled) {
     // two depths: statistics only (want_fxy = false: the mesh is used as a tree) or statistics + the caller-order
     // len / bbox / vertex blocks a query needs.  A mesh prepared light and later used as a query is prepared again;
@@ -498,16 +558,7 @@ void mesh_prepare(xr_mesh *mesh, bool want_fxy, bool stats_on_side, bool allow_s
             XR_LAUNCH("sample_stats", k_sample_stats<mc()>, grid, block, 0, mesh->node_xy.get(), mesh->n_node, mesh->faces_raw.get(),
                       F, m, SAMPLE_STRIDE, partials.get(), tail);
         });
-        if (!tail.done) {
-            std::unique_ptr<SideScope> side;
-            if (stats_on_side) side.reset(new SideScope);
-            XR_LAUNCH("reduce_stats", k_reduce_stats, dim3(1), dim3(256), 0, partials.get(), nb, mesh->stats.get(),
-                      mesh->stats_host, tail.seq);
-            XR_HIP(hipEventRecord(mesh->stats_event, launch_stream()));
-        }
-        mesh->stats_event_pending = !tail.done;
-        mesh->prepared = true;
-        mesh->stats_valid = false;
+        prepare_done(mesh, partials.get(), nb, tail, stats_on_side);
         mesh->stats_sampled = true;
         return;
     }
@@ -535,17 +586,53 @@ void mesh_prepare(xr_mesh *mesh, bool want_fxy, bool stats_on_side, bool allow_s
             XR_LAUNCH("prepare_stats", (k_prepare_faces<mc(), true>), grid, block, 0, mesh->node_xy.get(), mesh->faces_raw.get(), F,
                       m, (double *)nullptr, (uint8_t *)nullptr, (double *)nullptr, partials.get(), tail);
     });
-    if (!tail.done) {
-        // (a one-block kernel that ends with writes to pinned host memory: ~10 us, which only the host waits for)
-        std::unique_ptr<SideScope> side;
-        if (stats_on_side) side.reset(new SideScope);
-        XR_LAUNCH("reduce_stats", k_reduce_stats, dim3(1), dim3(256), 0, partials.get(), nb, mesh->stats.get(),
-                  mesh->stats_host, tail.seq);
-        XR_HIP(hipEventRecord(mesh->stats_event, launch_stream()));
+    prepare_done(mesh, partials.get(), nb, tail, stats_on_side);
+}
+
+// The front of a weight build in ONE launch (k_prepare_faces<., ., MT>): the tree's sampled statistics lead the query's preparation.
+// Taken where mesh_prepare(tree, false, true, true) would run k_sample_stats with its in-kernel tail and
+// mesh_prepare(query, true, true) k_prepare_faces of a dense mesh; every other pair gets exactly those two calls.  Both
+// meshes end in the state the two calls leave them in.
+void mesh_prepare_pair(xr_mesh *tree, xr_mesh *query) {
+    const int64_t S = tree->n_face, T = query->n_face;
+    const int64_t nb_sample = div_up(div_up(S, (int64_t)PREP_BLOCK), (int64_t)SAMPLE_STRIDE);
+    const int64_t nb_query = std::max<int64_t>(1, div_up(T, (int64_t)PREP_BLOCK));
+    const auto tri_or_quad = [](const xr_mesh *mesh) { return mesh->m == 3 || mesh->m == 4; }; // (the dense meshes there are)
+    const bool pair = option(OPT_FRONT_FUSED) != 0 && tree != query && tri_or_quad(tree) && tri_or_quad(query) &&
+                      !tree->prepared && S >= SAMPLE_MIN_FACES && !tree->has_attrs && nb_sample <= STATS_TAIL_MAX_BLOCKS &&
+                      !(query->prepared && query->has_attrs && !query->stats_sampled) &&
+                      !(stream_override() || current_lane() || engine().on_side) && nb_sample + nb_query < ((int64_t)1 << 31);
+    if (!pair) {
+        mesh_prepare(tree, false, /*stats_on_side=*/true, /*allow_sampled=*/true); // (bounds exact, mean extent sampled)
+        host_stamp(1);
+        mesh_prepare(query, true, /*stats_on_side=*/true); // (its statistics are first read by mesh_query_order)
+        return;
     }
-    mesh->stats_event_pending = !tail.done;
-    mesh->prepared = true;
-    mesh->stats_valid = false;
+    tree->stats.alloc(8);
+    DevBuf<double> t_partials((size_t)nb_sample * 8);
+    const StatsTail t_tail = stats_tail_for(tree, t_partials.get(), nb_sample); // (in-kernel: the conditions above are its own)
+    query->stats_sampled = false;
+    query->fxy.alloc((size_t)T * query->m * 2);
+    query->len.alloc((size_t)T);
+    query->fxy_valid = true;
+    query->has_attrs = true;
+    query->stats.alloc(8);
+    DevBuf<double> q_partials((size_t)nb_query * 8);
+    const StatsTail q_tail = stats_tail_for(query, q_partials.get(), nb_query);
+    const SampleArgs sample{tree->node_xy.get(), tree->n_node, tree->faces_raw.get(), S, SAMPLE_STRIDE, t_partials.get(), t_tail};
+    const dim3 grid((unsigned)(nb_sample + nb_query)), block(PREP_BLOCK);
+    const auto launch = [&](auto mt, auto mq) {
+        XR_LAUNCH("prepare_faces", (k_prepare_faces<mq(), false, mt()>), grid, block, 0, (int)nb_sample, sample, query->node_xy.get(),
+                  query->faces_raw.get(), T, query->fxy.get(), query->len.get(), q_partials.get(), q_tail);
+    };
+    const std::integral_constant<int, 3> m3;
+    const std::integral_constant<int, 4> m4;
+    if (tree->m == 3) query->m == 3 ? launch(m3, m3) : launch(m3, m4);
+    else query->m == 3 ? launch(m4, m3) : launch(m4, m4);
+    prepare_done(tree, t_partials.get(), nb_sample, t_tail, true);
+    tree->stats_sampled = true;
+    host_stamp(1);
+    prepare_done(query, q_partials.get(), nb_query, q_tail, true);
 }
 
 const double *mesh_area(xr_mesh *mesh) {

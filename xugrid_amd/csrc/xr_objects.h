@@ -182,6 +182,7 @@ struct xr_graph {
 
 namespace xr {
 void label_components(xr_graph *g); // labels = the smallest member id of every component (xr_fill.hip)
+void mesh_prepare_pair(xr_mesh *tree, xr_mesh *query); // the front of a weight build: both preparations, in one launch where it can be
 void mesh_prepare(xr_mesh *mesh, bool want_fxy = true, bool stats_on_side = false, bool allow_sampled = false); // stats_on_side: the reduction of the
     // statistics (only the HOST reads them) leaves the main stream: kernels queued behind the prepare pass do not wait for it
 const double *mesh_area(xr_mesh *mesh); // connectivity.area in the caller's face order (computed on first use)

@@ -1828,9 +1828,9 @@ static void overlap(xr_mesh *tree, xr_mesh *query, bool relative, xr_csr *csr, E
     // the tree side only needs its records (built from the raw mesh).  Its statistics go to the host through a one-block
     // kernel that ends with writes to pinned memory (~20 us): on the side stream as well, beside the preparation of the
     // query mesh, which is what the host waits behind anyway
-    mesh_prepare(tree, false, /*stats_on_side=*/true, /*allow_sampled=*/true); // (bounds exact, mean extent sampled)
-    host_stamp(1);
-    mesh_prepare(query, true, /*stats_on_side=*/true); // (its statistics are first read by mesh_query_order below)
+    // (that was the tree's FULL statistics pass; its sampled pass is latency, a tenth of the query side's bytes, and leads the
+    // query's grid in one launch: mesh_prepare_pair.  The query's statistics are first read by mesh_query_order below)
+    mesh_prepare_pair(tree, query);
     host_stamp(2);
     mesh_build_index(tree);
     host_stamp(3);
