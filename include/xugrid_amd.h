@@ -156,6 +156,8 @@ int xr_mesh_invalidate(xr_mesh *mesh);
 int xr_mesh_area(xr_mesh *mesh, double *area_out);
 /* Face centroids, connectivity.centroids (connectivity.py:636-664) -> float64[n_face,2]. */
 int xr_mesh_centroids(xr_mesh *mesh, double *centroids_out);
+/* ... the same values into device memory float64[n_face,2] (a copy of the array the mesh keeps). */
+int xr_mesh_centroids_dev(xr_mesh *mesh, double *out_dev);
 /* CCW-normalised connectivity as held on the device -> int64[n_face, n_max_node]. */
 int xr_mesh_faces(xr_mesh *mesh, int64_t *faces_out);
 /* The arrays the handle was created from: node_xy float64[n_node, 2] and the connectivity int64[n_face, m] in
@@ -592,6 +594,35 @@ int xr_graph_binary_iterate_dev(const xr_graph *graph, const uint8_t *in_dev, ui
  * levels_out (or NULL): the breadth-first levels run, every seed being a level of one.  The host reads one word per chunk of
  * levels, not per level; no kernel waits for another block. */
 int xr_graph_rcm_dev(const xr_graph *graph, int64_t *order_dev, int64_t *levels_out);
+
+/* ---- balanced part labels (xugrid Ugrid2d.label_partitions / partition, ugridbase.py:1508-1596) --------------------------- */
+/* labels_dev int64 [n] (a device pointer): a label in [0, n_part) for every vertex of the symmetric graph (ascending columns;
+ * the diagonal is ignored), from xy_dev float64 [n, 2] and weights_dev int64 [n], all >= 0 (NULL, or all zero: all ones).
+ * 1 <= n_part <= n, and 100 * n_part * sum(weights) must fit in int64.  The reference hands the graph to METIS, whose
+ * labels are not a function of its input that can be written down; the engine follows this rule (numpy: tests/partlabel_cases.py).
+ * With P = n_part, w the weights, T = sum(w):
+ * 1. Key.  lo, hi = the bounds of xy per axis, side = max(hi_x - lo_x, hi_y - lo_y); the cell of a coordinate v on its axis is
+ *    floor((v - lo) * (65536.0 / max(side, 1e-300))) clamped to [0, 65535] (two IEEE operations, not contracted); the key is
+ *    the 32-bit Hilbert index of (cx, cy): d = 0; for s = 32768, 16384 .. 1: rx = (x & s) > 0, ry = (y & s) > 0,
+ *    d += s * s * ((3 * rx) ^ ry); if ry == 0: (if rx == 1: x = 65535 - x, y = 65535 - y), swap x and y.
+ * 2. Seed.  order = the vertices by (key, id) ascending; before(v) = the sum of w over the vertices in front of v in order;
+ *    label = min(P - 1, before(v) * P / T) in integers.
+ * 3. Refinement.  L = max(ceil(T / P), floor(103 T / (100 P))), Lmin = min(floor(T / P), ceil(97 T / (100 P))); at most 16
+ *    synchronous rounds on a snapshot of the labels, none when P == 1 or floor(T / P) == 0.  In a round, for every vertex v
+ *    with label a: its neighbours (the entries of its row other than v) are counted per label; b = the label other than a with
+ *    the largest count, the smallest such label on a tie; gain = count[b] - count[a]; v is a candidate when gain > 0, and a
+ *    mover unless a neighbour is a candidate that comes first by (gain descending, id ascending) -- movers are an
+ *    independent set, so an accepted move lowers the edge cut by exactly its gain.  With W the parts' weights at the start
+ *    of the round: the movers into b, ranked by (gain descending, id ascending), pass the destination budget while the sum of
+ *    w over the movers into b ranked up to and including them is <= L - W[b]; the movers out of a, ranked the same way, pass
+ *    the source budget while that sum is <= W[a] - Lmin (both sums include movers that fail the other budget).  Movers that
+ *    pass both take label b.  A round that accepts nothing is the last.
+ * Every decision is integer arithmetic or an order-independent minimum / maximum: the labels are the same on every run.
+ * What holds: the edge cut never rises from round to round, and part weights that start within [Lmin, L] stay there.
+ * info (or NULL) int64[4]: rounds run (a last round without a move counts), moves accepted, edge cut of the seed, edge cut of
+ * the result.  State stays in HBM; the host reads the control words once per four rounds; no kernel waits for another block. */
+int xr_graph_partition_dev(const xr_graph *graph, const double *xy_dev, const int64_t *weights_dev, int64_t n_part,
+                           int64_t *labels_dev, int64_t *info);
 /* A new mesh with the nodes of `mesh` (all of them, used or not, coordinates copied) and the face table
  * faces[order_dev[i], :] (order_dev int64 [n_face], a device pointer; an id outside [0, n_face) is XR_ERR_INVALID). */
 int xr_mesh_reorder_faces_dev(const xr_mesh *mesh, const int64_t *order_dev, xr_mesh **out);

@@ -13,7 +13,7 @@ from .celltree import CellTree2d  # noqa: F401
 from .fill import laplace_interpolate  # noqa: F401
 from . import connectivity  # noqa: F401
 from .graph import binary_dilation, binary_erosion, connected_components, reverse_cuthill_mckee  # noqa: F401
-from .partition import labels_to_indices, merge_partitions, partition_by_label  # noqa: F401
+from .partition import label_partitions, labels_to_indices, merge_partitions, partition_by_label  # noqa: F401
 from .polygonize import polygonize  # noqa: F401
 from .regrid import (  # noqa: F401
     BarycentricInterpolator,

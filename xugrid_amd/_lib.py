@@ -62,6 +62,7 @@ SIGNATURES = {
     "xr_mesh_invalidate": (c_int, [vp]),
     "xr_mesh_area": (c_int, [vp, vp]),
     "xr_mesh_centroids": (c_int, [vp, vp]),
+    "xr_mesh_centroids_dev": (c_int, [vp, vp]),
     "xr_mesh_faces": (c_int, [vp, vp]),
     "xr_mesh_download": (c_int, [vp, vp, vp]),
     "xr_mesh_triangulate": (c_int, [vp, p_vp]),
@@ -150,6 +151,7 @@ SIGNATURES = {
     "xr_graph_binary_iterate_dev": (c_int, [vp, vp, vp, c_i64, c_int, c_i64, vp, vp]),
     "xr_graph_rcm_dev": (c_int, [vp, vp, p_i64]),
     "xr_mesh_reorder_faces_dev": (c_int, [vp, vp, p_vp]),
+    "xr_graph_partition_dev": (c_int, [vp, vp, vp, c_i64, vp, p_i64]),
     "xr_topology_facet_map_dev": (c_int, [vp, c_int, c_int, c_int, vp, c_int, c_i64, vp]),
     "xr_topology_facet_width": (c_int, [vp, c_int, c_int, p_i64]),
     "xr_facet_map_dev": (c_int, [vp, vp, c_i64, c_i64, c_i64, c_int, vp, c_int, c_i64, vp]),

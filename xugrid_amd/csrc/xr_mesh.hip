@@ -1434,6 +1434,17 @@ int xr_mesh_centroids(xr_mesh *mesh, double *centroids_out) {
     XR_API_END
 }
 
+int xr_mesh_centroids_dev(xr_mesh *mesh, double *out_dev) {
+    XR_API_BEGIN
+    XR_REQUIRE(mesh && (out_dev || mesh->n_face == 0), XR_ERR_INVALID, "xr_mesh_centroids_dev: NULL argument");
+    if (mesh->n_face > 0) {
+        const auto c = mesh_centroids_shared(mesh);
+        XR_HIP(hipMemcpyAsync(out_dev, c->get(), sizeof(double) * 2 * (size_t)mesh->n_face, hipMemcpyDeviceToDevice, launch_stream()));
+    }
+    dev_call_done();
+    XR_API_END
+}
+
 int xr_mesh_circumcenters_dev(xr_mesh *mesh, double *out_dev) {
     XR_API_BEGIN
     XR_REQUIRE(mesh && (out_dev || mesh->n_face == 0), XR_ERR_INVALID, "xr_mesh_circumcenters_dev: NULL argument");

@@ -376,6 +376,10 @@ class DeviceMesh(Handle):
         check(_lib.load().xr_mesh_centroids(self._h, _ptr(out)))
         return out
 
+    def centroids_dev(self) -> "DeviceArray":
+        """The centroids as a float64 ``(n_face, 2)`` device array (no host copy)."""
+        return self._derived_dev("xr_mesh_centroids_dev", (self.n_face, 2))
+
     def faces_ccw(self):
         out = np.empty((self.n_face, self.n_max_node), dtype=np.int64)
         check(_lib.load().xr_mesh_faces(self._h, _ptr(out)))
@@ -813,6 +817,13 @@ def labels_range(labels_ptr, n):
     lo, hi = ctypes.c_int64(), ctypes.c_int64()
     check(_lib.load().xr_labels_range_dev(ctypes.c_void_p(int(labels_ptr)), int(n), ctypes.byref(lo), ctypes.byref(hi)))
     return lo.value, hi.value
+
+
+def graph_partition_dev(graph_handle, xy_ptr, weights_ptr, n_part, labels_ptr):
+    """include/xugrid_amd.h: xr_graph_partition_dev on device pointers -> (rounds run, moves accepted, cut of the seed, cut)."""
+    info = (ctypes.c_int64 * 4)()
+    check(_lib.load().xr_graph_partition_dev(graph_handle, vp(xy_ptr), vp(weights_ptr), int(n_part), vp(labels_ptr), info))
+    return tuple(int(v) for v in info)
 
 
 def labels_order(labels_ptr, n, n_label, like=None):

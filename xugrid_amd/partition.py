@@ -6,13 +6,17 @@ The join half of the partition workflow (xugrid/ugrid/partitioning.py:16-148, ``
 ``merge_partitions`` joins grids into one: nodes that compare equal as doubles become one node (first occurrence kept, bit for
 bit), faces with the same node set become one face (first occurrence kept, slot order as given); the merged grid derives its
 own edges.  ``labels_to_indices`` / ``partition_by_label`` cut a grid by integer face labels; ``reindex_like`` /
-``index_like_device`` match two grids' coordinates.  "Which rows are equal and which came first" is answered by a key table
+``index_like_device`` match two grids' coordinates.  ``label_partitions`` makes such labels: ``n_part`` balanced parts of a graph
+by the deterministic rule of include/xugrid_amd.h (xr_graph_partition_dev; kernels in ``csrc/xr_partlabel.hip``, DESIGN section
+22) where the reference asks METIS.  "Which rows are equal and which came first" is answered by a key table
 in HBM, never by a sort; the table always runs on the device.
 
 Kinds of result, as ``subset``: host grids give a host ``Ugrid2d`` and numpy int64 indexes; any device-resident grid in the list
 gives a ``DeviceUgrid2d`` and ``DeviceArray`` indexes; torch data or labels give torch results.  The edge arithmetic runs on
 the device when every grid in the list is device-resident with a manifold topology, in numpy otherwise.
 """
+import operator
+
 import numpy as np
 
 from . import engine, netedit, subset
@@ -56,6 +60,96 @@ def partition_by_label(grid, labels, data=None):
             entry += (by.gather(data, getattr(grid, f"n_{facet}")),)
         out.append(entry)
     return out
+
+
+# ---- making labels -------------------------------------------------------------------------------------------------------------
+PART_MAX_ROUNDS = 16  # PL_MAX_ROUNDS, csrc/xr_partlabel.hip: refinement rounds at most
+PART_EPS = (3, 100)  # PL_EPS_NUM / PL_EPS_DEN: a part may weigh 1.03 sum(weights) / n_part
+DEVICE_WEIGHT_LIMIT = 2**31 - 1  # what ``engine.labels_range`` clamps to: a device weight must stay below it
+last_info = None  # {"rounds", "moves", "cut_seed", "cut"} of the last labelling (tests and profiles read it; None: nothing ran)
+
+
+def check_n_part(n_part, n):
+    n_part = operator.index(n_part)
+    if n_part < 1:
+        raise ValueError(f"n_part must be at least 1, received: {n_part}")
+    if n > 0 and n_part > n:
+        raise ValueError(f"n_part must be at most the number of elements ({n}), received: {n_part}")
+    return n_part
+
+
+def check_weights(weights, n, n_part):
+    """ugridbase.py:1508-1526 with its three messages, and ``100 * n_part * sum(weights)`` within int64 -> the weights as
+    ``int64_dev`` gives them, or ``(None, None, n)`` for none.  Host weights are checked without a device; device weights
+    through ``engine.labels_range`` (their sum is checked by the library)."""
+    total = n
+    if weights is not None:
+        info = None if isinstance(weights, (list, tuple)) else engine.device_array_info(weights)
+        a = np.asarray(weights) if info is None else None
+        shape, dtype = (a.shape, a.dtype) if info is None else info[1:]
+        if tuple(shape) != (n,):
+            raise ValueError(f"Wrong shape on weights. Expected a 1D array with {n} elements, received array with shape: {tuple(shape)}")
+        if not np.issubdtype(dtype, np.integer):
+            raise TypeError(f"Wrong type on weights. Expected an integer array, received: {dtype}")
+        if info is None:
+            if np.any(a < 0):
+                raise ValueError("Wrong values on weights. Weights should be greater or equal to zero.")
+            if 100.0 * n_part * float(np.sum(a, dtype=np.float64)) >= 2.0**63:  # (the exact sum below cannot wrap behind this)
+                raise ValueError(f"100 * n_part * sum(weights) does not fit in int64 (n_part {n_part})")
+            total = int(np.sum(a, dtype=np.int64)) or n  # (all zero: all ones)
+    if 100 * n_part * total > np.iinfo(np.int64).max:
+        raise ValueError(f"100 * n_part * sum(weights) does not fit in int64 (n_part {n_part}, sum {total})")
+    if weights is None or n == 0:
+        return None, (weights if weights is not None and info is not None else None), n
+    dev, like, _ = int64_dev(weights, "weights", n)
+    if like is not None:
+        lo, hi = engine.labels_range(engine.device_array_info(dev)[0], n)
+        if lo < 0:
+            raise ValueError("Wrong values on weights. Weights should be greater or equal to zero.")
+        if hi >= DEVICE_WEIGHT_LIMIT:
+            raise ValueError(f"Wrong values on weights. Weights in device memory should be smaller than {DEVICE_WEIGHT_LIMIT}.")
+    return dev, like, n
+
+
+def graph_labels(n, make_graph, coordinates, n_part, weights=None, device_out=False):
+    """The labels of ``label_partitions`` for the ``n`` vertices of ``make_graph()`` (a ``fill.DeviceGraph``) at
+    ``coordinates()`` ``(n, 2)`` (host or device float64); everything is validated before either is made.  Kinds: device
+    ``weights`` give labels of their kind, else ``device_out`` a ``DeviceArray``, else int64 numpy."""
+    global last_info
+    n_part = check_n_part(n_part, n)
+    w, like, _ = check_weights(weights, n, n_part)
+    to_numpy = like is None and not device_out
+    labels, ptr = (np.empty(n, dtype=np.int64), None) if to_numpy and n == 0 else engine.empty_like_device(like, (n,), np.int64)
+    if n == 0:
+        return labels
+    keep, xy_ptr, shape = xy_dev(coordinates(), "coordinates")
+    if tuple(shape) != (n, 2):
+        raise ValueError(f"expected coordinates of shape ({n}, 2), received: {tuple(shape)}")
+    graph = make_graph()  # (held until the call is back: the handle dies with its owner)
+    info = engine.graph_partition_dev(graph._h, xy_ptr, engine.device_array_info(w)[0] if w is not None else None, n_part, ptr)
+    last_info = dict(zip(("rounds", "moves", "cut_seed", "cut"), info))
+    return Index(dev=labels).emit(like, to_numpy)
+
+
+def canonical_graph(connectivity):
+    """The ``DeviceGraph`` of a scipy matrix with repeated entries summed and ascending columns."""
+    from .fill import DeviceGraph
+
+    csr = connectivity.tocsr().copy()  # (the caller's matrix keeps its repeated entries)
+    csr.sum_duplicates()
+    csr.sort_indices()
+    return DeviceGraph(csr)
+
+
+def label_partitions(connectivity, coordinates, n_part, weights=None):
+    """``n_part`` balanced parts of the symmetric scipy CSR ``connectivity`` ``(n, n)`` whose vertices lie at ``coordinates``
+    ``(n, 2)``: int64 labels ``(n,)`` by the rule of xr_graph_partition_dev -- a Hilbert-curve split of the integer
+    ``weights`` (default: all ones), then rounds of cut-lowering moves within a 3 % imbalance.  Repeated entries are summed
+    and indices sorted first; the diagonal is ignored.  numpy in -> numpy out, device weights in -> labels of their kind."""
+    from .fill import _check_square
+
+    n = _check_square(connectivity)
+    return graph_labels(n, lambda: canonical_graph(connectivity), lambda: coordinates, n_part, weights)
 
 
 # ---- merge ----------------------------------------------------------------------------------------------------------------

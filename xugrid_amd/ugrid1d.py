@@ -252,6 +252,21 @@ class Ugrid1d:
         exactly those the kept edges use.  ``return_index``: also the node and edge index."""
         return netedit.remove_self_loops(self, return_index)
 
+    def label_partitions(self, n_part, weights=None, return_device=False):
+        """int64 ``(n_edge,)`` labels ``0 .. n_part-1`` of ``n_part`` balanced parts of the edges, the core dimension
+        (ugridbase.py:1528-1571): the rule of ``Ugrid2d.label_partitions`` on ``edge_edge_connectivity`` and the edge
+        midpoints.  numpy out, an ``engine.DeviceArray`` with ``return_device``, device weights give labels of their kind."""
+        from . import partition
+
+        return partition.graph_labels(self.n_edge, lambda: partition.canonical_graph(self.edge_edge_connectivity),
+                                      lambda: self.edge_coordinates, n_part, weights, return_device)
+
+    def partition(self, n_part, weights=None):
+        """ugridbase.py:1573-1596: ``topology_subset`` of the edges of every label of ``label_partitions``."""
+        from . import partition
+
+        return [self.topology_subset(ids) for ids in partition.labels_to_indices(self.label_partitions(n_part, weights))]
+
     @staticmethod
     def merge_partitions(grids, return_index=False, data=None, dim=None):
         """partitioning.py:81-116, :137-148: the networks joined into one.  Nodes whose coordinates compare equal as doubles are
