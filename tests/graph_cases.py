@@ -173,3 +173,41 @@ def fsum_weights(indptr, indices, xy):
     d = xy[indices] - xy[rows]
     dist = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1])
     return (math.fsum(dist) / dist.size) / dist
+
+
+# ---- the summation order of the device reductions (csrc/xr_prims.h), restated -------------------------------------------------
+def block_sums(values):
+    """One value per thread -> one sum per block of 256: in every wave of 64 the xor butterfly over the offsets 32 .. 1,
+    then the four wave sums added in ascending wave number."""
+    v = np.zeros(-(-len(values) // 256) * 256)
+    v[:len(values)] = values
+    v = v.reshape(-1, 4, 64)
+    lanes = np.arange(64)
+    for offset in (32, 16, 8, 4, 2, 1):
+        v = v + v[:, :, lanes ^ offset]
+    wave = v[:, :, 0]
+    return ((wave[:, 0] + wave[:, 1]) + wave[:, 2]) + wave[:, 3]
+
+
+def folded_sum(partials):
+    """One block folds the partials: thread t adds the partials t, t + 256, ... to 0.0 in that order, then ``block_sums``."""
+    t = np.zeros(256)
+    for first in range(0, len(partials), 256):
+        piece = partials[first:first + 256]
+        t[:len(piece)] += piece
+    return block_sums(t)[0]
+
+
+def ordered_weights(indptr, indices, xy):
+    """mean(d) / d as the device computes it, bit for bit: a thread adds the distances of its row in entry order, the rows go
+    through ``block_sums`` and the blocks through ``folded_sum``."""
+    indptr = np.asarray(indptr, dtype=np.int64)
+    degree = np.diff(indptr)
+    rows = np.repeat(np.arange(len(degree)), degree)
+    d = xy[indices] - xy[rows]
+    dist = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1])
+    row_sum = np.zeros(len(degree))
+    for k in range(int(degree.max())):
+        has = degree > k
+        row_sum[has] += dist[indptr[:-1][has] + k]
+    return (folded_sum(block_sums(row_sum)) / dist.size) / dist

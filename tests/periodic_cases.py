@@ -175,6 +175,33 @@ SLACK_CASES = ("quads32", "shuffled", "dup", "big")
 _MADE, _EXPECTED = {}, {}
 
 
+# ---- meshes at the edges of the two-launch reduction of the x-range (256 threads per block, one partial per block, at most
+# 1024 blocks that stride).  The nodes are numbered column by column, so the left column sits in the first block only and the
+# right column in the last elements only: a reduction that drops its tail gets xmax wrong.
+def columns(nx, ny):
+    xy, faces = quads(nx, ny)
+    order = np.arange(len(xy)).reshape(ny + 1, nx + 1).T.ravel()  # new node k is old node order[k]
+    return xy[order], np.argsort(order)[faces], float(nx)
+
+
+def columns_and_one():
+    """16 x 16 nodes and an interior node stored twice: 257 nodes, one block and one lane."""
+    xy, faces, xmax = columns(15, 15)
+    k = faces[0, 2]  # (1, 1)
+    faces = faces.copy()
+    faces[0, 2] = len(xy)
+    return np.concatenate([xy, xy[k:k + 1]]), faces, xmax
+
+
+RANGE_MESHES = {
+    "nodes256": lambda: columns(15, 15),  # one full block
+    "nodes257": columns_and_one,
+    "nodes65536": lambda: columns(255, 255),  # 256 partials: one per thread of the fold
+    "nodes65792": lambda: columns(256, 255),  # 257 partials: thread 0 of the fold takes two, and the right column is the 257th
+    "nodes263169": lambda: columns(512, 512),  # past 1024 x 256: the first stage strides, and the right column is in the stride
+}
+
+
 def symmetric():
     """The two triangles of the reference's comment (ugrid2d.py:1515-1529): a periodic grid of three nodes whose faces share
     all three edges.  Both faces reach node 0 across more than half the domain, so both name its copy."""
@@ -183,7 +210,7 @@ def symmetric():
 
 def mesh(name):
     if name not in _MADE:
-        xy, faces, xmax = MESHES[name]()
+        xy, faces, xmax = (MESHES.get(name) or RANGE_MESHES[name])()
         _MADE[name] = (np.ascontiguousarray(xy, dtype=np.float64), np.ascontiguousarray(faces, dtype=np.int64), float(xmax))
     return _MADE[name]
 

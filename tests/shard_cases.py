@@ -292,6 +292,17 @@ def _straddle(S, T):
     return make
 
 
+def _fold(T):
+    """65 536 source faces and T target faces: the bounds reduction writes 256 partials (T = 0) or 257, the last of them the
+    target faces' alone, and one block folds them."""
+    def make():
+        sxy, sf = meshgen.triangle_mesh(33_000, 0)
+        _, _, txy, tf = _delaunay()
+        return sxy, np.ascontiguousarray(sf[:65_536]), txy, np.ascontiguousarray(tf[:T])
+
+    return make
+
+
 def _lattice1m():
     sxy, sf = meshgen.quad_mesh(np.arange(1025.0), np.arange(1025.0))
     txy, tf = meshgen.quad_mesh(256.0 + np.arange(513.0), 256.0 + np.arange(513.0))
@@ -308,6 +319,8 @@ _BUILDERS.update({f"straddle_S{S}_T{T}": _straddle(S, T) for S, T in STRADDLE_SI
 SMALL_CASES = tuple(_BUILDERS)
 LARGE_CASE = "lattice1m"
 _BUILDERS[LARGE_CASE] = _lattice1m
+FOLD_CASES = ("fold_T0", "fold_T200")
+_BUILDERS.update({"fold_T0": _fold(0), "fold_T200": _fold(200)})
 MANY_RANKS = ("delaunay", "outlier")  # also run with more ranks than a few, and more than faces
 _MADE = {}
 
@@ -326,6 +339,8 @@ class Case:
     def worlds(self):
         if self.name == LARGE_CASE:
             return (8,)
+        if self.name in FOLD_CASES:
+            return (3,)
         return (1, 2, 3, 8) + ((64, 4096) if self.name in MANY_RANKS else ())
 
     def ranks(self, world, mode):

@@ -136,6 +136,24 @@ def test_at_size_equals_the_numpy_rule(at_size, xr_option, strips):
     assert np.array_equal(burned, np.where(a["touched"] >= 0, values[np.maximum(a["touched"], 0)], np.nan), equal_nan=True)
 
 
+@pytest.mark.parametrize("n_vertex", [250, 256, 257, 65_536, 65_537, 65_792])
+def test_extent_at_the_edges_of_its_reduction(hip, n_vertex):
+    """The y-range that places the strips is a two-launch reduction over blocks of 256 segments: less than a block, one block,
+    one block and a lane, 256 partials, 257 with one segment and with a full block.  A circle, and as the LAST three vertices
+    a triangle above it whose apex comes last: only the last segments reach the top of the range, and faces lie under it."""
+    nodes, faces = meshgen.triangle_mesh(400, 0)
+    grid = make_grid(nodes, faces)
+    angle = 2.0 * np.pi * np.arange(n_vertex - 3) / (n_vertex - 3)
+    circle = np.column_stack((0.5 + 0.3 * np.cos(angle), 0.45 + 0.3 * np.sin(angle)))
+    polygons = ragged([[circle], [np.array([[0.3, 0.8], [0.7, 0.8], [0.5, 0.99]])]])
+    assert len(polygons[0]) == n_vertex
+    winner = polygon_winner_numpy(grid.centroids, *polygons, default_tolerance(nodes, faces))
+    assert (winner == 0).sum() > 100 and (winner == 1).sum() > 10 and (winner == -1).sum() > 100
+    values = np.array([3.0, 4.5])
+    burned = xa.burn_vector_geometry(grid, polygons=polygons + (values,), fill=-7.0)
+    assert np.array_equal(burned, np.where(winner >= 0, values[np.maximum(winner, 0)], -7.0))
+
+
 @pytest.mark.parametrize("strips", [0, 1, 2, 5, 10, 50, 100_000])
 def test_horizontal_edges_through_a_row_of_centroids(hip, xr_option, strips):
     """An 8 x 8 raster of unit cells (centroids at k + 0.5) and two rectangles whose horizontal edges run exactly through

@@ -58,6 +58,14 @@ def test_both_directions(hip, name, kind):
     check_both_directions(kind, name)
 
 
+@pytest.mark.parametrize("name", list(pc.RANGE_MESHES))
+def test_x_range_at_the_edges_of_its_reduction(hip, name):
+    """One block, one block and a lane, 256 and 257 partials, a first stage that strides: both directions, every array."""
+    xy, _, _ = pc.mesh(name)
+    assert len(xy) == int(name[len("nodes"):])
+    check_both_directions("host", name)
+
+
 def test_anchor_answers(hip):
     xy, faces, xmax = pc.mesh("quads32")
     wrapped, indexes = make_grid("host", xy, faces).to_periodic(return_index=True)

@@ -187,6 +187,20 @@ def assert_brute(points, queries, max_distance=np.inf, index=None):
     return got
 
 
+@pytest.mark.parametrize("n", [250, 256, 257, 65_536, 65_537, 65_792])
+def test_extent_at_the_edges_of_its_reduction(hip, n):
+    """The index's bounding box and point count are a two-launch reduction over blocks of 256 points: less than a block, one
+    block, one block and a lane, 256 partials, 257 with one point and with a full block.  The LAST point alone stretches the box
+    (up and to the right), and a quarter of the queries lie around it."""
+    rng = np.random.default_rng(n)
+    points = rng.uniform(0.0, 1.0, (n, 2))
+    points[-1] = (3.0, 2.5)
+    queries = np.concatenate([rng.uniform(-0.2, 1.2, (600, 2)), points[-1] + rng.uniform(-1.5, 1.5, (200, 2))])
+    got = assert_brute(points, queries)
+    assert (got == n - 1).sum() > 50
+    assert_brute(points, queries, 0.05)
+
+
 def test_ties_take_the_lowest_id(hip):
     """Queries at the nodes of a quad lattice against its face centroids: four equidistant centroids inside, two on the
     sides, one at the corners.  (scipy agrees with the lowest id on about half of such queries: not the yardstick here.)"""

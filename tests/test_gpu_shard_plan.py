@@ -93,6 +93,14 @@ def test_plan_equals_the_rule_on_a_million_faces(hip, mode):
     check_case(on_device(sc.LARGE_CASE, hip), mode)
 
 
+@pytest.mark.parametrize("mode", sc.MODES)
+@pytest.mark.parametrize("name", sc.FOLD_CASES)
+def test_plan_equals_the_rule_at_256_and_257_partial_bounds(hip, name, mode):
+    c = sc.case(name)
+    assert c.S == 65_536 and c.S + c.T in (65_536, 65_736)
+    check_case(on_device(name, hip), mode)
+
+
 def test_empty_ranks_return_nothing(hip):
     d = on_device("outlier", hip)
     for mode in ("morton", "balanced"):

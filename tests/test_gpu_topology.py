@@ -10,6 +10,7 @@ import sys
 
 import numpy as np
 import pytest
+from scipy.spatial import Delaunay
 
 import graph_cases as gc
 import xugrid_amd as xa
@@ -130,6 +131,20 @@ def test_graph_weights_against_fsum(name, facet):
     assert np.array_equal(again.view(np.int64), weights.view(np.int64))
     other = device_grid(xy, faces).device_topology().graph(facet).download()[2]
     assert np.array_equal(other.view(np.int64), weights.view(np.int64))
+
+
+@pytest.mark.parametrize("n_node,seed", [(250, 250), (256, 256), (257, 257), (65_536, 7), (65_537, 2)])
+def test_graph_weights_in_the_order_of_the_reduction(n_node, seed):
+    """The mean distance is a sum of doubles in a fixed order (csrc/xr_prims.h): threads, butterfly, waves, then the fold of
+    the blocks' partials -- restated in numpy and compared bit for bit.  The rows are the nodes of a Delaunay mesh: less than
+    a block, one block, one block and a lane, 256 partials and 257 (thread 0 of the fold takes two).  At these seeds the
+    sum in this order differs from the correctly rounded one or from numpy's pairwise one: another order would show."""
+    xy = np.random.default_rng(seed).random((n_node, 2))
+    faces = Delaunay(xy).simplices.astype(np.int64)
+    indptr, indices, weights = device_grid(xy, faces).device_topology().graph("node").download()
+    assert len(indptr) == n_node + 1
+    expected = gc.ordered_weights(indptr, indices, xy)
+    assert np.array_equal(weights.view(np.int64), expected.view(np.int64))
 
 
 def test_drop_device_caches_drops_the_topology():

@@ -85,30 +85,10 @@ k_burn_segments(const double2 *__restrict__ xy, int64_t n_vertex, const int64_t 
     key[i] = (int32_t)(group_off ? offset_owner(group_off, n_group, r) : r);
 }
 
-// block reduction of (min, max, max, sum) over the BB lanes -> out[0..3], written by thread 0
-__device__ __forceinline__ void burn_extent_reduce(double y0, double y1, double am, double dy, double *__restrict__ out) {
-    __shared__ double sh[4][BB / 64];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        y0 = fmin(y0, __shfl_xor(y0, o, 64));
-        y1 = fmax(y1, __shfl_xor(y1, o, 64));
-        am = fmax(am, __shfl_xor(am, o, 64));
-        dy += __shfl_xor(dy, o, 64);
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) sh[0][w] = y0, sh[1][w] = y1, sh[2][w] = am, sh[3][w] = dy;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int u = 1; u < BB / 64; u++) {
-            sh[0][0] = fmin(sh[0][0], sh[0][u]), sh[1][0] = fmax(sh[1][0], sh[1][u]);
-            sh[2][0] = fmax(sh[2][0], sh[2][u]), sh[3][0] += sh[3][u];
-        }
-        for (int u = 0; u < 4; u++) out[u] = sh[u][0];
-    }
-}
-
-// per block: ymin, ymax, the largest |coordinate| and the summed |dy| of the segments that count (len2 > 0)
+// per block: ymin, ymax, the largest |coordinate| and the summed |dy| of the segments that count (len2 > 0); the |dy| of a
+// block are summed in the order of block_reduce, the blocks' sums in that of k_fold_partials (xr_prims.h)
 __global__ void __launch_bounds__(BB) k_burn_extent(const double4 *__restrict__ seg, int64_t n, double *__restrict__ partial) {
+    __shared__ double lds[4 * (BB / 64)];
     const int64_t i = (int64_t)blockIdx.x * BB + threadIdx.x;
     double y0 = INFINITY, y1 = -INFINITY, am = 0.0, dy = 0.0;
     if (i < n) {
@@ -120,16 +100,11 @@ __global__ void __launch_bounds__(BB) k_burn_extent(const double4 *__restrict__ 
             dy = fabs(wy);
         }
     }
-    burn_extent_reduce(y0, y1, am, dy, partial + (int64_t)blockIdx.x * 4);
-}
-
-__global__ void __launch_bounds__(BB) k_burn_extent_final(const double *__restrict__ partial, int nb, double *__restrict__ out) {
-    double y0 = INFINITY, y1 = -INFINITY, am = 0.0, dy = 0.0;
-    for (int b = threadIdx.x; b < nb; b += BB) {
-        const double *p = partial + (int64_t)b * 4;
-        y0 = fmin(y0, p[0]), y1 = fmax(y1, p[1]), am = fmax(am, p[2]), dy += p[3];
+    block_reduce<BB, OpMin, OpMax, OpMax, OpSum>(lds, y0, y1, am, dy);
+    if (threadIdx.x == 0) {
+        double *out = partial + (int64_t)blockIdx.x * 4;
+        out[0] = y0, out[1] = y1, out[2] = am, out[3] = dy;
     }
-    burn_extent_reduce(y0, y1, am, dy, out);
 }
 
 // span[i] = (first, last) strip of segment i, (1, 0) for a segment no rule reads; count[strip * n_chunk + chunk] += 1 for
@@ -297,11 +272,11 @@ static void burn_polygons(xr_mesh *mesh, const double *coords_dev, int64_t n_ver
               n_vertex, ring_off, n_ring, polygon_off, n_polygon, 1, seg.get(), seg_polygon.get());
     // ---- the strips: extent of the segments, then their number from the mean y-range of a segment
     const unsigned nb = div_up(n_seg, BB);
-    DevBuf<double> partial((size_t)nb * 4), extent_dev(4);
-    XR_LAUNCH("burn_extent", k_burn_extent, dim3(nb), dim3(BB), 0, seg.get(), n_seg, partial.get());
-    XR_LAUNCH("burn_extent_final", k_burn_extent_final, dim3(1), dim3(BB), 0, partial.get(), (int)nb, extent_dev.get());
+    TwoStageReduce<BB, double, OpMin, OpMax, OpMax, OpSum> extent("burn_extent_final", nb, [&](double *partial) {
+        XR_LAUNCH("burn_extent", k_burn_extent, dim3(nb), dim3(BB), 0, seg.get(), n_seg, partial);
+    });
     double ext[4]; // ymin, ymax, largest |coordinate|, sum |dy|
-    d2h(ext, extent_dev.get(), sizeof(ext));
+    extent.read(ext);
     const bool any = std::isfinite(ext[0]) && std::isfinite(ext[1]) && ext[1] >= ext[0];
     if (any) {
         const int n_chunk = (int)div_up(n_seg, STRIP_CHUNK);

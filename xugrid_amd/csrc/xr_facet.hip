@@ -54,14 +54,8 @@ __global__ void __launch_bounds__(FB) k_facet_width(const int32_t *__restrict__ 
     __shared__ int sh[FB / 64];
     int w = 0;
     for (int64_t i = threadIdx.x; i < n; i += FB) w = max(w, ptr[i + 1] - ptr[i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) w = max(w, __shfl_xor(w, o, 64));
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int u = 1; u < FB / 64; u++) w = max(w, sh[u]);
-        out[0] = w;
-    }
+    block_reduce<FB, OpMax>(sh, w);
+    if (threadIdx.x == 0) out[0] = w;
 }
 
 // one lane per output element (t, j) of a slice; slices [blockIdx.y * KT, ...) of the K of this launch

@@ -18,6 +18,7 @@
 
 #include "xr_nn.h"
 #include "xr_objects.h"
+#include "xr_prims.h"
 #include "xr_topology.h"
 
 namespace xr {
@@ -26,18 +27,8 @@ enum FillStatus : int { FILL_CONVERGED = 0, FILL_MAXITER = 1, FILL_BREAKDOWN = 2
 
 static constexpr int FB = 256; // threads per block of the row kernels (one row per thread)
 
-// ---- fixed-order block sum (wave64 butterfly, then the four wave sums in wave order)
-__device__ __forceinline__ double block_sum(double v, double *sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) sh[w] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int i = 0; i < (int)(blockDim.x >> 6); i++) t += sh[i];
-    __syncthreads();
-    return t;
-}
+// Every sum over rows here is the fixed-order block reduction of xr_prims.h (wave64 butterfly, then the four wave sums in wave
+// order), and every sum over blocks its fold of the partials.
 
 // ---------------------------------------------------------------------------------------------
 // graph construction
@@ -119,8 +110,8 @@ k_fill_setup(const double *__restrict__ in, const int32_t *__restrict__ indptr, 
         p1[o] = 0.0;
         bb = b * b;
     }
-    const double t = block_sum(bb, sh);
-    if (threadIdx.x == 0) partial[k * gridDim.x + blockIdx.x] = t;
+    block_reduce_all<FB, OpSum>(sh, bb);
+    if (threadIdx.x == 0) partial[k * gridDim.x + blockIdx.x] = bb;
 }
 
 // per-slice state, one record per slice
@@ -130,10 +121,11 @@ struct CgState {
     int32_t active, status;
 };
 
-__device__ __forceinline__ double sum_partials(const double *__restrict__ part, int nb, double *sh) {
-    double t = 0.0;
-    for (int b = threadIdx.x; b < nb; b += blockDim.x) t += part[b];
-    return block_sum(t, sh);
+// the nb block partials of a slice in the fixed order of block_fold_partials (xr_prims.h), in every thread
+__device__ __forceinline__ double slice_total(const double *__restrict__ part, int nb, double *sh) {
+    double t[1];
+    block_fold_partials<true, FB, OpSum>(sh, part, nb, t);
+    return t[0];
 }
 
 // one block per slice: the scipy 1.15 `cg` prologue (bnrm2, atol = max(atol, rtol * bnrm2), bnrm2 == 0 -> x = 0)
@@ -143,7 +135,7 @@ k_cg_start(const double *__restrict__ partial, int nb, const uint8_t *__restrict
            int32_t *__restrict__ active_out) {
     __shared__ double sh[FB / 64];
     const int64_t k = blockIdx.x;
-    const double rr = sum_partials(partial + k * nb, nb, sh);
+    const double rr = slice_total(partial + k * nb, nb, sh);
     if (threadIdx.x) return;
     CgState s{};
     s.rho = rr;
@@ -187,8 +179,8 @@ k_cg_spmv(const int32_t *__restrict__ indptr, const int32_t *__restrict__ indice
         q[o] = qi;
         pq = pi * qi;
     }
-    const double t = block_sum(pq, sh);
-    if (threadIdx.x == 0) partial[k * gridDim.x + blockIdx.x] = t;
+    block_reduce_all<FB, OpSum>(sh, pq);
+    if (threadIdx.x == 0) partial[k * gridDim.x + blockIdx.x] = pq;
 }
 
 __global__ void __launch_bounds__(FB)
@@ -196,7 +188,7 @@ k_cg_alpha(const double *__restrict__ partial, int nb, CgState *__restrict__ st,
     __shared__ double sh[FB / 64];
     const int64_t k = blockIdx.x;
     if (!st[k].active) return;
-    const double pq = sum_partials(partial + k * nb, nb, sh);
+    const double pq = slice_total(partial + k * nb, nb, sh);
     if (threadIdx.x) return;
     if (!(pq > 0.0) || !isfinite(pq)) {
         st[k].active = 0;
@@ -223,8 +215,8 @@ k_cg_update(int64_t n, const uint8_t *__restrict__ unknown, const double *__rest
         r[o] = ri;
         rr = ri * ri;
     }
-    const double t = block_sum(rr, sh);
-    if (threadIdx.x == 0) partial[k * gridDim.x + blockIdx.x] = t;
+    block_reduce_all<FB, OpSum>(sh, rr);
+    if (threadIdx.x == 0) partial[k * gridDim.x + blockIdx.x] = rr;
 }
 
 // the top of scipy's next loop pass: stop when ||r|| < tol -- unless this was the last allowed iteration (scipy then
@@ -235,7 +227,7 @@ k_cg_beta(const double *__restrict__ partial, int nb, int64_t maxiter, CgState *
     __shared__ double sh[FB / 64];
     const int64_t k = blockIdx.x;
     if (!st[k].active) return;
-    const double rr = sum_partials(partial + k * nb, nb, sh);
+    const double rr = slice_total(partial + k * nb, nb, sh);
     if (threadIdx.x) return;
     CgState s = st[k];
     s.iter += 1;
@@ -546,15 +538,8 @@ k_graph_distance(const int32_t *__restrict__ indptr, const int32_t *__restrict__
             sum += v;
         }
     }
-    const double t = block_sum(sum, sh);
-    if (threadIdx.x == 0) partial[blockIdx.x] = t;
-}
-
-// one block: the partials in a fixed order -> total[0]
-__global__ void __launch_bounds__(FB) k_graph_distance_total(const double *__restrict__ partial, int nb, double *__restrict__ total) {
-    __shared__ double sh[FB / 64];
-    const double t = sum_partials(partial, nb, sh);
-    if (threadIdx.x == 0) total[0] = t;
+    block_reduce_all<FB, OpSum>(sh, sum);
+    if (threadIdx.x == 0) partial[blockIdx.x] = sum;
 }
 
 // d -> mean(d) / d
@@ -615,11 +600,11 @@ int xr_graph_from_topology(const xr_topology *t, int facet, xr_graph **out) {
         const auto centroids = face ? mesh_centroids_shared(t->mesh) : nullptr;
         const double *xy = face ? centroids->get() : t->mesh->node_xy.get();
         const unsigned nb = div_up(n, FB);
-        DevBuf<double> partial((size_t)nb + 1);
-        XR_LAUNCH("graph_distance", k_graph_distance, dim3(nb), dim3(FB), 0, g->indptr.get(), g->indices.get(), xy, n, g->data.get(),
-                  partial.get());
-        XR_LAUNCH("graph_distance_total", k_graph_distance_total, dim3(1), dim3(FB), 0, partial.get(), (int)nb, partial.get() + nb);
-        XR_LAUNCH("graph_weights", k_graph_weights, dim3(div_up(nnz, FB)), dim3(FB), 0, g->data.get(), nnz, partial.get() + nb);
+        TwoStageReduce<FB, double, OpSum> total("graph_distance_total", nb, [&](double *partial) {
+            XR_LAUNCH("graph_distance", k_graph_distance, dim3(nb), dim3(FB), 0, g->indptr.get(), g->indices.get(), xy, n, g->data.get(),
+                      partial);
+        });
+        XR_LAUNCH("graph_weights", k_graph_weights, dim3(div_up(nnz, FB)), dim3(FB), 0, g->data.get(), nnz, total.result());
     }
     label_components(g.get());
     stream_sync();

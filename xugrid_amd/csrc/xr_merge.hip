@@ -176,22 +176,17 @@ k_like_lookup(const double2 *__restrict__ key_a, const double2 *__restrict__ key
 
 // ---- labels
 enum LabelStatus : int { LB_MIN = 0, LB_MAX = 1 };
-// smallest and largest label: per wave through shuffles, per block through LDS, then one atomic pair per BLOCK (a million
+// smallest and largest label: the block's (block_reduce, xr_prims.h), then one atomic pair per BLOCK (a million
 // atomics on two words would queue up behind each other)
 __global__ void __launch_bounds__(256) k_label_range(const int64_t *__restrict__ labels, int64_t n, int32_t *__restrict__ status) {
-    __shared__ int32_t s_lo[4], s_hi[4];
+    __shared__ int32_t lds[2 * 4];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     int32_t lo = INT32_MAX, hi = -1;
     if (i < n) lo = hi = (int32_t)std::min<int64_t>(std::max<int64_t>(labels[i], -1), INT32_MAX); // (clamped: the host only asks "negative?" and "too many?")
-    for (int d = 32; d > 0; d >>= 1) {
-        lo = min(lo, __shfl_xor(lo, d));
-        hi = max(hi, __shfl_xor(hi, d));
-    }
-    if ((threadIdx.x & 63) == 0) s_lo[threadIdx.x >> 6] = lo, s_hi[threadIdx.x >> 6] = hi;
-    __syncthreads();
+    block_reduce<256, OpMin, OpMax>(lds, lo, hi);
     if (threadIdx.x == 0) {
-        atomicMin(status + LB_MIN, min(min(s_lo[0], s_lo[1]), min(s_lo[2], s_lo[3])));
-        atomicMax(status + LB_MAX, max(max(s_hi[0], s_hi[1]), max(s_hi[2], s_hi[3])));
+        atomicMin(status + LB_MIN, lo);
+        atomicMax(status + LB_MAX, hi);
     }
 }
 

@@ -126,8 +126,7 @@ k_net_edge_count(const int64_t *__restrict__ edges, int64_t n_edge, const int32_
         v = (long long)(nptr[a + 1] - nptr[a]) + (nptr[b + 1] - nptr[b]) - 2;
         rowlen[e] = (int32_t)v;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    v = wave_reduce<OpSum>(v);
     if ((threadIdx.x & 63) == 0 && v) atomicAdd(total, (unsigned long long)v);
 }
 

@@ -37,59 +37,13 @@ enum PlWide : int { PA_TOTAL, PA_MAXDEG, PA_CUT_SEED, PA_CUT_RESULT, PA_COUNT };
 
 __device__ __forceinline__ int64_t pl_weight(const int64_t *__restrict__ w, int32_t v) { return w ? w[v] : 1; }
 
-// ---- block primitives on 64-bit values ----------------------------------------------------------------------------------------
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// block-wide exclusive scan of one int64 per thread (every thread must get here; ends behind a barrier)
-__device__ __forceinline__ long long block_excl_scan_i64(long long v, long long *total, long long *lds /* >= PB / 64 */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-    }
-    if (lane == 63) lds[wave] = incl;
-    __syncthreads();
-    long long woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < PB / 64; w++) {
-        const long long s = lds[w];
-        if (w < wave) woff += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return woff + incl - v;
-}
-
-// the largest of one key per thread, in every thread (every thread must get here; ends behind a barrier)
-__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long v, unsigned long long *lds /* >= PB / 64 */) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long t = __shfl_xor(v, o, 64);
-        v = t > v ? t : v;
-    }
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    unsigned long long best = 0;
-#pragma unroll
-    for (int w = 0; w < PB / 64; w++) best = lds[w] > best ? lds[w] : best;
-    __syncthreads();
-    return best;
-}
-
 // ---- int64 exclusive scan over a device array: tiles of PB, the tiles' totals by one block, the totals added back ----------------
 __global__ void __launch_bounds__(PB)
 k_pl_scan_tiles(const int64_t *__restrict__ in, int64_t n, int64_t *__restrict__ out, int64_t *__restrict__ tile_total) {
     __shared__ long long lds[PB / 64];
     const int64_t i = (int64_t)blockIdx.x * PB + threadIdx.x;
     long long total;
-    const long long ex = block_excl_scan_i64(i < n ? in[i] : 0, &total, lds);
+    const long long ex = block_excl_scan<PB, long long>(i < n ? in[i] : 0, &total, lds);
     if (i < n) out[i] = ex;
     if (threadIdx.x == 0) tile_total[blockIdx.x] = total;
 }
@@ -99,7 +53,7 @@ __global__ void __launch_bounds__(PB) k_pl_scan_totals(int64_t *tile_total, int6
     for (int64_t base = 0; base < n_tile; base += PB) {
         const int64_t t = base + threadIdx.x;
         long long total;
-        const long long ex = block_excl_scan_i64(t < n_tile ? tile_total[t] : 0, &total, lds);
+        const long long ex = block_excl_scan<PB, long long>(t < n_tile ? tile_total[t] : 0, &total, lds);
         if (t < n_tile) tile_total[t] = carry + ex;
         carry += total;
     }
@@ -180,11 +134,10 @@ __device__ __forceinline__ void pl_rows(const int32_t *__restrict__ indptr, int6
 __global__ void __launch_bounds__(PB)
 k_pl_init(const int32_t *__restrict__ indptr, const double *__restrict__ xy, const int64_t *__restrict__ w, int64_t n,
           int32_t *__restrict__ ids, double *__restrict__ tile_bounds, unsigned long long *wide) {
-    __shared__ double red[PB / 64][4];
+    __shared__ double red[4 * (PB / 64)];
     __shared__ int32_t red_deg[PB / 64];
     __shared__ long long red_weight[PB / 64];
     const int64_t i = (int64_t)blockIdx.x * PB + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int32_t deg = 0;
     long long weight = 0;
     double lo_x = INFINITY, lo_y = INFINITY, hi_x = -INFINITY, hi_y = -INFINITY;
@@ -195,24 +148,10 @@ k_pl_init(const int32_t *__restrict__ indptr, const double *__restrict__ xy, con
         lo_x = hi_x = xy[2 * i];
         lo_y = hi_y = xy[2 * i + 1];
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        deg = max(deg, __shfl_xor(deg, o, 64));
-        lo_x = fmin(lo_x, __shfl_xor(lo_x, o, 64)), lo_y = fmin(lo_y, __shfl_xor(lo_y, o, 64));
-        hi_x = fmax(hi_x, __shfl_xor(hi_x, o, 64)), hi_y = fmax(hi_y, __shfl_xor(hi_y, o, 64));
-    }
-    weight = wave_sum_i64(weight);
-    if (lane == 0) {
-        red[wave][0] = lo_x, red[wave][1] = lo_y, red[wave][2] = hi_x, red[wave][3] = hi_y;
-        red_deg[wave] = deg, red_weight[wave] = weight;
-    }
-    __syncthreads();
+    block_reduce<PB, OpMin, OpMin, OpMax, OpMax>(red, lo_x, lo_y, hi_x, hi_y);
+    block_reduce<PB, OpMax>(red_deg, deg);
+    block_reduce<PB, OpSum>(red_weight, weight);
     if (threadIdx.x == 0) { // (one add per block: thousands of waves on one word wait in line)
-        for (int k = 1; k < PB / 64; k++) {
-            lo_x = fmin(lo_x, red[k][0]), lo_y = fmin(lo_y, red[k][1]);
-            hi_x = fmax(hi_x, red[k][2]), hi_y = fmax(hi_y, red[k][3]);
-            deg = max(deg, red_deg[k]), weight += red_weight[k];
-        }
         if (deg > 0) atomicMax(wide + PA_MAXDEG, (unsigned long long)deg);
         if (weight != 0) atomicAdd(wide + PA_TOTAL, (unsigned long long)weight);
         double *out = tile_bounds + 4 * (int64_t)blockIdx.x;
@@ -221,22 +160,13 @@ k_pl_init(const int32_t *__restrict__ indptr, const double *__restrict__ xy, con
 }
 
 // one block: frame = lo_x, lo_y, 65536 / max(side, 1e-300)
-__global__ void __launch_bounds__(PB) k_pl_frame(const double *__restrict__ tile_bounds, int64_t n_tile, double *__restrict__ frame) {
-    __shared__ double red[PB][4];
-    double lo_x = INFINITY, lo_y = INFINITY, hi_x = -INFINITY, hi_y = -INFINITY;
-    for (int64_t t = threadIdx.x; t < n_tile; t += PB) {
-        lo_x = fmin(lo_x, tile_bounds[4 * t]), lo_y = fmin(lo_y, tile_bounds[4 * t + 1]);
-        hi_x = fmax(hi_x, tile_bounds[4 * t + 2]), hi_y = fmax(hi_y, tile_bounds[4 * t + 3]);
-    }
-    red[threadIdx.x][0] = lo_x, red[threadIdx.x][1] = lo_y, red[threadIdx.x][2] = hi_x, red[threadIdx.x][3] = hi_y;
-    __syncthreads();
+__global__ void __launch_bounds__(PB) k_pl_frame(const double *__restrict__ tile_bounds, int n_tile, double *__restrict__ frame) {
+    __shared__ double red[4 * (PB / 64)];
+    double b[4]; // lo_x, lo_y, hi_x, hi_y
+    block_fold_partials<false, PB, OpMin, OpMin, OpMax, OpMax>(red, tile_bounds, n_tile, b);
     if (threadIdx.x == 0) {
-        for (int k = 1; k < PB; k++) {
-            lo_x = fmin(lo_x, red[k][0]), lo_y = fmin(lo_y, red[k][1]);
-            hi_x = fmax(hi_x, red[k][2]), hi_y = fmax(hi_y, red[k][3]);
-        }
-        const double side = fmax(hi_x - lo_x, hi_y - lo_y);
-        frame[0] = lo_x, frame[1] = lo_y, frame[2] = (double)PL_CELLS / fmax(side, 1e-300);
+        const double side = fmax(b[2] - b[0], b[3] - b[1]);
+        frame[0] = b[0], frame[1] = b[1], frame[2] = (double)PL_CELLS / fmax(side, 1e-300);
     }
 }
 
@@ -287,7 +217,7 @@ k_pl_seed(const int32_t *__restrict__ order, const int64_t *__restrict__ before,
     }
     const int32_t lead = __shfl(l, 0, 64); // (lane 0 holds the wave's first position: valid whenever any lane is)
     if (__all(l == lead || l < 0)) {
-        weight = wave_sum_i64(weight);
+        weight = wave_reduce<OpSum>(weight);
         if ((threadIdx.x & 63) == 0 && lead >= 0 && weight != 0) atomicAdd(part_weight + lead, (unsigned long long)weight);
     } else if (l >= 0 && weight != 0) {
         atomicAdd(part_weight + l, (unsigned long long)weight);
@@ -312,7 +242,7 @@ k_pl_cut(const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices
                 (void)block_excl_scan<PB>(differing(v, (int)threadIdx.x, PB), &total, lds);
                 if (threadIdx.x == 0) mine += total;
             });
-    mine = wave_sum_i64(mine);
+    mine = wave_reduce<OpSum>(mine);
     if ((threadIdx.x & 63) == 0 && mine != 0) atomicAdd(twice_cut, (unsigned long long)mine);
 }
 
@@ -377,7 +307,7 @@ k_pl_candidate(const int32_t *__restrict__ indptr, const int32_t *__restrict__ i
             }
             int own_total;
             (void)block_excl_scan<PB>(own, &own_total, lds);
-            best = block_max_u64(best, best_lds);
+            block_reduce_all<PB, OpMax>(best_lds, best);
             if (threadIdx.x == 0)
                 store(v, a, own_total, (int32_t)(best >> 32), best ? INT32_MAX - (int32_t)(best & 0xffffffffu) : -1);
         });
@@ -491,7 +421,7 @@ static void partition_labels(const xr_graph *g, const double *xy, const int64_t 
     XR_LAUNCH("pl_init", k_pl_init, dim3(nb), dim3(PB), 0, indptr, xy, w, n, list[0], bounds.get(), wide);
     unsigned long long h[PA_COUNT];
     d2h(h, wide, sizeof(h), [&] { // (the key needs nothing the host is waiting for)
-        XR_LAUNCH("pl_frame", k_pl_frame, dim3(1), dim3(PB), 0, bounds.get(), (int64_t)nb, frame);
+        XR_LAUNCH("pl_frame", k_pl_frame, dim3(1), dim3(PB), 0, bounds.get(), (int)nb, frame);
         XR_LAUNCH("pl_key", k_pl_key, dim3(nb), dim3(PB), 0, xy, n, frame, key);
     });
     int64_t T = (int64_t)h[PA_TOTAL];

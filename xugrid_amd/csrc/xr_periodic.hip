@@ -39,36 +39,16 @@ static constexpr int PERIODIC_REGS = 8;            // faces up to this width are
 static constexpr double CLOSE_ATOL = 1e-8, CLOSE_RTOL = 1e-5; // np.isclose / np.allclose defaults
 
 // ---- bounds: smallest and largest x (fmin / fmax skip a NaN)
-__device__ __forceinline__ void block_min_max(double &lo, double &hi, double *s_lo, double *s_hi) {
-    for (int d = 32; d > 0; d >>= 1) {
-        lo = fmin(lo, __shfl_xor(lo, d));
-        hi = fmax(hi, __shfl_xor(hi, d));
-    }
-    if ((threadIdx.x & 63) == 0) s_lo[threadIdx.x >> 6] = lo, s_hi[threadIdx.x >> 6] = hi;
-    __syncthreads();
-    lo = fmin(fmin(s_lo[0], s_lo[1]), fmin(s_lo[2], s_lo[3]));
-    hi = fmax(fmax(s_hi[0], s_hi[1]), fmax(s_hi[2], s_hi[3]));
-}
-
 // partial[2 b], partial[2 b + 1] = min, max of the x that block b strides over
 __global__ void __launch_bounds__(256) k_periodic_x_range(const double2 *__restrict__ xy, int64_t n, double *__restrict__ partial) {
-    __shared__ double s_lo[4], s_hi[4];
+    __shared__ double lds[2 * 4];
     double lo = INFINITY, hi = -INFINITY;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const double x = xy[i].x;
         lo = fmin(lo, x), hi = fmax(hi, x);
     }
-    block_min_max(lo, hi, s_lo, s_hi);
+    block_reduce<256, OpMin, OpMax>(lds, lo, hi);
     if (threadIdx.x == 0) partial[2 * blockIdx.x] = lo, partial[2 * blockIdx.x + 1] = hi;
-}
-
-// one block: out[0], out[1] = min, max over the n_partial pairs
-__global__ void __launch_bounds__(256) k_periodic_x_range_fold(const double *__restrict__ partial, int n_partial, double *__restrict__ out) {
-    __shared__ double s_lo[4], s_hi[4];
-    double lo = INFINITY, hi = -INFINITY;
-    for (int b = threadIdx.x; b < n_partial; b += 256) lo = fmin(lo, partial[2 * b]), hi = fmax(hi, partial[2 * b + 1]);
-    block_min_max(lo, hi, s_lo, s_hi);
-    if (threadIdx.x == 0) out[0] = lo, out[1] = hi;
 }
 
 // ---- wrap
@@ -244,12 +224,12 @@ __global__ void __launch_bounds__(256) k_periodic_iota(int64_t n, int64_t *__res
 static void node_x_range(const xr_mesh *mesh, double &xmin, double &xmax) {
     const int64_t N = mesh->n_node;
     const int blocks = (int)std::min<int64_t>(div_up(N, 256), PERIODIC_RANGE_BLOCKS);
-    DevBuf<double> partial((size_t)2 * blocks + 2);
     const double2 *xy = reinterpret_cast<const double2 *>(mesh->node_xy.get());
-    XR_LAUNCH("periodic_x_range", k_periodic_x_range, dim3(blocks), dim3(256), 0, xy, N, partial.get());
-    XR_LAUNCH("periodic_x_range_fold", k_periodic_x_range_fold, dim3(1), dim3(256), 0, partial.get(), blocks, partial.get() + 2 * blocks);
+    TwoStageReduce<256, double, OpMin, OpMax> range("periodic_x_range_fold", blocks, [&](double *partial) {
+        XR_LAUNCH("periodic_x_range", k_periodic_x_range, dim3(blocks), dim3(256), 0, xy, N, partial);
+    });
     double h[2];
-    d2h(h, partial.get() + 2 * blocks, sizeof(h));
+    range.read(h);
     xmin = h[0], xmax = h[1];
 }
 

@@ -298,8 +298,7 @@ k_pg_ring_sign(const int32_t *__restrict__ listed, const int32_t *__restrict__ r
         const double ax = node_xy[2 * a] - x0, ay = node_xy[2 * a + 1] - y0, bx = node_xy[2 * b] - x0, by = node_xy[2 * b + 1] - y0;
         sum += ax * by - bx * ay;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    sum = wave_reduce<OpSum>(sum); // (a sum of doubles: the order of xr_prims.h)
     if (lane == 0) ring_sign[r] = sum > 0.0 ? 1 : sum < 0.0 ? -1 : 0;
 }
 

@@ -1,7 +1,11 @@
-// xr_prims.h -- the small device idioms the mesh-operation units share: a per-wave counter and flag, the wave / block scan and the block sort of a row, the int32 -> int64
+// xr_prims.h -- the small device idioms the mesh-operation units share: a per-wave counter and flag, the wave / block
+// reduction and the two-launch reduction of an array, the wave / block scan and the block sort of a row, the int32 -> int64
 // widening on the way out of the library, and the compaction behind "flags -> exclusive scan -> ascending ids".  Kernels are
 // `static`: every translation unit that includes this header gets its own copy (as in xr_node_faces.h).
 #pragma once
+#include <limits>
+#include <type_traits>
+
 #include "xr_internal.h"
 
 namespace xr {
@@ -17,27 +21,165 @@ __device__ __forceinline__ void wave_flag(bool bad, int32_t *flag) {
     if (__ballot(bad) && (threadIdx.x & 63) == 0) *flag = 1;
 }
 
+// ---- reductions -----------------------------------------------------------------------------------------------------------------
+// THE ORDER IS A CONTRACT: results are compared bit for bit, and several callers sum doubles (the dot products of the Laplace
+// fill's CG and its mean edge length, the |dy| total that sizes the burn strips, the ring areas of polygonize).
+//   1. the 64 lane values of a wave are combined by the xor butterfly over the offsets 32, 16, 8, 4, 2, 1, each step
+//      v = op(v, the partner's v);
+//   2. the wave results are folded in ascending wave number, starting from wave 0's value: ((w0 op w1) op w2) op w3;
+//   3. the second stage of a two-launch reduction: thread t starts from the operator's identity and takes the partials
+//      t, t + BLOCK, t + 2 BLOCK, ... in that order; then 1 and 2.
+// Changing any of the three changes stored results without failing a test that compares within a tolerance.
+//
+// An operator: identity<T>() and apply(a, b).  Floating-point minimum and maximum are fmin / fmax (a NaN is passed over; only
+// an all-NaN input gives NaN), integer ones are comparisons.  The identity of a floating-point sum is +0.0, so a fold of
+// partials never hands on a -0.0.
+struct OpMin {
+    template <typename T> static constexpr T identity() {
+        return std::numeric_limits<T>::has_infinity ? std::numeric_limits<T>::infinity() : std::numeric_limits<T>::max();
+    }
+    template <typename T> __device__ __forceinline__ static T apply(T a, T b) {
+        if constexpr (std::is_floating_point_v<T>) return fmin(a, b);
+        else return b < a ? b : a;
+    }
+};
+struct OpMax {
+    template <typename T> static constexpr T identity() {
+        return std::numeric_limits<T>::has_infinity ? -std::numeric_limits<T>::infinity() : std::numeric_limits<T>::lowest();
+    }
+    template <typename T> __device__ __forceinline__ static T apply(T a, T b) {
+        if constexpr (std::is_floating_point_v<T>) return fmax(a, b);
+        else return b > a ? b : a;
+    }
+};
+struct OpSum {
+    template <typename T> static constexpr T identity() { return T(0); }
+    template <typename T> __device__ __forceinline__ static T apply(T a, T b) { return a + b; }
+};
+
+// step 1 of the order: the value of the whole wave, in every lane (every lane of the wave must get here)
+template <typename OP, typename T> __device__ __forceinline__ T wave_reduce(T v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = OP::apply(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// step 2: v[u] holds the value of the caller's wave under OPS[u] -> the block's.  ALL = false: in thread 0 only, and no barrier
+// behind the read of `lds` (a second call on the same `lds` needs one in front); ALL = true: in every thread, behind a barrier.
+// lds: sizeof...(OPS) * BLOCK / 64 values.  Every thread of the block must get here.
+template <bool ALL, int BLOCK, typename... OPS, typename T>
+__device__ __forceinline__ void block_fold_waves(T *lds, T (&v)[sizeof...(OPS)]) {
+    constexpr int W = BLOCK / 64;
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int u = 0; u < (int)sizeof...(OPS); u++) lds[u * W + wave] = v[u];
+    }
+    __syncthreads();
+    if (ALL || threadIdx.x == 0) {
+        int u = 0;
+        auto fold = [&](auto op) {
+            T r = lds[u * W];
+#pragma unroll
+            for (int w = 1; w < W; w++) r = decltype(op)::apply(r, lds[u * W + w]);
+            v[u++] = r;
+        };
+        (fold(OPS()), ...);
+    }
+    if (ALL) __syncthreads();
+}
+
+// steps 1 and 2: one value per thread and operator -> the block's (where, and `lds`: see block_fold_waves)
+template <bool ALL, int BLOCK, typename... OPS, typename T>
+__device__ __forceinline__ void block_reduce_array(T *lds, T (&v)[sizeof...(OPS)]) {
+    int u = 0;
+    ((v[u] = wave_reduce<OPS>(v[u]), u++), ...);
+    block_fold_waves<ALL, BLOCK, OPS...>(lds, v);
+}
+
+// ... of separate variables: block_reduce<256, OpMin, OpMax>(lds, lo, hi).  The results are in thread 0 ...
+template <int BLOCK, typename... OPS, typename T, typename... TS> __device__ __forceinline__ void block_reduce(T *lds, TS &...v) {
+    static_assert(sizeof...(OPS) == sizeof...(TS) && (std::is_same_v<T, TS> && ...), "one operator per value, one value type");
+    T a[] = {v...};
+    block_reduce_array<false, BLOCK, OPS...>(lds, a);
+    int u = 0;
+    ((v = a[u++]), ...);
+}
+// ... or in every thread
+template <int BLOCK, typename... OPS, typename T, typename... TS> __device__ __forceinline__ void block_reduce_all(T *lds, TS &...v) {
+    static_assert(sizeof...(OPS) == sizeof...(TS) && (std::is_same_v<T, TS> && ...), "one operator per value, one value type");
+    T a[] = {v...};
+    block_reduce_array<true, BLOCK, OPS...>(lds, a);
+    int u = 0;
+    ((v = a[u++]), ...);
+}
+
+// step 3 and the block reduction behind it, by one block: record b of `partial` holds one value per operator
+template <bool ALL, int BLOCK, typename... OPS, typename T>
+__device__ __forceinline__ void block_fold_partials(T *lds, const T *__restrict__ partial, int n_partial, T (&v)[sizeof...(OPS)]) {
+    constexpr int N = (int)sizeof...(OPS);
+    int u = 0;
+    ((v[u++] = OPS::template identity<T>()), ...);
+    for (int b = threadIdx.x; b < n_partial; b += BLOCK) {
+        const T *p = partial + (int64_t)b * N;
+        u = 0;
+        ((v[u] = OPS::apply(v[u], p[u]), u++), ...);
+    }
+    block_reduce_array<ALL, BLOCK, OPS...>(lds, v);
+}
+
+// the second launch of a two-launch reduction: one block, out[u] = OPS[u] over value u of the n_partial records
+template <int BLOCK, typename T, typename... OPS>
+static __global__ void __launch_bounds__(BLOCK) k_fold_partials(const T *__restrict__ partial, int n_partial, T *__restrict__ out) {
+    constexpr int N = (int)sizeof...(OPS);
+    __shared__ T lds[N * (BLOCK / 64)];
+    T v[N];
+    block_fold_partials<false, BLOCK, OPS...>(lds, partial, n_partial, v);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int u = 0; u < N; u++) out[u] = v[u];
+    }
+}
+
+// A two-launch reduction: first_stage(partial) launches the unit's own kernel, whose block b writes record b of n_block
+// records; the fold (timed as `fold_name`) leaves the sizeof...(OPS) results behind the records, where result() points.
+// read() brings them to the host: one read-back.
+template <int BLOCK, typename T, typename... OPS> struct TwoStageReduce {
+    static constexpr int N = (int)sizeof...(OPS);
+    DevBuf<T> buf;
+    unsigned n_block;
+    template <typename FIRST>
+    TwoStageReduce(const char *fold_name, unsigned n_block, FIRST &&first_stage) : buf((size_t)(n_block + 1) * N), n_block(n_block) {
+        first_stage(buf.get());
+        XR_LAUNCH(fold_name, (k_fold_partials<BLOCK, T, OPS...>), dim3(1), dim3(BLOCK), 0, buf.get(), (int)n_block, result());
+    }
+    T *result() { return buf.get() + (size_t)n_block * N; }
+    void read(T (&host)[N]) { d2h(host, result(), sizeof(host)); }
+};
+
+// ---- scans ----------------------------------------------------------------------------------------------------------------------
 // inclusive scan of one value per lane of the wave
-__device__ __forceinline__ int wave_incl_scan(int v) {
+template <typename T> __device__ __forceinline__ T wave_incl_scan(T v) {
     const int lane = threadIdx.x & 63;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
-        int t = __shfl_up(v, d, 64);
+        T t = __shfl_up(v, d, 64);
         if (lane >= d) v += t;
     }
     return v;
 }
 
-// block-wide exclusive scan of one value per thread; returns exclusive prefix, total via *total
-template <int BLOCK = 256> __device__ __forceinline__ int block_excl_scan(int v, int *total, int *lds /* >= BLOCK / 64 ints */) {
+// block-wide exclusive scan of one value per thread; returns exclusive prefix, total via *total (every thread must get here;
+// ends behind a barrier)
+template <int BLOCK = 256, typename T = int> __device__ __forceinline__ T block_excl_scan(T v, T *total, T *lds /* >= BLOCK / 64 values */) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = wave_incl_scan(v);
+    T incl = wave_incl_scan(v);
     if (lane == 63) lds[wave] = incl;
     __syncthreads();
-    int woff = 0, tot = 0;
+    T woff = 0, tot = 0;
 #pragma unroll
     for (int w = 0; w < BLOCK / 64; w++) {
-        int s = lds[w];
+        T s = lds[w];
         if (w < wave) woff += s;
         tot += s;
     }

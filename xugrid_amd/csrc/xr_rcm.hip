@@ -62,8 +62,7 @@ k_rcm_init(const int32_t *__restrict__ indptr, const int32_t *__restrict__ indic
         parent[i] = RCM_NONE;
         ids[i] = (int32_t)i;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) d = max(d, __shfl_xor(d, o, 64));
+    d = wave_reduce<OpMax>(d);
     if ((threadIdx.x & 63) == 0 && d > 0) atomicMax(ctl + RW_MAXDEG, d);
 }
 

@@ -35,35 +35,13 @@ __device__ __forceinline__ bool sp_takes_part(const double *__restrict__ values,
     return !values || (values[i] != values[i]) == want_nan;
 }
 
-// block reduction of a box and a count; thread 0 writes out[0..4] = xmin, xmax, ymin, ymax, count.  c is the count of the
-// caller's WAVE already: the kernel over the points lives on its cross-lane operations (12.4 us for 1M points with the four
-// box values, 15.1 us with a fifth value in the butterfly), and a ballot counts a wave for nothing.
-__device__ __forceinline__ void sp_box_reduce(double x0, double x1, double y0, double y1, double c, double *__restrict__ out) {
-    __shared__ double sh[5][SB / 64];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        x0 = fmin(x0, __shfl_xor(x0, o, 64));
-        x1 = fmax(x1, __shfl_xor(x1, o, 64));
-        y0 = fmin(y0, __shfl_xor(y0, o, 64));
-        y1 = fmax(y1, __shfl_xor(y1, o, 64));
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) sh[0][w] = x0, sh[1][w] = x1, sh[2][w] = y0, sh[3][w] = y1, sh[4][w] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int u = 1; u < SB / 64; u++) {
-            sh[0][0] = fmin(sh[0][0], sh[0][u]), sh[1][0] = fmax(sh[1][0], sh[1][u]);
-            sh[2][0] = fmin(sh[2][0], sh[2][u]), sh[3][0] = fmax(sh[3][0], sh[3][u]);
-            sh[4][0] += sh[4][u];
-        }
-        for (int u = 0; u < 5; u++) out[u] = sh[u][0];
-    }
-}
-
-// per block: the bounding box of its points that take part and their number -> partial[b * 5 ..] (NaN coordinates are
-// passed over by the box and counted)
+// per block: the bounding box of its points that take part and their number -> partial[b * 5 ..] = xmin, xmax, ymin, ymax,
+// count (NaN coordinates are passed over by the box and counted).  The count of a WAVE is a ballot, so the block reduction is
+// taken in its two steps: the kernel lives on its cross-lane operations (12.4 us for 1M points with the four box values, 15.1 us
+// with a fifth value in the butterfly).
 __global__ void __launch_bounds__(SB)
 k_sp_bbox(const double2 *__restrict__ xy, const double *__restrict__ values, int64_t n, double *__restrict__ partial) {
+    __shared__ double lds[5 * (SB / 64)];
     const int64_t i = (int64_t)blockIdx.x * SB + threadIdx.x;
     double x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
     const bool mine = i < n && sp_takes_part(values, false, i);
@@ -71,18 +49,11 @@ k_sp_bbox(const double2 *__restrict__ xy, const double *__restrict__ values, int
         const double2 p = xy[i];
         x0 = fmin(x0, p.x), x1 = fmax(x1, p.x), y0 = fmin(y0, p.y), y1 = fmax(y1, p.y);
     }
-    sp_box_reduce(x0, x1, y0, y1, (double)__popcll(__ballot(mine)), partial + (int64_t)blockIdx.x * 5);
-}
-
-__global__ void __launch_bounds__(SB) k_sp_bbox_final(const double *__restrict__ partial, int nb, double *__restrict__ out) {
-    double x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY, c = 0.0;
-    for (int b = threadIdx.x; b < nb; b += SB) {
-        const double *p = partial + (int64_t)b * 5;
-        x0 = fmin(x0, p[0]), x1 = fmax(x1, p[1]), y0 = fmin(y0, p[2]), y1 = fmax(y1, p[3]), c += p[4];
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    sp_box_reduce(x0, x1, y0, y1, c, out);
+    double v[5] = {wave_reduce<OpMin>(x0), wave_reduce<OpMax>(x1), wave_reduce<OpMin>(y0), wave_reduce<OpMax>(y1),
+                   (double)__popcll(__ballot(mine))};
+    block_fold_waves<false, SB, OpMin, OpMax, OpMin, OpMax, OpSum>(lds, v);
+    if (threadIdx.x == 0)
+        for (int u = 0; u < 5; u++) partial[(int64_t)blockIdx.x * 5 + u] = v[u];
 }
 
 // counting sort by grid cell of the points that take part, used for the indexed points and for the queries alike: histogram,
@@ -241,12 +212,11 @@ NnExtent nn_extent(const double *xy_dev, int64_t n, const double *values_dev) {
     NnExtent ext{{INFINITY, -INFINITY, INFINITY, -INFINITY}, 0};
     if (n <= 0) return ext;
     const unsigned nb = div_up(n, SB);
-    DevBuf<double> partial((size_t)nb * 5), box_dev(5);
-    XR_LAUNCH("sample_bbox", k_sp_bbox, dim3(nb), dim3(SB), 0, reinterpret_cast<const double2 *>(xy_dev), values_dev, n,
-              partial.get());
-    XR_LAUNCH("sample_bbox_final", k_sp_bbox_final, dim3(1), dim3(SB), 0, partial.get(), (int)nb, box_dev.get());
+    TwoStageReduce<SB, double, OpMin, OpMax, OpMin, OpMax, OpSum> box("sample_bbox_final", nb, [&](double *partial) {
+        XR_LAUNCH("sample_bbox", k_sp_bbox, dim3(nb), dim3(SB), 0, reinterpret_cast<const double2 *>(xy_dev), values_dev, n, partial);
+    });
     double h[5];
-    d2h(h, box_dev.get(), sizeof(h));
+    box.read(h);
     std::copy(h, h + 4, ext.box);
     ext.n = (int64_t)h[4];
     return ext;

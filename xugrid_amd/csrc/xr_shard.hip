@@ -67,58 +67,25 @@ __device__ __forceinline__ int face_geometry(const double *__restrict__ xy, cons
     return n;
 }
 
-// Bounds of a set of boxes, two stages: every block reduces its boxes (waves by shuffles, the block through LDS) and writes ONE
-// partial (min x, min y, max x, max y) to its slot; a one-block kernel folds the partials.  (One set of same-address atomics
+// Bounds of a set of boxes, two stages: every block reduces its boxes (block_reduce, xr_prims.h) and writes ONE partial
+// (min x, min y, max x, max y) to its slot; a one-block kernel folds the partials.  (One set of same-address atomics
 // per wave -- 375 k of them for a 1M + 1M pair -- cost 3 ms: the L2 serves a contended word at a few hundred million a second.)
-__device__ __forceinline__ void bounds_block_partial(double4 *__restrict__ partial, bool valid, double x0, double y0, double x1, double y1) {
-    __shared__ double4 sh[4];
+// A kernel calls this once per set: the barrier in front is for the LDS slots an earlier call may still be reading.
+__device__ __forceinline__ void bounds_of_block(double4 *__restrict__ partial, bool valid, double x0, double y0, double x1, double y1) {
+    __shared__ double sh[4 * 4];
     double a = valid ? x0 : INFINITY, c = valid ? y0 : INFINITY, d = valid ? x1 : -INFINITY, e = valid ? y1 : -INFINITY;
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        a = fmin(a, __shfl_xor(a, s, 64));
-        c = fmin(c, __shfl_xor(c, s, 64));
-        d = fmax(d, __shfl_xor(d, s, 64));
-        e = fmax(e, __shfl_xor(e, s, 64));
-    }
-    __syncthreads(); // (the LDS slots may still be read from an earlier call)
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = make_double4(a, c, d, e);
     __syncthreads();
-    if (threadIdx.x == 0) {
-        double4 r = sh[0];
-        for (int w = 1; w < 4; w++) {
-            r.x = fmin(r.x, sh[w].x); r.y = fmin(r.y, sh[w].y);
-            r.z = fmax(r.z, sh[w].z); r.w = fmax(r.w, sh[w].w);
-        }
-        partial[blockIdx.x] = r;
-    }
+    block_reduce<256, OpMin, OpMin, OpMax, OpMax>(sh, a, c, d, e);
+    if (threadIdx.x == 0) partial[blockIdx.x] = make_double4(a, c, d, e);
 }
 // partials [n_sets][n_blocks] -> Bounds[n_sets] (one block of 256 threads per set)
 __global__ void __launch_bounds__(256) k_shard_fold_bounds(const double4 *__restrict__ partial, int64_t n_blocks, Bounds *__restrict__ out) {
-    __shared__ double4 sh[4];
-    const double4 *p = partial + (int64_t)blockIdx.x * n_blocks;
-    double a = INFINITY, c = INFINITY, d = -INFINITY, e = -INFINITY;
-    for (int64_t i = threadIdx.x; i < n_blocks; i += 256) {
-        const double4 v = p[i];
-        a = fmin(a, v.x); c = fmin(c, v.y); d = fmax(d, v.z); e = fmax(e, v.w);
-    }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        a = fmin(a, __shfl_xor(a, s, 64));
-        c = fmin(c, __shfl_xor(c, s, 64));
-        d = fmax(d, __shfl_xor(d, s, 64));
-        e = fmax(e, __shfl_xor(e, s, 64));
-    }
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = make_double4(a, c, d, e);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double4 r = sh[0];
-        for (int w = 1; w < 4; w++) {
-            r.x = fmin(r.x, sh[w].x); r.y = fmin(r.y, sh[w].y);
-            r.z = fmax(r.z, sh[w].z); r.w = fmax(r.w, sh[w].w);
-        }
-        out[blockIdx.x].k[0] = dkey(r.x); out[blockIdx.x].k[1] = dkey(r.y);
-        out[blockIdx.x].k[2] = dkey(r.z); out[blockIdx.x].k[3] = dkey(r.w);
-    }
+    __shared__ double sh[4 * 4];
+    double r[4];
+    block_fold_partials<false, 256, OpMin, OpMin, OpMax, OpMax>(sh, reinterpret_cast<const double *>(partial + (int64_t)blockIdx.x * n_blocks),
+                                                                 (int)n_blocks, r);
+    if (threadIdx.x == 0)
+        for (int u = 0; u < 4; u++) out[blockIdx.x].k[u] = dkey(r[u]);
 }
 
 // pass 1: centroids of both meshes (stored) and their bounds
@@ -136,8 +103,8 @@ k_shard_centroids(const double *__restrict__ sxy, const int64_t *__restrict__ sf
     else if (valid) tcen[i - S] = make_double2(cx, cy);
     // (a block holds faces of one mesh except the one straddling S: the two reductions are masked per mesh; a face without a
     // valid node has no centroid -- its (0, 0) must not stretch the bounds the Morton cells are cut from)
-    bounds_block_partial(partial, is_src && n_nodes > 0, cx, cy, cx, cy);
-    bounds_block_partial(partial + gridDim.x, valid && !is_src && n_nodes > 0, cx, cy, cx, cy);
+    bounds_of_block(partial, is_src && n_nodes > 0, cx, cy, cx, cy);
+    bounds_of_block(partial + gridDim.x, valid && !is_src && n_nodes > 0, cx, cy, cx, cy);
 }
 
 __device__ __forceinline__ int raster_cell(double v, double lo, double f, int n) {
@@ -284,7 +251,7 @@ k_shard_box_bounds(const double *__restrict__ sxy, const int64_t *__restrict__ s
         face_geometry(txy, tf, i - S, mt, cx, cy, x0, y0, x1, y1);
         valid = x0 <= x1;
     }
-    bounds_block_partial(partial, valid, x0, y0, x1, y1);
+    bounds_of_block(partial, valid, x0, y0, x1, y1);
 }
 
 // pass 6: difference array of my source faces' boxes on the occupancy raster

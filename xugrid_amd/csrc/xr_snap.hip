@@ -78,9 +78,7 @@ k_snap_count(const double2 *__restrict__ xy, int64_t n, const double2 *__restric
         c -= 1;
         count[i] = c;
     }
-    unsigned long long sum = (unsigned long long)c;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    const unsigned long long sum = wave_reduce<OpSum>((unsigned long long)c);
     if ((threadIdx.x & 63) == 0 && sum) atomicAdd(total, sum);
 }
 

@@ -235,8 +235,7 @@ k_sg_rows(const int32_t *__restrict__ entry_face, const int32_t *__restrict__ in
         }
     }
     if constexpr (!FILL) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+        mine = wave_reduce<OpSum>(mine);
         // (one word for all waves is one atomic at a time: 88 000 waves on it were four fifths of this kernel)
         if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&total[(blockIdx.x % SG_TOTALS) * SG_TOTAL_STRIDE], mine);
     }

@@ -143,11 +143,7 @@ k_topo_nbrs_long(const int32_t *__restrict__ faces, int m, const int32_t *__rest
             cnt++;
             high += c > v;
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            cnt += __shfl_xor(cnt, o, 64);
-            high += __shfl_xor(high, o, 64);
-        }
+        cnt = wave_reduce<OpSum>(cnt), high = wave_reduce<OpSum>(high);
         if (lane == 0) {
             n_all[v] = cnt;
             n_high[v] = high;

@@ -193,11 +193,7 @@ k_vor_interior(const double *__restrict__ node_xy, const double *__restrict__ cx
     // atomicMin + one atomicMax per NODE on the same two words cost 0.13 ms of the kernel's 0.23 (A/B without them: 0.097)
     {
         int dmin = ok ? e - s : INT32_MAX, dmax = ok ? e - s : 0;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            dmin = min(dmin, __shfl_xor(dmin, d, 64));
-            dmax = max(dmax, __shfl_xor(dmax, d, 64));
-        }
+        dmin = wave_reduce<OpMin>(dmin), dmax = wave_reduce<OpMax>(dmax);
         if ((t & 63) == 0) {
             if (dmin < __hip_atomic_load(&deg_minmax[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&deg_minmax[0], dmin);
             if (dmax > __hip_atomic_load(&deg_minmax[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&deg_minmax[1], dmax);
