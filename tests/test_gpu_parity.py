@@ -97,7 +97,7 @@ def test_overlap_clockwise_and_fill_values(hip, oracle):
 
 def test_overlap_quadrilateral_targets_on_triangles(hip, oracle, monkeypatch, xr_option):
     """The shape of the reference's unstructured -> raster regridding: quadrilateral targets against a triangle source go
-    through the flag / compaction clip with a four-vertex subject (k_clip_quad_tri).  A raster whose cell lines pass through
+    through the flag / compaction clip with a four-vertex subject (k_clip_tri<., 4>).  A raster whose cell lines pass through
     source vertices (a lattice-split triangulation: exact contacts), a rotated and sheared quad mesh, clockwise quads,
     and a target that mixes quads with triangles (fill slot); bit-equal to the oracle and to the slot-loop kernel
     (XR_CLIP_QUAD=0), absolute and relative."""

@@ -18,6 +18,7 @@
 
 #include "xr_apply.h"
 #include "xr_reduce.h"
+#include "xr_prims.h"
 
 namespace xr {
 
@@ -255,9 +256,7 @@ k_apply_rows1(const int32_t *__restrict__ indptr, const int32_t *__restrict__ in
     }
     const bool skip = n_long_blocks > 0 && (e - s > APPLY_LONG); // reduced by the long-row blocks
     const int seg0 = __shfl(s, 0, 64);
-    int seg1 = e; // (lanes beyond T hold 0: the maximum is the end of the last valid row)
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) seg1 = max(seg1, __shfl_xor(seg1, d, 64));
+    const int seg1 = wave_reduce<OpMax>(e); // (lanes beyond T hold 0: the maximum is the end of the last valid row)
     if (skip) e = s;
     const bool jumpy = __any(skip);
     double2 *win = sh_win[wib];
@@ -265,9 +264,7 @@ k_apply_rows1(const int32_t *__restrict__ indptr, const int32_t *__restrict__ in
     auto next_chunk = [&](int c0) -> int {
         if (!jumpy) return c0;
         int mine = (e > s && e > c0) ? (s > c0 ? s : c0) : INT_MAX;
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) mine = min(mine, __shfl_xor(mine, d, 64));
-        return mine;
+        return wave_reduce<OpMin>(mine);
     };
     double normsum = 0.0;
     if (METHOD == XR_GEOMETRIC_MEAN) {
@@ -453,12 +450,7 @@ k_plan_build(const int32_t *__restrict__ indptr, const int32_t *__restrict__ ind
     int cnt = 0;
     for (int i = a0; i < a1; i++) cnt += (i == 0 || keys[i] != keys[i - 1]) ? 1 : 0;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int v = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += v;
-    }
+    const int incl = wave_incl_scan(cnt);
     if (lane == 63) sh_wave[wave] = incl;
     __syncthreads();
     int woff = 0, total = 0;
@@ -582,12 +574,7 @@ k_plan_build_group(const int32_t *__restrict__ indptr, const int32_t *__restrict
     int cnt = 0;
     for (int i = a0; i < a1; i++) cnt += (i == 0 || keys[i] != keys[i - 1]) ? 1 : 0;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int v = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += v;
-    }
+    const int incl = wave_incl_scan(cnt);
     __syncthreads();
     if (lane == 63) sh_wave[wave] = incl;
     __syncthreads();
@@ -1135,21 +1122,15 @@ k_apply_sorted(const int32_t *__restrict__ indptr, const int32_t *__restrict__ i
                 sv[i] = v;
                 si[i] = (uint16_t)(v == INFINITY && !(i < n && ld_src(src, indices[s + i]) == INFINITY) ? (i | 0x8000) : i);
             }
-#pragma unroll
-            for (int d = 32; d > 0; d >>= 1) {
-                n_valid += __shfl_xor(n_valid, d, 64);
-                w_max = fmax(w_max, __shfl_xor(w_max, d, 64));
-                v_min = fmin(v_min, __shfl_xor(v_min, d, 64));
-                v_max = fmax(v_max, __shfl_xor(v_max, d, 64));
-            }
+            n_valid = wave_reduce<OpSum>(n_valid), w_max = wave_reduce<OpMax>(w_max);
+            v_min = wave_reduce<OpMin>(v_min), v_max = wave_reduce<OpMax>(v_max);
             double res = NAN;
             if (METHOD == XR_PERCENTILE && (p == 0 || p == 100)) {
                 // reduce.py:172-176: _minimum / _maximum (NaN skipped; NaN if every weight of a valid entry is 0)
                 double wm = 0.0;
                 for (int i = lane; i < n; i += 64)
                     if (!(si[i] & 0x8000)) wm = fmax(wm, data[s + i]);
-#pragma unroll
-                for (int d = 32; d > 0; d >>= 1) wm = fmax(wm, __shfl_xor(wm, d, 64));
+                wm = wave_reduce<OpMax>(wm);
                 if (w_max != 0.0 && n_valid > 0 && wm != 0.0) res = p == 0 ? v_min : v_max;
                 if (lane == 0) out[k * T + t_out] = res;
                 continue;

@@ -17,6 +17,7 @@
 #include "xr_objects.h"
 #include "xr_agg.h"
 #include "xr_edge_clip.h"
+#include "xr_prims.h"
 
 namespace xr {
 
@@ -379,15 +380,7 @@ k_edge_walk(const double *__restrict__ edge_xy, int64_t n_edge, int64_t e_base, 
     // EDGE, in walk order (lane l's candidates behind those of the lanes below it): the clip's 64 lanes then read the same two
     // end points and neighbouring records -- a few lines per load instead of 64 (the clip is bound by the address rate of
     // its gathers, not by arithmetic: 7 loads x 64 lines per round).
-    {
-        int incl = stored;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int u = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += u;
-        }
-        sh_first[tid] = incl - stored;
-    }
+    sh_first[tid] = wave_incl_scan(stored) - stored;
     __syncthreads();
     int n_w[4], total = 0;
 #pragma unroll

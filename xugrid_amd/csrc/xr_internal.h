@@ -310,7 +310,7 @@ bool side_mark(); // record the fork point now; false: no side stream here (Side
 enum Option : int {
     OPT_OVERLAP_FUSED,     // 1: dense meshes of <= 4 nodes per face take the one-round-trip pipeline; 0: the general kernel chain
     OPT_QUEUE_MARGIN,      // > 0: capacity of the big faces' pair queue (tests force the regrow path with a tiny one)
-    OPT_CLIP_QUAD,         // 1: quadrilateral targets x triangle source through k_clip_quad_tri (general chain); 0: k_clip_small
+    OPT_CLIP_QUAD,         // 1: quadrilateral targets x triangle source through k_clip_tri<., 4> (general chain); 0: k_clip_small
     OPT_DUST,              // 1: rounding dust confirmed by the reference's pre-clip tests; 0: the round-3 behaviour
     OPT_DEBUG,             // bits: 1 one line per weight build, 2 apply-plan statistics, 4 Voronoi sizes (stderr)
     OPT_HOST_STAMPS,       // 1: wall-clock stamps along the host path of a weight build, averages at exit

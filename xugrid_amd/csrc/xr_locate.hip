@@ -10,6 +10,7 @@
 
 #include "xr_objects.h"
 #include "xr_point_in_face.h"
+#include "xr_prims.h"
 
 // query points of a barycentric construction + "inside the source grid" flags, resident in HBM (xr_locate_flags_begin)
 struct xr_points {
@@ -86,13 +87,7 @@ __device__ int locate_prepare(LocateBig &sh, const GridParams &g, const int32_t 
             bx0 = f32_below(p.x - tol - g.x0), bx1 = f32_above(p.x + tol - g.x0);
             by0 = f32_below(p.y - tol - g.y0), by1 = f32_above(p.y + tol - g.y0);
         }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            bx0 = fminf(bx0, __shfl_xor(bx0, d, 64));
-            bx1 = fmaxf(bx1, __shfl_xor(bx1, d, 64));
-            by0 = fminf(by0, __shfl_xor(by0, d, 64));
-            by1 = fmaxf(by1, __shfl_xor(by1, d, 64));
-        }
+        bx0 = wave_reduce<OpMin>(bx0), bx1 = wave_reduce<OpMax>(bx1), by0 = wave_reduce<OpMin>(by0), by1 = wave_reduce<OpMax>(by1);
         if ((threadIdx.x & 63) == 0) {
             const int w = threadIdx.x >> 6;
             sh.box[w][0] = bx0; sh.box[w][1] = bx1; sh.box[w][2] = by0; sh.box[w][3] = by1;
@@ -233,12 +228,7 @@ __device__ int locate_point(const double *__restrict__ rec_fxy, const uint8_t *_
     // the wave's list of parked candidates
     const bool overflow = nc > LOC_CAND;
     const int parked = overflow ? 0 : nc;
-    int incl = parked;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int v = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += v;
-    }
+    const int incl = wave_incl_scan(parked);
     const int total = __shfl(incl, 63, 64), excl = incl - parked;
     for (int k = 0; k < parked; k++) big.owner[wv][excl + k] = (uint16_t)(lane | (k << 8));
     __syncthreads(); // (the list, the candidates and every point's `best` word are in LDS)

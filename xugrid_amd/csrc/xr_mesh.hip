@@ -25,21 +25,19 @@ namespace xr {
 
 static constexpr int PREP_BLOCK = 256;
 
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = fmin(v, __shfl_down(v, d, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = fmax(v, __shfl_down(v, d, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-    return v;
-}
+// The eight statistics of a mesh, in the order of xr_mesh::stats and of a block's partial record: x and y bounds, sum and
+// maximum of the faces' bbox extents, largest bbox diagonal, sum of the numbering jumps (a sampled pass: faces sampled).  Their
+// operators are named here once; the order of every reduction is that of xr_prims.h, so the results are deterministic.
+// lds: 8 * BLOCK / 64 doubles; the results are in thread 0.
+template <int BLOCK, typename... OPS> struct StatsReduce {
+    // one value per thread and statistic -> the block's
+    __device__ __forceinline__ static void block(double *lds, double (&v)[8]) { block_reduce_array<false, BLOCK, OPS...>(lds, v); }
+    // the nb partial records the blocks of a statistics kernel left -> the mesh's
+    __device__ __forceinline__ static void partials(double *lds, const double *__restrict__ partial, int nb, double (&v)[8]) {
+        block_fold_partials<false, BLOCK, OPS...>(lds, partial, nb, v);
+    }
+};
+template <int BLOCK> using MeshStats = StatsReduce<BLOCK, OpMin, OpMax, OpMin, OpMax, OpSum, OpMax, OpMax, OpSum>;
 
 // ---------------------------------------------------------------------------------------------
 // per-face preparation.  MC > 0: compile-time vertices per face; MC == 0: runtime m <= 32.
@@ -92,8 +90,7 @@ struct StatsTail {
 };
 
 // (bid / nb: the block's index among the nb blocks that share the tail -- the whole grid, or one part of the paired k_prepare_faces')
-__device__ __forceinline__ void stats_tail(const StatsTail &t, const double (&a)[8], double (*lds)[PREP_BLOCK / 64], int64_t bid,
-                                           int64_t nb) {
+__device__ __forceinline__ void stats_tail(const StatsTail &t, const double (&a)[8], double *lds, int64_t bid, int64_t nb) {
     __shared__ int s_last;
     if (threadIdx.x == 0) {
         double *p = t.partials + bid * 8;
@@ -121,31 +118,19 @@ __device__ __forceinline__ void stats_tail(const StatsTail &t, const double (&a)
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     }
     __syncthreads();
-    double a0 = INFINITY, a1 = -INFINITY, a2 = INFINITY, a3 = -INFINITY, a4 = 0.0, a5 = 0.0, a6 = 0.0, a7 = 0.0;
+    // (the strided step of block_fold_partials, spelled out for the agent-scope loads)
+    double r[8] = {INFINITY, -INFINITY, INFINITY, -INFINITY, 0.0, 0.0, 0.0, 0.0};
     for (int64_t i = threadIdx.x; i < nb; i += PREP_BLOCK) {
         const double *p = t.partials + i * 8;
         double v[8];
 #pragma unroll
         for (int k = 0; k < 8; k++) v[k] = __hip_atomic_load(&p[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        a0 = fmin(a0, v[0]); a1 = fmax(a1, v[1]); a2 = fmin(a2, v[2]);
-        a3 = fmax(a3, v[3]); a4 += v[4]; a5 = fmax(a5, v[5]); a6 = fmax(a6, v[6]); a7 += v[7];
+        r[0] = fmin(r[0], v[0]); r[1] = fmax(r[1], v[1]); r[2] = fmin(r[2], v[2]); r[3] = fmax(r[3], v[3]);
+        r[4] += v[4]; r[5] = fmax(r[5], v[5]); r[6] = fmax(r[6], v[6]); r[7] += v[7];
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    a0 = wave_min(a0); a1 = wave_max(a1); a2 = wave_min(a2); a3 = wave_max(a3); a4 = wave_sum(a4); a5 = wave_max(a5);
-    a6 = wave_max(a6);
-    a7 = wave_sum(a7);
     __syncthreads(); // (lds still holds the block's own wave partials for thread 0 above)
-    if (lane == 0) {
-        lds[0][wave] = a0; lds[1][wave] = a1; lds[2][wave] = a2;
-        lds[3][wave] = a3; lds[4][wave] = a4; lds[5][wave] = a5; lds[6][wave] = a6; lds[7][wave] = a7;
-    }
-    __syncthreads();
+    MeshStats<PREP_BLOCK>::block(lds, r);
     if (threadIdx.x == 0) {
-        for (int w = 1; w < PREP_BLOCK / 64; w++) {
-            a0 = fmin(a0, lds[0][w]); a1 = fmax(a1, lds[1][w]); a2 = fmin(a2, lds[2][w]);
-            a3 = fmax(a3, lds[3][w]); a4 += lds[4][w]; a5 = fmax(a5, lds[5][w]); a6 = fmax(a6, lds[6][w]); a7 += lds[7][w];
-        }
-        const double r[8] = {a0, a1, a2, a3, a4, a5, a6, a7};
 #pragma unroll
         for (int k = 0; k < 8; k++) {
             t.stats[k] = r[k];
@@ -198,35 +183,24 @@ __device__ __forceinline__ void prepare_faces_block(int64_t bid, int64_t nb, con
     }
 
     // numbering coherence: distance between the bbox centres of consecutive faces (within a wave)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     {
         const double cx = 0.5 * (xmin + xmax), cy = 0.5 * (ymin + ymax);
         const double px = __shfl_up(cx, 1, 64), py = __shfl_up(cy, 1, 64);
         if (lane > 0 && f < n_face) jump = fmax(fabs(cx - px), fabs(cy - py));
     }
-    // block partials: bounds, sum and max of the bbox extents (fixed order -> deterministic)
-    __shared__ double lds[8][PREP_BLOCK / 64];
-    double r0 = wave_min(xmin), r1 = wave_max(xmax), r2 = wave_min(ymin), r3 = wave_max(ymax);
-    double r4 = wave_sum(ext), r5 = wave_max(ext), r6 = wave_max(diag), r7 = wave_sum(jump);
-    if (lane == 0) {
-        lds[0][wave] = r0; lds[1][wave] = r1; lds[2][wave] = r2;
-        lds[3][wave] = r3; lds[4][wave] = r4; lds[5][wave] = r5; lds[6][wave] = r6; lds[7][wave] = r7;
-    }
-    __syncthreads();
-    double a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (threadIdx.x == 0) {
-        double a0 = lds[0][0], a1 = lds[1][0], a2 = lds[2][0], a3 = lds[3][0], a4 = lds[4][0], a5 = lds[5][0], a6 = lds[6][0], a7 = lds[7][0];
-        for (int w = 1; w < PREP_BLOCK / 64; w++) {
-            a0 = fmin(a0, lds[0][w]); a1 = fmax(a1, lds[1][w]); a2 = fmin(a2, lds[2][w]);
-            a3 = fmax(a3, lds[3][w]); a4 += lds[4][w]; a5 = fmax(a5, lds[5][w]); a6 = fmax(a6, lds[6][w]); a7 += lds[7][w];
+    // block partials (only thread 0's `a` is the block's)
+    __shared__ double lds[8 * (PREP_BLOCK / 64)];
+    double a[8] = {xmin, xmax, ymin, ymax, ext, ext, diag, jump};
+    MeshStats<PREP_BLOCK>::block(lds, a);
+    if (tail.done == nullptr) { // (separate reduction kernel behind this one)
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 0; k < 8; k++) partials[bid * 8 + k] = a[k];
         }
-        if (tail.done == nullptr) { // (separate reduction kernel behind this one)
-            double *p = partials + bid * 8;
-            p[0] = a0; p[1] = a1; p[2] = a2; p[3] = a3; p[4] = a4; p[5] = a5; p[6] = a6; p[7] = a7;
-        }
-        a[0] = a0; a[1] = a1; a[2] = a2; a[3] = a3; a[4] = a4; a[5] = a5; a[6] = a6; a[7] = a7;
+    } else {
+        stats_tail(tail, a, lds, bid, nb);
     }
-    if (tail.done != nullptr) stats_tail(tail, a, lds, bid, nb);
 }
 
 template <int MC, bool LIGHT>
@@ -286,29 +260,17 @@ __device__ __forceinline__ void sample_stats_block(int64_t bid, int64_t nb, cons
         ny0 = fmin(ny0, p.y);
         ny1 = fmax(ny1, p.y);
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __shared__ double lds[8][PREP_BLOCK / 64];
-    double r0 = wave_min(nx0), r1 = wave_max(nx1), r2 = wave_min(ny0), r3 = wave_max(ny1);
-    double r4 = wave_sum(ext), r5 = wave_max(ext), r6 = wave_max(diag), r7 = wave_sum(cnt);
-    if (lane == 0) {
-        lds[0][wave] = r0; lds[1][wave] = r1; lds[2][wave] = r2;
-        lds[3][wave] = r3; lds[4][wave] = r4; lds[5][wave] = r5; lds[6][wave] = r6; lds[7][wave] = r7;
-    }
-    __syncthreads();
-    double a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (threadIdx.x == 0) {
-        double a0 = lds[0][0], a1 = lds[1][0], a2 = lds[2][0], a3 = lds[3][0], a4 = lds[4][0], a5 = lds[5][0], a6 = lds[6][0], a7 = lds[7][0];
-        for (int w = 1; w < PREP_BLOCK / 64; w++) {
-            a0 = fmin(a0, lds[0][w]); a1 = fmax(a1, lds[1][w]); a2 = fmin(a2, lds[2][w]);
-            a3 = fmax(a3, lds[3][w]); a4 += lds[4][w]; a5 = fmax(a5, lds[5][w]); a6 = fmax(a6, lds[6][w]); a7 += lds[7][w];
+    __shared__ double lds[8 * (PREP_BLOCK / 64)];
+    double a[8] = {nx0, nx1, ny0, ny1, ext, ext, diag, cnt};
+    MeshStats<PREP_BLOCK>::block(lds, a);
+    if (tail.done == nullptr) { // (separate reduction kernel behind this one)
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 0; k < 8; k++) partials[bid * 8 + k] = a[k];
         }
-        if (tail.done == nullptr) { // (separate reduction kernel behind this one)
-            double *p = partials + bid * 8;
-            p[0] = a0; p[1] = a1; p[2] = a2; p[3] = a3; p[4] = a4; p[5] = a5; p[6] = a6; p[7] = a7;
-        }
-        a[0] = a0; a[1] = a1; a[2] = a2; a[3] = a3; a[4] = a4; a[5] = a5; a[6] = a6; a[7] = a7;
+    } else {
+        stats_tail(tail, a, lds, bid, nb);
     }
-    if (tail.done != nullptr) stats_tail(tail, a, lds, bid, nb);
 }
 
 template <int MC>
@@ -381,33 +343,18 @@ __global__ void __launch_bounds__(256) k_faces_ccw(const double *__restrict__ no
     for (int j = 0; j < m; j++) out[f * m + j] = (flip && j < n) ? face[n - 1 - j] : face[j];
 }
 
+// the second launch of the statistics where the kernel's last block does not reduce the partials itself (stats_tail)
 __global__ void __launch_bounds__(256) k_reduce_stats(const double *__restrict__ partials, int64_t nb,
                                                      double *__restrict__ stats, double *stats_host, double seq) {
-    double a0 = INFINITY, a1 = -INFINITY, a2 = INFINITY, a3 = -INFINITY, a4 = 0.0, a5 = 0.0, a6 = 0.0, a7 = 0.0;
-    for (int64_t i = threadIdx.x; i < nb; i += 256) {
-        const double *p = partials + i * 8;
-        a0 = fmin(a0, p[0]); a1 = fmax(a1, p[1]); a2 = fmin(a2, p[2]);
-        a3 = fmax(a3, p[3]); a4 += p[4]; a5 = fmax(a5, p[5]); a6 = fmax(a6, p[6]); a7 += p[7];
-    }
-    __shared__ double lds[8][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    a0 = wave_min(a0); a1 = wave_max(a1); a2 = wave_min(a2); a3 = wave_max(a3); a4 = wave_sum(a4); a5 = wave_max(a5);
-    a6 = wave_max(a6);
-    a7 = wave_sum(a7);
-    if (lane == 0) {
-        lds[0][wave] = a0; lds[1][wave] = a1; lds[2][wave] = a2;
-        lds[3][wave] = a3; lds[4][wave] = a4; lds[5][wave] = a5; lds[6][wave] = a6; lds[7][wave] = a7;
-    }
-    __syncthreads();
+    __shared__ double lds[8 * 4];
+    double a[8];
+    MeshStats<256>::partials(lds, partials, (int)nb, a);
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; w++) {
-            a0 = fmin(a0, lds[0][w]); a1 = fmax(a1, lds[1][w]); a2 = fmin(a2, lds[2][w]);
-            a3 = fmax(a3, lds[3][w]); a4 += lds[4][w]; a5 = fmax(a5, lds[5][w]); a6 = fmax(a6, lds[6][w]); a7 += lds[7][w];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            stats[k] = a[k];
+            stats_host[k] = a[k];
         }
-        stats[0] = a0; stats[1] = a1; stats[2] = a2; stats[3] = a3; stats[4] = a4; stats[5] = a5; stats[6] = a6;
-        stats[7] = a7;
-        stats_host[0] = a0; stats_host[1] = a1; stats_host[2] = a2; stats_host[3] = a3; stats_host[4] = a4;
-        stats_host[5] = a5; stats_host[6] = a6; stats_host[7] = a7;
         // the host polls the sequence word (mesh_read_stats): behind the statistics, system scope
         __threadfence_system();
         __hip_atomic_store(&stats_host[8], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);

@@ -28,6 +28,7 @@
 // for operation; both are built with -ffp-contract=off, so areas agree bit for bit.
 #include "xr_objects.h"
 #include "xr_clip_tri.h"
+#include "xr_prims.h"
 
 namespace xr {
 
@@ -135,14 +136,7 @@ k_search(const double *__restrict__ q_bbox, const double *__restrict__ q_fxy, co
     if (threadIdx.x == 0) sh_nbig = 0;
     if (big0 < (int)n_tree || l_coop < l_split) {
         // the block's bounding box, then one coalesced pass over the big records
-        float bx0 = qx0, bx1 = qx1, by0 = qy0, by1 = qy1;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            bx0 = fminf(bx0, __shfl_xor(bx0, d, 64));
-            bx1 = fmaxf(bx1, __shfl_xor(bx1, d, 64));
-            by0 = fminf(by0, __shfl_xor(by0, d, 64));
-            by1 = fmaxf(by1, __shfl_xor(by1, d, 64));
-        }
+        float bx0 = wave_reduce<OpMin>(qx0), bx1 = wave_reduce<OpMax>(qx1), by0 = wave_reduce<OpMin>(qy0), by1 = wave_reduce<OpMax>(qy1);
         if ((threadIdx.x & 63) == 0) {
             const int w = threadIdx.x >> 6;
             sh_box[w][0] = bx0; sh_box[w][1] = bx1; sh_box[w][2] = by0; sh_box[w][3] = by1;
@@ -292,12 +286,7 @@ k_search(const double *__restrict__ q_bbox, const double *__restrict__ q_fxy, co
 #pragma unroll
     for (int j = 0; j < SLOTS; j++) own[j] = j < mine ? sh_slots[j][threadIdx.x] : 0;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int v = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += v;
-    }
+    const int incl = wave_incl_scan(mine);
     if (lane == 63) sh_wave[wave] = incl;
     __syncthreads(); // (also: every thread has read its slots)
     int woff = 0, total = 0;
@@ -361,16 +350,6 @@ __global__ void k_publish(const int32_t *__restrict__ src, int32_t *dst, int32_t
 // [xlo, xhi] the polygon's x-extent inside that slab (inflated by 1e-6 h against rounding).
 static constexpr int LONG_RUN = 128;
 
-__device__ __forceinline__ int wave_excl_scan_i32(int v, int lane) {
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-    }
-    return incl - v;
-}
-
 // FUSED: ONE walk parks the face's candidates in LDS (up to BIG_STAGE of them); the block then reserves the face's
 // stretch of the pair queue with one atomic and copies them out.  Faces with more candidates than the stage holds
 // walk a second time and write straight to the queue (the first walk has counted them); faces whose stretch does
@@ -414,8 +393,7 @@ k_search_big(const double *__restrict__ q_bbox, const double *__restrict__ q_fxy
             int c = 0;
             if (nb <= BIG_RANK_MAX)
                 for (int j = threadIdx.x; j < nb; j += 256) c += big_list[j] < t ? 1 : 0;
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
+            c = wave_reduce<OpSum>(c);
             if (lane == 0) sh_rankw[wv] = c;
         }
         __syncthreads();
@@ -549,7 +527,7 @@ k_search_big(const double *__restrict__ q_bbox, const double *__restrict__ q_fxy
                 const int my_r1 = len > LONG_RUN ? r0 : r1;
                 int cnt = 0;
                 for (int r = r0; r < my_r1; r++) cnt += rec_hit(rbb[r], rx0, rx1, qy0, qy1) ? 1 : 0;
-                const int excl = wave_excl_scan_i32(cnt, lane);
+                const int excl = wave_incl_scan(cnt) - cnt;
                 const int batch = __shfl(excl + cnt, 63, 64);
                 if (batch > 0) {
                     int slot0 = 0;
@@ -656,6 +634,24 @@ __device__ __forceinline__ bool sh_intersection(P2 a, P2 V, P2 r, P2 N, P2 &out)
 
 static constexpr double AREA_OVERFLOW = -1.0; // sentinel: polygon buffer too small, redo with MAXV=64
 
+// The end of every one-pair-per-thread clip kernel (every lane of the wave must get here): `area` is pair c's clipped area
+// or an overflow sentinel, t its target face (-1 in a lane without a pair), tf / sf the two faces' vertices.  Rounding dust is
+// confirmed, an overflow counted, the area stored, and the survivors are added to their rows' counts: the pairs of one target
+// face are contiguous, so a wave holds a few runs of equal t.
+__device__ __forceinline__ void clip_epilogue(double area, double dust, bool active, int64_t c, int t, const double2 *__restrict__ tf,
+                                              int nt, const double2 *__restrict__ sf, int ns, double *__restrict__ cand_area,
+                                              int32_t *__restrict__ overflow_count, int32_t *__restrict__ nnz_row) {
+    area = confirm_dust(area, dust, active, tf, nt, sf, ns);
+    if (active) {
+        if (area == TRI_AREA_OVERFLOW) {
+            area = AREA_OVERFLOW;
+            atomicAdd(overflow_count, 1);
+        }
+        cand_area[c] = area;
+    }
+    wave_run_add(t, active && area > 0, nnz_row);
+}
+
 template <int MAXV, int BLOCK>
 __global__ void __launch_bounds__(BLOCK)
 k_clip(const double *__restrict__ q_fxy, const uint8_t *__restrict__ q_len, const int32_t *__restrict__ q_off, int q_m,
@@ -667,17 +663,19 @@ k_clip(const double *__restrict__ q_fxy, const uint8_t *__restrict__ q_len, cons
     double2 *sh = reinterpret_cast<double2 *>(smem);
     const int64_t c = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     const bool active = c < n_cand && !(redo_only && cand_area[c] != AREA_OVERFLOW);
-    int t = -1;
+    int t = -1, nt = 0, ns = 0;
+    const double2 *tf = nullptr;
+    const double *sf = nullptr;
     double area = 0.0;
     if (active) {
     t = cand_tgt[c];
     const int s = cand_src[c];
     cand_sid[c] = rec_face[s];
-    const int nt = q_len[t], ns = s_len[s];
+    nt = q_len[t], ns = s_len[s];
     double2 *out = sh + threadIdx.x;                // out[j * BLOCK]
     double2 *in = sh + MAXV * BLOCK + threadIdx.x;  // in[j * BLOCK]
-    const double2 *tf = reinterpret_cast<const double2 *>(q_fxy) + face_vertex_base(q_off, t, q_m);
-    const double *sf = s_fxy + 2 * face_vertex_base(s_off, s, s_m);
+    tf = reinterpret_cast<const double2 *>(q_fxy) + face_vertex_base(q_off, t, q_m);
+    sf = s_fxy + 2 * face_vertex_base(s_off, s, s_m);
     for (int j = 0; j < nt; j++) out[j * BLOCK] = tf[j];
     int n_output = nt;
     bool overflow = false;
@@ -741,7 +739,6 @@ k_clip(const double *__restrict__ q_fxy, const uint8_t *__restrict__ q_len, cons
     }
     if (overflow) {
         area = AREA_OVERFLOW;
-        atomicAdd(overflow_count, 1);
     } else if (!empty) {
         // fan area from the first clipped vertex (local origin)
         const double2 a2 = out[0];
@@ -756,26 +753,8 @@ k_clip(const double *__restrict__ q_fxy, const uint8_t *__restrict__ q_len, cons
         }
         area = 0.5 * area;
     }
-    if (area > 0 && area <= dust && !pair_passes_box_and_sat(tf, nt, reinterpret_cast<const double2 *>(sf), ns)) area = 0.0;
-    cand_area[c] = area;
     } // active
-    // per-row survivor counts: candidates of one query face are contiguous, so a wave holds a
-    // few runs of equal t; the head lane of each run adds the run's survivor count.
-    {
-        const int lane = threadIdx.x & 63;
-        const int t_prev = __shfl_up(t, 1, 64);
-        const bool head = lane == 0 || t_prev != t;
-        const unsigned long long heads = __ballot(head);
-        const unsigned long long surv = __ballot(active && area > 0);
-        if (head && t >= 0) {
-            const unsigned long long above = lane == 63 ? 0ull : (heads >> (lane + 1));
-            const int next = above ? lane + 1 + (__ffsll((long long)above) - 1) : 64;
-            unsigned long long run = next == 64 ? ~0ull : ((1ull << next) - 1);
-            run &= ~((1ull << lane) - 1);
-            const int n = __popcll(surv & run);
-            if (n > 0) atomicAdd(&nnz_row[t], n);
-        }
-    }
+    clip_epilogue(area, dust, active, c, t, tf, nt, reinterpret_cast<const double2 *>(sf), ns, cand_area, overflow_count, nnz_row);
 }
 
 // Small-polygon variant (query + tree vertices <= MAXV, i.e. triangles / quads): the subject
@@ -785,7 +764,7 @@ k_clip(const double *__restrict__ q_fxy, const uint8_t *__restrict__ q_len, cons
 // The arithmetic and its order are those of k_clip / the oracle.
 // -> the pair's area (AREA_OVERFLOW: more than MAXV vertices; before the confirmation of rounding dust); `out` = the
 // thread's LDS column, out[j * BLOCK]
-template <int MAXV, int BLOCK, bool TRI>
+template <int MAXV, int BLOCK>
 __device__ __forceinline__ double clip_small_pair(const double2 *__restrict__ tf, int nt, const double *__restrict__ sf, int ns,
                                                   double2 *out) {
     double area = 0.0;
@@ -801,17 +780,11 @@ __device__ __forceinline__ double clip_small_pair(const double2 *__restrict__ tf
     }
     int length = nt;
     bool overflow = false, empty = false;
-    // all clipper vertices up front (three independent 16-byte loads for triangles)
-    P2 sv_all[TRI ? 3 : 1];
-    if (TRI) {
+    P2 r = load_p2(sf, ns - 1);
 #pragma unroll
-        for (int i = 0; i < 3; i++) sv_all[i] = load_p2(sf, i);
-    }
-    P2 r = TRI ? sv_all[2] : load_p2(sf, ns - 1);
-#pragma unroll
-    for (int i = 0; i < (TRI ? 3 : XR_MAX_FACE_NODES); i++) {
-        if (!TRI && i >= ns) break;
-        const P2 sv = TRI ? sv_all[i] : load_p2(sf, i);
+    for (int i = 0; i < XR_MAX_FACE_NODES; i++) {
+        if (i >= ns) break;
+        const P2 sv = load_p2(sf, i);
         const P2 U{sv.x - r.x, sv.y - r.y};
         if (U.x == 0 && U.y == 0) continue;
         const P2 N{-U.y, U.x};
@@ -884,7 +857,7 @@ __device__ __forceinline__ double clip_small_pair(const double2 *__restrict__ tf
     return area;
 }
 
-template <int MAXV, int BLOCK, bool TRI>
+template <int MAXV, int BLOCK>
 __global__ void __launch_bounds__(BLOCK)
 k_clip_small(const double *__restrict__ q_fxy, const uint8_t *__restrict__ q_len, const int32_t *__restrict__ q_off, int q_m,
              const int32_t *__restrict__ q_perm, const double *__restrict__ s_fxy,
@@ -899,129 +872,60 @@ k_clip_small(const double *__restrict__ q_fxy, const uint8_t *__restrict__ q_len
     if (lb >= n_blocks) return;
     const int64_t c = lb * BLOCK + threadIdx.x;
     const bool active = c < n_cand;
-    int t = -1;
+    int t = -1, nt = 0, ns = 0;
+    const double2 *tf = nullptr;
+    const double *sf = nullptr;
     double area = 0.0;
     if (active) {
         t = cand_tgt[c];
         const int s = cand_src[c];
         cand_sid[c] = rec_face[s];
-        // TRI: both meshes are pure triangle meshes -> vertex counts are compile-time constants
-        const int nt = TRI ? 3 : q_len[t], ns = TRI ? 3 : s_len[s];
-        const double2 *tf = reinterpret_cast<const double2 *>(q_fxy) + face_vertex_base(q_off, t, q_m);
-        const double *sf = s_fxy + 2 * face_vertex_base(s_off, s, s_m);
-        area = clip_small_pair<MAXV, BLOCK, TRI>(tf, nt, sf, ns, out);
-        if (area == AREA_OVERFLOW) atomicAdd(overflow_count, 1);
-        if (area > 0 && area <= dust && !pair_passes_box_and_sat(tf, nt, reinterpret_cast<const double2 *>(sf), ns)) area = 0.0;
-        cand_area[c] = area;
+        nt = q_len[t], ns = s_len[s];
+        tf = reinterpret_cast<const double2 *>(q_fxy) + face_vertex_base(q_off, t, q_m);
+        sf = s_fxy + 2 * face_vertex_base(s_off, s, s_m);
+        area = clip_small_pair<MAXV, BLOCK>(tf, nt, sf, ns, out);
     }
-    {
-        const int lane = threadIdx.x & 63;
-        const int t_prev = __shfl_up(t, 1, 64);
-        const bool head = lane == 0 || t_prev != t;
-        const unsigned long long heads = __ballot(head);
-        const unsigned long long surv = __ballot(active && area > 0);
-        if (head && t >= 0) {
-            const unsigned long long above = lane == 63 ? 0ull : (heads >> (lane + 1));
-            const int next = above ? lane + 1 + (__ffsll((long long)above) - 1) : 64;
-            unsigned long long run = next == 64 ? ~0ull : ((1ull << next) - 1);
-            run &= ~((1ull << lane) - 1);
-            const int n = __popcll(surv & run);
-            if (n > 0) atomicAdd(&nnz_row[t], n);
-        }
-    }
+    clip_epilogue(area, dust, active, c, t, tf, nt, reinterpret_cast<const double2 *>(sf), ns, cand_area, overflow_count, nnz_row);
 }
 
-// Triangle x triangle pairs (both meshes pure triangle meshes): the flag / compaction formulation of
-// xr_clip_tri.h -- about half the instructions of k_clip_small<6, 256, true>, same areas bit for bit.
-template <int BLOCK>
+// A triangle source against targets of N0 = 3 or 4 vertices: the flag / compaction formulation of xr_clip_tri.h -- about half the
+// instructions of k_clip_small, same areas bit for bit.  N0 = 3: both meshes are pure triangle meshes.  N0 = 4: quadrilateral
+// (raster / quad mesh) targets -- the shape of the reference's unstructured -> raster regridding -- whose faces may be triangles
+// with a fill slot (q_len, read for N0 = 4 only); replaces k_clip_small<8> for this pair of shapes.
+template <int BLOCK, int N0>
 __global__ void __launch_bounds__(BLOCK)
-k_clip_tri(const double *__restrict__ q_fxy, int q_m, const double *__restrict__ s_fxy, int s_m,
+k_clip_tri(const double *__restrict__ q_fxy, const uint8_t *__restrict__ q_len, const double *__restrict__ s_fxy,
            const int32_t *__restrict__ cand_tgt, const int32_t *__restrict__ cand_src, int64_t n_cand,
            double *__restrict__ cand_area, const int32_t *__restrict__ rec_face, int32_t *__restrict__ cand_sid,
            int32_t *__restrict__ overflow_count, int32_t *__restrict__ nnz_row, bool remap, double dust) {
+    static_assert(N0 == 3 || N0 == 4, "triangle or quadrilateral subject");
+    constexpr int MAXV = N0 == 3 ? TRI_MAXV : QUAD_MAXV;
+    // slots per lane: TRI_MAXV + 1, 112 bytes; QUAD_MAXV + 2, 144 bytes -- 128 would put the 16-byte accesses of all lanes on the
+    // same banks
+    constexpr int COL = N0 == 3 ? TRI_MAXV + 1 : QUAD_MAXV + 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    double2 *col = reinterpret_cast<double2 *>(smem) + threadIdx.x * (TRI_MAXV + 1); // the lane's TRI_MAXV + 1 slots
-    __shared__ uint2 sh_lut[TRI_LUT];
+    double2 *col = reinterpret_cast<double2 *>(smem) + threadIdx.x * COL;
+    __shared__ uint2 sh_lut[N0 == 3 ? TRI_LUT : QUAD_LUT];
     const int64_t n_blocks = (n_cand + BLOCK - 1) / BLOCK;
     const int64_t lb = xcd_block(n_blocks, remap);
     if (lb >= n_blocks) return;
-    tri_lut_init(sh_lut);
-    __syncthreads();
-    const int64_t c = lb * BLOCK + threadIdx.x;
-    const bool active = c < n_cand;
-    int t = -1, s = 0;
-    P2 tv[3] = {{0, 0}, {0, 0}, {0, 0}}, sv[3] = {{0, 0}, {0, 0}, {0, 0}};
-    if (active) {
-        t = cand_tgt[c];
-        s = cand_src[c];
-        cand_sid[c] = rec_face[s];
-        const double2 *tf = reinterpret_cast<const double2 *>(q_fxy) + (int64_t)t * q_m;
-        const double2 *sf = reinterpret_cast<const double2 *>(s_fxy) + (int64_t)s * s_m;
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            const double2 a = tf[j], b = sf[j];
-            tv[j] = P2{a.x, a.y};
-            sv[j] = P2{b.x, b.y};
-        }
-    }
-    double area = tri_clip_area(tv, sv, col, sh_lut, active);
-    area = confirm_dust(area, dust, active, reinterpret_cast<const double2 *>(q_fxy) + (int64_t)t * q_m, 3,
-                        reinterpret_cast<const double2 *>(s_fxy) + (int64_t)s * s_m, 3);
-    if (active) {
-        if (area == TRI_AREA_OVERFLOW) {
-            area = AREA_OVERFLOW;
-            atomicAdd(overflow_count, 1);
-        }
-        cand_area[c] = area;
-    }
-    {
-        const int lane = threadIdx.x & 63;
-        const int t_prev = __shfl_up(t, 1, 64);
-        const bool head = lane == 0 || t_prev != t;
-        const unsigned long long heads = __ballot(head);
-        const unsigned long long surv = __ballot(active && area > 0);
-        if (head && t >= 0) {
-            const unsigned long long above = lane == 63 ? 0ull : (heads >> (lane + 1));
-            const int next = above ? lane + 1 + (__ffsll((long long)above) - 1) : 64;
-            unsigned long long run = next == 64 ? ~0ull : ((1ull << next) - 1);
-            run &= ~((1ull << lane) - 1);
-            const int n = __popcll(surv & run);
-            if (n > 0) atomicAdd(&nnz_row[t], n);
-        }
-    }
-}
-
-// Quadrilateral (raster / quad mesh) targets against a triangle source -- the shape of the reference's unstructured ->
-// raster regridding: the same flag / compaction clip with a subject of up to four vertices (xr_clip_tri.h, MAXV = 7);
-// target faces may be triangles with a fill slot (q_len).  Replaces k_clip_small<8> for this pair of shapes.
-template <int BLOCK>
-__global__ void __launch_bounds__(BLOCK)
-k_clip_quad_tri(const double *__restrict__ q_fxy, const uint8_t *__restrict__ q_len, const double *__restrict__ s_fxy,
-                const int32_t *__restrict__ cand_tgt, const int32_t *__restrict__ cand_src, int64_t n_cand,
-                double *__restrict__ cand_area, const int32_t *__restrict__ rec_face, int32_t *__restrict__ cand_sid,
-                int32_t *__restrict__ overflow_count, int32_t *__restrict__ nnz_row, bool remap, double dust) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    // (QUAD_MAXV + 2 slots per lane: 144 bytes -- 128 would put the 16-byte accesses of all lanes on the same banks)
-    double2 *col = reinterpret_cast<double2 *>(smem) + threadIdx.x * (QUAD_MAXV + 2);
-    __shared__ uint2 sh_lut[QUAD_LUT];
-    const int64_t n_blocks = (n_cand + BLOCK - 1) / BLOCK;
-    const int64_t lb = xcd_block(n_blocks, remap);
-    if (lb >= n_blocks) return;
-    poly_lut_init<QUAD_MAXV>(sh_lut);
+    poly_lut_init<MAXV>(sh_lut);
     __syncthreads();
     const int64_t c = lb * BLOCK + threadIdx.x;
     const bool active = c < n_cand;
     int t = -1, n0 = 3, s = 0;
-    P2 tv[4] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}}, sv[3] = {{0, 0}, {0, 0}, {0, 0}};
+    P2 tv[N0] = {}, sv[3] = {};
     if (active) {
         t = cand_tgt[c];
         s = cand_src[c];
         cand_sid[c] = rec_face[s];
-        n0 = q_len[t];
-        const double2 *tf = reinterpret_cast<const double2 *>(q_fxy) + (int64_t)t * 4;
-        const double2 *sf = reinterpret_cast<const double2 *>(s_fxy) + (int64_t)s * 3;
+        if (N0 > 3) n0 = q_len[t];
+    }
+    const double2 *tf = reinterpret_cast<const double2 *>(q_fxy) + (int64_t)t * N0;
+    const double2 *sf = reinterpret_cast<const double2 *>(s_fxy) + (int64_t)s * 3;
+    if (active) {
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
+        for (int j = 0; j < N0; j++) {
             if (j < n0) {
                 const double2 a = tf[j];
                 tv[j] = P2{a.x, a.y};
@@ -1033,31 +937,8 @@ k_clip_quad_tri(const double *__restrict__ q_fxy, const uint8_t *__restrict__ q_
             sv[j] = P2{b.x, b.y};
         }
     }
-    double area = poly_clip_area<QUAD_MAXV, 4>(tv, n0, sv, col, sh_lut, active);
-    area = confirm_dust(area, dust, active, reinterpret_cast<const double2 *>(q_fxy) + (int64_t)t * 4, n0,
-                        reinterpret_cast<const double2 *>(s_fxy) + (int64_t)s * 3, 3);
-    if (active) {
-        if (area == TRI_AREA_OVERFLOW) {
-            area = AREA_OVERFLOW;
-            atomicAdd(overflow_count, 1);
-        }
-        cand_area[c] = area;
-    }
-    {
-        const int lane = threadIdx.x & 63;
-        const int t_prev = __shfl_up(t, 1, 64);
-        const bool head = lane == 0 || t_prev != t;
-        const unsigned long long heads = __ballot(head);
-        const unsigned long long surv = __ballot(active && area > 0);
-        if (head && t >= 0) {
-            const unsigned long long above = lane == 63 ? 0ull : (heads >> (lane + 1));
-            const int next = above ? lane + 1 + (__ffsll((long long)above) - 1) : 64;
-            unsigned long long run = next == 64 ? ~0ull : ((1ull << next) - 1);
-            run &= ~((1ull << lane) - 1);
-            const int n = __popcll(surv & run);
-            if (n > 0) atomicAdd(&nnz_row[t], n);
-        }
-    }
+    const double area = poly_clip_area<MAXV, N0>(tv, n0, sv, col, sh_lut, active);
+    clip_epilogue(area, dust, active, c, t, tf, n0, sf, 3, cand_area, overflow_count, nnz_row);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1124,12 +1005,7 @@ k_row_fill(const int32_t *__restrict__ cand_off, const int32_t *__restrict__ can
     sh_c0[threadIdx.x] = is_short ? c0 : -1;
     // block exclusive scan of the short-row lengths
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = slen;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int v = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += v;
-    }
+    const int incl = wave_incl_scan(slen);
     if (lane == 63) sh_wave[wave] = incl;
     __syncthreads();
     int woff = 0, total = 0;
@@ -1231,8 +1107,7 @@ k_row_fill_long(const int32_t *__restrict__ cand_off, const int32_t *__restrict_
     auto length_sum = [&](int k0, int k1) -> long long {
         long long v = 0;
         for (int k = k0 + tid; k < k1; k += 256) v += scan_nnz[long_rows[k]];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+        v = wave_reduce<OpSum>(v);
         __syncthreads();
         if (lane == 0) red[wave] = (int32_t)(v > 0x7fffffffll ? 0x7fffffff : v);
         __syncthreads();
@@ -1340,11 +1215,7 @@ k_row_fill_long(const int32_t *__restrict__ cand_off, const int32_t *__restrict_
                 acc += c;
             }
             // block exclusive scan of the per-thread totals
-            uint32_t incl = acc;
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t v = __shfl_up(incl, d, 64);
-                if (lane >= d) incl += v;
-            }
+            const uint32_t incl = wave_incl_scan(acc);
             if (lane == 63) red[wave] = (int32_t)incl;
             __syncthreads();
             uint32_t woff = 0, chunk_total = 0;
@@ -1429,19 +1300,19 @@ static void launch_clip_for(const xr_mesh *tree, const xr_mesh *query, const int
         // triangle x triangle: the clipped polygon never has more than 6 vertices
         constexpr int MAXV = 6;
         const size_t shmem = (size_t)(MAXV + 1) * BLOCK * sizeof(double2); // + one trash row for clamped pushes
-        XR_LAUNCH("clip_tri", (k_clip_tri<BLOCK>), grid, dim3(BLOCK), shmem,
-                      query->qo_fxy(), query->m, tree->rec_fxy.get(), tree->m, cand_tgt, cand_src, C, cand_area,
-                      tree->rec_face.get(), cand_sid, overflow_count, nnz_row, remap, dust);
+        XR_LAUNCH("clip_tri", (k_clip_tri<BLOCK, 3>), grid, dim3(BLOCK), shmem, query->qo_fxy(), (const uint8_t *)nullptr,
+                  tree->rec_fxy.get(), cand_tgt, cand_src, C, cand_area, tree->rec_face.get(), cand_sid, overflow_count, nnz_row, remap,
+                  dust);
     } else if (query->m == 4 && tree->m == 3 && option(OPT_CLIP_QUAD) != 0) {
         // quadrilateral targets (a raster) x triangle source (option "clip_quad" = 0: the slot-loop kernel, test switch)
         const size_t shmem = (size_t)(QUAD_MAXV + 2) * BLOCK * sizeof(double2);
-        XR_LAUNCH("clip_quad_tri", (k_clip_quad_tri<BLOCK>), grid, dim3(BLOCK), shmem,
+        XR_LAUNCH("clip_quad_tri", (k_clip_tri<BLOCK, 4>), grid, dim3(BLOCK), shmem,
                   query->qo_fxy(), query->qo_len(), tree->rec_fxy.get(), cand_tgt, cand_src, C, cand_area, tree->rec_face.get(),
                   cand_sid, overflow_count, nnz_row, remap, dust);
     } else {
         constexpr int MAXV = 8;
         const size_t shmem = (size_t)(MAXV + 1) * BLOCK * sizeof(double2); // + one trash row for clamped pushes
-        XR_LAUNCH("clip_small", (k_clip_small<MAXV, BLOCK, false>), grid, dim3(BLOCK),
+        XR_LAUNCH("clip_small", (k_clip_small<MAXV, BLOCK>), grid, dim3(BLOCK),
                   shmem, query->qo_fxy(), query->qo_len(), query->qo_off(), query->m, query->qo_perm(), tree->rec_fxy.get(),
                   tree->rec_len.get(), tree->record_off(), tree->m, cand_tgt, cand_src, C, cand_area, tree->rec_face.get(), cand_sid,
                   overflow_count, nnz_row, remap, dust);

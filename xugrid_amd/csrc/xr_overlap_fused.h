@@ -92,28 +92,6 @@ enum GenWord : int {
 };
 enum GenMailSlot : int { GMAIL_PAIRS = 0, GMAIL_NNZ = 1, GMAIL_CLIP_OVERFLOW = 2, GMAIL_N_PENDING = 3 };
 
-// block-wide exclusive scan of one int per thread (FB threads); returns the exclusive value, total in *total
-__device__ __forceinline__ int block_excl_scan(int v, int *sh_wave /*[FWAVES]*/, int *total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int u = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += u;
-    }
-    __syncthreads(); // (sh_wave may still be read from an earlier scan)
-    if (lane == 63) sh_wave[wave] = incl;
-    __syncthreads();
-    int woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < FWAVES; w++) {
-        if (w < wave) woff += sh_wave[w];
-        tot += sh_wave[w];
-    }
-    *total = tot;
-    return woff + incl - v;
-}
-
 // Persistent triangle x triangle clip over the regular pair queue: the number of pairs is read from device memory
 // (the search's queue cursor), so the launch needs no host round trip; every block walks chunks of 256 pairs.  Chunks are dealt so that every XCD works on one contiguous eighth of the queue (the order
 // k_search wrote it in: the vertex blocks are in that XCD's L2).
@@ -216,12 +194,10 @@ k_clip_tri_queue(const double *__restrict__ q_fxy, const double *__restrict__ re
                 ns = s_len[cur_s];
             }
             load_idx(slot + stride, n_tq, n_s);
-            if (active) {
-                const double2 *tf = tfx + (int64_t)cur_tq * q_m;
-                const double2 *sf = sfx + (int64_t)cur_s * s_m;
-                area = clip_small_pair<SMALL_MAXV, BLOCK, false>(tf, nt, reinterpret_cast<const double *>(sf), ns, col);
-                if (area > 0 && area <= dust && !pair_passes_box_and_sat(tf, nt, sf, ns)) area = 0.0;
-            }
+            const double2 *tf = tfx + (int64_t)cur_tq * q_m;
+            const double2 *sf = sfx + (int64_t)cur_s * s_m;
+            if (active) area = clip_small_pair<SMALL_MAXV, BLOCK>(tf, nt, reinterpret_cast<const double *>(sf), ns, col);
+            area = confirm_dust(area, dust, active, tf, nt, sf, ns);
         } else {
             P2 tv[3] = {{0, 0}, {0, 0}, {0, 0}}, sv[3] = {{0, 0}, {0, 0}, {0, 0}};
             if (active) {
@@ -234,7 +210,8 @@ k_clip_tri_queue(const double *__restrict__ q_fxy, const double *__restrict__ re
                 sid = rec_face[n_s];
             }
             load_idx(slot + stride, n_tq, n_s);
-            // (rounding dust of a pair the reference's pre-clip tests reject: the few lanes concerned fetch their vertices again)
+            // (rounding dust of a pair the reference's pre-clip tests reject: the few lanes concerned fetch their vertices again --
+            // confirm_dust spelled out, because the source id is read again too: holding it costs a register)
             area = tri_clip_area<CS>(tv, sv, col, sh_lut, active);
             const bool suspicious = active && area > 0 && area <= dust;
             if (__any(suspicious)) {
@@ -257,35 +234,11 @@ k_clip_tri_queue(const double *__restrict__ q_fxy, const double *__restrict__ re
             if (blk_first == blk_last) { // (uniform)
                 if (lane == 0 && blk_first >= 0 && surv) atomicAdd(&blk_surv[blk_first], __popcll(surv));
             } else {
-                const int blk_prev = __shfl_up(blk_now, 1, 64);
-                const bool head = lane == 0 || blk_prev != blk_now;
-                const unsigned long long heads = __ballot(head);
-                if (head && blk_now >= 0) {
-                    const unsigned long long above = lane == 63 ? 0ull : (heads >> (lane + 1));
-                    const int next = above ? lane + 1 + (__ffsll((long long)above) - 1) : 64;
-                    unsigned long long run = next == 64 ? ~0ull : ((1ull << next) - 1);
-                    run &= ~((1ull << lane) - 1);
-                    const int n = __popcll(surv & run);
-                    if (n > 0) atomicAdd(&blk_surv[blk_now], n);
-                }
+                wave_run_add(blk_now, active && area > 0, blk_surv);
             }
         }
-        if (COUNT == 2) {
-            // pairs of one target face are contiguous: the head lane of each run of equal faces adds the run's survivors
-            const int lane = tid & 63;
-            const int t_prev = __shfl_up(tq_now, 1, 64);
-            const bool head = lane == 0 || t_prev != tq_now;
-            const unsigned long long heads = __ballot(head);
-            const unsigned long long surv = __ballot(active && area > 0);
-            if (head && tq_now >= 0) {
-                const unsigned long long above = lane == 63 ? 0ull : (heads >> (lane + 1));
-                const int next = above ? lane + 1 + (__ffsll((long long)above) - 1) : 64;
-                unsigned long long run = next == 64 ? ~0ull : ((1ull << next) - 1);
-                run &= ~((1ull << lane) - 1);
-                const int n = __popcll(surv & run);
-                if (n > 0) atomicAdd(&nnz_row[tq_now], n);
-            }
-        }
+        // pairs of one target face are contiguous: the head lane of each run of equal faces adds the run's survivors
+        if (COUNT == 2) wave_run_add(tq_now, active && area > 0, nnz_row);
     }
     if (overflow) atomicOr(error_bits, 1);
 }
@@ -299,10 +252,8 @@ k_assemble_scan(const int32_t *__restrict__ blk_rows, const int32_t *__restrict_
                 bool remap, int32_t *__restrict__ base_rows, int32_t *__restrict__ base_nnz, FusedCounters *counters,
                 int32_t *__restrict__ indptr) {
     __shared__ long long sh_w[16];
-    __shared__ long long sh_carry;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) sh_carry = 0;
-    __syncthreads();
+    long long carry = 0; // (rows, entries) of the chunks in front, in every thread
     const int64_t per_xcd = (n_blocks + 7) >> 3;
     for (int b0 = 0; b0 < n_chain; b0 += 1024) {
         const int b = b0 + tid;
@@ -311,12 +262,9 @@ k_assemble_scan(const int32_t *__restrict__ blk_rows, const int32_t *__restrict_
             const int64_t lb = remap ? (int64_t)(b & 7) * per_xcd + (b >> 3) : b;
             if (lb < n_blocks) v = ((long long)blk_rows[lb] << 31) | (long long)blk_surv[lb];
         }
-        long long incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const long long o = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += o;
-        }
+        // (the block level stays spelled out: block_excl_scan<1024, long long> unrolls its sixteen 64-bit reads and takes the
+        // kernel from 56 to 72 registers, over the 64-register occupancy step)
+        const long long incl = wave_incl_scan(v);
         if (lane == 63) sh_w[wave] = incl;
         __syncthreads();
         long long woff = 0, tot = 0;
@@ -324,17 +272,16 @@ k_assemble_scan(const int32_t *__restrict__ blk_rows, const int32_t *__restrict_
             if (w < wave) woff += sh_w[w];
             tot += sh_w[w];
         }
-        const long long excl = sh_carry + woff + incl - v;
+        const long long excl = carry + woff + incl - v;
         if (b < n_chain) {
             base_nnz[b] = (int32_t)(excl & 0x7fffffffll);
             base_rows[b] = (int32_t)(excl >> 31);
         }
-        __syncthreads();
-        if (tid == 0) sh_carry += tot;
+        carry += tot;
         __syncthreads();
     }
     if (tid == 0) {
-        const long long entries = sh_carry & 0x7fffffffll, rows = sh_carry >> 31;
+        const long long entries = carry & 0x7fffffffll, rows = carry >> 31;
         counters->p_regular = (int32_t)entries; // entries of all regular rows
         counters->rows_regular = (int32_t)rows;
         indptr[rows] = (int32_t)entries;        // (= indptr[T] when there are no big faces)
@@ -406,8 +353,8 @@ k_assemble(const double *__restrict__ q_bbox, const double *__restrict__ q_fxy, 
     __syncthreads();
     const int my_nnz = regular ? sh_nnz[tid] : 0;
     int block_nnz = 0, block_rows = 0;
-    const int rowoff = block_excl_scan(my_nnz, sh_wave, &block_nnz);
-    const int rowidx = block_excl_scan(regular ? 1 : 0, sh_wave, &block_rows);
+    const int rowoff = block_excl_scan<FB>(my_nnz, &block_nnz, sh_wave);
+    const int rowidx = block_excl_scan<FB>(regular ? 1 : 0, &block_rows, sh_wave);
     sh_rowoff[tid] = (uint16_t)rowoff;
     const int b = (int)blockIdx.x, n_chain = (int)gridDim.x;
     if (blk_surv) {
@@ -421,8 +368,7 @@ k_assemble(const double *__restrict__ q_bbox, const double *__restrict__ q_fxy, 
             const int64_t plb = remap ? (int64_t)(hb & 7) * per_xcd + (hb >> 3) : hb;
             if (plb < n_blocks) acc += ((long long)blk_rows[plb] << 31) | (long long)blk_surv[plb];
         }
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d, 64);
+        acc = wave_reduce<OpSum>(acc);
         __shared__ long long sh_part[FWAVES];
         if ((tid & 63) == 0) sh_part[tid >> 6] = acc;
         __syncthreads();
@@ -548,9 +494,7 @@ __global__ void k_publish_all(int32_t *c /* the control block (CtlWord) */, Fuse
     // number of regular pairs, which takes the place of the single cursor CTL_REG_CURSOR)
     const bool region_lane = t >= CTL_LINE && t < CTL_LINE + 8;
     const int32_t cur = region_lane ? c[CTL_REGION_CURSOR + (t - CTL_LINE) * QCUR_STRIDE] : 0;
-    int32_t c_reg_sum = cur;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c_reg_sum += __shfl_xor(c_reg_sum, d, 64);
+    const int32_t c_reg_sum = wave_reduce<OpSum>(cur);
     if (t == CTL_REG_CURSOR) w = c_reg_sum;
     int slot = -1; // mailbox slot of control word t
     if (t <= CTL_BIG_OVERFLOW) slot = MAIL_REG_PAIRS + t;

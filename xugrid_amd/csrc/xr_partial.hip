@@ -3,6 +3,7 @@
 // include/xugrid_amd.h), the states of a row are combined across the shards and finalised.
 #include "xr_apply.h"
 #include "xr_reduce.h"
+#include "xr_prims.h"
 
 namespace xr {
 
@@ -99,18 +100,14 @@ k_apply_partial_w1(const int32_t *__restrict__ indptr, const int32_t *__restrict
     }
     const bool skip = skip_long && (e - s > APPLY_LONG);
     const int seg0 = __shfl(s, 0, 64);
-    int seg1 = e;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) seg1 = max(seg1, __shfl_xor(seg1, d, 64));
+    const int seg1 = wave_reduce<OpMax>(e);
     if (skip) e = s;
     const bool jumpy = __any(skip);
     double2 *win = sh_win[wib];
     auto next_chunk = [&](int c0) -> int { // first entry any lane still needs at or behind c0 (skipped long rows are not streamed)
         if (!jumpy) return c0;
         int mine = (e > s && e > c0) ? (s > c0 ? s : c0) : INT_MAX;
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) mine = min(mine, __shfl_xor(mine, d, 64));
-        return mine;
+        return wave_reduce<OpMin>(mine);
     };
     PartialState st = partial_identity(METHOD);
     for (int c0 = seg0; c0 < seg1; c0 += W1_CAP) {

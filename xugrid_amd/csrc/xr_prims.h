@@ -1,7 +1,8 @@
-// xr_prims.h -- the small device idioms the mesh-operation units share: a per-wave counter and flag, the wave / block
-// reduction and the two-launch reduction of an array, the wave / block scan and the block sort of a row, the int32 -> int64
-// widening on the way out of the library, and the compaction behind "flags -> exclusive scan -> ascending ids".  Kernels are
-// `static`: every translation unit that includes this header gets its own copy (as in xr_node_faces.h).
+// xr_prims.h -- the library's small device idioms, one copy each: a per-wave counter and flag, the per-run counter of a wave,
+// the wave / block reduction and the two-launch reduction of an array, the wave / block scan and the block sort of a row, the
+// int32 -> int64 widening on the way out of the library, and the compaction behind "flags -> exclusive scan -> ascending ids".
+// The regrid units (search, clip, assembly, mesh statistics, apply, locate) use them as the mesh-operation units do.  Kernels
+// are `static`: every translation unit that includes this header gets its own copy (as in xr_node_faces.h).
 #pragma once
 #include <limits>
 #include <type_traits>
@@ -19,6 +20,25 @@ __device__ __forceinline__ void wave_count(bool pred, int32_t *counter) {
 // *flag = 1 if `bad` holds for some lane of the wave: one plain store per such wave (every lane of the wave must get here)
 __device__ __forceinline__ void wave_flag(bool bad, int32_t *flag) {
     if (__ballot(bad) && (threadIdx.x & 63) == 0) *flag = 1;
+}
+
+// counts[key] += the lanes with `pred` among each maximal run of adjacent lanes with equal `key`: one atomic by the run's first
+// lane, none for a run without such a lane; lanes with key < 0 take no part (every lane of the wave must get here).  Sorted
+// keys -- the pairs of one target face are contiguous in a pair queue -- make that a few atomics per wave.
+__device__ __forceinline__ void wave_run_add(int key, bool pred, int32_t *counts) {
+    const int lane = threadIdx.x & 63;
+    const int prev = __shfl_up(key, 1, 64);
+    const bool head = lane == 0 || prev != key;
+    const unsigned long long heads = __ballot(head);
+    const unsigned long long surv = __ballot(pred);
+    if (head && key >= 0) {
+        const unsigned long long above = lane == 63 ? 0ull : (heads >> (lane + 1));
+        const int next = above ? lane + 1 + (__ffsll((long long)above) - 1) : 64;
+        unsigned long long run = next == 64 ? ~0ull : ((1ull << next) - 1);
+        run &= ~((1ull << lane) - 1);
+        const int n = __popcll(surv & run);
+        if (n > 0) atomicAdd(&counts[key], n);
+    }
 }
 
 // ---- reductions -----------------------------------------------------------------------------------------------------------------
