@@ -418,6 +418,9 @@ int xr_csr_expect_permuted(xr_csr *csr, int permuted);
  * the caller's numbering once, not per apply. */
 int xr_csr_output_stored_order(xr_csr *csr, int stored);
 int xr_csr_row_order(const xr_csr *csr, int64_t K_hint, int64_t *order_out);
+/* The STORED rows of more than 32 entries, which the applies reduce cooperatively, as the matrix' builder listed them (in no
+ * particular order): *n_out = their number, the first min(*n_out, capacity) of them -> rows_out.  For inspection and tests. */
+int xr_csr_long_rows(const xr_csr *csr, int64_t capacity, int64_t *rows_out, int64_t *n_out);
 int xr_csr_destroy(xr_csr *csr);
 
 /* ---- seam 2: apply ---------------------------------------------------------------------- */

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "xr_apply.h"
+#include "xr_overlap_tail.h"
 #include "xr_reduce.h"
 #include "xr_prims.h"
 
@@ -24,14 +25,52 @@ namespace xr {
 
 static constexpr int KT = 16; // source variables reduced per pass over the CSR (K >= 2)
 
+// Where the cooperative reducers find a listed row: its segment, the arrays the segment indexes, its output position.
+// CsrRows: stored row t of one CSR.
+struct CsrRows {
+    const int32_t *__restrict__ indptr, *__restrict__ indices;
+    const double *__restrict__ data;
+    const int32_t *__restrict__ row_order;
+    __device__ __forceinline__ void segment(int t, int &s, int &e) const {
+        s = indptr[t];
+        e = indptr[t + 1];
+    }
+    __device__ __forceinline__ const int32_t *columns(int) const { return indices; }
+    __device__ __forceinline__ const double *weights(int) const { return data; }
+    __device__ __forceinline__ int64_t out_row(int t) const { return row_order ? (int64_t)row_order[t] : t; }
+};
+// TailRows: the matrix of a fused weight build whose big faces' rows have not been copied behind the regular ones yet
+// (k_apply_tail1).  Stored rows [t_big, T) are rows 0 ... of the big faces' own CSR, row k the row of face slot_face[k] in
+// the query order.
+struct TailRows {
+    CsrRows reg;
+    int t_big;
+    const int32_t *__restrict__ big_indptr, *__restrict__ big_indices;
+    const double *__restrict__ big_data;
+    const int32_t *__restrict__ slot_face, *__restrict__ q_perm;
+    __device__ __forceinline__ void segment(int t, int &s, int &e) const {
+        const int32_t *ip = t >= t_big ? big_indptr + (t - t_big) : reg.indptr + t;
+        s = ip[0];
+        e = ip[1];
+    }
+    __device__ __forceinline__ const int32_t *columns(int t) const { return t >= t_big ? big_indices : reg.indices; }
+    __device__ __forceinline__ const double *weights(int t) const { return t >= t_big ? big_data : reg.data; }
+    __device__ __forceinline__ int64_t big_out_row(int k) const {
+        const int f = slot_face[k];
+        return q_perm ? (int64_t)q_perm[f] : f;
+    }
+    __device__ __forceinline__ int64_t out_row(int t) const { return t >= t_big ? big_out_row(t - t_big) : reg.out_row(t); }
+};
+
 // one listed row reduced by the whole block (all threads call; rows beyond APPLY_WAVE entries)
-template <int METHOD, typename SRC>
-__device__ __forceinline__ void apply_row_block(const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
-                                                const double *__restrict__ data, const int32_t *__restrict__ row_order,
-                                                int t, int64_t T, int64_t S, const SRC *__restrict__ source, int64_t K,
-                                                double *__restrict__ out, double (*lds)[3]) {
-    const int s = indptr[t], e = indptr[t + 1];
-    const int64_t t_out = row_order ? (int64_t)row_order[t] : t;
+template <int METHOD, typename SRC, typename ROWS>
+__device__ __forceinline__ void apply_row_block(const ROWS &rows, int t, int64_t T, int64_t S, const SRC *__restrict__ source,
+                                                int64_t K, double *__restrict__ out, double (*lds)[3]) {
+    int s, e;
+    rows.segment(t, s, e);
+    const int32_t *__restrict__ indices = rows.columns(t);
+    const double *__restrict__ data = rows.weights(t);
+    const int64_t t_out = rows.out_row(t);
     double normsum = 0.0;
     if (METHOD == XR_GEOMETRIC_MEAN) {
         Red<XR_SUM> ws; // b accumulates the weights
@@ -74,7 +113,7 @@ k_apply_long(const int32_t *__restrict__ indptr, const int32_t *__restrict__ ind
     __shared__ double lds[AP_BLOCK / 64][3];
     const int nl = *n_long;
     for (int li = blockIdx.x; li < nl; li += gridDim.x)
-        apply_row_block<METHOD, SRC>(indptr, indices, data, row_order, long_rows[li], T, S, source, K, out, lds);
+        apply_row_block<METHOD, SRC>(CsrRows{indptr, indices, data, row_order}, long_rows[li], T, S, source, K, out, lds);
 }
 
 // Listed rows with APPLY_LONG < entries <= APPLY_WAVE, KTILE source variables per pass, reduced by a GROUP of
@@ -150,41 +189,39 @@ __device__ __forceinline__ void apply_row_group(const int32_t *__restrict__ indi
 
 // the listed rows of APPLY_LONG + 1 ... APPLY_WAVE entries, dealt to `n_waves` waves (this one is `wave`); rows beyond
 // APPLY_WAVE entries are queued in huge_rows ([0] = count) when given, else left to the caller
-template <int METHOD, typename SRC, int KTILE>
-__device__ __forceinline__ void apply_wave_rows(const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
-                                                const double *__restrict__ data, const int32_t *__restrict__ row_order,
-                                                const int32_t *__restrict__ long_rows, int nl, int wave, int n_waves,
-                                                int64_t T, int64_t S, const SRC *__restrict__ source, int64_t K,
+template <int METHOD, typename SRC, int KTILE, typename ROWS>
+__device__ __forceinline__ void apply_wave_rows(const ROWS &rows, const int32_t *__restrict__ long_rows, int nl, int wave,
+                                                int n_waves, int64_t T, int64_t S, const SRC *__restrict__ source, int64_t K,
                                                 double *__restrict__ out, int32_t *__restrict__ huge_rows) {
     const int lane = threadIdx.x & 63;
     // pass 1: four listed rows per wave, 16 lanes each
     for (int li0 = wave * 4; li0 < nl; li0 += n_waves * 4) {
         const int li = li0 + (lane >> 4);
-        int s = 0, e = 0;
+        int t = 0, s = 0, e = 0;
         int64_t t_out = 0;
         if (li < nl) {
-            const int t = long_rows[li];
-            s = indptr[t];
-            e = indptr[t + 1];
-            t_out = row_order ? (int64_t)row_order[t] : t;
+            t = long_rows[li];
+            rows.segment(t, s, e);
+            t_out = rows.out_row(t);
             if (e - s > APPLY_GROUP16) e = s; // other passes
         }
         // (the shuffles inside are wave-wide: every lane takes part, idle groups carry empty rows)
         if (__any(e > s)) {
-            if (e > s) apply_row_group<METHOD, SRC, KTILE, 16>(indices, data, s, e, t_out, T, S, source, K, out);
+            if (e > s)
+                apply_row_group<METHOD, SRC, KTILE, 16>(rows.columns(t), rows.weights(t), s, e, t_out, T, S, source, K, out);
         }
     }
     // pass 2: one listed row per wave; rows beyond APPLY_WAVE entries are queued for the block kernel
     for (int li = wave; li < nl; li += n_waves) {
         const int t = long_rows[li];
-        const int s = indptr[t], e = indptr[t + 1];
+        int s, e;
+        rows.segment(t, s, e);
         if (e - s <= APPLY_GROUP16) continue;
         if (e - s > APPLY_WAVE) { // [0] = count
             if (huge_rows && lane == 0 && blockIdx.y == 0) huge_rows[1 + atomicAdd(huge_rows, 1)] = t;
             continue;
         }
-        const int64_t t_out = row_order ? (int64_t)row_order[t] : t;
-        apply_row_group<METHOD, SRC, KTILE, 64>(indices, data, s, e, t_out, T, S, source, K, out);
+        apply_row_group<METHOD, SRC, KTILE, 64>(rows.columns(t), rows.weights(t), s, e, rows.out_row(t), T, S, source, K, out);
     }
 }
 
@@ -195,8 +232,8 @@ k_apply_wave(const int32_t *__restrict__ indptr, const int32_t *__restrict__ ind
              const int32_t *__restrict__ n_long, int64_t T, int64_t S, const SRC *__restrict__ source, int64_t K,
              double *__restrict__ out, int32_t *__restrict__ huge_rows) {
     const int wave = (blockIdx.x * AP_BLOCK + threadIdx.x) >> 6, n_waves = gridDim.x * (AP_BLOCK / 64);
-    apply_wave_rows<METHOD, SRC, KTILE>(indptr, indices, data, row_order, long_rows, *n_long, wave, n_waves, T, S, source, K,
-                                        out, huge_rows);
+    apply_wave_rows<METHOD, SRC, KTILE>(CsrRows{indptr, indices, data, row_order}, long_rows, *n_long, wave, n_waves, T, S,
+                                        source, K, out, huge_rows);
 }
 
 // K = 1, every row in ONE launch.  Blocks [0, n_long_blocks) take the listed long rows (lane groups / waves, then the rows
@@ -208,45 +245,52 @@ k_apply_wave(const int32_t *__restrict__ indptr, const int32_t *__restrict__ ind
 // regridder.py:52-62).  No block barrier anywhere and 6 KB of LDS per wave: 24 waves per CU keep three dependent
 // round trips (row pointers -> entries -> source values) in flight, where the block-wide version of rounds 1-2 (32 KB
 // and four barriers per block) held 20 (MI355X, 1M x 1M benchmark: 42.6 -> see DESIGN section 5).
-template <int METHOD, typename SRC>
-__global__ void __launch_bounds__(AP_BLOCK)
-k_apply_rows1(const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices, const double *__restrict__ data,
-              const int32_t *__restrict__ row_order, const int32_t *__restrict__ long_rows,
-              const int32_t *__restrict__ n_long, int n_long_blocks, bool any_huge, int64_t T, int64_t S,
-              const SRC *__restrict__ source, double *__restrict__ out, const int32_t *__restrict__ gate) {
-    __shared__ double2 sh_win[AP_BLOCK / 64][W1_CAP]; // (.x = weight, .y = source value); 24 KB: 6 blocks per CU
-    if (gate && *gate == 0) return; // (enqueued behind a weight build whose attempt failed: the host redoes both)
-    double(*sh_merge)[3] = reinterpret_cast<double(*)[3]>(&sh_win[0][0]); // (long-row blocks stage nothing)
-    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
-    if ((int)blockIdx.x < n_long_blocks) {
-        const int nl = *n_long;
-        apply_wave_rows<METHOD, SRC, 1>(indptr, indices, data, row_order, long_rows, nl, (int)blockIdx.x * (AP_BLOCK / 64) + wib,
-                                        n_long_blocks * (AP_BLOCK / 64), T, S, source, 1, out, nullptr);
-        if (any_huge) {
-            // rows beyond the wave kernel's reach, a block each.  The block's share of the list is looked at by all its
-            // threads AT ONCE (entry li = block + n_long_blocks * thread: two dependent loads per thread, in flight
-            // together) and the few hits are parked in LDS -- walking the share entry by entry was a chain of ~9 x 2
-            // dependent round trips that made these blocks the last to finish (the kernel's 28 us on the benchmark).
-            int *sh_list = reinterpret_cast<int *>(&sh_win[1][0]), *sh_cnt = reinterpret_cast<int *>(&sh_win[2][0]);
-            for (int base = 0; base < nl; base += n_long_blocks * AP_BLOCK) {
-                if (threadIdx.x == 0) *sh_cnt = 0;
-                __syncthreads();
-                const int li = base + (int)blockIdx.x + n_long_blocks * (int)threadIdx.x;
-                if (li < nl) {
-                    const int t = long_rows[li];
-                    if (indptr[t + 1] - indptr[t] > APPLY_WAVE) sh_list[atomicAdd(sh_cnt, 1)] = t; // (at most one per thread)
-                }
-                __syncthreads();
-                const int n_hit = *sh_cnt;
-                for (int i = 0; i < n_hit; i++) // (uniform: every thread of the block works on the row)
-                    apply_row_block<METHOD, SRC>(indptr, indices, data, row_order, sh_list[i], T, S, source, 1, out, sh_merge);
-                __syncthreads();
+// The long-row role of the K = 1 kernels: block `block` of `n_blocks` leading blocks takes its share of the listed rows (lane
+// groups / waves, then the rows beyond APPLY_WAVE entries block by block).  sh_win: the block's window memory (these
+// blocks stage nothing in it).
+template <int METHOD, typename SRC, typename ROWS>
+__device__ __forceinline__ void rows1_long_role(const ROWS &rows, const int32_t *__restrict__ long_rows, int nl, int block,
+                                                int n_blocks, bool any_huge, int64_t T, int64_t S,
+                                                const SRC *__restrict__ source, double *__restrict__ out, double2 *sh_win) {
+    double(*sh_merge)[3] = reinterpret_cast<double(*)[3]>(sh_win);
+    const int wib = threadIdx.x >> 6;
+    apply_wave_rows<METHOD, SRC, 1>(rows, long_rows, nl, block * (AP_BLOCK / 64) + wib, n_blocks * (AP_BLOCK / 64), T, S, source, 1,
+                                    out, nullptr);
+    if (any_huge) {
+        // rows beyond the wave kernel's reach, a block each.  The block's share of the list is looked at by all its
+        // threads AT ONCE (entry li = block + n_blocks * thread: two dependent loads per thread, in flight
+        // together) and the few hits are parked in LDS -- walking the share entry by entry was a chain of ~9 x 2
+        // dependent round trips that made these blocks the last to finish (the kernel's 28 us on the benchmark).
+        int *sh_list = reinterpret_cast<int *>(sh_win + W1_CAP), *sh_cnt = reinterpret_cast<int *>(sh_win + 2 * W1_CAP);
+        for (int base = 0; base < nl; base += n_blocks * AP_BLOCK) {
+            if (threadIdx.x == 0) *sh_cnt = 0;
+            __syncthreads();
+            const int li = base + block + n_blocks * (int)threadIdx.x;
+            if (li < nl) {
+                const int t = long_rows[li];
+                int s, e;
+                rows.segment(t, s, e);
+                if (e - s > APPLY_WAVE) sh_list[atomicAdd(sh_cnt, 1)] = t; // (at most one per thread)
             }
+            __syncthreads();
+            const int n_hit = *sh_cnt;
+            for (int i = 0; i < n_hit; i++) // (uniform: every thread of the block works on the row)
+                apply_row_block<METHOD, SRC>(rows, sh_list[i], T, S, source, 1, out, sh_merge);
+            __syncthreads();
         }
-        return;
     }
+}
+
+// The regular role: block `block` of `n_blocks` takes AP_BLOCK of the stored rows [0, T), every wave on its own window.
+// skip_long: rows beyond APPLY_LONG entries are left to the long-row role.
+template <int METHOD, typename SRC>
+__device__ __forceinline__ void rows1_regular_role(const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                                   const double *__restrict__ data, const int32_t *__restrict__ row_order,
+                                                   int block, int n_blocks, bool skip_long, int64_t T,
+                                                   const SRC *__restrict__ source, double *__restrict__ out, double2 *sh_win) {
     // (last row blocks first: weights built by xr_overlap keep the rows of the big target faces at the end)
-    const int64_t row0 = ((int64_t)(gridDim.x - 1 - blockIdx.x) * (AP_BLOCK / 64) + wib) * 64;
+    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+    const int64_t row0 = ((int64_t)(n_blocks - 1 - block) * (AP_BLOCK / 64) + wib) * 64;
     if (row0 >= T) return;
     const int64_t t = row0 + lane;
     int s = 0, e = 0;
@@ -254,12 +298,12 @@ k_apply_rows1(const int32_t *__restrict__ indptr, const int32_t *__restrict__ in
         s = indptr[t];
         e = indptr[t + 1];
     }
-    const bool skip = n_long_blocks > 0 && (e - s > APPLY_LONG); // reduced by the long-row blocks
+    const bool skip = skip_long && (e - s > APPLY_LONG); // reduced by the long-row blocks
     const int seg0 = __shfl(s, 0, 64);
     const int seg1 = wave_reduce<OpMax>(e); // (lanes beyond T hold 0: the maximum is the end of the last valid row)
     if (skip) e = s;
     const bool jumpy = __any(skip);
-    double2 *win = sh_win[wib];
+    double2 *win = sh_win + (size_t)wib * W1_CAP;
     // first entry any lane still needs at or behind c0 (a window must not stream the entries of skipped long rows)
     auto next_chunk = [&](int c0) -> int {
         if (!jumpy) return c0;
@@ -322,6 +366,94 @@ k_apply_rows1(const int32_t *__restrict__ indptr, const int32_t *__restrict__ in
         }
         out[t_out] = r;
     }
+}
+
+template <int METHOD, typename SRC>
+__global__ void __launch_bounds__(AP_BLOCK)
+k_apply_rows1(const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices, const double *__restrict__ data,
+              const int32_t *__restrict__ row_order, const int32_t *__restrict__ long_rows,
+              const int32_t *__restrict__ n_long, int n_long_blocks, bool any_huge, int64_t T, int64_t S,
+              const SRC *__restrict__ source, double *__restrict__ out, const int32_t *__restrict__ gate) {
+    __shared__ double2 sh_win[AP_BLOCK / 64][W1_CAP]; // (.x = weight, .y = source value); 24 KB: 6 blocks per CU
+    if (gate && *gate == 0) return; // (enqueued behind a weight build whose attempt failed: the host redoes both)
+    if ((int)blockIdx.x < n_long_blocks)
+        return rows1_long_role<METHOD, SRC>(CsrRows{indptr, indices, data, row_order}, long_rows, *n_long, (int)blockIdx.x,
+                                            n_long_blocks, any_huge, T, S, source, out, &sh_win[0][0]);
+    rows1_regular_role<METHOD, SRC>(indptr, indices, data, row_order, (int)blockIdx.x - n_long_blocks,
+                                    (int)gridDim.x - n_long_blocks, n_long_blocks > 0, T, source, out, &sh_win[0][0]);
+}
+
+// k_apply_rows1 enqueued behind a fused weight build (overlap_tri) whose big faces' rows have NOT been copied behind the regular
+// ones: the launch makes that copy itself and needs it for nothing.  Three block-uniform roles:
+//   blocks [0, TAIL_PLACE_BLOCKS)     place_big_copy, the body of k_place_big (the matrix is complete behind the launch), then
+//                                     the big rows of at most APPLY_LONG entries, which are on no list: one lane each,
+//                                     sequentially in CSR order like a window lane -- eight entries' loads in flight
+//   the n_long_blocks behind them     the listed long rows; a listed row >= T - n_big is read from the big faces' own CSR
+//                                     (TailRows)
+//   the others                        the wave windows over the stored rows [0, T - n_big): indptr[T - n_big] is the assembly's
+// No block waits for, or reads, what another block of the launch writes; every row is summed in the order k_apply_rows1 sums it.
+// The launch runs behind k_publish_all, on the words it left in the matrix (TailWord): the gate, n_big, the regular rows'
+// entries, the number of listed rows.
+template <int METHOD, typename SRC>
+__global__ void __launch_bounds__(AP_BLOCK)
+k_apply_tail1(ApplyTail tail, const int32_t *__restrict__ long_rows, int n_long_blocks, int64_t T, int64_t S,
+              const SRC *__restrict__ source, double *__restrict__ out) {
+    __shared__ double2 sh_win[AP_BLOCK / 64][W1_CAP]; // 24 KB: 6 blocks per CU, as k_apply_rows1
+    const PlaceBig &p = tail.place;
+    if (tail.words[TAIL_GATE] == 0) return; // (a failed attempt: the host redoes build and apply; nothing is touched)
+    const int n_big = tail.words[TAIL_N_BIG];
+    const int t_big = (int)(T - n_big);
+    const int b = (int)blockIdx.x;
+    const TailRows rows{CsrRows{p.indptr, p.indices, p.data, p.row_order}, t_big, p.big_indptr, p.big_indices, p.big_data,
+                        p.slot_face, p.q_perm};
+    if (b < TAIL_PLACE_BLOCKS) {
+        if (n_big == 0) return;
+        // (the gate has made k_place_big's checks; the control block is at rest and not touched)
+        place_big_copy<true>(p, n_big, tail.words[TAIL_P_REGULAR], p.big_indptr[n_big], b, TAIL_PLACE_BLOCKS);
+        for (int k = b * AP_BLOCK + (int)threadIdx.x; k < n_big; k += TAIL_PLACE_BLOCKS * AP_BLOCK) {
+            const int s = p.big_indptr[k], e = p.big_indptr[k + 1];
+            if (e - s > APPLY_LONG) continue; // listed
+            double normsum = 0.0;
+            if (METHOD == XR_GEOMETRIC_MEAN) {
+                for (int j0 = s; j0 < e; j0 += 8) {
+                    double w[8];
+#pragma unroll
+                    for (int u = 0; u < 8; u++) w[u] = j0 + u < e ? p.big_data[j0 + u] : 0.0;
+#pragma unroll
+                    for (int u = 0; u < 8; u++)
+                        if (j0 + u < e) normsum += w[u];
+                }
+            }
+            Red<METHOD> red;
+            for (int j0 = s; j0 < e; j0 += 8) {
+                int col[8];
+                double w[8], v[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    col[u] = j0 + u < e ? p.big_indices[j0 + u] : -1;
+                    w[u] = j0 + u < e ? p.big_data[j0 + u] : 0.0;
+                }
+#pragma unroll
+                for (int u = 0; u < 8; u++) v[u] = col[u] >= 0 ? ld_src(source, (int64_t)col[u]) : 0.0;
+#pragma unroll
+                for (int u = 0; u < 8; u++)
+                    if (col[u] >= 0) red.add(v[u], w[u], normsum);
+            }
+            double r = NAN; // rows without entries stay NaN
+            if (e > s) {
+                r = red.fin();
+                if (METHOD == XR_GEOMETRIC_MEAN && normsum == 0) r = NAN;
+            }
+            out[rows.big_out_row(k)] = r;
+        }
+        return;
+    }
+    if (b < TAIL_PLACE_BLOCKS + n_long_blocks)
+        return rows1_long_role<METHOD, SRC>(rows, long_rows, tail.words[TAIL_N_LONG], b - TAIL_PLACE_BLOCKS, n_long_blocks, true, T,
+                                            S, source, out, &sh_win[0][0]);
+    const int n_lead = TAIL_PLACE_BLOCKS + n_long_blocks;
+    rows1_regular_role<METHOD, SRC>(p.indptr, p.indices, p.data, p.row_order, b - n_lead, (int)gridDim.x - n_lead, true, t_big,
+                                    source, out, &sh_win[0][0]);
 }
 
 // Many source variables (K >= 2): one thread per row keeps KTILE reducer states in registers and
@@ -1318,9 +1450,18 @@ static void launch_stream(const xr_csr *csr, const SRC *src, int64_t K, double *
         const int n_long_blocks = csr->has_long ? engine().num_cu / 2 : 0;
         const bool any_huge = csr->has_long && !(csr->max_row_len >= 0 && csr->max_row_len <= APPLY_WAVE);
         dim3 grid((unsigned)(div_up(csr->n, AP_BLOCK) + n_long_blocks), 1);
-        XR_LAUNCH("apply_rows1", (k_apply_rows1<METHOD, SRC>), grid, dim3(AP_BLOCK), 0, csr->indptr.get(), csr->indices.get(),
-                  csr->data.get(), row_order_of(csr), csr->long_rows.get(), csr->n_long.get(), n_long_blocks, any_huge,
-                  csr->n, csr->m, src, out, csr->apply_gated ? csr->n_long.get() + 1 : (const int32_t *)nullptr);
+        if (csr->apply_tail) {
+            // enqueued by the fused weight build in front of its place_big: this launch places the big rows itself
+            XR_REQUIRE(csr->apply_gated && n_long_blocks > 0 && row_order_of(csr) == csr->row_order.get() && !csr->has_col_perm,
+                       XR_ERR_INVALID, "xr_apply: the tail of a weight build needs its fresh matrix");
+            grid.x += TAIL_PLACE_BLOCKS;
+            XR_LAUNCH("apply_rows1", (k_apply_tail1<METHOD, SRC>), grid, dim3(AP_BLOCK), 0, *csr->apply_tail, csr->long_rows.get(),
+                      n_long_blocks, csr->n, csr->m, src, out);
+        } else {
+            XR_LAUNCH("apply_rows1", (k_apply_rows1<METHOD, SRC>), grid, dim3(AP_BLOCK), 0, csr->indptr.get(), csr->indices.get(),
+                      csr->data.get(), row_order_of(csr), csr->long_rows.get(), csr->n_long.get(), n_long_blocks, any_huge,
+                      csr->n, csr->m, src, out, csr->apply_gated ? csr->n_long.get() + 1 : (const int32_t *)nullptr);
+        }
     } else {
         if (use_plan) {
             // many variables: rows regrouped into 2-D tiles, then a blocked CSR with per-block distinct-column

@@ -426,6 +426,21 @@ int xr_csr_row_order(const xr_csr *csr, int64_t K_hint, int64_t *order_out) {
     XR_API_END
 }
 
+int xr_csr_long_rows(const xr_csr *csr, int64_t capacity, int64_t *rows_out, int64_t *n_out) {
+    XR_API_BEGIN
+    XR_REQUIRE(csr && n_out && (rows_out || capacity == 0) && capacity >= 0, XR_ERR_INVALID, "xr_csr_long_rows: invalid argument");
+    stream_sync();
+    const int64_t n = csr->n_long.get() ? read_scalar(csr->n_long.get()) : 0;
+    *n_out = n;
+    const int64_t take = n < capacity ? n : capacity;
+    if (take > 0) {
+        DevBuf<int64_t> wide((size_t)take);
+        download_wide(csr->long_rows.get(), take, rows_out, wide);
+        stream_sync();
+    }
+    XR_API_END
+}
+
 int xr_csr_destroy(xr_csr *csr) {
     XR_API_BEGIN
     if (csr) {

@@ -59,7 +59,7 @@ const OptionDef k_option_defs[] = {
     {"apply_contract", 0}, {"plan_merge", -1}, {"plan_dbg", 0}, {"apply_chunk_bytes", 0}, {"outer_apply", 0}, {"edge_big", 0},
     {"edge_stage", 0}, {"edge_queue", 0}, {"edge_sort", 1}, {"nn_query_sort", -1}, {"burn_strips", 0},
     {"facet_tile", 0}, {"scan_fused_tiles", 0}, {"merge_table_slack", 0},
-    {"front_fused", 1},
+    {"front_fused", 1}, {"tail_fused", 1},
 };
 static_assert(sizeof(k_option_defs) / sizeof(k_option_defs[0]) == OPT_COUNT, "one table row per enum Option");
 std::atomic<int64_t> g_options[OPT_COUNT];

@@ -330,6 +330,7 @@ enum Option : int {
     OPT_SCAN_FUSED_TILES,  // > 0: tiles up to which exclusive_scan_i32 runs its fused pair (xr_scan.hip; 0: SCAN_FUSED_TILES; tests force the three-kernel path with a tiny one)
     OPT_MERGE_TABLE_SLACK, // 1: the key table of xr_merge.hip takes the smallest legal capacity (long chains, wrap-around on small inputs); 0: >= 2 n
     OPT_FRONT_FUSED,       // 1: a weight build's front is one launch, the tree's sampling blocks lead the query's prepare_faces grid (mesh_prepare_pair); 0: two launches
+    OPT_TAIL_FUSED,        // 1: a K = 1 apply enqueued behind a fused weight build places the big faces' rows in its own launch (overlap_tri: publish -> apply); 0: place_big -> publish -> apply
     OPT_COUNT
 };
 int64_t option(Option o);

@@ -114,6 +114,10 @@ struct xr_mesh {
 static constexpr int XR_APPLY_LONG_ROW = 32;
 static constexpr int XR_APPLY_WAVE_ROW = 2048;
 
+namespace xr {
+struct ApplyTail; // xr_overlap_tail.h
+}
+
 // Device-resident MatrixCSR (xugrid/core/sparse.py:81-137), int32 structure + float64 data.
 struct xr_csr {
     int64_t n = 0, m = 0, nnz = 0;
@@ -129,6 +133,7 @@ struct xr_csr {
     xr::DevBuf<int32_t> long_rows; // [<= n]
     xr::DevBuf<int32_t> n_long;    // [1] device-side count ([2] for matrices of the triangle pipeline: [1] = apply gate)
     bool apply_gated = false;      // the K = 1 apply being enqueued must check n_long[1] (matrix not yet confirmed by the host)
+    const xr::ApplyTail *apply_tail = nullptr; // ... and takes the tail of that build into its launch (xr_overlap_tail.h; set around the enqueue only)
     int64_t max_row_len = -1;      // entries of the longest row if the builder reported it (-1: unknown)
     bool has_long = false;
     // Coarse Morton key per STORED row (tile of ~12 target extents).  Set by xr_overlap when the rows are kept

@@ -28,6 +28,7 @@
 // for operation; both are built with -ffp-contract=off, so areas agree bit for bit.
 #include "xr_objects.h"
 #include "xr_clip_tri.h"
+#include "xr_overlap_tail.h"
 #include "xr_prims.h"
 
 namespace xr {
@@ -49,7 +50,7 @@ __device__ __forceinline__ bool rec_hit(float4 b, float qx0, float qx1, float qy
 // hits, too many grid rows or too many visited records are "big" and go to the block-per-face
 // kernel instead.
 static constexpr int SLOTS = 16;
-static constexpr int QCUR_STRIDE = 32; // words between the cursors of the regular queue's eight regions: a 128-byte line each
+static_assert(SLOTS <= XR_APPLY_LONG_ROW, "a regular row is never one of the apply's long rows: only k_row_fill_long lists");
 static constexpr int TILE_RUN = 16; // rows per run in the tiling hint (128-byte output stores per variable).  Measured, K = 256 on
                                     // the benchmark matrix: runs of 64 rows / tiles of 24 extents 2.10 ms, 16 / 12: 1.72 ms (a qhull-numbered
                                     // target: long runs of consecutive ids are not compact); a lattice-numbered pair 0.99 ms either way
@@ -1073,10 +1074,13 @@ static constexpr int BM_WORDS = 32768;          // 128 KiB of bitmap
 static constexpr int BM_BITS = BM_WORDS * 32;   // ids per chunk
 static constexpr int BM_SEG = BM_WORDS / 256;   // words per thread segment
 static constexpr int BM_STAGE = 4096;           // candidates parked in LDS (16 KiB); longer rows re-read HBM
-static constexpr size_t ROW_FILL_LIGHT_LDS = sizeof(int32_t) * (8 + BM_STAGE); // LDS of a k_row_fill_long launch with row_class = 1
+static constexpr size_t ROW_FILL_LIGHT_LDS = sizeof(int32_t) * (16 + BM_STAGE); // LDS of a k_row_fill_long launch with row_class = 1
 static constexpr size_t ROW_FILL_LONG_LDS =                                    // ... of any other: + segment bases, bitmap, group counts
     ROW_FILL_LIGHT_LDS + sizeof(uint32_t) * (256 + BM_WORDS) + sizeof(uint16_t) * (BM_WORDS / 8);
 
+// LIST: the launch also writes the apply's list of long rows (apply_long_rows, listed, n_stored; scan_nnz mode).  A template
+// parameter, so that the launches that do not list -- the bitmap rows' is the one the weight build waits for -- carry none of it.
+template <bool LIST>
 __global__ void __launch_bounds__(256)
 k_row_fill_long(const int32_t *__restrict__ cand_off, const int32_t *__restrict__ cand_count,
                 const int32_t *__restrict__ cand_sid,
@@ -1091,31 +1095,61 @@ k_row_fill_long(const int32_t *__restrict__ cand_off, const int32_t *__restrict_
                 int32_t *__restrict__ scan_total = nullptr /* total entries, written */,
                 int row_class = 0 /* 0: every listed row; 1: only rows of at most ROW_BLOCK candidates -- the launch then needs
                                      ROW_FILL_LIGHT_LDS bytes of LDS instead of 150 KB, so its blocks find room beside other
-                                     kernels and every row gets a block of its own; 2: only the rows beyond ROW_BLOCK */) {
+                                     kernels and every row gets a block of its own; 2: only the rows beyond ROW_BLOCK */,
+                int32_t *__restrict__ apply_long_rows = nullptr /* optional (scan_nnz mode): the listed rows of more than
+                                                                   XR_APPLY_LONG_ROW entries are written to the apply's list
+                                                                   as STORED rows n_stored - n_long + li, counted in `listed` */,
+                FusedCounters *listed = nullptr, int64_t n_stored = 0) {
     __builtin_amdgcn_s_setprio(3); // side-stream kernel: its waves go first in the SIMDs' issue arbitration (see overlap_tri)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // (scratch and stage first: a row_class = 1 launch allocates nothing behind them)
-    int32_t *red = reinterpret_cast<int32_t *>(smem);           // [8] scratch
-    int32_t *stage = red + 8;                                   // [BM_STAGE]
+    int32_t *red = reinterpret_cast<int32_t *>(smem);           // [16] scratch
+    int32_t *stage = red + 16;                                  // [BM_STAGE]
     uint32_t *tbase = reinterpret_cast<uint32_t *>(stage + BM_STAGE); // [256] exclusive over thread segments
     uint32_t *bm = tbase + 256;                                 // [BM_WORDS]
     uint16_t *gcnt = reinterpret_cast<uint16_t *>(bm + BM_WORDS); // [BM_WORDS / 8] bits per 8 words -> prefix in segment
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (skip_if && *skip_if > 0) return;
     const int nl = *n_long;
-    // block-wide sum of the lengths of the listed rows [k0, k1) (scan_nnz mode)
-    auto length_sum = [&](int k0, int k1) -> long long {
+    // block-wide sum of the lengths of the listed rows [k0, k1) (scan_nnz mode); *n_longer: how many of them the apply reduces
+    // cooperatively (more than XR_APPLY_LONG_ROW entries), *longest: the longest of them
+    auto length_sum = [&](int k0, int k1, int *n_longer, int *longest) -> long long {
         long long v = 0;
-        for (int k = k0 + tid; k < k1; k += 256) v += scan_nnz[long_rows[k]];
+        int c = 0, m = 0;
+        for (int k = k0 + tid; k < k1; k += 256) {
+            const int len = scan_nnz[long_rows[k]];
+            v += len;
+            if (LIST) {
+                c += len > XR_APPLY_LONG_ROW ? 1 : 0;
+                m = len > m ? len : m;
+            }
+        }
         v = wave_reduce<OpSum>(v);
+        if (LIST) {
+            c = wave_reduce<OpSum>(c);
+            m = wave_reduce<OpMax>(m);
+        }
         __syncthreads();
-        if (lane == 0) red[wave] = (int32_t)(v > 0x7fffffffll ? 0x7fffffff : v);
+        if (lane == 0) {
+            red[wave] = (int32_t)(v > 0x7fffffffll ? 0x7fffffff : v);
+            if (LIST) {
+                red[4 + wave] = c;
+                red[8 + wave] = m;
+            }
+        }
         __syncthreads();
+        if (LIST) {
+            *n_longer = red[4] + red[5] + red[6] + red[7];
+            const int m01 = red[8] > red[9] ? red[8] : red[9], m23 = red[10] > red[11] ? red[10] : red[11];
+            *longest = m01 > m23 ? m01 : m23;
+        }
         return (long long)red[0] + red[1] + red[2] + red[3];
     };
     long long scan_base = 0; // offset of row blockIdx.x, advanced by gridDim.x rows per trip
+    int list_base = 0;       // ... its place among the listed rows of more than XR_APPLY_LONG_ROW entries
+    int list_max = 0;        // ... and the longest row in front of it
     if (scan_nnz) {
-        scan_base = length_sum(0, blockIdx.x < nl ? (int)blockIdx.x : nl);
+        scan_base = length_sum(0, blockIdx.x < nl ? (int)blockIdx.x : nl, &list_base, &list_max);
         if (blockIdx.x == 0 && nl == 0 && tid == 0) {
             scan_indptr[0] = 0;
             *scan_total = 0;
@@ -1128,16 +1162,36 @@ k_row_fill_long(const int32_t *__restrict__ cand_off, const int32_t *__restrict_
         if (scan_nnz) {
             const long long capped = scan_base > 0x7fffffffll ? 0x7fffffffll : scan_base;
             base = (int)capped;
+            int len_t = 0; // (thread 0: the row's own length, fetched beside the loads of the sum below)
             if (tid == 0) {
                 scan_indptr[li] = base;
+                if (LIST || li == nl - 1) len_t = scan_nnz[t];
+            }
+            const int next = li + (int)gridDim.x;
+            int longer = 0, longest = 0;
+            scan_base += length_sum(li, next < nl ? next : nl, &longer, &longest);
+            if (tid == 0) {
+                if (LIST) {
+                    // The apply's list of long rows, without an atomic (a thousand on one address are microseconds of the
+                    // big faces' chain): the row's place in it is the number of long rows in front of it in the list, and its
+                    // stored row is known without the assembly -- the listed rows go behind all others, in list order.  The
+                    // block of the last row has seen every row: it leaves their number and the longest one's length.
+                    // (The regular rows never have more than SLOTS entries: nobody else lists.)
+                    if (len_t > XR_APPLY_LONG_ROW) apply_long_rows[list_base] = (int32_t)(n_stored - nl + li);
+                    if (li == nl - 1) {
+                        const int n_listed = list_base + (len_t > XR_APPLY_LONG_ROW ? 1 : 0);
+                        listed->n_apply_long = n_listed;
+                        if (n_listed > 0) listed->max_row = len_t > list_max ? len_t : list_max;
+                    }
+                }
                 if (li == nl - 1) { // the last listed row closes the offsets
-                    const long long all = capped + scan_nnz[t];
+                    const long long all = capped + len_t;
                     scan_indptr[nl] = (int32_t)(all > 0x7fffffffll ? 0x7fffffff : all);
                     *scan_total = scan_indptr[nl];
                 }
             }
-            const int next = li + (int)gridDim.x;
-            scan_base += length_sum(li, next < nl ? next : nl);
+            list_base += longer;
+            list_max = longest > list_max ? longest : list_max;
         } else {
             base = row_base >= 0 ? indptr[row_base + li] : indptr[t];
         }
@@ -1374,15 +1428,23 @@ struct LongRows { // (the kernel's arguments of the same names)
     int64_t row_base;
     const int32_t *skip_if = nullptr, *scan_nnz = nullptr;
     int32_t *scan_indptr = nullptr, *scan_total = nullptr;
+    int32_t *apply_long_rows = nullptr; // (scan_nnz mode) the apply's list of long rows, FusedCounters that count it, stored rows
+    FusedCounters *listed = nullptr;
+    int64_t n_stored = 0;
 };
 static void launch_row_fill_long(int row_class, const xr_mesh *tree, const SearchLists &l, const double *tree_area, bool relative,
                                  const LongRows &r) {
-    allow_dynamic_lds<&k_row_fill_long>(ROW_FILL_LONG_LDS);
     const bool light = row_class == 1;
-    XR_LAUNCH(row_class == 2 ? "row_fill_huge" : "row_fill_long", k_row_fill_long, dim3(engine().num_cu * (light ? 6 : 1)), dim3(256),
-              light ? ROW_FILL_LIGHT_LDS : ROW_FILL_LONG_LDS, l.cand_off.get(), l.cand_count.get(), r.cand_sid, r.cand_area,
-              r.indptr, tree_area, relative, tree->n_face, r.indices, r.data, r.long_rows, r.n_long, r.row_base, r.skip_if,
-              r.scan_nnz, r.scan_indptr, r.scan_total, row_class);
+    // (both classes' launches walk the whole list for its offsets; ONE of them, not the bitmap rows', lists for the apply)
+    auto launch = [&](auto list) {
+        allow_dynamic_lds<&k_row_fill_long<list()>>(ROW_FILL_LONG_LDS);
+        XR_LAUNCH(row_class == 2 ? "row_fill_huge" : "row_fill_long", k_row_fill_long<list()>, dim3(engine().num_cu * (light ? 6 : 1)),
+                  dim3(256), light ? ROW_FILL_LIGHT_LDS : ROW_FILL_LONG_LDS, l.cand_off.get(), l.cand_count.get(), r.cand_sid,
+                  r.cand_area, r.indptr, tree_area, relative, tree->n_face, r.indices, r.data, r.long_rows, r.n_long, r.row_base,
+                  r.skip_if, r.scan_nnz, r.scan_indptr, r.scan_total, row_class, r.apply_long_rows, r.listed, r.n_stored);
+    };
+    if (light && r.apply_long_rows && r.scan_nnz) launch(std::true_type());
+    else launch(std::false_type());
 }
 
 // Triangle x triangle pairs (xr_overlap_fused.h): search -> persistent clip -> assembly with a look-back scan, the big
@@ -1394,6 +1456,7 @@ static void launch_row_fill_long(int row_class, const xr_mesh *tree, const Searc
 // round trip of the build is hidden behind the apply instead of standing between the two.
 struct EarlyApply {
     std::function<void(const xr_csr *)> fn;
+    bool takes_tail = false; // fn enqueues the K = 1 kernel that places the big rows itself (csr->apply_tail)
     bool done = false;
 };
 
@@ -1430,7 +1493,7 @@ static bool overlap_tri(xr_mesh *tree, xr_mesh *query, const double *tree_area, 
     // assembly becomes three passes of dependent loads, 0.066 -> 0.087 ms, DESIGN_HISTORY.md round 3)
     DevBuf<int32_t> cand_tgt((size_t)reg_capacity), cand_src((size_t)reg_capacity), cand_sid((size_t)reg_capacity);
     DevBuf<double> cand_area((size_t)reg_capacity);
-    csr->n_long.alloc(2); // [0] rows of more than XR_APPLY_LONG_ROW entries, [1] gate of an apply enqueued behind the build
+    csr->n_long.alloc(TAIL_WORDS); // [0] rows of more than XR_APPLY_LONG_ROW entries, [1] gate of an apply enqueued behind the build ... (TailWord)
     csr->row_order.alloc((size_t)T);
     csr->has_row_order = true;
     int32_t *const tile_key = csr->has_tile_key ? csr->tile_key.get() : nullptr;
@@ -1492,7 +1555,8 @@ static bool overlap_tri(xr_mesh *tree, xr_mesh *query, const double *tree_area, 
             // rows -- so the bitmap rows go to a SECOND side stream and run beside the light ones: the big faces' chain
             // behind the clip is one launch shorter where it is the step's critical path, 0.506 -> 0.500 ms in an A/B)
             const LongRows big_rows{big_sid.get(), big_area.get(), big_indptr.get(), big_indices.get(), big_data.get(), slot_face.get(),
-                                    n_big_dev, 0, n_pending_dev, l.nnz_row.get(), big_indptr.get(), &fc->p_big};
+                                    n_big_dev, 0, n_pending_dev, l.nnz_row.get(), big_indptr.get(), &fc->p_big,
+                                    csr->long_rows.get(), fc, T};
             SideForkScope fork;
             launch_row_fill_long(2, tree, l, tree_area, relative, big_rows);
             fork.end_launches();
@@ -1512,29 +1576,40 @@ static bool overlap_tri(xr_mesh *tree, xr_mesh *query, const double *tree_area, 
         XR_LAUNCH("assemble", k_assemble, dim3(grid), dim3(FB), 0, query->qo_bbox(), query->qo_fxy(), query->qo_len(), query->m,
                   query->qo_perm(), T, cand_tgt.get(), l.cand_off.get(), l.cand_count.get(), l.block_seg.get(), l.is_big.get(), cand_area.get(), cand_sid.get(),
                   tree_area, relative, tile, tile_key, fc,
-                  csr->indptr.get(), csr->indices.get(), csr->data.get(), csr->row_order.get(),
-                  csr->long_rows.get(), cap, remap, scan_mode == 1 ? blk_base.get() : (const int32_t *)nullptr,
+                  csr->indptr.get(), csr->indices.get(), csr->data.get(), csr->row_order.get(), cap, remap, scan_mode == 1 ? blk_base.get() : (const int32_t *)nullptr,
                   scan_mode == 1 ? blk_base.get() + grid : (const int32_t *)nullptr,
                   scan_mode == 2 ? blk_rows : (const int32_t *)nullptr, scan_mode == 2 ? blk_surv : (const int32_t *)nullptr);
         side_join();
-        XR_LAUNCH("place_big", k_place_big, dim3(64), dim3(256), 0, n_big_dev, slot_face.get(), big_indptr.get(),
-                  big_indices.get(), big_data.get(), T, query->qo_perm(), query->qo_bbox(), query->qo_fxy(), query->qo_len(),
-                  query->m, tile, tile_key, fc, csr->indptr.get(), csr->indices.get(),
-                  csr->data.get(), csr->row_order.get(), csr->long_rows.get(), cap, n_pending_dev);
-        host_stamp(5);
-        const int32_t seq = mailbox_next_seq();
-        XR_LAUNCH("publish", k_publish_all, dim3(1), dim3(64), 0, ctl, fc, csr->n_long.get(), mail, seq, cap, big_capacity);
-        if (ctl_cached) zero_scratch_done(1); // (the counters are zero again behind k_publish_all)
-        if (early) {
+        const PlaceBig place{n_big_dev, slot_face.get(), big_indptr.get(), big_indices.get(), big_data.get(), T, query->qo_perm(),
+                             query->qo_bbox(), query->qo_fxy(), query->qo_len(), query->m, tile, tile_key, fc, csr->indptr.get(),
+                             csr->indices.get(), csr->data.get(), csr->row_order.get(), cap, n_pending_dev};
+        // The tail.  Behind the join the big faces' rows lie complete in their own small CSR, and the list of long rows is final.
+        // An apply that can read them THERE (K = 1, xr_overlap_apply_dev) does not wait for their copy behind the regular rows:
+        // its launch leads with the blocks that make the copy (k_apply_tail1), one launch and one kernel boundary less between
+        // the assembly and the apply.  It stays BEHIND k_publish_all, which hands it n_big and the regular rows' entries with
+        // the gate (TailWord): the host's read-back and its enqueueing of the next build stay hidden behind the apply.
+        // (The apply in front of k_publish_all, on the control block itself, was measured: the host then learns the sizes
+        // one apply later and the device idles for its ~30 us of enqueueing, 0.469 -> 0.488 ms per step.)
+        const bool tail_fused = early && early->takes_tail && option(OPT_TAIL_FUSED) != 0;
+        auto enqueue_early = [&](const ApplyTail *tail) {
             // sizes unknown on the host yet: pessimistic flags (long rows possible, of any length) -- they only add blocks
             // that look at the device-side list of long rows and find it short or empty; results do not depend on them
             csr->nnz = 0;
             csr->has_long = true;
             csr->max_row_len = -1;
-            csr->apply_gated = true; // (the kernel looks at the gate k_publish_all has just set: a failed attempt is skipped)
+            csr->apply_gated = true; // (the kernel looks at the build's gate: a failed attempt is skipped)
+            csr->apply_tail = tail;
             early->fn(csr);
+            csr->apply_tail = nullptr;
             csr->apply_gated = false;
-        }
+        };
+        if (!tail_fused) XR_LAUNCH("place_big", k_place_big, dim3(TAIL_PLACE_BLOCKS), dim3(256), 0, place);
+        host_stamp(5);
+        const int32_t seq = mailbox_next_seq();
+        XR_LAUNCH("publish", k_publish_all, dim3(1), dim3(64), 0, ctl, fc, csr->n_long.get(), mail, seq, cap, big_capacity);
+        if (ctl_cached) zero_scratch_done(1); // (the counters are zero again behind k_publish_all)
+        const ApplyTail tail{place, csr->n_long.get()};
+        if (early) enqueue_early(tail_fused ? &tail : nullptr); // (gated by the word k_publish_all has just set)
         host_stamp(6);
         mailbox_wait_seq(seq);
         host_stamp(7);
@@ -1759,6 +1834,7 @@ int xr_overlap_apply_dev(xr_mesh *tree, xr_mesh *query, int relative, int method
     early.fn = [&](const xr_csr *c) { csr_apply_dev(c, method, percentile, source_dev, source_dtype, K, out_dev); };
     // one variable and a streaming reducer: the apply is one launch that needs no size on the host
     const bool can_early = K == 1 && method != XR_MODE && method != XR_PERCENTILE;
+    early.takes_tail = can_early;
     overlap(tree, query, relative != 0, csr.get(), can_early ? &early : nullptr);
     host_stamp(8);
     if (!early.done && K > 0) csr_apply_dev(csr.get(), method, percentile, source_dev, source_dtype, K, out_dev);

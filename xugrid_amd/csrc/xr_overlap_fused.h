@@ -33,35 +33,8 @@ namespace xr {
 static constexpr int FB = 256;            // faces (= threads) per block: the block granularity of k_search's queue stretches
 static constexpr int FWAVES = FB / 64;
 
-struct FusedCounters {                    // device words, zeroed before the launch
-    int32_t n_apply_long;                 // rows with more than XR_APPLY_LONG_ROW entries
-    int32_t error;                        // bit 0: clip buffer overflow, bit 2: CSR capacity
-    int32_t p_regular;                    // entries of all regular rows (k_assemble)
-    int32_t rows_regular;                 // regular rows
-    int32_t p_big;                        // entries of the big faces' rows (k_big_order)
-    int32_t pad0;                         // (unused)
-    int32_t max_row;                      // entries of the longest row (atomicMax)
-    int32_t pad2;
-};
-
-// ---- the words device and host share: ONE description, used by the kernels' launches, k_publish_all and overlap_tri ----
-// Control block of a fused build: CTL_WORDS device words, zero at rest (the engine's zero-at-rest scratch; k_publish_all
-// clears what the build raised), indexed by CtlWord.
-enum CtlWord : int {
-    CTL_REG_CURSOR = 0,     // pairs of the regular queue; the eight region cursors below count them, k_publish_all puts their sum here
-    CTL_BIG_CURSOR = 1,     // pairs in the big faces' queue (k_search_big)
-    CTL_N_BIG = 2,          // big faces (k_search)
-    CTL_N_PENDING = 3,      // big faces whose pairs did not fit their queue: > 0 makes the side-stream kernels skip, the host regrows
-    CTL_BIG_OVERFLOW = 4,   // clip overflows among the big pairs (reserved: they are reported through FusedCounters::error)
-    CTL_COUNTERS = 8,       // FusedCounters
-    CTL_LINE = 16,          // words [0, CTL_LINE) are one 64-byte stretch that k_publish_all fetches with one load per lane
-    CTL_REGION_CURSOR = 32, // cursors of the regular queue's eight regions (one per XCD), QCUR_STRIDE words = a 128-byte line apart
-    CTL_WORDS = CTL_REGION_CURSOR + 8 * QCUR_STRIDE
-};
-#define XR_CTL_COUNTER(field) (xr::CTL_COUNTERS + (int)(offsetof(xr::FusedCounters, field) / sizeof(int32_t))) // control word of a FusedCounters field
-static_assert(CTL_COUNTERS + sizeof(FusedCounters) / sizeof(int32_t) <= CTL_LINE && CTL_BIG_OVERFLOW < CTL_COUNTERS &&
-                  CTL_LINE <= CTL_REGION_CURSOR && CTL_LINE + 8 <= 64,
-              "the counters lie inside the line k_publish_all's one wave fetches, the region cursors behind it");
+// (FusedCounters, the control block's words -- CtlWord -- and the gate of an apply enqueued behind the build: xr_overlap_tail.h,
+// shared with the apply that takes the tail of the build into its own launch)
 // Mailbox record k_publish_all leaves for the host (pinned memory, engine().mailbox), indexed by MailSlot.
 enum MailSlot : int {
     MAIL_REG_PAIRS = 0,      // = CTL_REG_CURSOR ... the first five control words as they are
@@ -299,7 +272,7 @@ k_assemble(const double *__restrict__ q_bbox, const double *__restrict__ q_fxy, 
            const int32_t *__restrict__ cand_sid, const double *__restrict__ src_area, bool relative, MortonParams tile,
            int32_t *__restrict__ tile_key, FusedCounters *__restrict__ counters,
            int32_t *__restrict__ indptr, int32_t *__restrict__ indices, double *__restrict__ data, int32_t *__restrict__ row_order,
-           int32_t *__restrict__ apply_long_rows, int64_t csr_capacity, bool remap,
+           int64_t csr_capacity, bool remap,
            const int32_t *__restrict__ base_rows = nullptr, const int32_t *__restrict__ base_nnz = nullptr,
            const int32_t *__restrict__ blk_rows = nullptr, const int32_t *__restrict__ blk_surv = nullptr) {
     __shared__ int32_t sh_stage[SLOTS * FB];
@@ -397,10 +370,6 @@ k_assemble(const double *__restrict__ q_bbox, const double *__restrict__ q_fxy, 
             const int64_t mid = (t & ~(int64_t)(tile.n_run - 1)) + tile.n_run / 2;
             tile_key[r] = morton_key(tile, query_face_box_rt(q_bbox, q_fxy, q_len, q_m, mid < n_query ? mid : n_query - 1));
         }
-        if (my_nnz > XR_APPLY_LONG_ROW) {
-            apply_long_rows[atomicAdd(&counters->n_apply_long, 1)] = (int32_t)r;
-            atomicMax(&counters->max_row, my_nnz); // (long rows only: the apply asks whether any row exceeds its wave kernel)
-        }
     }
     bool overflow_cap = false;
     for (int i0 = tid; i0 < total; i0 += 4 * FB) {
@@ -438,47 +407,9 @@ k_assemble(const double *__restrict__ q_bbox, const double *__restrict__ q_fxy, 
 // Their order (by face id) is established inside k_search_big (slot_face), their offsets inside k_row_fill_long (scan_nnz
 // mode): the chain search_big -> clip -> row_fill_long is the critical path of the weight build, every launch less counts.
 
-// The finished rows of the big faces (ranked by k_row_fill_long into big_indices / big_data on the side stream) go
-// BEHIND the regular rows: stored row T - n_big + slot.  Grid-stride over rows and entries.
-__global__ void __launch_bounds__(256)
-k_place_big(const int32_t *__restrict__ n_big_dev, const int32_t *__restrict__ slot_face,
-            const int32_t *__restrict__ big_indptr, const int32_t *__restrict__ big_indices,
-            const double *__restrict__ big_data, int64_t n_query, const int32_t *__restrict__ q_perm,
-            const double *__restrict__ q_bbox, const double *__restrict__ q_fxy, const uint8_t *__restrict__ q_len, int q_m,
-            MortonParams tile, int32_t *__restrict__ tile_key,
-            FusedCounters *counters, int32_t *__restrict__ indptr, int32_t *__restrict__ indices,
-            double *__restrict__ data, int32_t *__restrict__ row_order, int32_t *__restrict__ apply_long_rows,
-            int64_t csr_capacity, const int32_t *__restrict__ skip_if) {
-    const int n_big = *n_big_dev;
-    if (n_big == 0 || *skip_if > 0) return;
-    const int64_t p_regular = counters->p_regular, t_reg = n_query - n_big;
-    const int64_t p_big = big_indptr[n_big];
-    if (p_regular + p_big > csr_capacity) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&counters->error, 4);
-        return;
-    }
-    const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
-    for (int64_t k = i0; k < n_big; k += stride) {
-        const int f = slot_face[k];
-        const int64_t r = t_reg + k;
-        const int n = big_indptr[k + 1] - big_indptr[k];
-        indptr[r] = (int32_t)(p_regular + big_indptr[k]);
-        row_order[r] = q_perm ? q_perm[f] : f;
-        if (tile_key) {
-            const int64_t mid = ((int64_t)f & ~(int64_t)(tile.n_run - 1)) + tile.n_run / 2;
-            tile_key[r] = morton_key(tile, query_face_box_rt(q_bbox, q_fxy, q_len, q_m, mid < n_query ? mid : n_query - 1));
-        }
-        if (n > XR_APPLY_LONG_ROW) {
-            apply_long_rows[atomicAdd(&counters->n_apply_long, 1)] = (int32_t)r;
-            atomicMax(&counters->max_row, n);
-        }
-    }
-    for (int64_t e = i0; e < p_big; e += stride) {
-        indices[p_regular + e] = big_indices[e];
-        data[p_regular + e] = big_data[e];
-    }
-    if (i0 == 0) indptr[n_query] = (int32_t)(p_regular + p_big);
-}
+// The finished rows of the big faces go BEHIND the regular ones (place_big_rows, xr_overlap_tail.h): as a launch of its own
+// wherever no K = 1 apply is enqueued behind the build -- that apply's launch takes these blocks in front of its own.
+__global__ void __launch_bounds__(256) k_place_big(PlaceBig p) { place_big_rows<false>(p, (int)blockIdx.x, (int)gridDim.x); }
 
 // sizes, error bits and the long-row count -> host mailbox / device word of the matrix (after everything else)
 // ... and clears all of them behind itself: the counter words are the engine's zero-at-rest scratch (the next xr_overlap
@@ -506,16 +437,14 @@ __global__ void k_publish_all(int32_t *c /* the control block (CtlWord) */, Fuse
     else if (t == XR_CTL_COUNTER(max_row)) slot = MAIL_MAX_ROW;
     if (slot >= 0) mail[slot] = w;
     if (region_lane) mail[MAIL_REGION_LEN + (t - CTL_LINE)] = cur;
-    if (t == XR_CTL_COUNTER(n_apply_long)) *n_apply_long_out = w;
+    if (t == XR_CTL_COUNTER(n_apply_long)) n_apply_long_out[TAIL_N_LONG] = w;
+    if (t == CTL_N_BIG) n_apply_long_out[TAIL_N_BIG] = w; // (for an apply that takes the place of k_place_big behind this kernel)
+    if (t == XR_CTL_COUNTER(p_regular)) n_apply_long_out[TAIL_P_REGULAR] = w;
     if (t == 0) {
-        // gate of an apply enqueued right behind this kernel (xr_overlap_apply_dev): open only if THIS attempt produced the
-        // final matrix -- the very conditions the host checks after its read-back (overlap_tri); a failed attempt leaves
-        // row pointers no kernel may follow
-        const int32_t c_reg = c_reg_sum, c_big = c[CTL_BIG_CURSOR], n_pending = c[CTL_N_PENDING], err = c[XR_CTL_COUNTER(error)],
-                      p_reg = c[XR_CTL_COUNTER(p_regular)], p_big = c[XR_CTL_COUNTER(p_big)];
-        const bool ok = c_reg >= 0 && c_big >= 0 && !(err & (1 | 4 | 8)) && n_pending == 0 && (int64_t)c_big <= big_capacity &&
-                        (int64_t)p_reg + p_big <= cap;
-        n_apply_long_out[1] = ok ? 1 : 0;
+        // gate of an apply enqueued right behind this kernel (xr_overlap_partial_dev; the apply of xr_overlap_apply_dev that runs
+        // IN FRONT of this kernel evaluates the same function itself): open only if THIS attempt produced the final matrix
+        const bool ok = fused_attempt_final(c, c_reg_sum, cap, big_capacity);
+        n_apply_long_out[TAIL_GATE] = ok ? 1 : 0;
     }
     __builtin_amdgcn_s_waitcnt(0); // (every load above has returned before the words are cleared)
     if (t < CTL_LINE) c[t] = 0;

@@ -1283,6 +1283,14 @@ class DeviceCSR(Handle):
         check(_lib.load().xr_csr_row_order(self._h, 0, _ptr(out)))
         return out
 
+    def long_rows(self):
+        """-> the stored rows of more than 32 entries as the builder listed them for the cooperative reducers (any order)"""
+        n = ctypes.c_int64()
+        check(_lib.load().xr_csr_long_rows(self._h, 0, None, ctypes.byref(n)))
+        out = np.empty(n.value, dtype=np.int64)
+        check(_lib.load().xr_csr_long_rows(self._h, n.value, _ptr(out), ctypes.byref(n)))
+        return out
+
     def download(self):
         """-> (data float64[nnz], indices intp[nnz], indptr intp[n+1])"""
         data = np.empty(self.nnz, dtype=np.float64)
