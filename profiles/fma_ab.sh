@@ -1,6 +1,6 @@
 #!/bin/bash
 # Run ON THE GPU BOX from the repository root:  bash profiles/fma_ab.sh <tag>
-# The price of bit-exactness: the search + clip translation unit built with -ffp-contract=fast (make -C xugrid_amd/csrc fma ->
+# The price of bit-exactness: the search + clip translation units built with -ffp-contract=fast (make -C xugrid_amd/csrc fma ->
 # libxugrid_amd_fma.so, an A/B artefact the product never loads) against the default -ffp-contract=off build: pair set and areas
 # against the CPU oracle at full size (1M -> 1M), kernel times (interleaved, 3 rounds), VALU instruction counts (one PMC pass each).
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/${1:-fma_ab}; mkdir -p $OUT

@@ -240,7 +240,7 @@ def test_overlap_fused_matches_general_chain(hip, monkeypatch, xr_option):
 
 def test_overlap_fused_pipeline_quads_and_mixed_meshes(hip, oracle, monkeypatch, xr_option):
     """Dense meshes of up to four nodes per face -- quadrilaterals, mixed triangle / quadrilateral meshes with -1 in the fourth slot
-    (the flexible-mesh case), a raster's quads against triangles -- take the one-round-trip pipeline of xr_overlap_fused.h with
+    (the flexible-mesh case), a raster's quads against triangles -- take the one-round-trip pipeline of xr_overlap_fused.hip with
     the register / LDS clip of k_clip_small inside the persistent queue kernel (round 5).  Every pair: the oracle's matrix bit for
     bit, and the identical CSR through the general kernel chain (XR_OVERLAP_FUSED=0); big faces (coarse targets), relative
     weights, a mixed mesh against itself."""

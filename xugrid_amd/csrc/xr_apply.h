@@ -3,6 +3,7 @@
 // separable weights).  Constants, a few host helpers, and the functions one of these units defines for the others.
 #pragma once
 #include "xr_objects.h"
+#include "xr_overlap_tail.h"
 
 namespace xr {
 
@@ -85,5 +86,12 @@ void ensure_tiled(const xr_csr *csr);                             // the row til
 int prepare_for_apply(const xr_csr *csr, int64_t K);              // row tiling + apply plan in front of a shared-scope apply
 // xr_apply.hip
 void ensure_plan(const xr_csr *csr);                              // the apply plan of the many-variable kernels (exclusive scope)
+// the apply of a finished matrix on the calling thread's launch stream (xr_apply.hip) and its partial states for the
+// source-sharded apply (xr_partial.hip).  ctx: the apply is enqueued behind a weight build the host has not confirmed yet (K = 1,
+// overlap_tri) -- it obeys the build's gate and may take the build's tail into its launch (ApplyContext, xr_overlap_tail.h)
+void csr_apply_dev(const xr_csr *csr, int method, double percentile, const void *src_dev, int dtype, int64_t K, double *out_dev,
+                   const ApplyContext *ctx = nullptr);
+void csr_partial_dev(const xr_csr *csr, int method, const void *src_dev, int dtype, int64_t K, double *out_dev, int rows_layout,
+                     const ApplyContext *ctx = nullptr);
 
 } // namespace xr

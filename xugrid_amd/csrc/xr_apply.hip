@@ -17,7 +17,6 @@
 #include <vector>
 
 #include "xr_apply.h"
-#include "xr_overlap_tail.h"
 #include "xr_reduce.h"
 #include "xr_prims.h"
 
@@ -1387,14 +1386,17 @@ static void launch_plan(const xr_csr *csr, const SRC *src, int64_t K, double *ou
 }
 
 template <int METHOD, typename SRC>
-static void launch_stream(const xr_csr *csr, const SRC *src, int64_t K, double *out) {
+static void launch_stream(const xr_csr *csr, const SRC *src, int64_t K, double *out, const ApplyContext *ctx) {
+    // (enqueued behind a weight build whose sizes the host has not read yet: the context's flags, not the matrix')
+    const bool has_long = ctx ? ctx->has_long : csr->has_long;
+    const int64_t max_row_len = ctx ? ctx->max_row_len : csr->max_row_len;
     // The long rows (hull slivers: a few hundred latency-bound rows).  With many variables they run on the side stream BESIDE
     // the short ones -- disjoint output rows (0.25 ms of the 1.9 ms at K = 256).  For one variable the fork / join events
     // cost more than the 30 us they could hide (0.069 -> 0.075 ms): there they follow apply_stream in line, which also
     // zeroes their queue counter (no memset launch), and the block-per-row kernel is skipped when the builder reported
     // that no row exceeds the wave kernel's reach.
     DevBuf<int32_t> huge;
-    if (csr->has_long) huge.alloc((size_t)(csr->nnz / APPLY_WAVE + 2));
+    if (has_long) huge.alloc((size_t)(csr->nnz / APPLY_WAVE + 2));
     auto launch_long_rows = [&](bool zeroed) {
         if (!zeroed) XR_HIP(hipMemsetAsync(huge.get(), 0, sizeof(int32_t), launch_stream()));
         if (K == 1) {
@@ -1412,7 +1414,7 @@ static void launch_stream(const xr_csr *csr, const SRC *src, int64_t K, double *
                       csr->indices.get(), csr->data.get(), row_order_of(csr), csr->long_rows.get(), csr->n_long.get(),
                       csr->n, csr->m, src, K, out, huge.get());
         }
-        if (csr->max_row_len >= 0 && csr->max_row_len <= APPLY_WAVE) return; // no row for the block kernel
+        if (max_row_len >= 0 && max_row_len <= APPLY_WAVE) return; // no row for the block kernel
         // rows beyond APPLY_WAVE entries, as queued by the wave kernel: one block each
         const unsigned gy = (unsigned)(K < 8 ? K : 8);
         dim3 grid((unsigned)engine().num_cu * (8 / gy), gy); // 8 blocks per CU; blocks past the count exit at once
@@ -1420,7 +1422,7 @@ static void launch_stream(const xr_csr *csr, const SRC *src, int64_t K, double *
                   csr->indices.get(), csr->data.get(), row_order_of(csr), huge.get() + 1, huge.get(),
                   csr->n, csr->m, src, K, out);
     };
-    const bool long_on_side = csr->has_long && K >= PLAN_KT;
+    const bool long_on_side = has_long && K >= PLAN_KT;
     const bool use_plan = K > 1 && K >= PLAN_KT && option(OPT_APPLY_PLAN) != 0; // (measurement / test switch)
     if (use_plan) { // (built once per matrix, on the main stream, in front of the fork)
         ensure_tiled(csr);
@@ -1434,7 +1436,7 @@ static void launch_stream(const xr_csr *csr, const SRC *src, int64_t K, double *
         if (csr->plan_n_unplanned <= 0) return;
         dim3 grid((unsigned)csr->plan_n_unplanned, div_up(K, 4));
         XR_LAUNCH("apply_direct", (k_apply_direct<METHOD, SRC, 4>), grid, dim3(AP_BLOCK), 0, csr->indptr.get(),
-                  csr->indices.get(), csr->data.get(), row_order_of(csr), csr->has_long, csr->n, csr->m, src, K, out,
+                  csr->indices.get(), csr->data.get(), row_order_of(csr), has_long, csr->n, csr->m, src, K, out,
                   csr->plan_unplanned.get());
     };
     // with a plan the side work is launched BEHIND the plan kernel but depends only on what precedes it (side_mark): the host
@@ -1447,20 +1449,20 @@ static void launch_stream(const xr_csr *csr, const SRC *src, int64_t K, double *
     }
     if (K == 1) {
         // one launch: long-row blocks in front, then one wave per 64 stored rows
-        const int n_long_blocks = csr->has_long ? engine().num_cu / 2 : 0;
-        const bool any_huge = csr->has_long && !(csr->max_row_len >= 0 && csr->max_row_len <= APPLY_WAVE);
+        const int n_long_blocks = has_long ? engine().num_cu / 2 : 0;
+        const bool any_huge = has_long && !(max_row_len >= 0 && max_row_len <= APPLY_WAVE);
         dim3 grid((unsigned)(div_up(csr->n, AP_BLOCK) + n_long_blocks), 1);
-        if (csr->apply_tail) {
+        if (ctx && ctx->tail) {
             // enqueued by the fused weight build in front of its place_big: this launch places the big rows itself
-            XR_REQUIRE(csr->apply_gated && n_long_blocks > 0 && row_order_of(csr) == csr->row_order.get() && !csr->has_col_perm,
+            XR_REQUIRE(ctx->gate && n_long_blocks > 0 && row_order_of(csr) == csr->row_order.get() && !csr->has_col_perm,
                        XR_ERR_INVALID, "xr_apply: the tail of a weight build needs its fresh matrix");
             grid.x += TAIL_PLACE_BLOCKS;
-            XR_LAUNCH("apply_rows1", (k_apply_tail1<METHOD, SRC>), grid, dim3(AP_BLOCK), 0, *csr->apply_tail, csr->long_rows.get(),
+            XR_LAUNCH("apply_rows1", (k_apply_tail1<METHOD, SRC>), grid, dim3(AP_BLOCK), 0, *ctx->tail, csr->long_rows.get(),
                       n_long_blocks, csr->n, csr->m, src, out);
         } else {
             XR_LAUNCH("apply_rows1", (k_apply_rows1<METHOD, SRC>), grid, dim3(AP_BLOCK), 0, csr->indptr.get(), csr->indices.get(),
                       csr->data.get(), row_order_of(csr), csr->long_rows.get(), csr->n_long.get(), n_long_blocks, any_huge,
-                      csr->n, csr->m, src, out, csr->apply_gated ? csr->n_long.get() + 1 : (const int32_t *)nullptr);
+                      csr->n, csr->m, src, out, ctx ? ctx->gate : (const int32_t *)nullptr);
         }
     } else {
         if (use_plan) {
@@ -1484,11 +1486,11 @@ static void launch_stream(const xr_csr *csr, const SRC *src, int64_t K, double *
             // a few variables: register-resident k-tiles, direct gathers, no LDS
             dim3 grid(div_up(csr->n, AP_BLOCK), div_up(K, KT));
             XR_LAUNCH("apply_direct", (k_apply_direct<METHOD, SRC, KT>), grid, dim3(AP_BLOCK), 0, csr->indptr.get(),
-                      csr->indices.get(), csr->data.get(), row_order_of(csr), csr->has_long, csr->n, csr->m, src, K,
+                      csr->indices.get(), csr->data.get(), row_order_of(csr), has_long, csr->n, csr->m, src, K,
                       out, (const int32_t *)nullptr);
         }
     }
-    if (csr->has_long && K > 1 && !long_on_side) launch_long_rows(false); // (a few variables: in line, behind the short rows)
+    if (has_long && K > 1 && !long_on_side) launch_long_rows(false); // (a few variables: in line, behind the short rows)
     if (long_on_side) side_join();
 }
 
@@ -1518,15 +1520,16 @@ static void launch_workspace(const xr_csr *csr, const SRC *src, int64_t K, doubl
 }
 
 template <typename SRC>
-static void apply_dispatch(const xr_csr *csr, int method, double p, const SRC *src, int64_t K, double *out) {
+static void apply_dispatch(const xr_csr *csr, int method, double p, const SRC *src, int64_t K, double *out, const ApplyContext *ctx) {
     if (csr->n == 0 || K == 0) return;
     // (Until round 4 many variables were walked in host-side groups of 128; since round 5 the many-variable kernel orders its
     // own work by groups of 64 variables -- k_apply_plan, L2-blocked order.)
     with_reducer(method, [&](auto m) {
         constexpr int METHOD = decltype(m)::value;
         if constexpr (streamed_reducer<METHOD>) {
-            launch_stream<METHOD, SRC>(csr, src, K, out);
+            launch_stream<METHOD, SRC>(csr, src, K, out, ctx);
         } else {
+            XR_REQUIRE(!ctx, XR_ERR_INVALID, "internal: a gated apply is a streaming reducer");
             if (METHOD == XR_PERCENTILE)
                 XR_REQUIRE(p >= 0.0 && p <= 100.0, XR_ERR_INVALID,
                            "percentile must be in the range [0, 100], received: %g", p);
@@ -1535,16 +1538,18 @@ static void apply_dispatch(const xr_csr *csr, int method, double p, const SRC *s
     });
 }
 
-static void apply_dev(const xr_csr *csr, int method, double p, const void *src, int dtype, int64_t K, double *out) {
+static void apply_dev(const xr_csr *csr, int method, double p, const void *src, int dtype, int64_t K, double *out,
+                      const ApplyContext *ctx = nullptr) {
     with_source_type(dtype, [&](auto tag) {
         using SRC = decltype(tag);
         DevBuf<char> permuted; // (goes back to the pool at return; the pool hands blocks out in stream order)
-        apply_dispatch<SRC>(csr, method, p, stored_source(csr, static_cast<const SRC *>(src), K, permuted), K, out);
+        apply_dispatch<SRC>(csr, method, p, stored_source(csr, static_cast<const SRC *>(src), K, permuted), K, out, ctx);
     });
 }
 
-void csr_apply_dev(const xr_csr *csr, int method, double percentile, const void *src_dev, int dtype, int64_t K, double *out_dev) {
-    apply_dev(csr, method, percentile, src_dev, dtype, K, out_dev);
+void csr_apply_dev(const xr_csr *csr, int method, double percentile, const void *src_dev, int dtype, int64_t K, double *out_dev,
+                   const ApplyContext *ctx) {
+    apply_dev(csr, method, percentile, src_dev, dtype, K, out_dev, ctx);
 }
 
 } // namespace xr

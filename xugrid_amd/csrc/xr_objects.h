@@ -114,10 +114,6 @@ struct xr_mesh {
 static constexpr int XR_APPLY_LONG_ROW = 32;
 static constexpr int XR_APPLY_WAVE_ROW = 2048;
 
-namespace xr {
-struct ApplyTail; // xr_overlap_tail.h
-}
-
 // Device-resident MatrixCSR (xugrid/core/sparse.py:81-137), int32 structure + float64 data.
 struct xr_csr {
     int64_t n = 0, m = 0, nnz = 0;
@@ -131,9 +127,8 @@ struct xr_csr {
     bool has_row_order = false;
     // stored rows with more than XR_APPLY_LONG_ROW entries (reduced by one wave or block each in the apply)
     xr::DevBuf<int32_t> long_rows; // [<= n]
-    xr::DevBuf<int32_t> n_long;    // [1] device-side count ([2] for matrices of the triangle pipeline: [1] = apply gate)
-    bool apply_gated = false;      // the K = 1 apply being enqueued must check n_long[1] (matrix not yet confirmed by the host)
-    const xr::ApplyTail *apply_tail = nullptr; // ... and takes the tail of that build into its launch (xr_overlap_tail.h; set around the enqueue only)
+    xr::DevBuf<int32_t> n_long;    // [1] device-side count (matrices of the fused build: TAIL_WORDS = 4 words, indexed by TailWord --
+                                   // the count, the gate of an apply enqueued behind the build, n_big, p_regular; xr_overlap_tail.h)
     int64_t max_row_len = -1;      // entries of the longest row if the builder reported it (-1: unknown)
     bool has_long = false;
     // Coarse Morton key per STORED row (tile of ~12 target extents).  Set by xr_overlap when the rows are kept
@@ -197,10 +192,6 @@ void mesh_build_index(xr_mesh *mesh);
 void flush_pending_points(); // launch the deferred source-side kernels of pending xr_points handles (xr_locate.hip)
 void flush_pending_points_of(const xr_mesh *mesh); // ... if one of them reads `mesh`, before its arrays are released
 void mesh_read_stats(xr_mesh *mesh, bool need_exact = false); // need_exact: statistics over ALL faces (sampled ones are redone)
-// the apply of a finished (or, K = 1, of a just-enqueued) matrix on the calling thread's launch stream (xr_apply.hip), and its
-// partial states for the source-sharded apply (xr_partial.hip)
-void csr_apply_dev(const xr_csr *csr, int method, double percentile, const void *src_dev, int dtype, int64_t K, double *out_dev);
-void csr_partial_dev(const xr_csr *csr, int method, const void *src_dev, int dtype, int64_t K, double *out_dev, int rows_layout);
 void mesh_centroids_dev(xr_mesh *mesh, double *cxy_dev);    // connectivity.centroids into device memory [n_face*2]
 std::shared_ptr<xr::DevBuf<double>> mesh_centroids_shared(xr_mesh *mesh); // ... computed once per mesh, shared with the callers
 // locate_points on device-resident points (xr_locate.hip); tolerance < 0: the mesh's default.  The mesh must have faces.  -> the tolerance used

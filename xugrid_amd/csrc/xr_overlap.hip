@@ -5,9 +5,9 @@
 // normalisation (:133-134) and MatrixCSR.from_triplet (xugrid/regrid/regridder.py:433-435,
 // xugrid/core/sparse.py:61-78).
 //
-// Two pipelines.  Triangle x triangle pairs (the benchmark) take overlap_tri() below: search -> persistent bit-mask clip
-// -> per-block scan -> assembly, big faces on a side stream, ONE host round trip (kernels in xr_overlap_fused.h,
-// xr_clip_tri.h).  Everything else takes the general chain (all on the engine stream):
+// Two pipelines.  Dense meshes of at most 4 nodes per face (triangle x triangle: the benchmark) take overlap_tri(),
+// xr_overlap_fused.hip: search -> persistent clip -> per-block scan -> assembly, big faces on a side stream, ONE host round
+// trip.  Everything else takes the general chain, overlap_general() in xr_overlap_general.hip (all on the engine stream):
 //   search         one thread per query (target) face walks the tree mesh's hierarchical grid and
 //                  parks the bbox-overlapping tree records in 16 LDS slots; the block reserves its
 //                  stretch of the candidate-pair queue with one atomic and writes it compacted
@@ -24,12 +24,11 @@
 // Query faces whose bbox spans many grid rows/records are searched by one block each
 // (k_search_big) instead of one thread.
 //
-// The clip arithmetic mirrors oracle/xr_oracle.c (clip_polygons / sh_polygon_area) operation
-// for operation; both are built with -ffp-contract=off, so areas agree bit for bit.
-#include "xr_objects.h"
-#include "xr_clip_tri.h"
-#include "xr_overlap_tail.h"
-#include "xr_prims.h"
+// THIS unit holds what both pipelines use -- k_search, k_search_big, k_row_fill_long and their launchers (declared in
+// xr_overlap.h), the dust threshold, the rows' tiling keys -- and the entry points.  Device code of the clips: xr_clip.h.
+#include "xr_overlap.h"
+#include "xr_apply.h"
+#include "xr_clip.h"
 
 namespace xr {
 
@@ -41,28 +40,9 @@ namespace xr {
 // of tests, so those faces are queued and handled by one block each (k_search_big).
 static constexpr int BIG_VISITS = 160; // records visited by one thread before it gives up
 
-__device__ __forceinline__ bool rec_hit(float4 b, float qx0, float qx1, float qy0, float qy1) {
-    return box_gap(b, qx0, qx1, qy0, qy1) < 0.0f;
-}
-
-// One traversal per query face: hits are parked in SLOTS LDS slots per face and counted; the block
-// then compacts them into its stretch of the candidate-pair queue.  Faces with more than SLOTS
-// hits, too many grid rows or too many visited records are "big" and go to the block-per-face
-// kernel instead.
-static constexpr int SLOTS = 16;
-static_assert(SLOTS <= XR_APPLY_LONG_ROW, "a regular row is never one of the apply's long rows: only k_row_fill_long lists");
 static constexpr int TILE_RUN = 16; // rows per run in the tiling hint (128-byte output stores per variable).  Measured, K = 256 on
                                     // the benchmark matrix: runs of 64 rows / tiles of 24 extents 2.10 ms, 16 / 12: 1.72 ms (a qhull-numbered
                                     // target: long runs of consecutive ids are not compact); a lattice-numbered pair 0.99 ms either way
-
-// XCD-aware block order (launch the grid rounded up to a multiple of 8): hardware block b runs on XCD b % 8; every
-// XCD gets a CONTIGUOUS range of logical blocks (= one spatial region of the Morton-ordered work list), so that the
-// lines shared by neighbouring blocks stay in one L2.  -> logical block (>= n_blocks: nothing to do)
-__device__ __forceinline__ int64_t xcd_block(int64_t n_blocks, bool remap) {
-    if (!remap) return blockIdx.x;
-    const int64_t per_xcd = (n_blocks + 7) >> 3;
-    return (int64_t)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-}
 
 // Level split: the walk only visits the grid levels that hold the bulk of the records.  The records of the upper
 // levels (a Delaunay hull's slivers: a few hundred of a million) are the TAIL of the record arrays (levels are
@@ -329,15 +309,6 @@ k_search(const double *__restrict__ q_bbox, const double *__restrict__ q_fxy, co
     }
 }
 
-// deposit one device word in the host mailbox (pinned memory)
-__global__ void k_publish(const int32_t *__restrict__ src, int32_t *dst, int32_t *src2, int32_t *dst2) {
-    if (threadIdx.x == 0) {
-        *dst = *src;
-        *dst2 = *src2;
-        *src2 = 0; // the counter is reused afterwards
-    }
-}
-
 // One block per big query face.  The face is scan-converted against the grid: for grid row cy of
 // level l only the cells under the polygon's x-extent inside the y-slab of that row are visited
 // (a thin hull sliver touches O(length) cells instead of the O(length^2) cells of its bbox).
@@ -550,508 +521,6 @@ k_search_big(const double *__restrict__ q_bbox, const double *__restrict__ q_fxy
             }
         }
         } // pass
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// What the reference does with a candidate pair BEFORE it clips (numba_celltree, restated in oracle/xr_oracle.c): the two
-// faces' exact boxes must overlap STRICTLY (boxes_intersect, :530) and the separating-axis test must not separate them
-// (sat_intersect, :757; touching counts as intersecting).  For faces that overlap properly both tests pass and the engine
-// skips them.  They matter where faces merely touch or are degenerate: there the clip returns slivers of 1e-20 ... 1e-36
-// that the reference never computes --
-//   * a mesh against itself (or a mesh sharing its nodes): neighbours across a corner have boxes that touch, not overlap
-//     (23 pairs of 60 394 on a 60k-face Delaunay mesh; the engine's float boxes are supersets and let them through),
-//   * zero-area and needle source faces: the clip of a target by a segment leaves rounding dust the SAT rejects.
-// A pair that fails either test has faces whose interiors are disjoint up to a penetration of a few ulp(coordinate), so the
-// clip's area for it is at most ~1e-15 * |coordinate| * perimeter.  overlap_dust_threshold() bounds that for EVERY pair of
-// the two meshes (largest coordinate x the smaller mesh's largest face extent, with a factor of four to spare); the clip kernels run the two
-// tests -- on the float64 vertices, fetched again -- only for the lanes whose area is positive and below it: a handful
-// per million pairs on unrelated meshes, the touching neighbours on related ones.  The tests' arithmetic is the oracle's
-// (order and orientation of the vertices do not enter: min / max of the same products).
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool pair_passes_box_and_sat(const double2 *__restrict__ a, int na, const double2 *__restrict__ b, int nb) {
-    double ax0 = INFINITY, ax1 = -INFINITY, ay0 = INFINITY, ay1 = -INFINITY, bx0 = INFINITY, bx1 = -INFINITY, by0 = INFINITY, by1 = -INFINITY;
-    for (int j = 0; j < na; j++) {
-        const double2 q = a[j];
-        ax0 = fmin(ax0, q.x), ax1 = fmax(ax1, q.x), ay0 = fmin(ay0, q.y), ay1 = fmax(ay1, q.y);
-    }
-    for (int j = 0; j < nb; j++) {
-        const double2 q = b[j];
-        bx0 = fmin(bx0, q.x), bx1 = fmax(bx1, q.x), by0 = fmin(by0, q.y), by1 = fmax(by1, q.y);
-    }
-    if (!(ax0 < bx1 && bx0 < ax1 && ay0 < by1 && by0 < ay1)) return false;
-    for (int pass = 0; pass < 2; pass++) {
-        const double2 *p = pass ? b : a;
-        const int np = pass ? nb : na;
-        for (int i = 0; i < np; i++) {
-            const double2 v0 = p[i], v1 = p[i + 1 < np ? i + 1 : 0];
-            const double nx = -(v1.y - v0.y), ny = v1.x - v0.x; // edge normal
-            if (nx == 0 && ny == 0) continue;
-            double amin = INFINITY, amax = -INFINITY, bmin = INFINITY, bmax = -INFINITY;
-            for (int j = 0; j < na; j++) {
-                const double2 q = a[j];
-                const double d = nx * q.x + ny * q.y;
-                amin = d < amin ? d : amin;
-                amax = d > amax ? d : amax;
-            }
-            for (int j = 0; j < nb; j++) {
-                const double2 q = b[j];
-                const double d = nx * q.x + ny * q.y;
-                bmin = d < bmin ? d : bmin;
-                bmax = d > bmax ? d : bmax;
-            }
-            if (amax < bmin || bmax < amin) return false;
-        }
-    }
-    return true;
-}
-// -> the pair's area after the reference's pre-clip tests: unchanged, or 0 for rounding dust of a pair they reject
-__device__ __forceinline__ double confirm_dust(double area, double dust, bool active, const double2 *__restrict__ a, int na,
-                                               const double2 *__restrict__ b, int nb) {
-    const bool suspicious = active && area > 0 && area <= dust;
-    if (__any(suspicious)) {
-        if (suspicious && !pair_passes_box_and_sat(a, na, b, nb)) area = 0.0;
-    }
-    return area;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Sutherland-Hodgman clip + fan area.  LDS: two polygon buffers per thread, [vertex][thread].
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool sh_inside(P2 p, P2 r, P2 U) { return U.x * (p.y - r.y) > U.y * (p.x - r.x); }
-
-__device__ __forceinline__ bool sh_intersection(P2 a, P2 V, P2 r, P2 N, P2 &out) {
-    const double wx = r.x - a.x, wy = r.y - a.y;
-    const double nw = N.x * wx + N.y * wy;
-    const double nv = N.x * V.x + N.y * V.y;
-    if (nv != 0) {
-        const double tt = nw / nv;
-        out.x = a.x + tt * V.x;
-        out.y = a.y + tt * V.y;
-        return true;
-    }
-    return false;
-}
-
-static constexpr double AREA_OVERFLOW = -1.0; // sentinel: polygon buffer too small, redo with MAXV=64
-
-// The end of every one-pair-per-thread clip kernel (every lane of the wave must get here): `area` is pair c's clipped area
-// or an overflow sentinel, t its target face (-1 in a lane without a pair), tf / sf the two faces' vertices.  Rounding dust is
-// confirmed, an overflow counted, the area stored, and the survivors are added to their rows' counts: the pairs of one target
-// face are contiguous, so a wave holds a few runs of equal t.
-__device__ __forceinline__ void clip_epilogue(double area, double dust, bool active, int64_t c, int t, const double2 *__restrict__ tf,
-                                              int nt, const double2 *__restrict__ sf, int ns, double *__restrict__ cand_area,
-                                              int32_t *__restrict__ overflow_count, int32_t *__restrict__ nnz_row) {
-    area = confirm_dust(area, dust, active, tf, nt, sf, ns);
-    if (active) {
-        if (area == TRI_AREA_OVERFLOW) {
-            area = AREA_OVERFLOW;
-            atomicAdd(overflow_count, 1);
-        }
-        cand_area[c] = area;
-    }
-    wave_run_add(t, active && area > 0, nnz_row);
-}
-
-template <int MAXV, int BLOCK>
-__global__ void __launch_bounds__(BLOCK)
-k_clip(const double *__restrict__ q_fxy, const uint8_t *__restrict__ q_len, const int32_t *__restrict__ q_off, int q_m,
-       const int32_t *__restrict__ q_perm, const double *__restrict__ s_fxy, const uint8_t *__restrict__ s_len, const int32_t *__restrict__ s_off,
-       int s_m, const int32_t *__restrict__ cand_tgt, const int32_t *__restrict__ cand_src, int64_t n_cand,
-       double *__restrict__ cand_area, bool redo_only, const int32_t *__restrict__ rec_face,
-       int32_t *__restrict__ cand_sid, int32_t *__restrict__ overflow_count, int32_t *__restrict__ nnz_row, double dust) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    double2 *sh = reinterpret_cast<double2 *>(smem);
-    const int64_t c = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    const bool active = c < n_cand && !(redo_only && cand_area[c] != AREA_OVERFLOW);
-    int t = -1, nt = 0, ns = 0;
-    const double2 *tf = nullptr;
-    const double *sf = nullptr;
-    double area = 0.0;
-    if (active) {
-    t = cand_tgt[c];
-    const int s = cand_src[c];
-    cand_sid[c] = rec_face[s];
-    nt = q_len[t], ns = s_len[s];
-    double2 *out = sh + threadIdx.x;                // out[j * BLOCK]
-    double2 *in = sh + MAXV * BLOCK + threadIdx.x;  // in[j * BLOCK]
-    tf = reinterpret_cast<const double2 *>(q_fxy) + face_vertex_base(q_off, t, q_m);
-    sf = s_fxy + 2 * face_vertex_base(s_off, s, s_m);
-    for (int j = 0; j < nt; j++) out[j * BLOCK] = tf[j];
-    int n_output = nt;
-    bool overflow = false;
-    P2 r = load_p2(sf, ns - 1);
-    bool empty = false;
-    for (int i = 0; i < ns; i++) {
-        const P2 sv = load_p2(sf, i);
-        const P2 U{sv.x - r.x, sv.y - r.y};
-        if (U.x == 0 && U.y == 0) continue;
-        const P2 N{-U.y, U.x};
-        const int length = n_output;
-        {
-            double2 *tmp = in;
-            in = out;
-            out = tmp;
-        }
-        n_output = 0;
-        const double2 a2 = in[(length - 1) * BLOCK];
-        P2 a{a2.x, a2.y};
-        bool a_inside = sh_inside(a, r, U);
-        for (int j = 0; j < length; j++) {
-            const double2 b2 = in[j * BLOCK];
-            const P2 b{b2.x, b2.y};
-            const P2 V{b.x - a.x, b.y - a.y};
-            if (V.x == 0 && V.y == 0) continue;
-            bool b_inside = sh_inside(b, r, U);
-            if (b_inside) {
-                if (!a_inside) {
-                    P2 pt;
-                    if (sh_intersection(a, V, r, N, pt)) {
-                        if (n_output < MAXV) out[n_output * BLOCK] = make_double2(pt.x, pt.y);
-                        else overflow = true;
-                        n_output++;
-                    }
-                }
-                if (n_output < MAXV) out[n_output * BLOCK] = b2;
-                else overflow = true;
-                n_output++;
-            } else if (a_inside) {
-                P2 pt;
-                if (sh_intersection(a, V, r, N, pt)) {
-                    if (n_output < MAXV) out[n_output * BLOCK] = make_double2(pt.x, pt.y);
-                    else overflow = true;
-                    n_output++;
-                } else {
-                    b_inside = true;
-                    if (n_output < MAXV) out[n_output * BLOCK] = b2;
-                    else overflow = true;
-                    n_output++;
-                }
-            }
-            a = b;
-            a_inside = b_inside;
-        }
-        if (overflow) break;
-        if (n_output < 3) {
-            empty = true;
-            break;
-        }
-        r = sv;
-    }
-    if (overflow) {
-        area = AREA_OVERFLOW;
-    } else if (!empty) {
-        // fan area from the first clipped vertex (local origin)
-        const double2 a2 = out[0];
-        const double2 b2 = out[BLOCK];
-        double ux = b2.x - a2.x, uy = b2.y - a2.y;
-        for (int i = 2; i < n_output; i++) {
-            const double2 c2 = out[i * BLOCK];
-            const double vx = a2.x - c2.x, vy = a2.y - c2.y;
-            area += fabs(ux * vy - uy * vx);
-            ux = vx;
-            uy = vy;
-        }
-        area = 0.5 * area;
-    }
-    } // active
-    clip_epilogue(area, dust, active, c, t, tf, nt, reinterpret_cast<const double2 *>(sf), ns, cand_area, overflow_count, nnz_row);
-}
-
-// Small-polygon variant (query + tree vertices <= MAXV, i.e. triangles / quads): the subject
-// polygon lives in REGISTERS (statically indexed, loops fully unrolled and predicated on the
-// current length); only the output polygon, whose write index is data dependent, is staged in
-// LDS ([vertex][thread]).  Half the LDS of the generic kernel -> twice the resident waves.
-// The arithmetic and its order are those of k_clip / the oracle.
-// -> the pair's area (AREA_OVERFLOW: more than MAXV vertices; before the confirmation of rounding dust); `out` = the
-// thread's LDS column, out[j * BLOCK]
-template <int MAXV, int BLOCK>
-__device__ __forceinline__ double clip_small_pair(const double2 *__restrict__ tf, int nt, const double *__restrict__ sf, int ns,
-                                                  double2 *out) {
-    double area = 0.0;
-    P2 in[MAXV];
-    P2 last{0.0, 0.0};
-#pragma unroll
-    for (int j = 0; j < MAXV; j++) {
-        if (j < nt) {
-            const double2 v = tf[j];
-            in[j] = P2{v.x, v.y};
-            last = in[j];
-        }
-    }
-    int length = nt;
-    bool overflow = false, empty = false;
-    P2 r = load_p2(sf, ns - 1);
-#pragma unroll
-    for (int i = 0; i < XR_MAX_FACE_NODES; i++) {
-        if (i >= ns) break;
-        const P2 sv = load_p2(sf, i);
-        const P2 U{sv.x - r.x, sv.y - r.y};
-        if (U.x == 0 && U.y == 0) continue;
-        const P2 N{-U.y, U.x};
-        int n_output = 0;
-        P2 a = last;
-        bool a_inside = sh_inside(a, r, U);
-#pragma unroll
-        for (int j = 0; j < MAXV; j++) {
-            if (j < length) {
-                // flat body: the only nested divergent region is the division of a crossing
-                const P2 b = in[j];
-                const P2 V{b.x - a.x, b.y - a.y};
-                const bool live = !(V.x == 0 && V.y == 0);
-                bool b_inside = sh_inside(b, r, U);
-                const bool cross = live && (b_inside != a_inside);
-                P2 pt{0.0, 0.0};
-                bool have_pt = false;
-                if (cross) have_pt = sh_intersection(a, V, r, N, pt);
-                // S-H emission: entering -> [pt] b ; inside -> b ; leaving -> pt, or (parallel-edge
-                // quirk) b, which then counts as inside
-                const bool quirk = cross && !b_inside && !have_pt;
-                if (cross && have_pt) {
-                    out[(n_output < MAXV ? n_output : MAXV) * BLOCK] = make_double2(pt.x, pt.y);
-                    n_output++;
-                    last = pt;
-                }
-                b_inside = b_inside || quirk;
-                if (live && b_inside) {
-                    out[(n_output < MAXV ? n_output : MAXV) * BLOCK] = make_double2(b.x, b.y);
-                    n_output++;
-                    last = b;
-                }
-                if (live) {
-                    a = b;
-                    a_inside = b_inside;
-                }
-            }
-        }
-        overflow = n_output > MAXV;
-        if (overflow) break;
-        if (n_output < 3) {
-            empty = true;
-            break;
-        }
-        length = n_output;
-#pragma unroll
-        for (int j = 0; j < MAXV; j++) {
-            if (j < length) {
-                const double2 v = out[j * BLOCK];
-                in[j] = P2{v.x, v.y};
-            }
-        }
-        r = sv;
-    }
-    if (overflow) return AREA_OVERFLOW;
-    if (!empty) {
-        const P2 a0 = in[0];
-        double ux = in[1].x - a0.x, uy = in[1].y - a0.y;
-#pragma unroll
-        for (int i = 2; i < MAXV; i++) {
-            if (i < length) {
-                const double vx = a0.x - in[i].x, vy = a0.y - in[i].y;
-                area += fabs(ux * vy - uy * vx);
-                ux = vx;
-                uy = vy;
-            }
-        }
-        area = 0.5 * area;
-    }
-    return area;
-}
-
-template <int MAXV, int BLOCK>
-__global__ void __launch_bounds__(BLOCK)
-k_clip_small(const double *__restrict__ q_fxy, const uint8_t *__restrict__ q_len, const int32_t *__restrict__ q_off, int q_m,
-             const int32_t *__restrict__ q_perm, const double *__restrict__ s_fxy,
-             const uint8_t *__restrict__ s_len, const int32_t *__restrict__ s_off, int s_m, const int32_t *__restrict__ cand_tgt,
-             const int32_t *__restrict__ cand_src, int64_t n_cand, double *__restrict__ cand_area,
-             const int32_t *__restrict__ rec_face, int32_t *__restrict__ cand_sid,
-             int32_t *__restrict__ overflow_count, int32_t *__restrict__ nnz_row, bool remap, double dust) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    double2 *out = reinterpret_cast<double2 *>(smem) + threadIdx.x; // out[j * BLOCK]
-    const int64_t n_blocks = (n_cand + BLOCK - 1) / BLOCK;
-    const int64_t lb = xcd_block(n_blocks, remap);
-    if (lb >= n_blocks) return;
-    const int64_t c = lb * BLOCK + threadIdx.x;
-    const bool active = c < n_cand;
-    int t = -1, nt = 0, ns = 0;
-    const double2 *tf = nullptr;
-    const double *sf = nullptr;
-    double area = 0.0;
-    if (active) {
-        t = cand_tgt[c];
-        const int s = cand_src[c];
-        cand_sid[c] = rec_face[s];
-        nt = q_len[t], ns = s_len[s];
-        tf = reinterpret_cast<const double2 *>(q_fxy) + face_vertex_base(q_off, t, q_m);
-        sf = s_fxy + 2 * face_vertex_base(s_off, s, s_m);
-        area = clip_small_pair<MAXV, BLOCK>(tf, nt, sf, ns, out);
-    }
-    clip_epilogue(area, dust, active, c, t, tf, nt, reinterpret_cast<const double2 *>(sf), ns, cand_area, overflow_count, nnz_row);
-}
-
-// A triangle source against targets of N0 = 3 or 4 vertices: the flag / compaction formulation of xr_clip_tri.h -- about half the
-// instructions of k_clip_small, same areas bit for bit.  N0 = 3: both meshes are pure triangle meshes.  N0 = 4: quadrilateral
-// (raster / quad mesh) targets -- the shape of the reference's unstructured -> raster regridding -- whose faces may be triangles
-// with a fill slot (q_len, read for N0 = 4 only); replaces k_clip_small<8> for this pair of shapes.
-template <int BLOCK, int N0>
-__global__ void __launch_bounds__(BLOCK)
-k_clip_tri(const double *__restrict__ q_fxy, const uint8_t *__restrict__ q_len, const double *__restrict__ s_fxy,
-           const int32_t *__restrict__ cand_tgt, const int32_t *__restrict__ cand_src, int64_t n_cand,
-           double *__restrict__ cand_area, const int32_t *__restrict__ rec_face, int32_t *__restrict__ cand_sid,
-           int32_t *__restrict__ overflow_count, int32_t *__restrict__ nnz_row, bool remap, double dust) {
-    static_assert(N0 == 3 || N0 == 4, "triangle or quadrilateral subject");
-    constexpr int MAXV = N0 == 3 ? TRI_MAXV : QUAD_MAXV;
-    // slots per lane: TRI_MAXV + 1, 112 bytes; QUAD_MAXV + 2, 144 bytes -- 128 would put the 16-byte accesses of all lanes on the
-    // same banks
-    constexpr int COL = N0 == 3 ? TRI_MAXV + 1 : QUAD_MAXV + 2;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    double2 *col = reinterpret_cast<double2 *>(smem) + threadIdx.x * COL;
-    __shared__ uint2 sh_lut[N0 == 3 ? TRI_LUT : QUAD_LUT];
-    const int64_t n_blocks = (n_cand + BLOCK - 1) / BLOCK;
-    const int64_t lb = xcd_block(n_blocks, remap);
-    if (lb >= n_blocks) return;
-    poly_lut_init<MAXV>(sh_lut);
-    __syncthreads();
-    const int64_t c = lb * BLOCK + threadIdx.x;
-    const bool active = c < n_cand;
-    int t = -1, n0 = 3, s = 0;
-    P2 tv[N0] = {}, sv[3] = {};
-    if (active) {
-        t = cand_tgt[c];
-        s = cand_src[c];
-        cand_sid[c] = rec_face[s];
-        if (N0 > 3) n0 = q_len[t];
-    }
-    const double2 *tf = reinterpret_cast<const double2 *>(q_fxy) + (int64_t)t * N0;
-    const double2 *sf = reinterpret_cast<const double2 *>(s_fxy) + (int64_t)s * 3;
-    if (active) {
-#pragma unroll
-        for (int j = 0; j < N0; j++) {
-            if (j < n0) {
-                const double2 a = tf[j];
-                tv[j] = P2{a.x, a.y};
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            const double2 b = sf[j];
-            sv[j] = P2{b.x, b.y};
-        }
-    }
-    const double area = poly_clip_area<MAXV, N0>(tv, n0, sv, col, sh_lut, active);
-    clip_epilogue(area, dust, active, c, t, tf, n0, sf, 3, cand_area, overflow_count, nnz_row);
-}
-
-// ---------------------------------------------------------------------------------------------
-// CSR assembly
-// ---------------------------------------------------------------------------------------------
-// recount of the survivors per row; only used after the rare clip-buffer overflow redo
-__global__ void __launch_bounds__(256) k_row_count(const int32_t *__restrict__ cand_off,
-                                                  const int32_t *__restrict__ cand_count,
-                                                  const double *__restrict__ cand_area, int64_t n_query,
-                                                  const int32_t *__restrict__ q_perm,
-                                                  int32_t *__restrict__ nnz_row) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= n_query) return;
-    int n = 0;
-    for (int c = cand_off[t]; c < cand_off[t] + cand_count[t]; c++) n += cand_area[c] > 0 ? 1 : 0;
-    nnz_row[t] = n;
-}
-
-static constexpr int ROW_SHORT = 24; // rows with more candidates go to the block-per-row kernel
-
-static constexpr int ROW_LDS = 3072; // short-row candidate entries one block can stage in LDS
-
-// One block = 256 consecutive query faces (query order).  The candidate entries of the block's
-// SHORT rows (<= ROW_SHORT candidates; long rows go to k_row_fill_long) are packed into LDS -- the
-// block's candidate segment is contiguous, so the loads are coalesced -- then the block works
-// ENTRY-parallel: each thread takes entries, ranks a survivor among the survivors of its row
-// (adjacent in LDS) and writes it to its final CSR position.  Rows are stored in QUERY order
-// (row r belongs to the caller's face q_perm[r], xr_csr::row_order).
-__global__ void __launch_bounds__(256)
-k_row_fill(const int32_t *__restrict__ cand_off, const int32_t *__restrict__ cand_count,
-           const int2 *__restrict__ block_seg, const uint8_t *__restrict__ is_big,
-           const int32_t *__restrict__ cand_tgt, const int32_t *__restrict__ cand_sid,
-           const double *__restrict__ cand_area, int64_t n_query,
-           const int32_t *__restrict__ indptr, const double *__restrict__ src_area, bool relative,
-           int32_t *__restrict__ indices, double *__restrict__ data, int32_t *__restrict__ long_rows,
-           int32_t *__restrict__ n_long, int32_t *__restrict__ apply_long_rows,
-           int32_t *__restrict__ n_apply_long, bool remap) {
-    __shared__ int32_t sh_src[ROW_LDS];  // tree face id of a survivor, INT_MAX for area <= 0
-    __shared__ uint16_t sh_row[ROW_LDS];
-    __shared__ int32_t sh_c0[256];   // first candidate of the row (global index)
-    __shared__ int32_t sh_lds[257];  // LDS offset of the row (short rows only), [256] = total
-    __shared__ int32_t sh_ptr[256];  // CSR offset of the row
-    __shared__ int32_t sh_wave[4];
-    const int64_t n_blocks = (n_query + 255) / 256;
-    const int64_t lb = xcd_block(n_blocks, remap);
-    if (lb >= n_blocks) return;
-    const int64_t t0 = lb * 256;
-    const int64_t t = t0 + threadIdx.x;
-    // the candidates of the block's rows that k_search wrote itself (all but its "big" faces) are one stretch
-    const int2 seg = block_seg[lb];
-    const int seg0 = seg.x, seg1 = seg.x + seg.y;
-    int c0 = 0, len = 0;
-    bool is_short = true; // packed here; everything else (long rows, and the "big" faces of the search, whose
-                          // candidates live elsewhere in the queue) goes to the block-per-row kernel
-    if (t < n_query) {
-        c0 = cand_off[t];
-        len = cand_count[t];
-        is_short = len <= ROW_SHORT && !is_big[t];
-        sh_ptr[threadIdx.x] = indptr[t];
-        if (!is_short) long_rows[atomicAdd(n_long, 1)] = (int32_t)t;
-        if (indptr[t + 1] - indptr[t] > XR_APPLY_LONG_ROW) apply_long_rows[atomicAdd(n_apply_long, 1)] = (int32_t)t;
-    }
-    const int slen = is_short ? len : 0;
-    sh_c0[threadIdx.x] = is_short ? c0 : -1;
-    // block exclusive scan of the short-row lengths
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int incl = wave_incl_scan(slen);
-    if (lane == 63) sh_wave[wave] = incl;
-    __syncthreads();
-    int woff = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-        if (w < wave) woff += sh_wave[w];
-        total += sh_wave[w];
-    }
-    sh_lds[threadIdx.x] = woff + incl - slen;
-    if (threadIdx.x == 0) sh_lds[256] = total;
-    __syncthreads();
-    if (total <= ROW_LDS) {
-        for (int j = seg0 + threadIdx.x; j < seg1; j += 256) {
-            const int row = cand_tgt[j] - (int)t0;
-            const int rc0 = sh_c0[row];
-            if (rc0 < 0) continue; // entry of a long row
-            const int k = sh_lds[row] + (j - rc0);
-            sh_src[k] = cand_area[j] > 0 ? cand_sid[j] : 0x7fffffff;
-            sh_row[k] = (uint16_t)row;
-        }
-        __syncthreads();
-        for (int k = threadIdx.x; k < total; k += 256) {
-            const int s = sh_src[k];
-            if (s == 0x7fffffff) continue;
-            const int row = sh_row[k];
-            const int a0 = sh_lds[row], a1 = row == 255 ? total : sh_lds[row + 1];
-            int rank = 0;
-            for (int i = a0; i < a1; i++) rank += sh_src[i] < s ? 1 : 0;
-            const double a = cand_area[sh_c0[row] + (k - a0)];
-            const int pos = sh_ptr[row] + rank;
-            indices[pos] = s;
-            data[pos] = relative ? a / src_area[s] : a;
-        }
-    } else if (t < n_query && is_short) {
-        // more short-row candidates than the LDS stage holds: rank straight from memory
-        const int base = indptr[t];
-        for (int i = c0; i < c0 + len; i++) {
-            const double a = cand_area[i];
-            if (!(a > 0)) continue;
-            const int s = cand_sid[i];
-            int rank = 0;
-            for (int j = c0; j < c0 + len; j++) rank += (cand_area[j] > 0 && cand_sid[j] < s) ? 1 : 0;
-            indices[base + rank] = s;
-            data[base + rank] = relative ? a / src_area[s] : a;
-        }
     }
 }
 
@@ -1300,17 +769,6 @@ k_row_fill_long(const int32_t *__restrict__ cand_off, const int32_t *__restrict_
     }
 }
 
-} // namespace xr
-#include "xr_overlap_fused.h"
-namespace xr {
-
-static bool debug_fused() { return (option(OPT_DEBUG) & 1) != 0; }
-// Which kernels take the XCD-aware block order (xcd_block): clip + search fetch 15 % fewer HBM bytes with it (PMC: clip
-// 161 -> 130 MB, search 56 -> 48 MB per launch) at an unchanged clip time and a 5 % shorter search; row_fill loses more on
-// the then interleaved queue than it gains.
-static constexpr bool REMAP_CLIP = true, REMAP_SEARCH = true, REMAP_ROW_FILL = false;
-static unsigned xcd_grid(int64_t n_blocks, bool remap) { return (unsigned)(remap ? (n_blocks + 7) / 8 * 8 : n_blocks); }
-
 // Upper bound, for every pair of faces of the two meshes, of the area the clip can return for a pair the reference's pre-clip
 // tests reject (pair_passes_box_and_sat).  Such a pair's true intersection is at most ~3 ulp(coordinate) deep (the SAT's
 // projections) and the clip's crossing points are off by a few ulp(coordinate) more: a sliver of width <= ~8 eps |coordinate|
@@ -1318,7 +776,7 @@ static unsigned xcd_grid(int64_t n_blocks, bool remap) { return (unsigned)(remap
 // times that (64 eps = 1.4e-14), M the largest coordinate magnitude, ext the smaller of the two meshes' largest face extents
 // (both statistics are on the host when the clip is launched; a sampled tree statistic is bounded by the domain).  The
 // smaller the threshold the fewer lanes fetch their vertices again: on the 1M benchmark 1e-12 M ext cost the clip 7 us.
-static double overlap_dust_threshold(const xr_mesh *tree, const xr_mesh *query) {
+double overlap_dust_threshold(const xr_mesh *tree, const xr_mesh *query) {
     double mag = 0.0, ext = INFINITY;
     for (const xr_mesh *m : {tree, query}) {
         const double *h = m->h_stats;
@@ -1328,71 +786,9 @@ static double overlap_dust_threshold(const xr_mesh *tree, const xr_mesh *query) 
     return option(OPT_DUST) == 0 ? 0.0 : 5.7e-14 * mag * ext; // (option "dust" = 0: measurement switch, no confirmation)
 }
 
-template <int MAXV, int BLOCK>
-static void launch_clip(const xr_mesh *tree, const xr_mesh *query, const int32_t *cand_tgt, const int32_t *cand_src,
-                        int64_t C, double *cand_area, bool redo_only, int32_t *cand_sid, int32_t *overflow_count,
-                        int32_t *nnz_row) {
-    constexpr size_t shmem = (size_t)2 * MAXV * BLOCK * sizeof(double2);
-    allow_dynamic_lds<&k_clip<MAXV, BLOCK>>(shmem);
-    XR_LAUNCH(MAXV == 8 ? "clip_v8" : (MAXV == 16 ? "clip_v16" : "clip_v64"), (k_clip<MAXV, BLOCK>),
-              dim3(div_up(C, BLOCK)), dim3(BLOCK), shmem, query->qo_fxy(), query->qo_len(), query->qo_off(), query->m,
-              query->qo_perm(), tree->rec_fxy.get(), tree->rec_len.get(), tree->record_off(), tree->m, cand_tgt, cand_src, C, cand_area,
-              redo_only, tree->rec_face.get(), cand_sid, overflow_count, nnz_row, overlap_dust_threshold(tree, query));
-}
-
-static void launch_clip_for(const xr_mesh *tree, const xr_mesh *query, const int32_t *cand_tgt, const int32_t *cand_src,
-                            int64_t C, double *cand_area, int32_t *cand_sid, int32_t *overflow_count,
-                            int32_t *nnz_row) {
-    const int vmax = query->m + tree->m;
-    if (vmax > 16) return launch_clip<64, 64>(tree, query, cand_tgt, cand_src, C, cand_area, false, cand_sid, overflow_count, nnz_row);
-    if (vmax > 8) return launch_clip<16, 128>(tree, query, cand_tgt, cand_src, C, cand_area, false, cand_sid, overflow_count, nnz_row);
-    constexpr int BLOCK = 256;
-    const bool remap = REMAP_CLIP;
-    const dim3 grid(xcd_grid(div_up(C, BLOCK), remap));
-    const double dust = overlap_dust_threshold(tree, query);
-    if (vmax <= 6) {
-        // triangle x triangle: the clipped polygon never has more than 6 vertices
-        constexpr int MAXV = 6;
-        const size_t shmem = (size_t)(MAXV + 1) * BLOCK * sizeof(double2); // + one trash row for clamped pushes
-        XR_LAUNCH("clip_tri", (k_clip_tri<BLOCK, 3>), grid, dim3(BLOCK), shmem, query->qo_fxy(), (const uint8_t *)nullptr,
-                  tree->rec_fxy.get(), cand_tgt, cand_src, C, cand_area, tree->rec_face.get(), cand_sid, overflow_count, nnz_row, remap,
-                  dust);
-    } else if (query->m == 4 && tree->m == 3 && option(OPT_CLIP_QUAD) != 0) {
-        // quadrilateral targets (a raster) x triangle source (option "clip_quad" = 0: the slot-loop kernel, test switch)
-        const size_t shmem = (size_t)(QUAD_MAXV + 2) * BLOCK * sizeof(double2);
-        XR_LAUNCH("clip_quad_tri", (k_clip_tri<BLOCK, 4>), grid, dim3(BLOCK), shmem,
-                  query->qo_fxy(), query->qo_len(), tree->rec_fxy.get(), cand_tgt, cand_src, C, cand_area, tree->rec_face.get(),
-                  cand_sid, overflow_count, nnz_row, remap, dust);
-    } else {
-        constexpr int MAXV = 8;
-        const size_t shmem = (size_t)(MAXV + 1) * BLOCK * sizeof(double2); // + one trash row for clamped pushes
-        XR_LAUNCH("clip_small", (k_clip_small<MAXV, BLOCK>), grid, dim3(BLOCK),
-                  shmem, query->qo_fxy(), query->qo_len(), query->qo_off(), query->m, query->qo_perm(), tree->rec_fxy.get(),
-                  tree->rec_len.get(), tree->record_off(), tree->m, cand_tgt, cand_src, C, cand_area, tree->rec_face.get(), cand_sid,
-                  overflow_count, nnz_row, remap, dust);
-    }
-}
-
-// ---- launches both pipelines share --------------------------------------------------------------------------------------
-// what the search leaves per target face and per block of 256 of them
-struct SearchLists {
-    DevBuf<int32_t> cand_count, cand_off, big_list, pending, nnz_row;
-    DevBuf<uint8_t> is_big;
-    DevBuf<int2> block_seg;
-    explicit SearchLists(int64_t T)
-        : cand_count((size_t)T), cand_off((size_t)T + 1), big_list((size_t)T), pending((size_t)T), nnz_row((size_t)T),
-          is_big((size_t)T), block_seg((size_t)div_up(T, 256)) {}
-};
-// the pair queue a kernel appends to
-struct PairQueue {
-    int32_t *tgt, *src, *cursor;
-    int64_t capacity; // (of one region where the queue is the fused pipeline's eight regions with a cursor each)
-};
-
-// k_search over every target face.  PACKED: the owner byte rides in the record id's top byte where the tree has at most
-// 2^24 faces.  blk_rows / blk_surv: the fused pipeline's per-block counts; its queue is then eight regions.
-static void launch_search(const xr_mesh *tree, const xr_mesh *query, const SearchLists &l, const PairQueue &q, int32_t *n_big,
-                          const MortonParams &tile, int32_t *tile_key, int32_t *blk_rows = nullptr, int32_t *blk_surv = nullptr) {
+// ---- launches both pipelines share (declared in xr_overlap.h) ------------------------------------------------------------
+void launch_search(const xr_mesh *tree, const xr_mesh *query, const SearchLists &l, const PairQueue &q, int32_t *n_big,
+                   const MortonParams &tile, int32_t *tile_key, int32_t *blk_rows, int32_t *blk_surv) {
     const int64_t T = query->n_face;
     const dim3 grid(xcd_grid(div_up(T, 256), REMAP_SEARCH));
     auto launch = [&](auto packed) {
@@ -1407,33 +803,24 @@ static void launch_search(const xr_mesh *tree, const xr_mesh *query, const Searc
     else launch(std::false_type());
 }
 
-// k_search_big<true>: the listed big faces, one block each, into `q`; faces that do not fit it are listed in l.pending
-static void launch_search_big(const xr_mesh *tree, const xr_mesh *query, const SearchLists &l, const PairQueue &q,
-                              const int32_t *n_big, int32_t *n_pending, int32_t *slot_face = nullptr) {
+void launch_search_big(const xr_mesh *tree, const xr_mesh *query, const SearchLists &l, const PairQueue &q, const int32_t *n_big,
+                       int32_t *n_pending, int32_t *slot_face) {
     XR_LAUNCH("search_big", k_search_big<true>, dim3(engine().num_cu * 8), dim3(256), sizeof(int32_t) * (size_t)BIG_STAGE,
               query->qo_bbox(), query->qo_fxy(), query->qo_len(), query->qo_off(), query->m, tree->grid, tree->cell_start.get(),
               tree->rec_bb.get(), tree->rec_face.get(), l.big_list.get(), n_big, l.cand_off.get(), l.cand_count.get(), q.tgt,
               q.src, q.cursor, q.capacity, l.pending.get(), n_pending, BIG_STAGE, slot_face);
 }
 
-// k_row_fill_long over one class of the listed rows: 0 every row; 1 the rows of at most ROW_BLOCK candidates (16 KB of LDS:
-// six blocks per CU, resident beside other kernels); 2 the longer ones (the bitmap: a CU per block).
-struct LongRows { // (the kernel's arguments of the same names)
-    const int32_t *cand_sid;
-    const double *cand_area;
-    const int32_t *indptr;
-    int32_t *indices;
-    double *data;
-    const int32_t *long_rows, *n_long;
-    int64_t row_base;
-    const int32_t *skip_if = nullptr, *scan_nnz = nullptr;
-    int32_t *scan_indptr = nullptr, *scan_total = nullptr;
-    int32_t *apply_long_rows = nullptr; // (scan_nnz mode) the apply's list of long rows, FusedCounters that count it, stored rows
-    FusedCounters *listed = nullptr;
-    int64_t n_stored = 0;
-};
-static void launch_row_fill_long(int row_class, const xr_mesh *tree, const SearchLists &l, const double *tree_area, bool relative,
-                                 const LongRows &r) {
+void launch_search_big_fill(const xr_mesh *tree, const xr_mesh *query, const SearchLists &l, const PairQueue &q,
+                            const int32_t *n_pending) {
+    XR_LAUNCH("search_big_fill", k_search_big<false>, dim3(engine().num_cu * 8), dim3(256), sizeof(int32_t), query->qo_bbox(),
+              query->qo_fxy(), query->qo_len(), query->qo_off(), query->m, tree->grid, tree->cell_start.get(), tree->rec_bb.get(),
+              tree->rec_face.get(), l.pending.get(), n_pending, l.cand_off.get(), l.cand_count.get(), q.tgt, q.src,
+              (int32_t *)nullptr, q.capacity, (int32_t *)nullptr, (int32_t *)nullptr, 0);
+}
+
+void launch_row_fill_long(int row_class, const xr_mesh *tree, const SearchLists &l, const double *tree_area, bool relative,
+                          const LongRows &r) {
     const bool light = row_class == 1;
     // (both classes' launches walk the whole list for its offsets; ONE of them, not the bitmap rows', lists for the apply)
     auto launch = [&](auto list) {
@@ -1445,204 +832,6 @@ static void launch_row_fill_long(int row_class, const xr_mesh *tree, const Searc
     };
     if (light && r.apply_long_rows && r.scan_nnz) launch(std::true_type());
     else launch(std::false_type());
-}
-
-// Triangle x triangle pairs (xr_overlap_fused.h): search -> persistent clip -> assembly with a look-back scan, the big
-// faces of the search (hull slivers ...) on a side stream, their rows stored behind the regular ones; ONE host round
-// trip at the very end (sizes + error bits).  -> false if the pair has to go through the general pipeline after all
-// (a clip that needs more than 6 vertices: floating-point degenerate input; or the look-back chain gave up).
-// An apply the caller wants right behind the weight build (xr_overlap_apply_dev).  The triangle pipeline enqueues it BEFORE
-// the host has read the sizes back -- the K = 1 apply kernel takes everything it needs from device memory -- so the one host
-// round trip of the build is hidden behind the apply instead of standing between the two.
-struct EarlyApply {
-    std::function<void(const xr_csr *)> fn;
-    bool takes_tail = false; // fn enqueues the K = 1 kernel that places the big rows itself (csr->apply_tail)
-    bool done = false;
-};
-
-static bool overlap_tri(xr_mesh *tree, xr_mesh *query, const double *tree_area, bool relative, xr_csr *csr,
-                        const MortonParams &tile, EarlyApply *early) {
-    const int64_t T = query->n_face;
-    hipStream_t st = launch_stream();
-    const int64_t n_blocks = div_up(T, FB);
-    const bool remap = REMAP_SEARCH;
-    const unsigned grid = xcd_grid(n_blocks, remap);
-    const int64_t margin_opt = option(OPT_QUEUE_MARGIN); // test hook: a tiny margin forces the regrow path
-    int64_t big_capacity = margin_opt > 0 ? margin_opt : ((int64_t)4 << 20);
-    // the regular pair queue: eight regions (one per XCD) of region_cap pairs each -- every block of 256 faces parks at most
-    // 256 x SLOTS pairs and an XCD takes ceil(n_blocks / 8) blocks
-    const int64_t region_cap = div_up(div_up(T, FB), 8) * FB * SLOTS;
-    const int64_t reg_capacity = 8 * region_cap;
-    int64_t per_face = 8; // CSR entries reserved per target face (+ the big queue); regrown if the matrix is denser
-    int32_t *mail = const_cast<int32_t *>(engine().mailbox);
-    // The control words (CtlWord, xr_overlap_fused.h) come from the engine's zero-at-rest scratch (k_publish_all clears them
-    // again after copying them to the mailbox); behind them, per block of 256 target faces: survivors (clip), regular faces
-    // (search) -- k_search clears its block's survivor count: no memset in front of the search.
-    DevBuf<int32_t> ctl_tail(2 * (size_t)grid), ctl_own;
-    int32_t *blk_surv = ctl_tail.get(), *blk_rows = blk_surv + grid;
-    DevBuf<int32_t> blk_base(2 * (size_t)grid); // first stored row / CSR base of every hardware block (k_assemble_scan)
-    // Row bases of the assembly: every assembly block sums the counts of the blocks in front of it itself (scan_mode 2) -- it reads
-    // b words in block b, O(blocks^2) L2 reads in total: fine for a few thousand blocks (1M faces: 62 MB), 6 GB for the 39k blocks
-    // of a 10M-face target (measured: 10M -> 10M 4.39 -> 4.89 ms) -- so from 8192 blocks on a one-block scan kernel between clip and
-    // assembly provides them (scan_mode 1, as until round 3).  (Until round 5 a decoupled look-back inside k_assemble was a third
-    // form, behind a switch; it lost in round 3 and is gone.)
-    const int scan_mode = grid <= 8192 ? 2 : 1;
-    SearchLists l(T);
-    DevBuf<int32_t> slot_face((size_t)T), big_indptr((size_t)T + 1);
-    // (measured and removed: the clip writing only its survivors, compacted in place over the queue -- the HBM bytes drop, but the
-    // assembly becomes three passes of dependent loads, 0.066 -> 0.087 ms, DESIGN_HISTORY.md round 3)
-    DevBuf<int32_t> cand_tgt((size_t)reg_capacity), cand_src((size_t)reg_capacity), cand_sid((size_t)reg_capacity);
-    DevBuf<double> cand_area((size_t)reg_capacity);
-    csr->n_long.alloc(TAIL_WORDS); // [0] rows of more than XR_APPLY_LONG_ROW entries, [1] gate of an apply enqueued behind the build ... (TailWord)
-    csr->row_order.alloc((size_t)T);
-    csr->has_row_order = true;
-    int32_t *const tile_key = csr->has_tile_key ? csr->tile_key.get() : nullptr;
-    // k_clip_tri_queue, persistent, over a pair queue.  KIND 0, triangle x triangle: the flag / compaction clip of xr_clip_tri.h;
-    // KIND 1, any other pair of dense meshes (<= 4 nodes per face: quadrilaterals, mixed meshes with fill values, a raster
-    // against triangles): the register / LDS clip of k_clip_small<8>, which also reads the faces' lengths.
-    // COUNT 2: the big faces' queue, survivors per face; COUNT 1: the regular queue's eight regions, survivors per block.
-    const bool tri_pair = tree->m == 3 && query->m == 3;
-    const double dust = overlap_dust_threshold(tree, query);
-    auto launch_clip_queue = [&](const char *name, auto count, int blocks_per_cu, const PairQueue &q, double *area, int32_t *sid,
-                                 int32_t *error, int32_t *nnz_row, const int32_t *skip_if, int32_t *blk_surv) {
-        constexpr int BLOCK = 256;
-        const int64_t capacity = count() == 1 ? -q.capacity : q.capacity; // (< 0: eight regions of that many pairs)
-        auto launch = [&](auto kind, size_t maxv, const uint8_t *q_len, const uint8_t *s_len) {
-            XR_LAUNCH(name, (k_clip_tri_queue<BLOCK, count(), kind()>), dim3(engine().num_cu * blocks_per_cu), dim3(BLOCK),
-                      (maxv + 1) * BLOCK * sizeof(double2), query->qo_fxy(), tree->rec_fxy.get(), tree->rec_face.get(), q.tgt, q.src,
-                      q.cursor, capacity, area, sid, error, nnz_row, skip_if, blk_surv, dust, q_len, s_len, query->m, tree->m);
-        };
-        if (tri_pair) launch(std::integral_constant<int, 0>(), TRI_MAXV, nullptr, nullptr);
-        else launch(std::integral_constant<int, 1>(), 8, query->qo_len(), tree->rec_len.get());
-    };
-    for (int attempt = 0;; attempt++) {
-        XR_REQUIRE(attempt < 8, XR_ERR_LIMIT, "xr_overlap: the weight matrix does not fit the device buffers");
-        const int64_t cap = per_face * T + big_capacity;
-        XR_REQUIRE(cap < ((int64_t)1 << 31), XR_ERR_LIMIT, "nnz exceeds the int32 range");
-        csr->indices.alloc((size_t)cap);
-        csr->data.alloc((size_t)cap);
-        csr->long_rows.alloc((size_t)(cap / XR_APPLY_LONG_ROW + 1));
-        DevBuf<int32_t> big_tgt((size_t)big_capacity), big_src((size_t)big_capacity), big_sid((size_t)big_capacity),
-            big_indices((size_t)big_capacity);
-        DevBuf<double> big_area((size_t)big_capacity), big_data((size_t)big_capacity);
-        int32_t *ctl = zero_scratch(1, CTL_WORDS);
-        const bool ctl_cached = ctl != nullptr;
-        if (!ctl_cached) {
-            ctl_own.alloc(CTL_WORDS);
-            ctl = ctl_own.get();
-            XR_HIP(hipMemsetAsync(ctl, 0, CTL_WORDS * sizeof(int32_t), st));
-        }
-        FusedCounters *fc = reinterpret_cast<FusedCounters *>(ctl + CTL_COUNTERS);
-        int32_t *const region_cursors = ctl + CTL_REGION_CURSOR, *const big_cursor = ctl + CTL_BIG_CURSOR,
-                       *const n_big_dev = ctl + CTL_N_BIG, *const n_pending_dev = ctl + CTL_N_PENDING;
-        const PairQueue reg_queue{cand_tgt.get(), cand_src.get(), region_cursors, region_cap},
-            big_queue{big_tgt.get(), big_src.get(), big_cursor, big_capacity};
-        launch_search(tree, query, l, reg_queue, n_big_dev, tile, nullptr, blk_rows, blk_surv);
-        {
-            // ---- side stream: everything about the big faces except their final placement
-            SideScope side;
-            launch_search_big(tree, query, l, big_queue, n_big_dev, n_pending_dev, slot_face.get());
-            // (pairs of a face that did not fit are missing: the error is seen at the end and everything is redone)
-            launch_clip_queue("clip_big", std::integral_constant<int, 2>(), 1, big_queue, big_area.get(), big_sid.get(),
-                              &fc->error, l.nnz_row.get(), n_pending_dev, nullptr);
-            // (rows in face order: ranked inside search_big; their offsets: scanned inside row_fill_long -- two launches less
-            // in what is the critical path of the whole weight build)
-            // Two launches: the rows of at most ROW_BLOCK candidates (all but a handful) with 16 KB of LDS per block -- a block
-            // per row, resident beside the clip and the assembly -- and the few longer ones with the bitmap (150 KB, a CU per
-            // block).  As ONE launch every block needed a whole CU: it could not start before the clip's blocks had left and
-            // then walked ~5 rows in turn -- 54-64 us, ending after the assembly (round-4 timeline).
-            // (round 6: the two launches are independent -- each scans the row lengths itself and fills only its own class of
-            // rows -- so the bitmap rows go to a SECOND side stream and run beside the light ones: the big faces' chain
-            // behind the clip is one launch shorter where it is the step's critical path, 0.506 -> 0.500 ms in an A/B)
-            const LongRows big_rows{big_sid.get(), big_area.get(), big_indptr.get(), big_indices.get(), big_data.get(), slot_face.get(),
-                                    n_big_dev, 0, n_pending_dev, l.nnz_row.get(), big_indptr.get(), &fc->p_big,
-                                    csr->long_rows.get(), fc, T};
-            SideForkScope fork;
-            launch_row_fill_long(2, tree, l, tree_area, relative, big_rows);
-            fork.end_launches();
-            launch_row_fill_long(1, tree, l, tree_area, relative, big_rows);
-        }
-        // Persistent blocks per CU: five fill the LDS and the register files (best for the clip alone).  The big faces' chain
-        // on the side stream then gets few wave slots while the clip runs; with its kernels at raised wave priority and only
-        // three launches long (search_big -> clip -> row_fill_long) it still ends about when k_assemble does: 3, 4 and 5
-        // blocks per CU all give the same step (0.635 ms) -- measured after the chain lost two launches; before, 3 was
-        // 4 % faster because the chain was the critical path.
-        // (KIND 1: k_clip_small's LDS columns are 36 KB per block, four persistent blocks per CU)
-        launch_clip_queue(tri_pair ? "clip_tri" : "clip_small", std::integral_constant<int, 1>(), tri_pair ? 5 : 4, reg_queue,
-                          cand_area.get(), cand_sid.get(), &fc->error, nullptr, nullptr, blk_surv);
-        if (scan_mode == 1)
-            XR_LAUNCH("assemble_scan", k_assemble_scan, dim3(1), dim3(1024), 0, blk_rows, blk_surv, (int64_t)n_blocks, (int)grid,
-                      remap, blk_base.get(), blk_base.get() + grid, fc, csr->indptr.get());
-        XR_LAUNCH("assemble", k_assemble, dim3(grid), dim3(FB), 0, query->qo_bbox(), query->qo_fxy(), query->qo_len(), query->m,
-                  query->qo_perm(), T, cand_tgt.get(), l.cand_off.get(), l.cand_count.get(), l.block_seg.get(), l.is_big.get(), cand_area.get(), cand_sid.get(),
-                  tree_area, relative, tile, tile_key, fc,
-                  csr->indptr.get(), csr->indices.get(), csr->data.get(), csr->row_order.get(), cap, remap, scan_mode == 1 ? blk_base.get() : (const int32_t *)nullptr,
-                  scan_mode == 1 ? blk_base.get() + grid : (const int32_t *)nullptr,
-                  scan_mode == 2 ? blk_rows : (const int32_t *)nullptr, scan_mode == 2 ? blk_surv : (const int32_t *)nullptr);
-        side_join();
-        const PlaceBig place{n_big_dev, slot_face.get(), big_indptr.get(), big_indices.get(), big_data.get(), T, query->qo_perm(),
-                             query->qo_bbox(), query->qo_fxy(), query->qo_len(), query->m, tile, tile_key, fc, csr->indptr.get(),
-                             csr->indices.get(), csr->data.get(), csr->row_order.get(), cap, n_pending_dev};
-        // The tail.  Behind the join the big faces' rows lie complete in their own small CSR, and the list of long rows is final.
-        // An apply that can read them THERE (K = 1, xr_overlap_apply_dev) does not wait for their copy behind the regular rows:
-        // its launch leads with the blocks that make the copy (k_apply_tail1), one launch and one kernel boundary less between
-        // the assembly and the apply.  It stays BEHIND k_publish_all, which hands it n_big and the regular rows' entries with
-        // the gate (TailWord): the host's read-back and its enqueueing of the next build stay hidden behind the apply.
-        // (The apply in front of k_publish_all, on the control block itself, was measured: the host then learns the sizes
-        // one apply later and the device idles for its ~30 us of enqueueing, 0.469 -> 0.488 ms per step.)
-        const bool tail_fused = early && early->takes_tail && option(OPT_TAIL_FUSED) != 0;
-        auto enqueue_early = [&](const ApplyTail *tail) {
-            // sizes unknown on the host yet: pessimistic flags (long rows possible, of any length) -- they only add blocks
-            // that look at the device-side list of long rows and find it short or empty; results do not depend on them
-            csr->nnz = 0;
-            csr->has_long = true;
-            csr->max_row_len = -1;
-            csr->apply_gated = true; // (the kernel looks at the build's gate: a failed attempt is skipped)
-            csr->apply_tail = tail;
-            early->fn(csr);
-            csr->apply_tail = nullptr;
-            csr->apply_gated = false;
-        };
-        if (!tail_fused) XR_LAUNCH("place_big", k_place_big, dim3(TAIL_PLACE_BLOCKS), dim3(256), 0, place);
-        host_stamp(5);
-        const int32_t seq = mailbox_next_seq();
-        XR_LAUNCH("publish", k_publish_all, dim3(1), dim3(64), 0, ctl, fc, csr->n_long.get(), mail, seq, cap, big_capacity);
-        if (ctl_cached) zero_scratch_done(1); // (the counters are zero again behind k_publish_all)
-        const ApplyTail tail{place, csr->n_long.get()};
-        if (early) enqueue_early(tail_fused ? &tail : nullptr); // (gated by the word k_publish_all has just set)
-        host_stamp(6);
-        mailbox_wait_seq(seq);
-        host_stamp(7);
-        const int32_t C_reg = mail[MAIL_REG_PAIRS], C_big = mail[MAIL_BIG_PAIRS], n_big = mail[MAIL_N_BIG], n_pending = mail[MAIL_N_PENDING];
-        const int32_t err = mail[MAIL_ERROR], rows_regular = mail[MAIL_ROWS_REGULAR], n_apply_long = mail[MAIL_N_APPLY_LONG],
-                      p_regular = mail[MAIL_P_REGULAR], p_big = mail[MAIL_P_BIG];
-        XR_REQUIRE(C_reg >= 0 && C_big >= 0, XR_ERR_LIMIT, "candidate pair count exceeds the int32 range");
-        if (debug_fused()) {
-            const int32_t *len = mail + MAIL_REGION_LEN;
-            fprintf(stderr, "[tri] T=%lld C=%d big: %d faces %d pairs (%d pending) p_regular=%d p_big=%d err=%d rows=%d long=%d regions %d %d %d %d %d %d %d %d of %lld\n",
-                    (long long)T, C_reg, n_big, C_big, n_pending, p_regular, p_big, err, rows_regular, n_apply_long, len[0], len[1], len[2],
-                    len[3], len[4], len[5], len[6], len[7], (long long)region_cap);
-        }
-        if (err & 1) {
-            csr->has_row_order = false; // (the general pipeline stores the rows in query order)
-            return false;
-        }
-        if (n_pending > 0 || C_big > big_capacity) { // some big faces needed more room than the margin
-            big_capacity = (int64_t)C_big + 1024;
-            continue;
-        }
-        if ((err & 4) || (int64_t)p_regular + p_big > cap) {
-            per_face *= 2;
-            continue;
-        }
-        XR_REQUIRE(rows_regular == T - n_big, XR_ERR_INVALID, "xr_overlap: internal row count mismatch");
-        tree->last_candidates = (int64_t)C_reg + C_big;
-        csr->nnz = (int64_t)p_regular + p_big;
-        csr->has_long = n_apply_long > 0; // rows of more than XR_APPLY_LONG_ROW entries (none: the apply skips their kernels)
-        csr->max_row_len = n_apply_long > 0 ? mail[MAIL_MAX_ROW] : XR_APPLY_LONG_ROW;
-        if (early) early->done = true; // (the apply enqueued in THIS attempt saw the final matrix)
-        return true;
-    }
 }
 
 // Rows kept in the caller's (coherent, but typically strip-like) numbering get a coarse Morton key each: tiles of 12-24 mean
@@ -1667,105 +856,6 @@ static MortonParams tile_key_params(const xr_mesh *query, xr_csr *csr) {
     csr->tile_key_range = (int64_t)1 << (2 * bits);
     csr->has_tile_key = bits > 0;
     return tile;
-}
-
-// The general kernel chain (the head of this file), all on the engine stream: two host round trips, rows in query order.
-static void overlap_general(xr_mesh *tree, xr_mesh *query, const double *tree_area, bool relative, xr_csr *csr,
-                            const MortonParams &tile) {
-    const int64_t T = query->n_face;
-    hipStream_t st = launch_stream();
-    DevBuf<int32_t> counters(GEN_WORDS); // (GenWord, xr_overlap_fused.h)
-    auto word = [&](GenWord w) { return counters.get() + w; };
-    XR_HIP(hipMemsetAsync(counters.get(), 0, sizeof(int32_t) * GEN_WORDS, st));
-    // --- candidate search.  k_search appends the candidates of its 256 faces to the pair queue itself (one
-    // atomic reservation per block); the few "big" faces are counted, reserve their stretch, and are filled by
-    // the block-per-face kernels.  The queue is sized for the regular faces (at most SLOTS candidates each) plus
-    // a margin for the big ones; if the big faces need more, it is regrown before they are filled (rare).
-    SearchLists l(T);
-    const int64_t margin_opt = option(OPT_QUEUE_MARGIN); // test hook: a tiny margin forces the regrow path
-    int64_t capacity = T * SLOTS + (margin_opt > 0 ? margin_opt : ((int64_t)4 << 20));
-    XR_REQUIRE(capacity < ((int64_t)1 << 31), XR_ERR_LIMIT, "candidate pair queue exceeds the int32 range");
-    DevBuf<int32_t> cand_tgt((size_t)capacity), cand_src((size_t)capacity);
-    const PairQueue queue{cand_tgt.get(), cand_src.get(), word(GEN_QUEUE_CURSOR), capacity};
-    launch_search(tree, query, l, queue, word(GEN_N_BIG), tile, csr->has_tile_key ? csr->tile_key.get() : nullptr);
-    launch_search_big(tree, query, l, queue, word(GEN_N_BIG), word(GEN_N_PENDING));
-    // queue length and number of big faces still to be filled -> host
-    int32_t *mail = const_cast<int32_t *>(engine().mailbox);
-    XR_LAUNCH("publish", k_publish, dim3(1), dim3(64), 0, word(GEN_QUEUE_CURSOR), mail + GMAIL_PAIRS, word(GEN_N_PENDING),
-              mail + GMAIL_N_PENDING);
-    mailbox_wait();
-    const int32_t C32 = mail[GMAIL_PAIRS], n_pending = mail[GMAIL_N_PENDING];
-    XR_REQUIRE(C32 >= 0, XR_ERR_LIMIT, "candidate pair count exceeds the int32 range");
-    const int64_t C = C32;
-    tree->last_candidates = C;
-    if (n_pending > 0) {
-        // some big faces need more room than the margin: move what is there to a larger queue, then fill them
-        DevBuf<int32_t> bigger_tgt((size_t)C), bigger_src((size_t)C);
-        XR_HIP(hipMemcpyAsync(bigger_tgt.get(), cand_tgt.get(), sizeof(int32_t) * (size_t)capacity, hipMemcpyDeviceToDevice, st));
-        XR_HIP(hipMemcpyAsync(bigger_src.get(), cand_src.get(), sizeof(int32_t) * (size_t)capacity, hipMemcpyDeviceToDevice, st));
-        stream_sync();
-        cand_tgt = std::move(bigger_tgt);
-        cand_src = std::move(bigger_src);
-        capacity = C;
-        h2d(word(GEN_N_PENDING), &n_pending, sizeof(int32_t)); // (k_publish zeroed the device copy)
-        XR_LAUNCH("search_big_fill", k_search_big<false>, dim3(engine().num_cu * 8), dim3(256), sizeof(int32_t), query->qo_bbox(),
-                  query->qo_fxy(), query->qo_len(), query->qo_off(), query->m, tree->grid, tree->cell_start.get(), tree->rec_bb.get(),
-                  tree->rec_face.get(), l.pending.get(), word(GEN_N_PENDING), l.cand_off.get(), l.cand_count.get(), cand_tgt.get(),
-                  cand_src.get(), (int32_t *)nullptr, capacity, (int32_t *)nullptr, (int32_t *)nullptr, 0);
-        XR_HIP(hipMemsetAsync(word(GEN_N_PENDING), 0, sizeof(int32_t), st));
-    }
-    // (the word of GEN_N_PENDING is zero again: from here on it is GEN_N_LONG_ROWS)
-    DevBuf<int32_t> cand_sid((size_t)C);
-    DevBuf<double> cand_area((size_t)C);
-    if (C > 0) {
-        // --- clip (+ per-row survivor counts)
-        launch_clip_for(tree, query, cand_tgt.get(), cand_src.get(), C, cand_area.get(), cand_sid.get(), word(GEN_CLIP_OVERFLOW),
-                        l.nnz_row.get());
-    }
-    // --- rows
-    // P is needed on the host anyway; the overflow counter travels in the same mailbox round trip
-    exclusive_scan_i32(l.nnz_row.get(), csr->indptr.get(), T, mail + GMAIL_NNZ, word(GEN_CLIP_OVERFLOW), mail + GMAIL_CLIP_OVERFLOW);
-    mailbox_wait();
-    int32_t nnz = mail[GMAIL_NNZ];
-    if (mail[GMAIL_CLIP_OVERFLOW] > 0) {
-        // polygon buffer overflow in the small-MAXV kernel (floating-point degenerate pairs):
-        // redo those pairs with the oracle's buffer size, then recount every row.
-        XR_HIP(hipMemsetAsync(word(GEN_CLIP_OVERFLOW), 0, sizeof(int32_t), st));
-        XR_HIP(hipMemsetAsync(l.nnz_row.get(), 0, sizeof(int32_t) * (size_t)T, st));
-        launch_clip<64, 64>(tree, query, cand_tgt.get(), cand_src.get(), C, cand_area.get(), true, cand_sid.get(),
-                            word(GEN_CLIP_OVERFLOW), l.nnz_row.get());
-        XR_LAUNCH("row_recount", k_row_count, dim3(div_up(T, 256)), dim3(256), 0, l.cand_off.get(), l.cand_count.get(),
-                  cand_area.get(), T, query->qo_perm(), l.nnz_row.get());
-        exclusive_scan_i32(l.nnz_row.get(), csr->indptr.get(), T);
-        nnz = read_scalar(csr->indptr.get() + T);
-    }
-    XR_REQUIRE(nnz >= 0, XR_ERR_LIMIT, "nnz exceeds the int32 range");
-    const int64_t P = nnz;
-    csr->nnz = P;
-    csr->indices.alloc((size_t)P);
-    csr->data.alloc((size_t)P);
-    // rows are best processed in the query mesh's spatial order (apply kernels)
-    if (query->qo_perm()) {
-        csr->row_order.alloc((size_t)T);
-        XR_HIP(hipMemcpyAsync(csr->row_order.get(), query->qo_perm(), sizeof(int32_t) * (size_t)T,
-                              hipMemcpyDeviceToDevice, st));
-        csr->has_row_order = true;
-    }
-    if (P > 0) {
-        DevBuf<int32_t> long_rows((size_t)T);
-        csr->long_rows.alloc((size_t)(P / XR_APPLY_LONG_ROW + 1));
-        csr->n_long.alloc(1);
-        csr->has_long = true;
-        XR_HIP(hipMemsetAsync(csr->n_long.get(), 0, sizeof(int32_t), st));
-        const bool remap = REMAP_ROW_FILL;
-        XR_LAUNCH("row_fill", k_row_fill, dim3(xcd_grid(div_up(T, 256), remap)), dim3(256), 0, l.cand_off.get(), l.cand_count.get(),
-                  l.block_seg.get(), l.is_big.get(), cand_tgt.get(), cand_sid.get(), cand_area.get(), T, csr->indptr.get(), tree_area, relative,
-                  csr->indices.get(), csr->data.get(), long_rows.get(), word(GEN_N_LONG_ROWS), csr->long_rows.get(),
-                  csr->n_long.get(), remap);
-        launch_row_fill_long(0, tree, l, tree_area, relative,
-                             LongRows{cand_sid.get(), cand_area.get(), csr->indptr.get(), csr->indices.get(), csr->data.get(),
-                                      long_rows.get(), word(GEN_N_LONG_ROWS), -1});
-    }
 }
 
 static void overlap(xr_mesh *tree, xr_mesh *query, bool relative, xr_csr *csr, EarlyApply *early = nullptr) {
@@ -1797,7 +887,7 @@ static void overlap(xr_mesh *tree, xr_mesh *query, bool relative, xr_csr *csr, E
         return;
     }
     const MortonParams tile = tile_key_params(query, csr);
-    // dense meshes of at most 4 nodes per face: the single-round-trip pipeline of xr_overlap_fused.h (option "overlap_fused"
+    // dense meshes of at most 4 nodes per face: the single-round-trip pipeline of xr_overlap_fused.hip (option "overlap_fused"
     // = 0: test / measurement switch back to the general kernel chain)
     const bool fused = option(OPT_OVERLAP_FUSED) != 0 && tree->m <= DENSE_MAX_NODES && query->m <= DENSE_MAX_NODES &&
                        (T + 8 * FB) * SLOTS < ((int64_t)1 << 31);
@@ -1831,7 +921,7 @@ int xr_overlap_apply_dev(xr_mesh *tree, xr_mesh *query, int relative, int method
     host_stamp(0);
     Building<xr_csr> csr(OnFailure::WaitFirst);
     EarlyApply early;
-    early.fn = [&](const xr_csr *c) { csr_apply_dev(c, method, percentile, source_dev, source_dtype, K, out_dev); };
+    early.fn = [&](const xr_csr *c, const ApplyContext *ctx) { csr_apply_dev(c, method, percentile, source_dev, source_dtype, K, out_dev, ctx); };
     // one variable and a streaming reducer: the apply is one launch that needs no size on the host
     const bool can_early = K == 1 && method != XR_MODE && method != XR_PERCENTILE;
     early.takes_tail = can_early;
@@ -1856,7 +946,7 @@ int xr_overlap_partial_dev(xr_mesh *tree, xr_mesh *query, int relative, int meth
     XR_REQUIRE(K < 65536, XR_ERR_LIMIT, "xr_overlap_partial_dev: at most 65535 variables per call");
     Building<xr_csr> csr(OnFailure::WaitFirst);
     EarlyApply early;
-    early.fn = [&](const xr_csr *c) { csr_partial_dev(c, method, source_dev, source_dtype, K, out_dev, rows_layout); };
+    early.fn = [&](const xr_csr *c, const ApplyContext *ctx) { csr_partial_dev(c, method, source_dev, source_dtype, K, out_dev, rows_layout, ctx); };
     const bool can_early = K == 1; // (one variable: the wave-window kernel needs no size on the host)
     overlap(tree, query, relative != 0, csr.get(), can_early ? &early : nullptr);
     if (!early.done && K > 0) csr_partial_dev(csr.get(), method, source_dev, source_dtype, K, out_dev, rows_layout);

@@ -1,5 +1,6 @@
-// xr_overlap_fused.h -- triangle x triangle pairs without the host in the loop (included by xr_overlap.hip; reference
-// seam: CellTree2d.intersect_faces + weights /= area + MatrixCSR.from_triplet, xugrid/regrid/unstructured.py:109-135,
+// xr_overlap_fused.hip -- dense meshes of at most 4 nodes per face without the host in the loop: the fused pipeline of the
+// weight construction, its kernels and its host side, overlap_tri (the other two units: xr_overlap.hip, xr_overlap_general.hip;
+// reference seam: CellTree2d.intersect_faces + weights /= area + MatrixCSR.from_triplet, xugrid/regrid/unstructured.py:109-135,
 // xugrid/regrid/regridder.py:433-435).
 //
 // The general kernel chain search -> [host: C] -> clip (+ row counts by global atomics) -> scan (2 launches) -> [host: nnz]
@@ -26,15 +27,13 @@
 // clip rounds per block make every generation of resident blocks last as long as its slowest member); rows of the
 // assembly placed by ONE returning 64-bit atomic per block instead of the look-back: 4000 atomics on one address cost
 // 30 us (and a "last block done" counter another 27 us).
-#pragma once
+#include "xr_overlap.h"
+#include "xr_clip.h"
 
 namespace xr {
 
-static constexpr int FB = 256;            // faces (= threads) per block: the block granularity of k_search's queue stretches
-static constexpr int FWAVES = FB / 64;
-
-// (FusedCounters, the control block's words -- CtlWord -- and the gate of an apply enqueued behind the build: xr_overlap_tail.h,
-// shared with the apply that takes the tail of the build into its own launch)
+// (FusedCounters, the control block's words -- CtlWord --, the verdict on an attempt and the gate of an apply enqueued behind the
+// build: xr_overlap_tail.h, shared with the apply that takes the tail of the build into its own launch; FB, SLOTS: xr_overlap.h)
 // Mailbox record k_publish_all leaves for the host (pinned memory, engine().mailbox), indexed by MailSlot.
 enum MailSlot : int {
     MAIL_REG_PAIRS = 0,      // = CTL_REG_CURSOR ... the first five control words as they are
@@ -53,17 +52,6 @@ enum MailSlot : int {
 };
 static_assert(MAIL_BIG_OVERFLOW - MAIL_REG_PAIRS == CTL_BIG_OVERFLOW - CTL_REG_CURSOR && MAIL_FUSED_SLOTS <= MAIL_SEQ_SLOT,
               "the first control words map to the first mailbox slots one to one");
-
-// The general chain (overlap_general) keeps four device words and uses four mailbox slots of its own.
-enum GenWord : int {
-    GEN_CLIP_OVERFLOW = 0, // pairs whose clipped polygon did not fit the small buffer (redone with the oracle's size)
-    GEN_N_PENDING = 1,     // big faces that did not fit the queue; k_publish hands it to the host and zeroes it ...
-    GEN_N_LONG_ROWS = 1,   // ... so that the same word then counts the rows k_row_fill leaves to k_row_fill_long
-    GEN_N_BIG = 2,         // big faces (k_search)
-    GEN_QUEUE_CURSOR = 3,  // pairs in the queue
-    GEN_WORDS = 4
-};
-enum GenMailSlot : int { GMAIL_PAIRS = 0, GMAIL_NNZ = 1, GMAIL_CLIP_OVERFLOW = 2, GMAIL_N_PENDING = 3 };
 
 // Persistent triangle x triangle clip over the regular pair queue: the number of pairs is read from device memory
 // (the search's queue cursor), so the launch needs no host round trip; every block walks chunks of 256 pairs.  Chunks are dealt so that every XCD works on one contiguous eighth of the queue (the order
@@ -86,7 +74,7 @@ k_clip_tri_queue(const double *__restrict__ q_fxy, const double *__restrict__ re
                  int32_t *__restrict__ nnz_row /* optional: survivors per target face, counted by atomics */,
                  const int32_t *__restrict__ skip_if /* optional: nothing is done when this device word is > 0 */,
                  int32_t *__restrict__ blk_surv = nullptr /* optional: survivors per BLOCK of 256 target faces (k_assemble_scan) */,
-                 double dust = 0.0 /* areas up to this are confirmed by the reference's pre-clip tests (xr_overlap.hip: confirm_dust) */,
+                 double dust = 0.0 /* areas up to this are confirmed by the reference's pre-clip tests (xr_clip.h: confirm_dust) */,
                  const uint8_t *__restrict__ q_len = nullptr, const uint8_t *__restrict__ s_len = nullptr, int q_m = 3, int s_m = 3) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int CS = 1; // (stride between a lane's slots)
@@ -441,10 +429,11 @@ __global__ void k_publish_all(int32_t *c /* the control block (CtlWord) */, Fuse
     if (t == CTL_N_BIG) n_apply_long_out[TAIL_N_BIG] = w; // (for an apply that takes the place of k_place_big behind this kernel)
     if (t == XR_CTL_COUNTER(p_regular)) n_apply_long_out[TAIL_P_REGULAR] = w;
     if (t == 0) {
-        // gate of an apply enqueued right behind this kernel (xr_overlap_partial_dev; the apply of xr_overlap_apply_dev that runs
-        // IN FRONT of this kernel evaluates the same function itself): open only if THIS attempt produced the final matrix
-        const bool ok = fused_attempt_final(c, c_reg_sum, cap, big_capacity);
-        n_apply_long_out[TAIL_GATE] = ok ? 1 : 0;
+        // gate of an apply enqueued right behind this kernel: open only if THIS attempt produced the final matrix -- the
+        // verdict the host reaches from the mailbox with the same function (fused_outcome, xr_overlap_tail.h)
+        const FusedOutcome verdict = fused_outcome(c_reg_sum, c[CTL_BIG_CURSOR], c[CTL_N_PENDING], c[XR_CTL_COUNTER(error)],
+                                                   c[XR_CTL_COUNTER(p_regular)], c[XR_CTL_COUNTER(p_big)], cap, big_capacity);
+        n_apply_long_out[TAIL_GATE] = verdict == FUSED_FINAL ? 1 : 0;
     }
     __builtin_amdgcn_s_waitcnt(0); // (every load above has returned before the words are cleared)
     if (t < CTL_LINE) c[t] = 0;
@@ -454,6 +443,265 @@ __global__ void k_publish_all(int32_t *c /* the control block (CtlWord) */, Fuse
     // release covers the stores of all its lanes)
     __threadfence_system();
     if (t == 0) __hip_atomic_store(&mail[MAIL_SEQ_SLOT], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+static bool debug_fused() { return (option(OPT_DEBUG) & 1) != 0; }
+
+// ---- the host side ------------------------------------------------------------------------------------------------------
+// overlap_tri() enqueues one ATTEMPT at the matrix -- sized for per_face entries per target face and big_capacity pairs of
+// the big faces -- reads the mailbox once, and decides with fused_outcome (xr_overlap_tail.h), the function k_publish_all
+// set the gate with.  The stages of an attempt are the functions below, in the order the loop of overlap_tri calls them.
+
+// What one build is given, the sizes that follow from it, and the buffers that survive its attempts.
+struct FusedBuild {
+    xr_mesh *const tree, *const query;
+    const double *const tree_area;
+    const bool relative;
+    xr_csr *const csr;
+    const MortonParams &tile;
+    int32_t *const tile_key;
+    const int64_t T = query->n_face, n_blocks = div_up(T, FB);
+    const bool remap = REMAP_SEARCH;
+    const unsigned grid = xcd_grid(n_blocks, remap);
+    // the regular pair queue: eight regions (one per XCD) of region_cap pairs each -- every block of 256 faces parks at most
+    // 256 x SLOTS pairs and an XCD takes ceil(n_blocks / 8) blocks
+    const int64_t region_cap = div_up(div_up(T, FB), 8) * FB * SLOTS;
+    const int64_t reg_capacity = 8 * region_cap;
+    // Row bases of the assembly: every assembly block sums the counts of the blocks in front of it itself (scan_mode 2) -- it reads
+    // b words in block b, O(blocks^2) L2 reads in total: fine for a few thousand blocks (1M faces: 62 MB), 6 GB for the 39k blocks
+    // of a 10M-face target (measured: 10M -> 10M 4.39 -> 4.89 ms) -- so from 8192 blocks on a one-block scan kernel between clip and
+    // assembly provides them (scan_mode 1, as until round 3).  (Until round 5 a decoupled look-back inside k_assemble was a third
+    // form, behind a switch; it lost in round 3 and is gone.)
+    const int scan_mode = grid <= 8192 ? 2 : 1;
+    // (launch_clip_queue) KIND 0, triangle x triangle; KIND 1, any other pair of dense meshes
+    const bool tri_pair = tree->m == 3 && query->m == 3;
+    const double dust = overlap_dust_threshold(tree, query);
+    // Behind the control words (CtlWord, xr_overlap_tail.h), per block of 256 target faces: survivors (clip), regular faces
+    // (search) -- k_search clears its block's survivor count: no memset in front of the search.
+    DevBuf<int32_t> ctl_tail{2 * (size_t)grid}, ctl_own; // (ctl_own: the control words, where the engine's scratch is taken)
+    int32_t *const blk_surv = ctl_tail.get(), *const blk_rows = blk_surv + grid;
+    DevBuf<int32_t> blk_base{2 * (size_t)grid}; // first stored row / CSR base of every hardware block (k_assemble_scan)
+    SearchLists l{T};
+    DevBuf<int32_t> slot_face{(size_t)T}, big_indptr{(size_t)T + 1};
+    // (measured and removed: the clip writing only its survivors, compacted in place over the queue -- the HBM bytes drop, but the
+    // assembly becomes three passes of dependent loads, 0.066 -> 0.087 ms, DESIGN_HISTORY.md round 3)
+    DevBuf<int32_t> cand_tgt{(size_t)reg_capacity}, cand_src{(size_t)reg_capacity}, cand_sid{(size_t)reg_capacity};
+    DevBuf<double> cand_area{(size_t)reg_capacity};
+};
+
+// What one attempt allocates for its capacities, and the control block it runs on.
+struct FusedAttempt {
+    int64_t cap = 0, big_capacity = 0; // entries the CSR / pairs the big faces' queue have room for
+    DevBuf<int32_t> big_tgt, big_src, big_sid, big_indices;
+    DevBuf<double> big_area, big_data;
+    // The control words (CtlWord) come from the engine's zero-at-rest scratch (k_publish_all clears them again after copying
+    // them to the mailbox)
+    int32_t *ctl = nullptr;
+    bool ctl_cached = false;
+    FusedCounters *fc = nullptr;
+    int32_t *n_big_dev = nullptr, *n_pending_dev = nullptr;
+    PairQueue reg_queue{}, big_queue{};
+};
+
+// what k_publish_all left in the mailbox (MailSlot)
+struct FusedMail {
+    int32_t c_reg, c_big, n_big, n_pending, err, rows_regular, n_apply_long, p_regular, p_big, max_row;
+};
+
+// k_clip_tri_queue, persistent, over a pair queue.  KIND 0, triangle x triangle: the flag / compaction clip of xr_clip_tri.h;
+// KIND 1, any other pair of dense meshes (<= 4 nodes per face: quadrilaterals, mixed meshes with fill values, a raster
+// against triangles): the register / LDS clip of k_clip_small<8>, which also reads the faces' lengths.
+// COUNT 2: the big faces' queue, survivors per face; COUNT 1: the regular queue's eight regions, survivors per block.
+template <int COUNT>
+static void launch_clip_queue(const FusedBuild &b, const char *name, int blocks_per_cu, const PairQueue &q, double *area,
+                              int32_t *sid, int32_t *error, int32_t *nnz_row, const int32_t *skip_if, int32_t *blk_surv) {
+    constexpr int BLOCK = 256;
+    const int64_t capacity = COUNT == 1 ? -q.capacity : q.capacity; // (< 0: eight regions of that many pairs)
+    auto launch = [&](auto kind, size_t maxv, const uint8_t *q_len, const uint8_t *s_len) {
+        XR_LAUNCH(name, (k_clip_tri_queue<BLOCK, COUNT, kind()>), dim3(engine().num_cu * blocks_per_cu), dim3(BLOCK),
+                  (maxv + 1) * BLOCK * sizeof(double2), b.query->qo_fxy(), b.tree->rec_fxy.get(), b.tree->rec_face.get(), q.tgt, q.src,
+                  q.cursor, capacity, area, sid, error, nnz_row, skip_if, blk_surv, b.dust, q_len, s_len, b.query->m, b.tree->m);
+    };
+    if (b.tri_pair) launch(std::integral_constant<int, 0>(), TRI_MAXV, nullptr, nullptr);
+    else launch(std::integral_constant<int, 1>(), 8, b.query->qo_len(), b.tree->rec_len.get());
+}
+
+// (1) the matrix and the big faces' buffers sized for this attempt's capacities; a control block that is zero
+static void attempt_allocate(FusedBuild &b, FusedAttempt &a, int64_t per_face, int64_t big_capacity) {
+    a.big_capacity = big_capacity;
+    a.cap = per_face * b.T + big_capacity;
+    XR_REQUIRE(a.cap < ((int64_t)1 << 31), XR_ERR_LIMIT, "nnz exceeds the int32 range");
+    b.csr->indices.alloc((size_t)a.cap);
+    b.csr->data.alloc((size_t)a.cap);
+    b.csr->long_rows.alloc((size_t)(a.cap / XR_APPLY_LONG_ROW + 1));
+    for (DevBuf<int32_t> *buf : {&a.big_tgt, &a.big_src, &a.big_sid, &a.big_indices}) buf->alloc((size_t)big_capacity);
+    a.big_area.alloc((size_t)big_capacity);
+    a.big_data.alloc((size_t)big_capacity);
+    a.ctl = zero_scratch(1, CTL_WORDS);
+    a.ctl_cached = a.ctl != nullptr;
+    if (!a.ctl_cached) {
+        b.ctl_own.alloc(CTL_WORDS);
+        a.ctl = b.ctl_own.get();
+        XR_HIP(hipMemsetAsync(a.ctl, 0, CTL_WORDS * sizeof(int32_t), launch_stream()));
+    }
+    a.fc = reinterpret_cast<FusedCounters *>(a.ctl + CTL_COUNTERS);
+    a.n_big_dev = a.ctl + CTL_N_BIG;
+    a.n_pending_dev = a.ctl + CTL_N_PENDING;
+    a.reg_queue = PairQueue{b.cand_tgt.get(), b.cand_src.get(), a.ctl + CTL_REGION_CURSOR, b.region_cap};
+    a.big_queue = PairQueue{a.big_tgt.get(), a.big_src.get(), a.ctl + CTL_BIG_CURSOR, big_capacity};
+}
+
+// (2) the search: regular faces into the eight regions of the regular queue, big faces listed
+static void enqueue_search(const FusedBuild &b, const FusedAttempt &a) {
+    launch_search(b.tree, b.query, b.l, a.reg_queue, a.n_big_dev, b.tile, nullptr, b.blk_rows, b.blk_surv);
+}
+
+// (3) side streams: everything about the big faces except their final placement
+static void enqueue_big_chain(const FusedBuild &b, const FusedAttempt &a) {
+    SideScope side;
+    launch_search_big(b.tree, b.query, b.l, a.big_queue, a.n_big_dev, a.n_pending_dev, b.slot_face.get());
+    // (pairs of a face that did not fit are missing: the error is seen at the end and everything is redone)
+    launch_clip_queue<2>(b, "clip_big", 1, a.big_queue, a.big_area.get(), a.big_sid.get(), &a.fc->error, b.l.nnz_row.get(),
+                         a.n_pending_dev, nullptr);
+    // (rows in face order: ranked inside search_big; their offsets: scanned inside row_fill_long -- two launches less
+    // in what is the critical path of the whole weight build)
+    // Two launches: the rows of at most ROW_BLOCK candidates (all but a handful) with 16 KB of LDS per block -- a block
+    // per row, resident beside the clip and the assembly -- and the few longer ones with the bitmap (150 KB, a CU per
+    // block).  As ONE launch every block needed a whole CU: it could not start before the clip's blocks had left and
+    // then walked ~5 rows in turn -- 54-64 us, ending after the assembly (round-4 timeline).
+    // (round 6: the two launches are independent -- each scans the row lengths itself and fills only its own class of
+    // rows -- so the bitmap rows go to a SECOND side stream and run beside the light ones: the big faces' chain
+    // behind the clip is one launch shorter where it is the step's critical path, 0.506 -> 0.500 ms in an A/B)
+    const LongRows big_rows{a.big_sid.get(), a.big_area.get(), b.big_indptr.get(), a.big_indices.get(), a.big_data.get(),
+                            b.slot_face.get(), a.n_big_dev, 0, a.n_pending_dev, b.l.nnz_row.get(), b.big_indptr.get(), &a.fc->p_big,
+                            b.csr->long_rows.get(), a.fc, b.T};
+    SideForkScope fork;
+    launch_row_fill_long(2, b.tree, b.l, b.tree_area, b.relative, big_rows);
+    fork.end_launches();
+    launch_row_fill_long(1, b.tree, b.l, b.tree_area, b.relative, big_rows);
+}
+
+// (4) main stream: the persistent clip over the regular queue, then the assembly of the regular rows
+static void enqueue_regular(const FusedBuild &b, const FusedAttempt &a) {
+    // Persistent blocks per CU: five fill the LDS and the register files (best for the clip alone).  The big faces' chain
+    // on the side stream then gets few wave slots while the clip runs; with its kernels at raised wave priority and only
+    // three launches long (search_big -> clip -> row_fill_long) it still ends about when k_assemble does: 3, 4 and 5
+    // blocks per CU all give the same step (0.635 ms) -- measured after the chain lost two launches; before, 3 was
+    // 4 % faster because the chain was the critical path.
+    // (KIND 1: k_clip_small's LDS columns are 36 KB per block, four persistent blocks per CU)
+    launch_clip_queue<1>(b, b.tri_pair ? "clip_tri" : "clip_small", b.tri_pair ? 5 : 4, a.reg_queue, b.cand_area.get(),
+                         b.cand_sid.get(), &a.fc->error, nullptr, nullptr, b.blk_surv);
+    const xr_mesh *query = b.query;
+    xr_csr *csr = b.csr;
+    const unsigned grid = b.grid;
+    if (b.scan_mode == 1)
+        XR_LAUNCH("assemble_scan", k_assemble_scan, dim3(1), dim3(1024), 0, b.blk_rows, b.blk_surv, (int64_t)b.n_blocks, (int)grid,
+                  b.remap, b.blk_base.get(), b.blk_base.get() + grid, a.fc, csr->indptr.get());
+    XR_LAUNCH("assemble", k_assemble, dim3(grid), dim3(FB), 0, query->qo_bbox(), query->qo_fxy(), query->qo_len(), query->m,
+              query->qo_perm(), b.T, b.cand_tgt.get(), b.l.cand_off.get(), b.l.cand_count.get(), b.l.block_seg.get(), b.l.is_big.get(),
+              b.cand_area.get(), b.cand_sid.get(), b.tree_area, b.relative, b.tile, b.tile_key, a.fc, csr->indptr.get(),
+              csr->indices.get(), csr->data.get(), csr->row_order.get(), a.cap, b.remap,
+              b.scan_mode == 1 ? b.blk_base.get() : (const int32_t *)nullptr,
+              b.scan_mode == 1 ? b.blk_base.get() + grid : (const int32_t *)nullptr,
+              b.scan_mode == 2 ? b.blk_rows : (const int32_t *)nullptr, b.scan_mode == 2 ? b.blk_surv : (const int32_t *)nullptr);
+}
+
+// (5) The tail.  Behind the join the big faces' rows lie complete in their own small CSR, and the list of long rows is final.
+// An apply that can read them THERE (K = 1, xr_overlap_apply_dev) does not wait for their copy behind the regular rows:
+// its launch leads with the blocks that make the copy (k_apply_tail1), one launch and one kernel boundary less between
+// the assembly and the apply.  It stays BEHIND k_publish_all, which hands it n_big and the regular rows' entries with
+// the gate (TailWord): the host's read-back and its enqueueing of the next build stay hidden behind the apply.
+// (The apply in front of k_publish_all, on the control block itself, was measured: the host then learns the sizes
+// one apply later and the device idles for its ~30 us of enqueueing, 0.469 -> 0.488 ms per step.)
+// -> what places the big rows: k_place_big here (!tail_fused), or the apply's launch
+static PlaceBig enqueue_tail(const FusedBuild &b, const FusedAttempt &a, bool tail_fused) {
+    side_join();
+    const xr_mesh *query = b.query;
+    xr_csr *csr = b.csr;
+    const PlaceBig place{a.n_big_dev, b.slot_face.get(), b.big_indptr.get(), a.big_indices.get(), a.big_data.get(), b.T,
+                         query->qo_perm(), query->qo_bbox(), query->qo_fxy(), query->qo_len(), query->m, b.tile, b.tile_key, a.fc,
+                         csr->indptr.get(), csr->indices.get(), csr->data.get(), csr->row_order.get(), a.cap, a.n_pending_dev};
+    if (!tail_fused) XR_LAUNCH("place_big", k_place_big, dim3(TAIL_PLACE_BLOCKS), dim3(256), 0, place);
+    return place;
+}
+
+// (6) publish -- sizes and error bits to the mailbox, the gate and the tail's words to the matrix, the control block zero
+// again -- then the early apply, gated by the word k_publish_all has just set.  -> the sequence number the mailbox will show
+static int32_t enqueue_publish_and_apply(const FusedBuild &b, const FusedAttempt &a, const PlaceBig &place, bool tail_fused,
+                                         EarlyApply *early) {
+    host_stamp(5);
+    const int32_t seq = mailbox_next_seq();
+    XR_LAUNCH("publish", k_publish_all, dim3(1), dim3(64), 0, a.ctl, a.fc, b.csr->n_long.get(), const_cast<int32_t *>(engine().mailbox),
+              seq, a.cap, a.big_capacity);
+    if (a.ctl_cached) zero_scratch_done(1); // (the counters are zero again behind k_publish_all)
+    if (early) {
+        const ApplyTail tail{place, b.csr->n_long.get()};
+        const ApplyContext ctx{b.csr->n_long.get() + TAIL_GATE, tail_fused ? &tail : nullptr};
+        early->fn(b.csr, &ctx);
+    }
+    host_stamp(6);
+    return seq;
+}
+
+// (7) the one host round trip of the build
+static FusedMail read_back(int32_t seq) {
+    mailbox_wait_seq(seq);
+    host_stamp(7);
+    const int32_t *mail = const_cast<const int32_t *>(engine().mailbox);
+    return FusedMail{mail[MAIL_REG_PAIRS], mail[MAIL_BIG_PAIRS], mail[MAIL_N_BIG], mail[MAIL_N_PENDING], mail[MAIL_ERROR],
+                     mail[MAIL_ROWS_REGULAR], mail[MAIL_N_APPLY_LONG], mail[MAIL_P_REGULAR], mail[MAIL_P_BIG], mail[MAIL_MAX_ROW]};
+}
+
+bool overlap_tri(xr_mesh *tree, xr_mesh *query, const double *tree_area, bool relative, xr_csr *csr, const MortonParams &tile,
+                 EarlyApply *early) {
+    FusedBuild b{tree, query, tree_area, relative, csr, tile, csr->has_tile_key ? csr->tile_key.get() : nullptr};
+    const int64_t T = b.T;
+    csr->n_long.alloc(TAIL_WORDS); // (TailWord: the rows of more than XR_APPLY_LONG_ROW entries, the gate of an apply enqueued behind the build ...)
+    csr->row_order.alloc((size_t)T);
+    csr->has_row_order = true;
+    const bool tail_fused = early && early->takes_tail && option(OPT_TAIL_FUSED) != 0;
+    const int64_t margin_opt = option(OPT_QUEUE_MARGIN); // test hook: a tiny margin forces the regrow path
+    int64_t big_capacity = margin_opt > 0 ? margin_opt : ((int64_t)4 << 20);
+    int64_t per_face = 8; // CSR entries reserved per target face (+ the big queue); regrown if the matrix is denser
+    for (int attempt = 0;; attempt++) {
+        XR_REQUIRE(attempt < 8, XR_ERR_LIMIT, "xr_overlap: the weight matrix does not fit the device buffers");
+        FusedAttempt a;
+        attempt_allocate(b, a, per_face, big_capacity);
+        enqueue_search(b, a);
+        enqueue_big_chain(b, a);
+        enqueue_regular(b, a);
+        const PlaceBig place = enqueue_tail(b, a, tail_fused);
+        const int32_t seq = enqueue_publish_and_apply(b, a, place, tail_fused, early);
+        const FusedMail m = read_back(seq);
+        const FusedOutcome verdict = fused_outcome(m.c_reg, m.c_big, m.n_pending, m.err, m.p_regular, m.p_big, a.cap, a.big_capacity);
+        XR_REQUIRE(verdict != FUSED_LIMIT, XR_ERR_LIMIT, "candidate pair count exceeds the int32 range");
+        if (debug_fused()) {
+            const int32_t *len = const_cast<const int32_t *>(engine().mailbox) + MAIL_REGION_LEN;
+            fprintf(stderr, "[tri] T=%lld C=%d big: %d faces %d pairs (%d pending) p_regular=%d p_big=%d err=%d rows=%d long=%d regions %d %d %d %d %d %d %d %d of %lld\n",
+                    (long long)T, m.c_reg, m.n_big, m.c_big, m.n_pending, m.p_regular, m.p_big, m.err, m.rows_regular, m.n_apply_long, len[0],
+                    len[1], len[2], len[3], len[4], len[5], len[6], len[7], (long long)b.region_cap);
+        }
+        switch (verdict) {
+        case FUSED_GENERAL:
+            csr->has_row_order = false; // (the general pipeline stores the rows in query order)
+            return false;
+        case FUSED_GROW_BIG: // some big faces needed more room than the margin
+            big_capacity = (int64_t)m.c_big + 1024;
+            continue;
+        case FUSED_GROW_CSR:
+            per_face *= 2;
+            continue;
+        default: // FUSED_FINAL
+            break;
+        }
+        XR_REQUIRE(m.rows_regular == T - m.n_big, XR_ERR_INVALID, "xr_overlap: internal row count mismatch");
+        tree->last_candidates = (int64_t)m.c_reg + m.c_big;
+        csr->nnz = (int64_t)m.p_regular + m.p_big;
+        csr->has_long = m.n_apply_long > 0; // rows of more than XR_APPLY_LONG_ROW entries (none: the apply skips their kernels)
+        csr->max_row_len = m.n_apply_long > 0 ? m.max_row : XR_APPLY_LONG_ROW;
+        if (early) early->done = true; // (the apply enqueued in THIS attempt saw the final matrix)
+        return true;
+    }
 }
 
 } // namespace xr

@@ -1,7 +1,8 @@
-// xr_overlap_tail.h -- what the fused weight build (xr_overlap_fused.h, included by xr_overlap.hip) and the K = 1 apply
-// enqueued behind it (xr_apply.hip: k_apply_tail1) share: the control block's words, the condition "this attempt produced
-// the final matrix", and the placement of the big faces' rows behind the regular ones -- a launch of its own
-// (k_place_big) or the leading blocks of the apply's launch.
+// xr_overlap_tail.h -- what the fused weight build (xr_overlap_fused.hip) and the K = 1 apply enqueued behind it
+// (xr_apply.hip: k_apply_tail1, xr_partial.hip) share: the control block's words, the verdict on an attempt -- ONE function,
+// evaluated by k_publish_all for the gate and by overlap_tri after its read-back --, the context an apply enqueued behind the
+// build is handed, and the placement of the big faces' rows behind the regular ones -- a launch of its own (k_place_big) or
+// the leading blocks of the apply's launch.
 #pragma once
 #include <cstddef>
 
@@ -13,7 +14,7 @@ static constexpr int QCUR_STRIDE = 32; // words between the cursors of the regul
 
 struct FusedCounters {                    // device words, zeroed before the launch
     int32_t n_apply_long;                 // rows with more than XR_APPLY_LONG_ROW entries
-    int32_t error;                        // bit 0: clip buffer overflow, bit 2: CSR capacity
+    int32_t error;                        // bit 0 (1): clip buffer overflow, bit 2 (4): CSR capacity -- no other bit is ever set
     int32_t p_regular;                    // entries of all regular rows (k_assemble)
     int32_t rows_regular;                 // regular rows
     int32_t p_big;                        // entries of the big faces' rows (k_big_order)
@@ -41,14 +42,25 @@ static_assert(CTL_COUNTERS + sizeof(FusedCounters) / sizeof(int32_t) <= CTL_LINE
                   CTL_LINE <= CTL_REGION_CURSOR && CTL_LINE + 8 <= 64,
               "the counters lie inside the line k_publish_all's one wave fetches, the region cursors behind it");
 
-// "THIS attempt produced the final matrix" -- the very conditions the host checks after its read-back (overlap_tri); a
-// failed attempt leaves row pointers no kernel may follow.  c: the control block, c_reg: the pairs of the regular queue (the sum of its
-// eight regions' cursors), cap / big_capacity: entries the CSR / the big faces' queue have room for.
-__device__ __forceinline__ bool fused_attempt_final(const int32_t *c, int32_t c_reg, int64_t cap, int64_t big_capacity) {
-    const int32_t c_big = c[CTL_BIG_CURSOR], n_pending = c[CTL_N_PENDING], err = c[XR_CTL_COUNTER(error)],
-                  p_reg = c[XR_CTL_COUNTER(p_regular)], p_big = c[XR_CTL_COUNTER(p_big)];
-    return c_reg >= 0 && c_big >= 0 && !(err & (1 | 4 | 8)) && n_pending == 0 && (int64_t)c_big <= big_capacity &&
-           (int64_t)p_reg + p_big <= cap;
+// The verdict on one attempt of the fused build, from the words k_publish_all sends to the mailbox.  ONE function for both
+// sides: k_publish_all opens the gate of an apply enqueued behind the build only on FUSED_FINAL, and overlap_tri switches on
+// the same value after its read-back -- so the host never declares a step done whose apply left at a closed gate.  A failed
+// attempt leaves row pointers no kernel may follow.  c_reg: the pairs of the regular queue (the sum of its eight regions'
+// cursors), c_big: those of the big faces' queue, cap / big_capacity: entries the CSR / the big faces' queue have room for.
+enum FusedOutcome : int {
+    FUSED_FINAL = 0, // the attempt produced the final matrix
+    FUSED_LIMIT,     // a pair count left the int32 range: XR_ERR_LIMIT
+    FUSED_GENERAL,   // a clip needed more vertices than its buffer holds (error bit 0): the general chain
+    FUSED_GROW_BIG,  // big faces' pairs did not fit their queue: again with a longer one
+    FUSED_GROW_CSR   // the matrix is denser than the CSR reserved (error bit 2, or the big rows found no room): per_face doubles
+};
+__host__ __device__ inline FusedOutcome fused_outcome(int32_t c_reg, int32_t c_big, int32_t n_pending, int32_t err, int32_t p_regular,
+                                                      int32_t p_big, int64_t cap, int64_t big_capacity) {
+    if (c_reg < 0 || c_big < 0) return FUSED_LIMIT;
+    if (err & 1) return FUSED_GENERAL;
+    if (n_pending > 0 || (int64_t)c_big > big_capacity) return FUSED_GROW_BIG;
+    if ((err & 4) || (int64_t)p_regular + p_big > cap) return FUSED_GROW_CSR;
+    return FUSED_FINAL;
 }
 
 // The finished rows of the big faces (ranked by k_row_fill_long into big_indices / big_data on the side stream) go
@@ -71,6 +83,7 @@ struct PlaceBig {
     const int32_t *skip_if;
 };
 
+#ifdef __HIPCC__
 // Grid-stride over rows and entries, by block `block` of `n_blocks` blocks of 256 threads.  (Which of these rows the apply
 // reduces cooperatively is listed where their lengths are first known, by k_row_fill_long.)
 // IN_TAIL: the blocks run beside blocks that read the regular rows' pointers up to indptr[T - n_big] -- the word the assembly
@@ -109,12 +122,22 @@ __device__ __forceinline__ void place_big_rows(const PlaceBig &p, int block, int
     }
     place_big_copy<IN_TAIL>(p, n_big, p_regular, p_big, block, n_blocks);
 }
+#endif
 
-// What the K = 1 apply's launch needs to take the place of k_place_big and to read the big rows from the big faces' own CSR
-// (xr_csr::apply_tail, set by overlap_tri around the early apply's callback only).
+// What the K = 1 apply's launch needs to take the place of k_place_big and to read the big rows from the big faces' own CSR.
 struct ApplyTail {
     PlaceBig place;
     const int32_t *words; // what k_publish_all left in the matrix' own words (xr_csr::n_long), indexed by TailWord
+};
+// What overlap_tri hands an apply it enqueues behind an attempt, before the host has read the attempt's sizes back
+// (csr_apply_dev, csr_partial_dev; callers with a finished matrix pass none).  The sizes of the matrix are then not known on
+// the host: the apply assumes long rows of any length -- that only adds blocks which look at the device-side list of long rows
+// and find it short or empty; results do not depend on it.
+struct ApplyContext {
+    const int32_t *gate;   // the build's gate word (TAIL_GATE): every block of the apply leaves unless the attempt was final
+    const ApplyTail *tail; // the apply's launch places the big rows itself (k_apply_tail1), or null
+    bool has_long = true;     // (in place of xr_csr::has_long / max_row_len: long rows possible, of any length)
+    int64_t max_row_len = -1;
 };
 // xr_csr::n_long of a matrix of the fused build, written by k_publish_all
 enum TailWord : int { TAIL_N_LONG = 0, TAIL_GATE = 1, TAIL_N_BIG = 2, TAIL_P_REGULAR = 3, TAIL_WORDS = 4 };

@@ -365,14 +365,15 @@ k_reduce_partial_rows_k1(const double *__restrict__ rows, const int64_t *__restr
 using namespace xr;
 
 // the partial state of every stored row (xr_apply_partial_dev; also enqueued right behind a weight build by
-// xr_overlap_partial_dev, then gated like the early apply: csr->apply_gated)
+// xr_overlap_partial_dev, then gated like the early apply: ctx)
 void xr::csr_partial_dev(const xr_csr *csr, int method, const void *source_dev, int source_dtype, int64_t K, double *out_dev,
-                         int rows_layout) {
+                         int rows_layout, const ApplyContext *ctx) {
+    const bool has_long = ctx ? ctx->has_long : csr->has_long;
     XR_REQUIRE(partial_components(method) > 0, XR_ERR_INVALID, "reducer %d does not decompose over source shards", method);
     with_source_type(source_dtype, [&](auto tag) {
         using SRC = decltype(tag);
         XR_REQUIRE(K >= 0 && K < 65536, XR_ERR_LIMIT, "xr_apply_partial_dev: K out of range (tile the variables)");
-        const int32_t *gate = csr->apply_gated ? csr->n_long.get() + 1 : (const int32_t *)nullptr;
+        const int32_t *gate = ctx ? ctx->gate : (const int32_t *)nullptr;
         XR_REQUIRE(!gate || K == 1, XR_ERR_INVALID, "internal: a gated partial apply is one variable");
         if (csr->n == 0 || K == 0) return;
         XR_REQUIRE(source_dev || csr->m == 0, XR_ERR_INVALID, "xr_apply_partial_dev: NULL source");
@@ -384,29 +385,29 @@ void xr::csr_partial_dev(const xr_csr *csr, int method, const void *source_dev, 
             dim3 grid(div_up(csr->n, 128), (unsigned)div_up(K, PKT));
             const size_t rows_shmem = sizeof(double) * 128 * (size_t)(partial_components(method) * PKT + 1);
             XR_LAUNCH("apply_partial", (k_apply_partial_rows<SRC, PKT>), grid, dim3(128), rows_shmem, method, csr->indptr.get(),
-                      csr->indices.get(), csr->data.get(), row_order_of(csr), csr->n, csr->m, src, K, out_dev, csr->has_long);
+                      csr->indices.get(), csr->data.get(), row_order_of(csr), csr->n, csr->m, src, K, out_dev, has_long);
         } else if (K >= PKT) {
             dim3 grid(div_up(csr->n, 256), (unsigned)div_up(K, PKT));
             XR_LAUNCH("apply_partial", (k_apply_partial_kt<SRC, PKT>), grid, dim3(256), 0, method, csr->indptr.get(),
                       csr->indices.get(), csr->data.get(), row_order_of(csr), csr->n, csr->m, src, K, out_dev,
-                      rows_layout != 0, csr->has_long);
+                      rows_layout != 0, has_long);
         } else if (K == 1) {
             // one variable: the wave-window kernel, one specialisation per reducer; the long rows in its first blocks
-            const int n_long_blocks = csr->has_long ? engine().num_cu / 2 : 0;
+            const int n_long_blocks = has_long ? engine().num_cu / 2 : 0;
             dim3 grid((unsigned)(div_up(csr->n, AP_BLOCK) + n_long_blocks));
             long_done = true;
             with_decomposable(method, [&](auto m) {
                 XR_LAUNCH("apply_partial", (k_apply_partial_w1<decltype(m)::value, SRC>), grid, dim3(AP_BLOCK), 0,
                           csr->indptr.get(), csr->indices.get(), csr->data.get(), row_order_of(csr), csr->n, csr->m, src,
-                          out_dev, rows_layout != 0, csr->has_long, gate, csr->long_rows.get(), csr->n_long.get(),
+                          out_dev, rows_layout != 0, has_long, gate, csr->long_rows.get(), csr->n_long.get(),
                           n_long_blocks);
             });
         } else { // K = 2 ... 7: one thread per (stored row, variable)
             dim3 grid(div_up(csr->n, 256), (unsigned)K);
             XR_LAUNCH("apply_partial", k_apply_partial<SRC>, grid, dim3(256), 0, method, csr->indptr.get(), csr->indices.get(),
-                      csr->data.get(), row_order_of(csr), csr->n, csr->m, src, K, out_dev, rows_layout != 0, csr->has_long);
+                      csr->data.get(), row_order_of(csr), csr->n, csr->m, src, K, out_dev, rows_layout != 0, has_long);
         }
-        if (csr->has_long && !long_done) {
+        if (has_long && !long_done) {
             dim3 lgrid(64, (unsigned)K);
             XR_LAUNCH("apply_partial_long", k_apply_partial_long<SRC>, lgrid, dim3(256), 0, method, csr->indptr.get(),
                       csr->indices.get(), csr->data.get(), row_order_of(csr), csr->long_rows.get(), csr->n_long.get(),
