@@ -19,7 +19,7 @@ from xugrid_amd import meshgen
 
 pytestmark = pytest.mark.gpu
 
-SAMPLE_MIN_FACES = 131072  # xr_mesh.hip: smaller trees take the full statistics pass
+SAMPLE_MIN_FACES = 131072  # xr_mesh_front.hip: smaller trees take the full statistics pass
 _cache = {}
 
 
@@ -81,7 +81,7 @@ def build(hip, sxy, sf, txy, tf, same_handle=False):
 def assert_same_csr(a, b, tag, query_sorted):
     """a == b, byte for byte.  `query_sorted`: the build launched `order_scatter`, i.e. the engine sorted the query itself (a
     numbering that is not spatially coherent, such as the first faces of a Delaunay mesh).  Inside a cell of that sort the
-    order follows the atomics (xr_mesh.hip: "unspecified"), so the stored row order differs from build to build of ONE
+    order follows the atomics (xr_mesh_order.hip: "unspecified"), so the stored row order differs from build to build of ONE
     form; what is left to ask of it then is that it is a permutation of the rows -- the matrix in the caller's numbering is
     compared all the same."""
     for name, x, y in zip(("indptr", "indices", "data"), a, b):

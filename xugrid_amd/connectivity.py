@@ -3,7 +3,7 @@ Host-side (numpy) mesh algebra needed around the hot path -- the subset of
 xugrid/ugrid/connectivity.py used by the regridders: polygon closing
 (:372-382), dense connectivity inversion (:325-333), unique edges (:419-457) and the raster
 bounds helper of xugrid/conversion.py:272-282.  Face areas and centroids are computed on the
-device (xugrid_amd/csrc/xr_mesh.hip), not here.
+device (xugrid_amd/csrc/xr_mesh_front.hip, xr_mesh_derived.hip), not here.
 Also the adjacency matrices of the fills (xugrid/ugrid/connectivity.py:487-531): face -> face through shared edges and
 node -> node along edges, both symmetric scipy CSR whose data is the id of the connecting edge.
 """

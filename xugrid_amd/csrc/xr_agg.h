@@ -1,4 +1,4 @@
-// xr_agg.h -- block-level aggregation of global atomics (device code only; included by the kernels that use it: xr_mesh.hip's
+// xr_agg.h -- block-level aggregation of global atomics (device code only; included by the kernels that use it: xr_mesh_order.hip's
 // two sorting passes, xr_edges.hip's clip).
 #pragma once
 

@@ -247,7 +247,7 @@ static void touched_max(xr_mesh *mesh, const double4 *seg, int64_t n_seg, const 
             mesh_face_coords(mesh);
         }
         XR_LAUNCH("burn_row_max", k_burn_row_max, dim3(div_up(csr->n, BB)), dim3(BB), 0, csr->indptr.get(), csr->indices.get(),
-                  csr->n, key, interior_only ? mesh->fxy.get() : (const double *)nullptr, mesh->len.get(), mesh->caller_off(),
+                  csr->n, key, interior_only ? mesh->prep.fxy.get() : (const double *)nullptr, mesh->prep.len.get(), mesh->caller_off(),
                   mesh->m, seg, winner);
     }
     stream_sync(); // (the matrix goes back to the pool behind its reader)
@@ -264,7 +264,7 @@ static void burn_polygons(xr_mesh *mesh, const double *coords_dev, int64_t n_ver
     if (n_vertex == 0) return;
     mesh_prepare(mesh, false);
     mesh_read_stats(mesh, /*need_exact=*/true);
-    const double tol = 1e-12 * mesh->h_stats[6]; // the default tolerance of xr_locate_points
+    const double tol = 1e-12 * mesh->stats.h[stat::MAX_DIAGONAL]; // the default tolerance of xr_locate_points
     const int64_t n_seg = n_vertex;
     DevBuf<double4> seg((size_t)n_seg);
     DevBuf<int32_t> seg_polygon((size_t)n_seg);

@@ -21,7 +21,7 @@
 
 namespace xr {
 
-static constexpr int EDGE_WALK_PAD = 8;    // records of padding behind rec_bb (xr_mesh.hip allocates them; WALK_PAD of the face search)
+static constexpr int EDGE_WALK_PAD = MeshIndex::REC_BB_PAD; // records of padding behind rec_bb (as WALK_PAD of the face search)
 static constexpr int EDGE_BIG_CELLS = 64;  // edges whose box covers more grid cells (all levels) get a wave of their own
 static constexpr int ROW_SORT_SMALL = 16;  // rows up to this length are insertion-sorted by one thread (k_edge_rows_sort)
 static constexpr int ROW_SORT_LDS = 4096;  // rows up to this length are sorted in LDS by one block
@@ -727,7 +727,7 @@ static void edge_length_csr(xr_mesh *tree, const double *edge_xy_host, int64_t n
     const double *edge_xy = edge_xy_dev ? edge_xy_dev : edge_xy_own.get();
     DevBuf<int32_t> row_count((size_t)F), big_list((size_t)n_edge), counters((size_t)EQ_WORDS);
     const size_t edge_bytes = sizeof(double) * 4 * (size_t)n_edge;
-    const GridParams &g = tree->grid;
+    const GridParams &g = tree->index.grid;
     const int grid_persistent = engine().num_cu * 8;
     const int big_cells = option(OPT_EDGE_BIG) > 0 ? (int)option(OPT_EDGE_BIG) : EDGE_BIG_CELLS;                          // test / tuning hook
     const int stage_cap = option(OPT_EDGE_STAGE) > 0 ? (int)std::min<int64_t>(option(OPT_EDGE_STAGE), EDGE_STAGE) : EDGE_STAGE; // test hook
@@ -748,8 +748,8 @@ static void edge_length_csr(xr_mesh *tree, const double *edge_xy_host, int64_t n
             XR_LAUNCH("edges_tile_scatter", k_edge_tile_scatter, dim3(div_up(ne, 256)), dim3(256), 0, tile_of.get() + 2 * e0, ne, e0,
                       tile_start.get(), perm.get() + e0);
         }
-        XR_LAUNCH("edges_walk", k_edge_walk, dim3(div_up(ne, 256)), dim3(256), 0, edge_xy, ne, e0, g, tree->cell_start.get(),
-                  tree->rec_bb.get(), queue, region_cap, counters.get(), big_list.get(), big_cells, stage_cap,
+        XR_LAUNCH("edges_walk", k_edge_walk, dim3(div_up(ne, 256)), dim3(256), 0, edge_xy, ne, e0, g, tree->index.cell_start.get(),
+                  tree->index.rec_bb.get(), queue, region_cap, counters.get(), big_list.get(), big_cells, stage_cap,
                   sorted ? perm.get() + e0 : (const int32_t *)nullptr);
     };
     bool uploaded = edge_xy_dev != nullptr;
@@ -789,13 +789,13 @@ static void edge_length_csr(xr_mesh *tree, const double *edge_xy_host, int64_t n
             walk(0, n_edge, queue.get(), region_cap);
         }
         uploaded = true;
-        XR_LAUNCH("edges_walk_big", k_edge_walk_big, dim3(grid_persistent), dim3(256), 0, edge_xy, g, tree->cell_start.get(),
-                  tree->rec_bb.get(), queue.get(), region_cap, counters.get(), big_list.get());
+        XR_LAUNCH("edges_walk_big", k_edge_walk_big, dim3(grid_persistent), dim3(256), 0, edge_xy, g, tree->index.cell_start.get(),
+                  tree->index.rec_bb.get(), queue.get(), region_cap, counters.get(), big_list.get());
         // (a persistent grid of what is resident: 92-96 registers with the next round's operands in flight, five waves per SIMD)
         // (the flat vertex blocks of a polygon mesh: the run-time form)
         with_nodes_per_face(tree->ragged() ? 0 : tree->m, [&](auto mc) {
             XR_LAUNCH("edges_clip", k_edge_clip<mc()>, dim3(engine().num_cu * (mc() > 0 ? 5 : 7)), dim3(256), 0, edge_xy,
-                      tree->rec_fxy.get(), tree->rec_len.get(), tree->record_off(), tree->m, tree->rec_face.get(), queue.get(),
+                      tree->index.rec_fxy.get(), tree->index.rec_len.get(), tree->record_off(), tree->m, tree->index.rec_face.get(), queue.get(),
                       queue_len.get(), queue_rank.get(), region_cap, counters.get(), row_count.get());
         });
         exclusive_scan_i32(row_count.get(), csr->indptr.get(), F);
@@ -897,7 +897,7 @@ int xr_edge_pieces(xr_mesh *tree, const xr_csr *csr, const double *edge_xy, int6
         DevBuf<double> xy((size_t)n_edge * 4), out((size_t)csr->nnz * 4);
         h2d(xy.get(), edge_xy, sizeof(double) * 4 * (size_t)n_edge);
         XR_LAUNCH("edge_pieces", k_edge_pieces, dim3(div_up(csr->n, 256)), dim3(256), 0, csr->indptr.get(),
-                  csr->indices.get(), csr->n, tree->fxy.get(), tree->len.get(), tree->caller_off(), tree->m, xy.get(), out.get());
+                  csr->indices.get(), csr->n, tree->prep.fxy.get(), tree->prep.len.get(), tree->caller_off(), tree->m, xy.get(), out.get());
         d2h(intersections, out.get(), sizeof(double) * 4 * (size_t)csr->nnz);
         stream_sync();
     }

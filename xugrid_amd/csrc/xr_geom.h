@@ -1,22 +1,22 @@
 // xr_geom.h -- device-side geometry types shared by the mesh / overlap / locate kernels.
 //
-// HBM layout of a mesh (struct xr_mesh), all face-major so that no hot kernel chases
+// HBM layout of a mesh (struct xr_mesh and its stages, xr_objects.h), all face-major so that no hot kernel chases
 // connectivity -> node indirections:
 //   fxy   f64 [n_face][M][2]  CCW-normalised vertex coordinates of every face (M = n_max_node;
 //                             48 B per triangle); slots >= len are never read.  Meshes with M > DENSE_MAX_NODES
 //                             (polygon meshes, e.g. the M = 22 Voronoi mesh of the barycentric path with ~6 real
 //                             vertices per cell) keep the blocks FLAT with offsets instead: f64 [sum len][2] +
-//                             off i32 [n_face + 1] (fxy_off / q_off / rec_off); face_vertex_base() hides the difference
+//                             off i32 [n_face + 1] (prep.fxy_off / qo.off / index.rec_off); face_vertex_base() hides the difference
 //   len   u8  [n_face]        number of valid vertices (polygon_length)
 //   bbox  f64 [n_face][4]     xmin, xmax, ymin, ymax -- polygon meshes only (the index build reads it); for dense meshes
 //                             a face's box is taken from its vertices where it is needed (query_face_box below)
 //   area  f64 [n_face]        connectivity.area on the caller's vertex order
 // The raw upload (node_xy f64[N][2], faces_raw i32[F][M], the CSR-style flat connectivity with the
 // implicit offset f*M) is only read once, by the prepare kernel.
-// Two spatially sorted copies exist (counting sort, xr_mesh.hip):
-//   query order  q_perm/q_fxy/q_len (+ q_bbox, polygon meshes): faces grouped by the Morton code of a coarse cell, so a
+// Two spatially sorted copies exist (counting sort, xr_mesh_order.hip):
+//   query order  qo.perm / fxy / len (+ bbox, polygon meshes): faces grouped by the Morton code of a coarse cell, so a
 //                256-face block is a compact 2-D patch (search/clip/row kernels walk this order)
-//   tree index   hierarchical uniform grid, one insertion per face: level l has square cells of
+//   tree index   (index.*) hierarchical uniform grid, one insertion per face: level l has square cells of
 //                size h0 * 2^l; a face lives on the lowest level whose cell size exceeds its bbox
 //                extent, in the cell holding its bbox lower-left corner
 //     cell_start i32 [n_cell+1]  CSR offsets cell -> record run, all levels concatenated
@@ -30,6 +30,12 @@
 #include <cstdint>
 
 namespace xr {
+
+// The eight statistics of a mesh (xr_mesh::stats, a block's partial record): x and y bounds, sum and maximum of the faces' bbox
+// extents, largest bbox diagonal, sum of the numbering jumps -- a sampled pass leaves the number of faces it looked at there.
+namespace stat {
+enum Slot : int { XMIN, XMAX, YMIN, YMAX, SUM_EXTENT, MAX_EXTENT, MAX_DIAGONAL, SUM_JUMP, N_SLOTS, FACES_SAMPLED = SUM_JUMP };
+}
 
 struct P2 {
     double x, y;
@@ -86,7 +92,7 @@ __device__ __forceinline__ P2 load_p2(const double *__restrict__ xy, int i) {
 // float64 box (xmin, xmax, ymin, ymax) of face t of a query-order (or caller-order) vertex block.  Dense meshes (MC = 3, 4)
 // store no box: it is the fmin / fmax over the face's `len` vertices -- the values k_prepare_faces reduces, so cell coordinates
 // and float boxes derived from it are the ones a stored box gave; a fill slot is never read.  Polygon meshes (MC = 0) keep
-// a stored box (the index build reads it, xr_mesh.hip).
+// a stored box (the index build reads it, xr_mesh_order.hip).
 template <int MC>
 __device__ __forceinline__ double4 query_face_box(const double *__restrict__ q_bbox, const double *__restrict__ q_fxy,
                                                   const uint8_t *__restrict__ q_len, int64_t t) {

@@ -165,7 +165,7 @@ template <typename T> struct DevBuf {
     size_t bytes() const { return n * sizeof(T); }
 };
 
-// A buffer of points that is either the holder's own or SHARED with the mesh whose face centroids it holds (xr_mesh::centroids_dev:
+// A buffer of points that is either the holder's own or SHARED with the mesh whose face centroids it holds (xr_mesh::centroids:
 // the reference caches `Ugrid2d.centroids` on the grid, ugrid2d.py; here the device copy is kept until the mesh is invalidated or
 // destroyed -- a handle that shares it keeps it alive beyond that).
 struct PointsBuf {
@@ -375,6 +375,7 @@ template <typename T> struct Building {
     OnFailure rule;
     explicit Building(OnFailure r = OnFailure::FreeOnly) : rule(r) {}
     Building(const Building &) = delete;
+    Building(Building &&) = default; // (a helper hands its handle on: new_raw_mesh)
     Building &operator=(const Building &) = delete;
     ~Building() {
         if (!p || rule != OnFailure::WaitFirst) return;

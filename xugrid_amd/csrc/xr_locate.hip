@@ -638,7 +638,7 @@ k_raster_points(const double *__restrict__ x, const double *__restrict__ y, int6
 static double resolve_tolerance(xr_mesh *mesh, double tolerance) {
     if (tolerance >= 0) return tolerance;
     mesh_read_stats(mesh, /*need_exact=*/true); // (the largest bbox diagonal over ALL faces)
-    return 1e-12 * mesh->h_stats[6]; // ugridbase.py:1165-1170
+    return 1e-12 * mesh->stats.h[stat::MAX_DIAGONAL]; // ugridbase.py:1165-1170
 }
 
 // the locate pass of xr_locate_points on points that are already in HBM, for other translation units (xr_burn.hip):
@@ -649,8 +649,8 @@ double locate_points_dev(xr_mesh *mesh, const double *pts_dev, int64_t n, double
     mesh_build_index(mesh);
     const double tol = resolve_tolerance(mesh, tolerance);
     if (n > 0)
-        XR_LAUNCH("locate_points", k_locate, dim3(div_up(n, 256)), dim3(256), 0, mesh->rec_fxy.get(), mesh->rec_len.get(),
-                  mesh->record_off(), mesh->m, mesh->grid, mesh->cell_start.get(), mesh->rec_bb.get(), mesh->rec_face.get(),
+        XR_LAUNCH("locate_points", k_locate, dim3(div_up(n, 256)), dim3(256), 0, mesh->index.rec_fxy.get(), mesh->index.rec_len.get(),
+                  mesh->record_off(), mesh->m, mesh->index.grid, mesh->index.cell_start.get(), mesh->index.rec_bb.get(), mesh->index.rec_face.get(),
                   mesh->n_face, pts_dev, n, tol, out_dev);
     return tol;
 }
@@ -718,9 +718,9 @@ int xr_locate_points(xr_mesh *mesh, const double *points, int64_t n, double tole
         DevBuf<int64_t> out((size_t)n);
         h2d(pts.get(), points, sizeof(double) * 2 * (size_t)n);
         if (mesh->n_face > 0) {
-            XR_LAUNCH("locate_points", k_locate, dim3(div_up(n, 256)), dim3(256), 0, mesh->rec_fxy.get(),
-                      mesh->rec_len.get(), mesh->record_off(), mesh->m, mesh->grid, mesh->cell_start.get(), mesh->rec_bb.get(),
-                      mesh->rec_face.get(), mesh->n_face, pts.get(), n, tol, out.get());
+            XR_LAUNCH("locate_points", k_locate, dim3(div_up(n, 256)), dim3(256), 0, mesh->index.rec_fxy.get(),
+                      mesh->index.rec_len.get(), mesh->record_off(), mesh->m, mesh->index.grid, mesh->index.cell_start.get(), mesh->index.rec_bb.get(),
+                      mesh->index.rec_face.get(), mesh->n_face, pts.get(), n, tol, out.get());
             d2h(face_index_out, out.get(), sizeof(int64_t) * (size_t)n);
             stream_sync();
         } else {
@@ -748,9 +748,9 @@ int xr_locate_raster(xr_mesh *mesh, const double *x, int64_t nx, const double *y
             h2d(dy.get(), y, sizeof(double) * (size_t)ny);
             XR_LAUNCH("raster_points", k_raster_points, dim3(div_up(n, 256)), dim3(256), 0, dx.get(), dy.get(), nx, n,
                       pts.get());
-            XR_LAUNCH("locate_points", k_locate, dim3(div_up(n, 256)), dim3(256), 0, mesh->rec_fxy.get(),
-                      mesh->rec_len.get(), mesh->record_off(), mesh->m, mesh->grid, mesh->cell_start.get(), mesh->rec_bb.get(),
-                      mesh->rec_face.get(), mesh->n_face, pts.get(), n, tol, out.get());
+            XR_LAUNCH("locate_points", k_locate, dim3(div_up(n, 256)), dim3(256), 0, mesh->index.rec_fxy.get(),
+                      mesh->index.rec_len.get(), mesh->record_off(), mesh->m, mesh->index.grid, mesh->index.cell_start.get(), mesh->index.rec_bb.get(),
+                      mesh->index.rec_face.get(), mesh->n_face, pts.get(), n, tol, out.get());
             d2h(face_index_out, out.get(), sizeof(int64_t) * (size_t)n);
             stream_sync();
         } else {
@@ -775,9 +775,9 @@ int xr_barycentric(xr_mesh *mesh, const double *points, int64_t n, double tolera
             DevBuf<double> pts((size_t)n * 2), w((size_t)n * m);
             DevBuf<int64_t> out((size_t)n);
             h2d(pts.get(), points, sizeof(double) * 2 * (size_t)n);
-            XR_LAUNCH("barycentric", k_barycentric, dim3(div_up(n, 256)), dim3(256), 0, mesh->rec_fxy.get(),
-                      mesh->rec_len.get(), mesh->record_off(), m, mesh->grid, mesh->cell_start.get(), mesh->rec_bb.get(),
-                      mesh->rec_face.get(), mesh->n_face, pts.get(), n, tol, out.get(), w.get());
+            XR_LAUNCH("barycentric", k_barycentric, dim3(div_up(n, 256)), dim3(256), 0, mesh->index.rec_fxy.get(),
+                      mesh->index.rec_len.get(), mesh->record_off(), m, mesh->index.grid, mesh->index.cell_start.get(), mesh->index.rec_bb.get(),
+                      mesh->index.rec_face.get(), mesh->n_face, pts.get(), n, tol, out.get(), w.get());
             d2h(face_index_out, out.get(), sizeof(int64_t) * (size_t)n);
             d2h(weights_out, w.get(), sizeof(double) * (size_t)n * m);
             stream_sync();
@@ -882,47 +882,47 @@ static void barycentric_csr(xr_mesh *voronoi, xr_mesh *source, xr_mesh *query, c
             std::vector<int64_t> host(n_tail + n_map);
             if (n_tail > 0) memcpy(host.data(), vertex_face, sizeof(int64_t) * n_tail);
             if (n_map > 0) memcpy(host.data() + n_tail, node_to_node_map, sizeof(int64_t) * n_map);
-            const bool same = voronoi->bary_ids.get() && voronoi->bary_n_identity == n_identity &&
-                              voronoi->bary_n_extra == n_extra && voronoi->bary_ids_host == host;
+            const bool same = voronoi->bary.ids.get() && voronoi->bary.n_identity == n_identity &&
+                              voronoi->bary.n_extra == n_extra && voronoi->bary.ids_host == host;
             if (!same) {
-                voronoi->bary_flag_valid = false;
-                voronoi->bary_ids.alloc((size_t)(nv + 2 * n_extra + 1));
-                if (!host.empty()) h2d(voronoi->bary_ids.get() + n_identity, host.data(), sizeof(int64_t) * host.size());
-                voronoi->bary_ids_host = std::move(host);
-                voronoi->bary_n_identity = n_identity;
-                voronoi->bary_n_extra = n_extra;
+                voronoi->bary.flag_valid = false;
+                voronoi->bary.ids.alloc((size_t)(nv + 2 * n_extra + 1));
+                if (!host.empty()) h2d(voronoi->bary.ids.get() + n_identity, host.data(), sizeof(int64_t) * host.size());
+                voronoi->bary.ids_host = std::move(host);
+                voronoi->bary.n_identity = n_identity;
+                voronoi->bary.n_extra = n_extra;
             }
         }
-        int64_t *const vface = voronoi->bary_ids.get(), *const n2n = voronoi->bary_ids.get() + nv;
+        int64_t *const vface = voronoi->bary.ids.get(), *const n2n = voronoi->bary.ids.get() + nv;
         if (!reference_order) mesh_faces_ccw_dev(voronoi, faces_ccw.get(), false);
         DevBuf<uint8_t> n_pos((size_t)n);
-        if (!voronoi->bary_flag_valid) {
-            voronoi->bary_cell_flag.alloc((size_t)voronoi->n_face);
+        if (!voronoi->bary.flag_valid) {
+            voronoi->bary.cell_flag.alloc((size_t)voronoi->n_face);
             XR_LAUNCH("bary_cell_flag", k_bary_cell_flag, dim3(div_up(voronoi->n_face, 256)), dim3(256), 0, voronoi->faces_raw.get(),
-                      voronoi->n_face, m, nv - n_extra, voronoi->bary_cell_flag.get());
-            voronoi->bary_flag_valid = true;
+                      voronoi->n_face, m, nv - n_extra, voronoi->bary.cell_flag.get());
+            voronoi->bary.flag_valid = true;
         }
-        const uint8_t *const cell_flag_p = voronoi->bary_cell_flag.get();
-        XR_LAUNCH("barycentric", k_barycentric_cm, dim3(div_up(n, 256)), dim3(256), 0, voronoi->rec_fxy.get(),
-                  voronoi->rec_len.get(), voronoi->record_off(), m, voronoi->grid, voronoi->cell_start.get(), voronoi->rec_bb.get(),
-                  voronoi->rec_face.get(), voronoi->n_face, pts.get(), n, tol, face.get(), w.get(), cell_flag_p, n_pos.get());
+        const uint8_t *const cell_flag_p = voronoi->bary.cell_flag.get();
+        XR_LAUNCH("barycentric", k_barycentric_cm, dim3(div_up(n, 256)), dim3(256), 0, voronoi->index.rec_fxy.get(),
+                  voronoi->index.rec_len.get(), voronoi->record_off(), m, voronoi->index.grid, voronoi->index.cell_start.get(), voronoi->index.rec_bb.get(),
+                  voronoi->index.rec_face.get(), voronoi->n_face, pts.get(), n, tol, face.get(), w.get(), cell_flag_p, n_pos.get());
         if (join_later) {
             side_join();
             pre->on_side = false;
         }
         // the flags from the faces around each point's cell, behind the barycentric kernel
-        const int64_t *vface_tab = voronoi->bary_ids.get();
+        const int64_t *vface_tab = voronoi->bary.ids.get();
         mesh_face_coords(source); // (its face-major vertex block in the caller's order: built once per mesh)
         mesh_prepare(source, false); // (the index for the points the star leaves open: still there unless the mesh was
         mesh_build_index(source);    // invalidated since the handle was made)
         with_nodes_per_face(source->ragged() ? 0 : source->m, [&](auto msv) {
             XR_LAUNCH("star_flag", k_star_flag<msv()>, dim3(div_up(n, 256)), dim3(256), 0, face.get(), voronoi->faces_raw.get(), m,
-                      n_identity, vface_tab, nv - n_extra, source->fxy.get(), source->len.get(), source->caller_off(), source->m,
+                      n_identity, vface_tab, nv - n_extra, source->prep.fxy.get(), source->prep.len.get(), source->caller_off(), source->m,
                       pts.get(), n, tol_source, inside.get());
         });
-        XR_LAUNCH("locate_flag", k_locate_flag, dim3(div_up(n, 256)), dim3(256), 0, source->rec_fxy.get(),
-                  source->rec_len.get(), source->record_off(), source->m, source->grid, source->cell_start.get(),
-                  source->rec_bb.get(), source->rec_face.get(), source->n_face, pts.get(), n, tol_source, inside.get());
+        XR_LAUNCH("locate_flag", k_locate_flag, dim3(div_up(n, 256)), dim3(256), 0, source->index.rec_fxy.get(),
+                  source->index.rec_len.get(), source->record_off(), source->m, source->index.grid, source->index.cell_start.get(),
+                  source->index.rec_bb.get(), source->index.rec_face.get(), source->n_face, pts.get(), n, tol_source, inside.get());
         if (reference_order)
             XR_LAUNCH("bary_fix_count", k_bary_fix_count<int32_t>, dim3(div_up(n, 256)), dim3(256), 0, face.get(), w.get(), m,
                       voronoi->faces_raw.get(), voronoi->node_xy.get(), n2n, nv - n_extra, inside.get(), n, count.get(), n_pos.get());
@@ -1099,9 +1099,9 @@ int xr_locate_csr(xr_mesh *tree, xr_mesh *query, const double *points, int64_t n
             h2d(pts.get(), points, sizeof(double) * 2 * (size_t)n);
         }
         DevBuf<int32_t> col((size_t)n), found((size_t)n);
-        XR_LAUNCH("locate_col", k_locate_col, dim3(div_up(n, 256)), dim3(256), 0, tree->rec_fxy.get(),
-                  tree->rec_len.get(), tree->record_off(), tree->m, tree->grid, tree->cell_start.get(), tree->rec_bb.get(),
-                  tree->rec_face.get(), tree->n_face, pts.get(), n, tol, col.get(), found.get());
+        XR_LAUNCH("locate_col", k_locate_col, dim3(div_up(n, 256)), dim3(256), 0, tree->index.rec_fxy.get(),
+                  tree->index.rec_len.get(), tree->record_off(), tree->m, tree->index.grid, tree->index.cell_start.get(), tree->index.rec_bb.get(),
+                  tree->index.rec_face.get(), tree->n_face, pts.get(), n, tol, col.get(), found.get());
         exclusive_scan_i32(found.get(), csr->indptr.get(), n);
         // (a point has at most one entry: the arrays hold n, and the fill is enqueued in front of the read-back of nnz)
         csr->indices.alloc((size_t)n);

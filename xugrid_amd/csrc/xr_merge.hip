@@ -296,9 +296,7 @@ int xr_merge_meshes_dev(xr_mesh *const *parts, int64_t n_part, xr_merge **out) {
     for (int p = 0; p <= P; p++) nodes.bound[p] = h[p], faces.bound[p] = h[P + 1 + p];
     const int64_t Nn = nodes.bound[P], Fn = faces.bound[P];
 
-    Building<xr_mesh> mesh;
-    mesh->m = m, mesh->n_node = Nn, mesh->n_face = Fn;
-    mesh->node_xy.alloc((size_t)Nn * 2), mesh->faces_raw.alloc((size_t)(Fn * m));
+    Building<xr_mesh> mesh = new_raw_mesh(Nn, Fn, m);
     nodes.keep.alloc((size_t)Nn), faces.keep.alloc((size_t)Fn);
     if (Nn > 0)
         XR_LAUNCH("merge_compact_xy", k_merge_compact_xy, dim3(div_up(N, 256)), dim3(256), 0, node_flag.get(), node_rank.get(), N,

@@ -6,106 +6,166 @@
 #include "xr_geom.h"
 #include "xr_internal.h"
 
-// Device-resident face topology + derived per-face data, in three stages (layout: xr_geom.h):
-//   raw      what the caller uploaded (node_xy, faces_raw)
-//   prepared per-face arrays in the CALLER's face order (fxy, len, bbox, area, stats)
-//   query    the same arrays permuted into a spatially coherent order (Morton order of coarse
+// Device-resident face topology + derived per-face data.  A mesh IS its raw upload; everything else hangs off it in stages, one
+// small struct per lifetime (layout: xr_geom.h).  Every stage lists its buffers once, in bytes() and release():
+//   raw      what the caller uploaded (node_xy, faces_raw) + where the mesh came from
+//   stats    the eight statistics of the faces and their way to the host (MeshStatsBox)
+//   prep     per-face arrays in the CALLER's face order (fxy, len, bbox, area)
+//   qo       the same arrays permuted into a spatially coherent order (Morton order of coarse
 //            cells) -- used when the mesh is the QUERY (regridding target) side
 //   index    the same arrays permuted into grid-cell order + cell_start -- used when the mesh is
 //            the TREE (regridding source) side
-struct xr_mesh {
+//   centroids, bary   caches other units keep on the mesh
+namespace xr {
+struct StatsTail; // the hand-off words a statistics kernel gets (xr_mesh.h)
+
+struct MeshRaw {
     int64_t n_node = 0, n_face = 0;
     int m = 0; // n_max_node_per_face
-
-    xr::DevBuf<double> node_xy;    // [n_node*2]
-    xr::DevBuf<int32_t> faces_raw; // [n_face*m] caller's vertex order, fill -> -1
-
-    // ---- prepared (caller's face order)
-    bool prepared = false;  // statistics known
-    bool has_attrs = false; // ... and len / bbox / fxy filled (prepared as a query)
-    bool area_valid = false;
-    xr::DevBuf<double> fxy;   // [n_face*m*2] CCW-normalised vertex coordinates per face (only if fxy_valid:
-                              // needed when the mesh is a query kept in the caller's numbering)
-    bool fxy_valid = false;
-    xr::DevBuf<int32_t> fxy_off; // [n_face+1] only for ragged() meshes: fxy is flat, face f starts at vertex fxy_off[f]
-    xr::DevBuf<uint8_t> len;  // [n_face]
-    xr::DevBuf<double> bbox;  // [n_face*4] xmin,xmax,ymin,ymax; ragged() meshes only (dense ones: query_face_box, xr_geom.h)
-    xr::DevBuf<double> area;  // [n_face]   connectivity.area on the caller's vertex order (mesh_area, on demand)
-    hipEvent_t centroids_event = nullptr;   // recorded behind the kernel that filled centroids_dev, on centroids_stream: a user on
-    hipStream_t centroids_stream = nullptr; // another stream (the handles' kernels run on the side stream) waits for it
-    std::shared_ptr<xr::DevBuf<double>> centroids_dev; // [n_face*2] connectivity.centroids, on demand (mesh_centroids_shared); kept like
-                                                       // the reference's cached Ugrid2d.centroids until the mesh is invalidated
-    xr::DevBuf<double> stats; // [8] xmin,xmax,ymin,ymax,sum_extent,max_extent,max_diagonal,sum_jump (device)
-    bool stats_valid = false;
-    bool stats_sampled = false; // h_stats[4..6] come from a sample of the faces ([7] = faces sampled): enough to size a grid, NOT for the default tolerance
-    double h_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    // the reduction kernel also deposits the statistics in pinned host memory; the host waits on an event
-    // recorded right behind it, so kernels queued later (the other mesh's prepare) keep the GPU busy meanwhile
-    double *stats_host = nullptr; // [9] pinned: the statistics + the sequence word the publishing block stores last
-    hipEvent_t stats_event = nullptr;
-    xr::DevBuf<unsigned> stats_done; // [1] blocks that have delivered their partial (zero at rest; stats_tail, xr_mesh.hip)
-    double stats_seq = 0.0;          // sequence number of the last statistics launch (what stats_host[8] must show)
-    bool stats_event_pending = false; // a reduction kernel + event were enqueued for the last launch (fallback of the poll)
-    bool stats_polled = false;       // the statistics of the last launch arrive through the sequence word (no event recorded)
-    xr_mesh() = default;
-    xr_mesh(const xr_mesh &) = delete;
-    xr_mesh &operator=(const xr_mesh &) = delete;
-    ~xr_mesh() {
-        if (stats_host) (void)hipHostFree(stats_host);
-        if (centroids_event) (void)hipEventDestroy(centroids_event);
-        if (stats_event) (void)hipEventDestroy(stats_event);
-    }
-
-    // ---- query order.  If the caller's face numbering is already spatially coherent (mean distance
-    // between consecutive faces <= a few face extents) the caller's order IS the query order:
-    // no permutation, no copies (query_identity); the accessors below hide the difference.
-    bool query_ready = false;
-    bool query_identity = false;
-    xr::DevBuf<int32_t> q_perm; // [n_face] position -> caller's face id
-    xr::DevBuf<double> q_fxy;   // [n_face*m*2], ragged(): [sum len * 2]
-    xr::DevBuf<int32_t> q_off;  // [n_face+1] ragged() only
-    xr::DevBuf<uint8_t> q_len;  // [n_face]
-    xr::DevBuf<double> q_bbox;  // [n_face*4] ragged() only
-
-    // ---- tree index (records in grid-cell order)
-    bool indexed = false;
-    xr::GridParams grid{};
-    xr::DevBuf<int32_t> cell_start; // [n_cells+1]
-    xr::DevBuf<float> rec_bb;       // [n_face*4] conservative f32 bbox relative to the grid origin
-    xr::DevBuf<int32_t> rec_face;   // [n_face]   record -> caller's face id
-    xr::DevBuf<double> rec_fxy;     // [n_face*m*2], ragged(): [sum len * 2]
-    xr::DevBuf<int32_t> rec_off;    // [n_face+1] ragged() only
-    xr::DevBuf<uint8_t> rec_len;    // [n_face]
-
-    int64_t last_candidates = 0;
-
-    // ---- kept when this mesh is the fan triangulation of another (xr_mesh_triangulate): the source face of every triangle
-    xr::DevBuf<int32_t> tri_face; // [n_face]
+    DevBuf<double> node_xy;    // [n_node*2]
+    DevBuf<int32_t> faces_raw; // [n_face*m] caller's vertex order, fill -> -1
+    // kept when this mesh is the fan triangulation of another (xr_mesh_triangulate): the source face of every triangle
+    DevBuf<int32_t> tri_face; // [n_face]
     bool is_triangulation = false;
-
-    // ---- kept when this mesh was cut out of another (xr_mesh_subset_dev, xr_subset.hip): the source node of every node, ascending
-    xr::DevBuf<int32_t> sub_node; // [n_node]
+    // kept when this mesh was cut out of another (xr_mesh_subset_dev, xr_subset.hip): the source node of every node, ascending
+    DevBuf<int32_t> sub_node; // [n_node]
     bool is_subset = false;
+    size_t bytes() const { return node_xy.bytes() + faces_raw.bytes() + tri_face.bytes() + sub_node.bytes(); }
+};
 
-    // ---- kept by the barycentric construction when this mesh is a Voronoi tessellation (xr_locate.hip:barycentric_csr): the
-    // vertex -> face table with the interpolation map behind it, and the flags of the cells that hold a substitute vertex --
-    // a second interpolator on a cached tessellation uploads and recomputes nothing (its first kernel then runs BESIDE the
-    // source-side locate pass instead of behind a copy)
-    std::vector<int64_t> bary_ids_host;  // what was uploaded (tail of the vertex table, then the map)
-    xr::DevBuf<int64_t> bary_ids;        // [n_node + 2 n_extra + 1]
-    int64_t bary_n_identity = -1, bary_n_extra = -1;
-    xr::DevBuf<uint8_t> bary_cell_flag;  // [n_face], valid for bary_n_extra
-    bool bary_flag_valid = false;
+// The statistics of a mesh and their hand-off.  The reduction (a kernel's last block, or k_reduce_stats behind it) deposits them
+// in the device copy and in pinned host memory and stores the launch's sequence number behind them; the host polls that word,
+// or waits on the event recorded behind k_reduce_stats, so kernels queued later (the other mesh's prepare) keep the GPU busy
+// meanwhile.  One launch goes begin() -> kernel -> enqueued(); read() brings the values to h[] (xr_mesh_front.hip).
+struct MeshStatsBox {
+    DevBuf<double> dev;            // [8] device copy
+    double h[stat::N_SLOTS] = {0, 0, 0, 0, 0, 0, 0, 0}; // host values, indexed by stat::Slot (xr_geom.h)
+    double *host = nullptr;        // [9] pinned: the statistics + the sequence word the publishing block stores last
+    hipEvent_t event = nullptr;
+    DevBuf<unsigned> done;         // blocks that have delivered their partial (zero at rest; stats_tail, xr_mesh_front.hip)
+    double seq = 0.0;              // sequence number of the last statistics launch (what host[8] must show)
+    bool launched = false;         // a statistics kernel has run for the mesh as it is (the mesh is "prepared")
+    bool event_pending = false;    // a reduction kernel + event were enqueued for the last launch (fallback of the poll)
+    bool polled = false;           // the statistics of the last launch arrive through the sequence word (no event recorded)
+    bool valid = false;            // h[] holds the last launch's values
+    bool sampled = false; // h[stat::SUM_EXTENT..MAX_DIAGONAL] come from a sample of the faces: enough to size a grid, NOT for the default tolerance
+    ~MeshStatsBox() { // (not copyable: DevBuf)
+        if (host) (void)hipHostFree(host);
+        if (event) (void)hipEventDestroy(event);
+    }
+    size_t bytes() const { return dev.bytes(); }
+    void release() { // (`sampled` describes the last launch and is overwritten by the next; the counters stay, zero at rest)
+        launched = valid = false;
+        dev.release();
+    }
+    StatsTail begin(double *partials, int64_t nb); // next sequence number; the pinned page and the counters on first use
+    void enqueued(const double *partials, int64_t nb, const StatsTail &tail, bool on_side); // behind the kernel: k_reduce_stats where its last block does not reduce
+    void read(); // wait for the last launch's values
+};
+
+struct MeshPrepared { // caller's face order
+    bool has_attrs = false; // len / bbox / fxy filled (prepared as a query)
+    bool fxy_valid = false;
+    bool area_valid = false;
+    DevBuf<double> fxy;      // [n_face*m*2] CCW-normalised vertex coordinates per face (only if fxy_valid:
+                             // needed when the mesh is a query kept in the caller's numbering)
+    DevBuf<int32_t> fxy_off; // [n_face+1] only for ragged() meshes: fxy is flat, face f starts at vertex fxy_off[f]
+    DevBuf<uint8_t> len;     // [n_face]
+    DevBuf<double> bbox;     // [n_face*4] xmin,xmax,ymin,ymax; ragged() meshes only (dense ones: query_face_box, xr_geom.h)
+    DevBuf<double> area;     // [n_face]   connectivity.area on the caller's vertex order (mesh_area, on demand)
+    size_t bytes() const { return fxy.bytes() + fxy_off.bytes() + len.bytes() + bbox.bytes() + area.bytes(); }
+    void release() {
+        has_attrs = fxy_valid = area_valid = false;
+        fxy.release(), fxy_off.release(), len.release(), bbox.release(), area.release();
+    }
+};
+
+// If the caller's face numbering is already spatially coherent (mean distance between consecutive faces <= a few face
+// extents) the caller's order IS the query order: no permutation, no copies (identity); xr_mesh::qo_*() hide the difference.
+struct MeshQueryOrder {
+    bool ready = false;
+    bool identity = false;
+    DevBuf<int32_t> perm; // [n_face] position -> caller's face id
+    DevBuf<double> fxy;   // [n_face*m*2], ragged(): [sum len * 2]
+    DevBuf<int32_t> off;  // [n_face+1] ragged() only
+    DevBuf<uint8_t> len;  // [n_face]
+    DevBuf<double> bbox;  // [n_face*4] ragged() only
+    size_t bytes() const { return perm.bytes() + fxy.bytes() + off.bytes() + len.bytes() + bbox.bytes(); }
+    void release() {
+        ready = identity = false;
+        perm.release(), fxy.release(), off.release(), len.release(), bbox.release();
+    }
+};
+
+struct MeshIndex { // tree index (records in grid-cell order)
+    // records of padding behind rec_bb: the record walks (k_search, k_edge_walk) issue several unclamped loads at once, and the
+    // ones beyond a run's end -- masked afterwards -- must stay inside the array
+    static constexpr int REC_BB_PAD = 8;
+    bool ready = false;
+    GridParams grid{};
+    DevBuf<int32_t> cell_start; // [n_cells+1]
+    DevBuf<float> rec_bb;       // [(n_face + REC_BB_PAD)*4] conservative f32 bbox relative to the grid origin
+    DevBuf<int32_t> rec_face;   // [n_face]   record -> caller's face id
+    DevBuf<double> rec_fxy;     // [n_face*m*2], ragged(): [sum len * 2]
+    DevBuf<int32_t> rec_off;    // [n_face+1] ragged() only
+    DevBuf<uint8_t> rec_len;    // [n_face]
+    size_t bytes() const {
+        return cell_start.bytes() + rec_bb.bytes() + rec_face.bytes() + rec_fxy.bytes() + rec_off.bytes() + rec_len.bytes();
+    }
+    void release() {
+        ready = false;
+        cell_start.release(), rec_bb.release(), rec_face.release(), rec_fxy.release(), rec_off.release(), rec_len.release();
+    }
+};
+
+// connectivity.centroids, on demand (mesh_centroids_shared); kept like the reference's cached Ugrid2d.centroids until the mesh
+// is invalidated
+struct MeshCentroids {
+    std::shared_ptr<DevBuf<double>> dev; // [n_face*2]
+    hipEvent_t event = nullptr;   // recorded behind the kernel that filled dev, on `stream`: a user on another stream
+    hipStream_t stream = nullptr; // (the handles' kernels run on the side stream) waits for it
+    MeshCentroids() = default;
+    MeshCentroids(const MeshCentroids &) = delete;
+    MeshCentroids &operator=(const MeshCentroids &) = delete;
+    ~MeshCentroids() {
+        if (event) (void)hipEventDestroy(event);
+    }
+    size_t bytes() const { return dev ? dev->bytes() : 0; }
+    void release() { dev.reset(); } // (a handle that shares them keeps them)
+};
+
+// Kept by the barycentric construction when this mesh is a Voronoi tessellation (xr_locate.hip:barycentric_csr, its only
+// reader): the vertex -> face table with the interpolation map behind it, and the flags of the cells that hold a substitute
+// vertex -- a second interpolator on a cached tessellation uploads and recomputes nothing (its first kernel then runs BESIDE the
+// source-side locate pass instead of behind a copy).  Describes the raw mesh: xr_mesh_invalidate keeps it, and
+// xr_mesh_device_bytes has never counted it.
+struct MeshBaryCache {
+    std::vector<int64_t> ids_host; // what was uploaded (tail of the vertex table, then the map)
+    DevBuf<int64_t> ids;           // [n_node + 2 n_extra + 1]
+    int64_t n_identity = -1, n_extra = -1;
+    DevBuf<uint8_t> cell_flag;     // [n_face], valid for n_extra
+    bool flag_valid = false;
+};
+} // namespace xr
+
+struct xr_mesh : xr::MeshRaw {
+    xr::MeshStatsBox stats;
+    xr::MeshPrepared prep;
+    xr::MeshQueryOrder qo;
+    xr::MeshIndex index;
+    xr::MeshCentroids centroids;
+    xr::MeshBaryCache bary;
+    int64_t last_candidates = 0;
 
     // vertex blocks flat + offsets instead of dense [n_face][m] (xr_geom.h)
     bool ragged() const { return m > xr::DENSE_MAX_NODES; }
-    const int32_t *caller_off() const { return ragged() ? fxy_off.get() : nullptr; }
-    const int32_t *record_off() const { return ragged() ? rec_off.get() : nullptr; }
-    const int32_t *qo_off() const { return !ragged() ? nullptr : query_identity ? fxy_off.get() : q_off.get(); }
-    const double *qo_fxy() const { return query_identity ? fxy.get() : q_fxy.get(); }
-    const uint8_t *qo_len() const { return query_identity ? len.get() : q_len.get(); }
-    const double *qo_bbox() const { return query_identity ? bbox.get() : q_bbox.get(); } // nullptr for dense meshes
-    const int32_t *qo_perm() const { return query_identity ? nullptr : q_perm.get(); } // nullptr = identity
+    const int32_t *caller_off() const { return ragged() ? prep.fxy_off.get() : nullptr; }
+    const int32_t *record_off() const { return ragged() ? index.rec_off.get() : nullptr; }
+    const int32_t *qo_off() const { return !ragged() ? nullptr : qo.identity ? prep.fxy_off.get() : qo.off.get(); }
+    const double *qo_fxy() const { return qo.identity ? prep.fxy.get() : qo.fxy.get(); }
+    const uint8_t *qo_len() const { return qo.identity ? prep.len.get() : qo.len.get(); }
+    const double *qo_bbox() const { return qo.identity ? prep.bbox.get() : qo.bbox.get(); } // nullptr for dense meshes
+    const int32_t *qo_perm() const { return qo.identity ? nullptr : qo.perm.get(); } // nullptr = identity
 };
 
 // Rows with more entries than this are not walked by one thread but reduced cooperatively in the apply kernels:
@@ -182,6 +242,8 @@ struct xr_graph {
 
 namespace xr {
 void label_components(xr_graph *g); // labels = the smallest member id of every component (xr_fill.hip)
+// a mesh handle with its sizes set and node_xy / faces_raw allocated, for the caller to fill (xr_mesh.hip)
+Building<xr_mesh> new_raw_mesh(int64_t n_node, int64_t n_face, int m, OnFailure rule = OnFailure::FreeOnly);
 void mesh_prepare_pair(xr_mesh *tree, xr_mesh *query); // the front of a weight build: both preparations, in one launch where it can be
 void mesh_prepare(xr_mesh *mesh, bool want_fxy = true, bool stats_on_side = false, bool allow_sampled = false); // stats_on_side: the reduction of the
     // statistics (only the HOST reads them) leaves the main stream: kernels queued behind the prepare pass do not wait for it

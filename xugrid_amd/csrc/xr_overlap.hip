@@ -27,6 +27,7 @@
 // THIS unit holds what both pipelines use -- k_search, k_search_big, k_row_fill_long and their launchers (declared in
 // xr_overlap.h), the dust threshold, the rows' tiling keys -- and the entry points.  Device code of the clips: xr_clip.h.
 #include "xr_overlap.h"
+#include "xr_mesh_plan.h"
 #include "xr_apply.h"
 #include "xr_clip.h"
 
@@ -49,7 +50,7 @@ static constexpr int TILE_RUN = 16; // rows per run in the tiling hint (128-byte
 // concatenated); when that tail is short (<= BIGREC_MAX) every block filters it against its own bounding box once
 // (coalesced) and its faces test the few survivors from LDS, instead of every face walking 5-6 all but empty levels:
 // the dependent cell_start -> record round trips of those levels were most of the search time.
-static constexpr int WALK_PAD = 8;       // records of padding behind rec_bb (xr_mesh.hip allocates them): the walk's unclamped loads
+static constexpr int WALK_PAD = MeshIndex::REC_BB_PAD; // records of padding behind rec_bb: the walk's unclamped loads
 static constexpr int BIGREC_MAX = 1024;  // records of the upper grid levels handled as a list
 static constexpr int BIGREC_BLOCK = 64;  // ... of which at most this many may touch one block's bounding box
 
@@ -779,9 +780,11 @@ k_row_fill_long(const int32_t *__restrict__ cand_off, const int32_t *__restrict_
 double overlap_dust_threshold(const xr_mesh *tree, const xr_mesh *query) {
     double mag = 0.0, ext = INFINITY;
     for (const xr_mesh *m : {tree, query}) {
-        const double *h = m->h_stats;
-        mag = std::max(mag, std::max(std::max(fabs(h[0]), fabs(h[1])), std::max(fabs(h[2]), fabs(h[3]))));
-        ext = std::min(ext, m->stats_sampled ? std::max(h[1] - h[0], h[3] - h[2]) : h[5]);
+        const double *h = m->stats.h;
+        mag = std::max(mag, std::max(std::max(fabs(h[stat::XMIN]), fabs(h[stat::XMAX])),
+                                     std::max(fabs(h[stat::YMIN]), fabs(h[stat::YMAX]))));
+        ext = std::min(ext, m->stats.sampled ? std::max(h[stat::XMAX] - h[stat::XMIN], h[stat::YMAX] - h[stat::YMIN])
+                                             : h[stat::MAX_EXTENT]);
     }
     return option(OPT_DUST) == 0 ? 0.0 : 5.7e-14 * mag * ext; // (option "dust" = 0: measurement switch, no confirmation)
 }
@@ -794,7 +797,7 @@ void launch_search(const xr_mesh *tree, const xr_mesh *query, const SearchLists 
     auto launch = [&](auto packed) {
         with_nodes_per_face(query->m, [&](auto mc) {
             XR_LAUNCH("search", (k_search<decltype(packed)::value, mc()>), grid, dim3(256), 0, query->qo_bbox(), query->qo_fxy(),
-                      query->qo_len(), T, tree->grid, tree->n_face, tree->cell_start.get(), tree->rec_bb.get(), l.cand_count.get(),
+                      query->qo_len(), T, tree->index.grid, tree->n_face, tree->index.cell_start.get(), tree->index.rec_bb.get(), l.cand_count.get(),
                       l.cand_off.get(), q.tgt, q.src, q.cursor, l.block_seg.get(), l.is_big.get(), l.big_list.get(), n_big, tile,
                       tile_key, l.nnz_row.get(), REMAP_SEARCH, blk_rows, blk_surv, blk_rows ? (int)q.capacity : 0);
         });
@@ -806,16 +809,16 @@ void launch_search(const xr_mesh *tree, const xr_mesh *query, const SearchLists 
 void launch_search_big(const xr_mesh *tree, const xr_mesh *query, const SearchLists &l, const PairQueue &q, const int32_t *n_big,
                        int32_t *n_pending, int32_t *slot_face) {
     XR_LAUNCH("search_big", k_search_big<true>, dim3(engine().num_cu * 8), dim3(256), sizeof(int32_t) * (size_t)BIG_STAGE,
-              query->qo_bbox(), query->qo_fxy(), query->qo_len(), query->qo_off(), query->m, tree->grid, tree->cell_start.get(),
-              tree->rec_bb.get(), tree->rec_face.get(), l.big_list.get(), n_big, l.cand_off.get(), l.cand_count.get(), q.tgt,
+              query->qo_bbox(), query->qo_fxy(), query->qo_len(), query->qo_off(), query->m, tree->index.grid, tree->index.cell_start.get(),
+              tree->index.rec_bb.get(), tree->index.rec_face.get(), l.big_list.get(), n_big, l.cand_off.get(), l.cand_count.get(), q.tgt,
               q.src, q.cursor, q.capacity, l.pending.get(), n_pending, BIG_STAGE, slot_face);
 }
 
 void launch_search_big_fill(const xr_mesh *tree, const xr_mesh *query, const SearchLists &l, const PairQueue &q,
                             const int32_t *n_pending) {
     XR_LAUNCH("search_big_fill", k_search_big<false>, dim3(engine().num_cu * 8), dim3(256), sizeof(int32_t), query->qo_bbox(),
-              query->qo_fxy(), query->qo_len(), query->qo_off(), query->m, tree->grid, tree->cell_start.get(), tree->rec_bb.get(),
-              tree->rec_face.get(), l.pending.get(), n_pending, l.cand_off.get(), l.cand_count.get(), q.tgt, q.src,
+              query->qo_fxy(), query->qo_len(), query->qo_off(), query->m, tree->index.grid, tree->index.cell_start.get(), tree->index.rec_bb.get(),
+              tree->index.rec_face.get(), l.pending.get(), n_pending, l.cand_off.get(), l.cand_count.get(), q.tgt, q.src,
               (int32_t *)nullptr, q.capacity, (int32_t *)nullptr, (int32_t *)nullptr, 0);
 }
 
@@ -840,21 +843,14 @@ void launch_row_fill_long(int row_class, const xr_mesh *tree, const SearchLists 
 static MortonParams tile_key_params(const xr_mesh *query, xr_csr *csr) {
     MortonParams tile{};
     csr->has_tile_key = false;
-    if (!query->query_identity) return tile;
+    if (!query->qo.identity) return tile;
     const int64_t T = query->n_face;
-    const double *hs = query->h_stats;
-    double span = std::max(hs[1] - hs[0], hs[3] - hs[2]);
-    if (!(span > 0)) span = 1.0;
     // tile edge <= 12 mean extents (the side count is a power of two): about one block of 256 triangles per tile
-    double h = 12.0 * hs[4] / (double)T;
-    if (!(h > 0)) h = span;
-    int bits = 0;
-    while (bits < 12 && ldexp(h, bits) < span) bits++;
-    tile = MortonParams{hs[0], hs[2], (double)(1 << bits) / (span * (1.0 + 1e-9)), 1 << bits};
+    tile = morton_cover(query->stats.h, T, 12.0, 0, 12);
     tile.n_run = TILE_RUN;
     csr->tile_key.alloc((size_t)T);
-    csr->tile_key_range = (int64_t)1 << (2 * bits);
-    csr->has_tile_key = bits > 0;
+    csr->tile_key_range = (int64_t)tile.n_side * tile.n_side;
+    csr->has_tile_key = tile.n_side > 1;
     return tile;
 }
 

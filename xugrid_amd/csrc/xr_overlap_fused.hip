@@ -519,11 +519,11 @@ static void launch_clip_queue(const FusedBuild &b, const char *name, int blocks_
     const int64_t capacity = COUNT == 1 ? -q.capacity : q.capacity; // (< 0: eight regions of that many pairs)
     auto launch = [&](auto kind, size_t maxv, const uint8_t *q_len, const uint8_t *s_len) {
         XR_LAUNCH(name, (k_clip_tri_queue<BLOCK, COUNT, kind()>), dim3(engine().num_cu * blocks_per_cu), dim3(BLOCK),
-                  (maxv + 1) * BLOCK * sizeof(double2), b.query->qo_fxy(), b.tree->rec_fxy.get(), b.tree->rec_face.get(), q.tgt, q.src,
+                  (maxv + 1) * BLOCK * sizeof(double2), b.query->qo_fxy(), b.tree->index.rec_fxy.get(), b.tree->index.rec_face.get(), q.tgt, q.src,
                   q.cursor, capacity, area, sid, error, nnz_row, skip_if, blk_surv, b.dust, q_len, s_len, b.query->m, b.tree->m);
     };
     if (b.tri_pair) launch(std::integral_constant<int, 0>(), TRI_MAXV, nullptr, nullptr);
-    else launch(std::integral_constant<int, 1>(), 8, b.query->qo_len(), b.tree->rec_len.get());
+    else launch(std::integral_constant<int, 1>(), 8, b.query->qo_len(), b.tree->index.rec_len.get());
 }
 
 // (1) the matrix and the big faces' buffers sized for this attempt's capacities; a control block that is zero

@@ -337,8 +337,8 @@ static void launch_clip(const xr_mesh *tree, const xr_mesh *query, const int32_t
     allow_dynamic_lds<&k_clip<MAXV, BLOCK>>(shmem);
     XR_LAUNCH(MAXV == 8 ? "clip_v8" : (MAXV == 16 ? "clip_v16" : "clip_v64"), (k_clip<MAXV, BLOCK>),
               dim3(div_up(C, BLOCK)), dim3(BLOCK), shmem, query->qo_fxy(), query->qo_len(), query->qo_off(), query->m,
-              query->qo_perm(), tree->rec_fxy.get(), tree->rec_len.get(), tree->record_off(), tree->m, cand_tgt, cand_src, C, cand_area,
-              redo_only, tree->rec_face.get(), cand_sid, overflow_count, nnz_row, overlap_dust_threshold(tree, query));
+              query->qo_perm(), tree->index.rec_fxy.get(), tree->index.rec_len.get(), tree->record_off(), tree->m, cand_tgt, cand_src, C, cand_area,
+              redo_only, tree->index.rec_face.get(), cand_sid, overflow_count, nnz_row, overlap_dust_threshold(tree, query));
 }
 
 static void launch_clip_for(const xr_mesh *tree, const xr_mesh *query, const int32_t *cand_tgt, const int32_t *cand_src,
@@ -356,20 +356,20 @@ static void launch_clip_for(const xr_mesh *tree, const xr_mesh *query, const int
         constexpr int MAXV = 6;
         const size_t shmem = (size_t)(MAXV + 1) * BLOCK * sizeof(double2); // + one trash row for clamped pushes
         XR_LAUNCH("clip_tri", (k_clip_tri<BLOCK, 3>), grid, dim3(BLOCK), shmem, query->qo_fxy(), (const uint8_t *)nullptr,
-                  tree->rec_fxy.get(), cand_tgt, cand_src, C, cand_area, tree->rec_face.get(), cand_sid, overflow_count, nnz_row, remap,
+                  tree->index.rec_fxy.get(), cand_tgt, cand_src, C, cand_area, tree->index.rec_face.get(), cand_sid, overflow_count, nnz_row, remap,
                   dust);
     } else if (query->m == 4 && tree->m == 3 && option(OPT_CLIP_QUAD) != 0) {
         // quadrilateral targets (a raster) x triangle source (option "clip_quad" = 0: the slot-loop kernel, test switch)
         const size_t shmem = (size_t)(QUAD_MAXV + 2) * BLOCK * sizeof(double2);
         XR_LAUNCH("clip_quad_tri", (k_clip_tri<BLOCK, 4>), grid, dim3(BLOCK), shmem,
-                  query->qo_fxy(), query->qo_len(), tree->rec_fxy.get(), cand_tgt, cand_src, C, cand_area, tree->rec_face.get(),
+                  query->qo_fxy(), query->qo_len(), tree->index.rec_fxy.get(), cand_tgt, cand_src, C, cand_area, tree->index.rec_face.get(),
                   cand_sid, overflow_count, nnz_row, remap, dust);
     } else {
         constexpr int MAXV = 8;
         const size_t shmem = (size_t)(MAXV + 1) * BLOCK * sizeof(double2); // + one trash row for clamped pushes
         XR_LAUNCH("clip_small", (k_clip_small<MAXV, BLOCK>), grid, dim3(BLOCK),
-                  shmem, query->qo_fxy(), query->qo_len(), query->qo_off(), query->m, query->qo_perm(), tree->rec_fxy.get(),
-                  tree->rec_len.get(), tree->record_off(), tree->m, cand_tgt, cand_src, C, cand_area, tree->rec_face.get(), cand_sid,
+                  shmem, query->qo_fxy(), query->qo_len(), query->qo_off(), query->m, query->qo_perm(), tree->index.rec_fxy.get(),
+                  tree->index.rec_len.get(), tree->record_off(), tree->m, cand_tgt, cand_src, C, cand_area, tree->index.rec_face.get(), cand_sid,
                   overflow_count, nnz_row, remap, dust);
     }
 }

@@ -343,10 +343,7 @@ int xr_mesh_reorder_faces_dev(const xr_mesh *mesh, const int64_t *order_dev, xr_
     *out = nullptr;
     const int64_t F = mesh->n_face, N = mesh->n_node;
     const int m = mesh->m;
-    Building<xr_mesh> made(OnFailure::WaitFirst);
-    made->n_node = N, made->n_face = F, made->m = m;
-    made->node_xy.alloc((size_t)N * 2);
-    made->faces_raw.alloc((size_t)(F * m));
+    Building<xr_mesh> made = new_raw_mesh(N, F, m, OnFailure::WaitFirst);
     if (N > 0)
         XR_HIP(hipMemcpyAsync(made->node_xy.get(), mesh->node_xy.get(), sizeof(double) * (size_t)N * 2, hipMemcpyDeviceToDevice,
                               launch_stream()));

@@ -409,7 +409,7 @@ void snapgrid_build(xr_snapgrid *h, xr_mesh *mesh, const xr_topology *topology, 
         auto rows = [&](auto fill, int32_t *cursor, int32_t *u_seg, int32_t *u_edge, double4 *u_xy, int32_t *order, int64_t n_row) {
             with_nodes_per_face(topology->m, [&](auto mc) {
                 XR_LAUNCH(fill() ? "snapgrid_rows_fill" : "snapgrid_rows_count", (k_sg_rows<fill(), mc()>), dim3(div_up(P, SG)), dim3(SG),
-                          0, entry_face.get(), csr->indices.get(), P, mesh->fxy.get(), mesh->len.get(), mesh->caller_off(), mesh->m,
+                          0, entry_face.get(), csr->indices.get(), P, mesh->prep.fxy.get(), mesh->prep.len.get(), mesh->caller_off(), mesh->m,
                           seg.get(), reinterpret_cast<const double2 *>(centroids->get()), topology->face_edge.get(), topology->m,
                           reinterpret_cast<const int2 *>(topology->edge_face.get()), tolerance, count.get(), seg_hist.get(),
                           total_dev.get(), row_off.get(), bucket_start.get(), cursor, u_seg, u_edge, u_xy, order, n_row);

@@ -674,12 +674,7 @@ int xr_voronoi_mesh(const xr_voronoi *v, const double *extra_xy, int64_t n_extra
             table[(size_t)(r * mb + j)] = (int32_t)c;
         }
     }
-    Building<xr_mesh> mesh;
-    mesh->n_node = n_vertex;
-    mesh->n_face = n_cell;
-    mesh->m = m;
-    mesh->node_xy.alloc((size_t)n_vertex * 2);
-    mesh->faces_raw.alloc((size_t)(n_cell * m));
+    Building<xr_mesh> mesh = new_raw_mesh(n_vertex, n_cell, m);
     if (n_generator > 0)
         XR_HIP(hipMemcpyAsync(mesh->node_xy.get(), v->centroids.get(), sizeof(double) * 2 * (size_t)n_generator,
                               hipMemcpyDeviceToDevice, launch_stream()));

@@ -630,7 +630,7 @@ class Ugrid2d:
 
         return periodic.to_nonperiodic(self, xmax, data, dim, return_index)
 
-    # ---- meshes and per-face geometry derived on the device (csrc/xr_mesh.hip: triangulation, circumcenters, perimeter,
+    # ---- meshes and per-face geometry derived on the device (csrc/xr_mesh_derived.hip: triangulation, circumcenters, perimeter,
     # face bounds; csrc/xr_voronoi.hip: the tessellations)
     _device_resident = False  # True: the mesh exists in HBM only; derived grids stay there and indices are device arrays
 
