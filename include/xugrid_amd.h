@@ -436,6 +436,32 @@ int xr_apply_outer(xr_outer *outer, int method, double percentile, const void *s
                    int source_dtype, int64_t K, double *out);
 int xr_apply_outer_dev(xr_outer *outer, int method, double percentile, const void *source_dev,
                        int source_dtype, int64_t K, double *out_dev);
+/* ---- the adjoint of the apply: target-side quantities (gradients, residuals, sensitivities) back onto the source ------
+ * For the reducers that are linear in the source values for a fixed NaN pattern -- XR_MEAN, XR_SUM,
+ * XR_FIRST_ORDER_CONSERVATIVE, XR_SELECT; every other id is XR_ERR_INVALID -- with W the T x S matrix in the ids the applies
+ * use (entries e = (i, j, w) at storage position p), v the forward input (K, S), g (K, T) float64:
+ *     valid(k, e) = !isnan(v[k, j]);   Wsum[k, i] = sum of w over the valid entries of row i, by the forward's own row walk
+ *     row i is live for k when Wsum[k, i] != 0 (XR_SELECT: when it is not empty)
+ *     r[k, i] = g[k, i] / Wsum[k, i] (XR_MEAN), g[k, i] (the others)
+ *     coefficient of e: w (XR_MEAN, XR_FIRST_ORDER_CONSERVATIVE), 1 (XR_SUM), 1 on the row's last entry else 0 (XR_SELECT)
+ *     out[k, j] = sum of r[k, i] * coefficient(e) over the entries of column j whose row is live, in ascending (i, p) order;
+ *                 +0.0 for an empty sum and wherever v[k, j] is NaN (XR_SELECT ignores NaN: its forward copies them)
+ * A row that is not live contributes nothing whatever g holds there; on live rows plain IEEE arithmetic applies.  Columns of
+ * more than 32 entries are summed by a wave, of more than 2048 by a block, in a fixed order: no floating-point atomics, the
+ * same bits on every call.  source == NULL: no NaN in the source.  out: float64 (K, S).
+ * The first call transposes the weights on the device and keeps the result inside the handle (12 bytes per entry + 4 per
+ * column and listed long column; xr_csr_drop_transpose releases it, the next call rebuilds it).  xr_csr_transpose returns that
+ * structure as an independent S x T matrix: rows = the columns of `csr` in the caller's ids, entries in ascending (i, p).
+ * A matrix whose source blocks arrive pre-permuted (xr_csr_expect_permuted) is XR_ERR_INVALID. */
+int xr_csr_transpose(const xr_csr *csr, xr_csr **out);
+int xr_csr_drop_transpose(xr_csr *csr);
+int xr_apply_csr_adjoint(const xr_csr *csr, int method, const void *source, int source_dtype, const double *grad,
+                         int64_t K, double *out);
+int xr_apply_csr_adjoint_dev(const xr_csr *csr, int method, const void *source_dev, int source_dtype,
+                             const double *grad_dev, int64_t K, double *out_dev);
+/* ... on factored separable weights: through the materialised CSR the handle keeps (xr_outer_csr) */
+int xr_apply_outer_adjoint_dev(xr_outer *outer, int method, const void *source_dev, int source_dtype,
+                               const double *grad_dev, int64_t K, double *out_dev);
 /* CentroidLocatorRegridder._regrid, regridder.py:400-409: out[k,row[i]] = source[k,col[i]],
  * NaN elsewhere.  rows must be unique (they are target indices of located centroids). */
 int xr_apply_coo(const int64_t *row, const int64_t *col, int64_t nnz, int64_t T,

@@ -123,6 +123,11 @@ SIGNATURES = {
     "xr_apply_csr": (c_int, [vp, c_int, c_f64, vp, c_int, c_i64, vp]),
     "xr_apply_csr_dev": (c_int, [vp, c_int, c_f64, vp, c_int, c_i64, vp]),
     "xr_apply_coo": (c_int, [vp, vp, c_i64, c_i64, vp, c_int, c_i64, c_i64, vp]),
+    "xr_csr_transpose": (c_int, [vp, p_vp]),
+    "xr_csr_drop_transpose": (c_int, [vp]),
+    "xr_apply_csr_adjoint": (c_int, [vp, c_int, vp, c_int, vp, c_i64, vp]),
+    "xr_apply_csr_adjoint_dev": (c_int, [vp, c_int, vp, c_int, vp, c_i64, vp]),
+    "xr_apply_outer_adjoint_dev": (c_int, [vp, c_int, vp, c_int, vp, c_i64, vp]),
     "xr_partial_components": (c_int, [c_int]),
     "xr_partial_combine_is_max": (c_int, [c_int]),
     "xr_apply_partial_dev": (c_int, [vp, c_int, vp, c_int, c_i64, vp, c_int]),

@@ -17,6 +17,9 @@ static constexpr int AP_BLOCK = 256;
 // the reference's sequential loop (agreement ~1e-15 relative instead of bit-exact).
 static constexpr int APPLY_LONG = XR_APPLY_LONG_ROW;
 static constexpr int APPLY_WAVE = XR_APPLY_WAVE_ROW;
+// ... by a group of 16 lanes up to APPLY_GROUP16 entries, by all 64 beyond (apply_row_group, xr_apply.hip; the row pass of
+// the adjoint walks the same way, xr_adjoint.hip)
+static constexpr int APPLY_GROUP16 = 512;
 
 // the wave window of the K = 1 kernels (k_apply_rows1, k_apply_partial_w1)
 static constexpr int W1_CAP = 384; // entries per wave window: 64 rows x 4 entries (the mean of a triangle pair) + slack for the tail
@@ -93,5 +96,12 @@ void csr_apply_dev(const xr_csr *csr, int method, double percentile, const void 
                    const ApplyContext *ctx = nullptr);
 void csr_partial_dev(const xr_csr *csr, int method, const void *src_dev, int dtype, int64_t K, double *out_dev, int rows_layout,
                      const ApplyContext *ctx = nullptr);
+
+// xr_adjoint.hip
+void ensure_transposed(const xr_csr *csr);                        // the transposed weights of the adjoint (exclusive scope)
+int prepare_for_adjoint(const xr_csr *csr, int method);           // ... in front of a shared-scope adjoint (checks the reducer first)
+// the adjoint of csr_apply_dev for the reducers that are linear in the source (src_dev may be NULL: no NaN in the source)
+void csr_adjoint_dev(const xr_csr *csr, int method, const void *src_dev, int dtype, const double *grad_dev, int64_t K,
+                     double *out_dev);
 
 } // namespace xr

@@ -120,8 +120,7 @@ k_apply_long(const int32_t *__restrict__ indptr, const int32_t *__restrict__ ind
 // The lanes of a group stride the row (entry j goes to lane j % G), so the CSR entries are read coalesced and
 // -- rows are sorted by column -- neighbouring lanes gather neighbouring source values; the group's partial
 // states are merged by a butterfly of log2(G) shuffles.  A lane's first four entries stay in registers across
-// the variable tiles.
-static constexpr int APPLY_GROUP16 = 512;
+// the variable tiles.  (APPLY_GROUP16: xr_apply.h)
 
 template <int METHOD, typename SRC, int KTILE, int G>
 __device__ __forceinline__ void apply_row_group(const int32_t *__restrict__ indices, const double *__restrict__ data,

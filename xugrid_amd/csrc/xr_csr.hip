@@ -163,6 +163,9 @@ void ensure_tiled(const xr_csr *ccsr) {
     csr->n_long = std::move(t_nlong);
     csr->has_long = nl > 0;
     csr->plan_ready = false;
+    // transposed weights built while the matrix delivered in stored order hold stored row positions: stale from here on
+    // (built in the caller's ids they are untouched: ensure_transposed, xr_adjoint.hip)
+    if (csr->tr_output_stored) csr->tr_ready = false;
     csr->tile_key.release();
 }
 

@@ -213,6 +213,17 @@ struct xr_csr {
     xr::DevBuf<int32_t> plan_ucol;   // [n_blocks * PLAN_UMAX]
     xr::DevBuf<int32_t> plan_nuniq;  // [n_blocks], -1 = block not planned (falls back to direct gathers)
     xr::DevBuf<uint16_t> plan_loc;   // [nnz]
+    // the transposed weights of the adjoint apply (built lazily, xr_adjoint.hip: ensure_transposed), in the ids the applies
+    // use -- caller's columns, output rows -- with a copy of every weight: per column the entries in ascending (row, storage
+    // position).  Built in the caller's row ids, no re-layout of the stored matrix touches them; built in stored positions
+    // (tr_output_stored), the row tiling invalidates them (ensure_tiled) and the next adjoint rebuilds them
+    bool tr_ready = false;
+    bool tr_output_stored = false;  // the row ids are stored positions (the matrix delivered in stored order when this was built)
+    xr::DevBuf<int32_t> tr_indptr;  // [m+1]
+    xr::DevBuf<uint32_t> tr_row;    // [nnz] row id; bit 31: the entry is the last of its row (what XR_SELECT copies)
+    xr::DevBuf<double> tr_w;        // [nnz]
+    xr::DevBuf<int32_t> tr_long;    // [tr_n_long] columns with more than XR_APPLY_LONG_ROW entries, ascending
+    int64_t tr_n_long = 0, tr_max_len = 0;
 };
 
 // Separable (rectilinear) weights kept as the two per-axis sparse matrices (xugrid/regrid/structured.py:503-601): the

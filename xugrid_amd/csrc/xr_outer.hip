@@ -335,6 +335,19 @@ int xr_apply_outer_dev(xr_outer *o, int method, double percentile, const void *s
     XR_API_END
 }
 
+// the adjoint of the apply (xr_adjoint.hip) needs the entries of a column side by side: through the materialised CSR
+int xr_apply_outer_adjoint_dev(xr_outer *o, int method, const void *source_dev, int source_dtype, const double *grad_dev,
+                               int64_t K, double *out_dev) {
+    XR_API_BEGIN
+    XR_REQUIRE(o && K >= 0 && ((grad_dev && out_dev) || K == 0), XR_ERR_INVALID, "xr_apply_outer_adjoint_dev: invalid argument");
+    if (const int rc = prepare_for_adjoint(o->csr, method)) return rc; // (the reducer is checked before anything is built)
+    if (!o->csr) o->csr = outer_materialise(o);
+    ensure_transposed(o->csr);
+    csr_adjoint_dev(o->csr, method, source_dev, source_dtype, grad_dev, K, out_dev);
+    dev_call_done();
+    XR_API_END
+}
+
 int xr_apply_outer(xr_outer *o, int method, double percentile, const void *source, int source_dtype, int64_t K, double *out) {
     XR_API_BEGIN
     XR_REQUIRE(o && (source || K == 0) && (out || K == 0), XR_ERR_INVALID, "xr_apply_outer: NULL argument");

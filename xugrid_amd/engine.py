@@ -1171,6 +1171,48 @@ def _apply_dev(fn, weights, source_ptr, dtype, K, out_ptr, method_id, percentile
              ctypes.c_void_p(out_ptr)))
 
 
+# the reducers whose apply has an adjoint: linear in the source values for a fixed NaN pattern (include/xugrid_amd.h)
+ADJOINT_METHOD_IDS = frozenset(METHOD_IDS[name] for name in ("mean", "sum", "first_order_conservative", "select"))
+
+
+def check_adjoint_method(method_id, name=None):
+    """NotImplementedError naming the reducer unless its apply has an adjoint."""
+    if int(method_id) not in ADJOINT_METHOD_IDS:
+        if name is None:
+            name = next((k for k, v in METHOD_IDS.items() if v == int(method_id)), f"id {method_id}")
+        raise NotImplementedError(
+            f"the adjoint (gradient) of the {name!r} reduction is not implemented: its coefficients depend on the source "
+            "values themselves; mean, sum, first_order_conservative / conductance and the centroid locator are served"
+        )
+
+
+def _adjoint_host(fn, weights, source, grad, method_id, out):
+    """The host-array adjoint of DeviceCSR through the C entry point ``fn``: grad (K, T), source (K, S) or None ->
+    float64 (K, S)."""
+    check_adjoint_method(method_id)
+    g = np.ascontiguousarray(np.asarray(grad), dtype=np.float64)
+    if g.ndim != 2 or g.shape[1] != weights.n:
+        raise ValueError(f"grad must be 2-D (n_extra, {weights.n}), received shape {g.shape}")
+    K = g.shape[0]
+    src, dtype = (None, XR_F64) if source is None else _source_2d(source)
+    if src is not None and src.shape != (K, weights.m):
+        raise ValueError(f"source must have shape {(K, weights.m)}, received {src.shape}")
+    if out is None:
+        out = np.empty((K, weights.m), dtype=np.float64)
+    elif out.shape != (K, weights.m) or out.dtype != np.float64 or not out.flags.c_contiguous:
+        raise ValueError(f"out must be a C-contiguous float64 array of shape {(K, weights.m)}")
+    check(fn(weights._h, int(method_id), None if src is None else _ptr(src), dtype, _ptr(g), K, _ptr(out)))
+    return out
+
+
+def _adjoint_dev(fn, weights, source_ptr, dtype, grad_ptr, K, out_ptr, method_id):
+    """The device-pointer adjoint of DeviceCSR / DeviceOuter through the C entry point ``fn`` (``source_ptr`` 0 / None: no
+    NaN in the source)."""
+    check_adjoint_method(method_id)
+    check(fn(weights._h, int(method_id), ctypes.c_void_p(source_ptr) if source_ptr else None, int(dtype),
+             ctypes.c_void_p(grad_ptr), int(K), ctypes.c_void_p(out_ptr)))
+
+
 class DeviceCSR(Handle):
     """MatrixCSR resident in HBM: rows = target faces, columns = source faces."""
 
@@ -1309,6 +1351,28 @@ class DeviceCSR(Handle):
         """Device-pointer variant (e.g. torch tensor .data_ptr()); no host transfer."""
         _apply_dev(_lib.load().xr_apply_csr_dev, self, source_ptr, dtype, K, out_ptr, method_id, percentile)
 
+    def transpose(self) -> "DeviceCSR":
+        """The transposed matrix (S x T) as an independent handle, in the ids the applies use: row j holds the entries of
+        column j in ascending (row, storage position) order -- what ``scipy.sparse.csr_matrix(...).T.tocsr()`` gives,
+        duplicates kept.  Built on the device; the structure stays cached inside this matrix for ``adjoint``."""
+        handle = ctypes.c_void_p()
+        check(_lib.load().xr_csr_transpose(self._h, ctypes.byref(handle)))
+        return DeviceCSR(handle)
+
+    def drop_transpose(self):
+        """Release the cached transposed weights (about 12 bytes per entry); the next ``adjoint`` rebuilds them."""
+        check(_lib.load().xr_csr_drop_transpose(self._h))
+
+    def adjoint(self, source, grad, method_id=0, out=None):
+        """The adjoint of ``apply`` for the reducers that are linear in the source (mean, sum, first_order_conservative,
+        select): grad (K, T) -> float64 (K, S).  ``source``: the forward input (K, S), read for its NaN pattern only;
+        None = no NaN.  Contract: include/xugrid_amd.h, xr_apply_csr_adjoint."""
+        return _adjoint_host(_lib.load().xr_apply_csr_adjoint, self, source, grad, method_id, out)
+
+    def adjoint_dev(self, source_ptr, dtype, grad_ptr, K, out_ptr, method_id=0):
+        """Device-pointer variant: grad float64 (K, T) and out float64 (K, S) in HBM; ``source_ptr`` may be 0 / None."""
+        _adjoint_dev(_lib.load().xr_apply_csr_adjoint_dev, self, source_ptr, dtype, grad_ptr, K, out_ptr, method_id)
+
     def partial_dev(self, source_ptr, dtype, K, out_ptr, method_id, rows_layout):
         """partial reducer state over this matrix' columns (multi-GPU split): planes [C, K, n] or rows [n, C * K]"""
         check(
@@ -1354,6 +1418,13 @@ class DeviceOuter(Handle):
 
     def apply_dev(self, source_ptr, dtype, K, out_ptr, method_id=0, percentile=0.0):
         _apply_dev(_lib.load().xr_apply_outer_dev, self, source_ptr, dtype, K, out_ptr, method_id, percentile)
+
+    def adjoint(self, source, grad, method_id=0, out=None):
+        """As ``DeviceCSR.adjoint``: the entries of a column are needed side by side, so it runs on the materialised product."""
+        return self.csr().adjoint(source, grad, method_id, out)
+
+    def adjoint_dev(self, source_ptr, dtype, grad_ptr, K, out_ptr, method_id=0):
+        _adjoint_dev(_lib.load().xr_apply_outer_adjoint_dev, self, source_ptr, dtype, grad_ptr, K, out_ptr, method_id)
 
 
 SHARD_MODES = {"hash": 0, "morton": 1, "balanced": 2}

@@ -214,6 +214,13 @@ class BaseRegridder(abc.ABC):
             return self._regrid_array(data)
         info = engine.device_array_info(data)
         if info is not None:
+            if engine.is_torch(data) and data.requires_grad:
+                from .. import autograd
+
+                if autograd.grad_enabled():
+                    # a tensor of an autograd graph: the result carries a grad_fn whose backward is ``regrid_adjoint``
+                    # (an unsupported reduction raises instead of returning a result cut from the graph)
+                    return autograd.regrid(self, data)
             return self._regrid_device(data, info)
         if hasattr(data, "values") and hasattr(data, "dims"):
             values = np.asarray(data.values)
@@ -232,6 +239,82 @@ class BaseRegridder(abc.ABC):
             values = np.transpose(values, [dims.index(d) for d in other] + [dims.index(d) for d in source_dims])
             return self._regrid_array(np.ascontiguousarray(values))
         raise TypeError(f"Expected DataArray or UgridDataAray, received: {type(data).__name__}")
+
+    # ---- adjoint of the apply (no counterpart in the reference)
+    def _adjoint_method(self):
+        """The reducer id of ``regrid_adjoint``; NotImplementedError naming the method where the apply has no adjoint."""
+        if getattr(self, "_method", True) is None:
+            raise NotImplementedError("the adjoint (gradient) of a custom Python reduction is not implemented")
+        method_id, _ = self._apply_method()
+        engine.check_adjoint_method(method_id, getattr(getattr(self, "_method", None), "name", None))
+        return method_id
+
+    def _leading_shape(self, shape, grid, what):
+        nd = grid.ndim
+        if len(shape) < nd or tuple(shape[len(shape) - nd:]) != tuple(grid.shape):
+            raise ValueError(
+                f"{what} does not contain regridder {'target' if grid is self._target else 'source'} dimensions: trailing "
+                f"shape {grid.shape} expected, received {tuple(shape)}"
+            )
+        return tuple(shape[: len(shape) - nd])
+
+    def regrid_adjoint(self, grad, data=None):
+        """
+        The adjoint of ``regrid``: target-side quantities (an upstream gradient, residuals, sensitivities) back onto the
+        source grid.  For the reductions that are linear in the data for a fixed NaN pattern -- ``mean``, ``sum``,
+        ``first_order_conservative`` / ``conductance``, the centroid locator and the barycentric interpolator -- it is the
+        exact transpose of what ``regrid`` computes; any other method raises NotImplementedError.
+
+        grad: ``(..., *target.shape)``, numpy or a device array; data: the forward input ``(..., *source.shape)`` with the
+        same leading dimensions, read for its NaN pattern only (None: no NaN).  Returns float64 ``(..., *source.shape)`` of
+        the same kind as ``grad``: zero where ``data`` is NaN, and nothing flows from target cells the forward left NaN.
+        The summation order is fixed: the same bits on every call.
+        """
+        method_id = self._adjoint_method()
+        if isinstance(grad, np.ndarray):
+            lead = self._leading_shape(grad.shape, self._target, "grad")
+            g = np.ascontiguousarray(grad, dtype=np.float64).reshape((-1, self._target.size))
+            src = None
+            if data is not None:
+                if not isinstance(data, np.ndarray):
+                    raise TypeError("grad and data must be of the same kind (both numpy, or both on the device)")
+                if self._leading_shape(data.shape, self._source, "data") != lead:
+                    raise ValueError(f"data and grad differ in their leading dimensions: {data.shape} and {grad.shape}")
+                src = data.reshape((-1, self._source.size))
+            weights = self._checked_device_weights()
+            return weights.adjoint(src, g, method_id).reshape(lead + tuple(self._source.shape))
+        info = engine.device_array_info(grad)
+        if info is None:
+            raise TypeError(f"Expected numpy.ndarray or a device array. Received: {type(grad).__name__}")
+        g_ptr, g_shape, g_dtype = info
+        if g_dtype != np.dtype(np.float64):
+            raise TypeError(f"a device gradient must be float64, received {g_dtype}")
+        lead = self._leading_shape(g_shape, self._target, "grad")
+        K = int(np.prod(lead, dtype=np.int64)) if lead else 1
+        src_ptr, dtype_id = 0, engine.XR_F64
+        if data is not None:
+            d_info = engine.device_array_info(data)
+            if d_info is None:
+                raise TypeError("grad and data must be of the same kind (both numpy, or both on the device)")
+            src_ptr, d_shape, d_dtype = d_info
+            if d_dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+                raise TypeError(f"device data must be float64 or float32, received {d_dtype}")
+            if self._leading_shape(d_shape, self._source, "data") != lead:
+                raise ValueError(f"data and grad differ in their leading dimensions: {tuple(d_shape)} and {tuple(g_shape)}")
+            dtype_id = engine.XR_F64 if d_dtype == np.dtype(np.float64) else engine.XR_F32
+            engine.sync_producer(data)
+        out, out_ptr = engine.empty_like_device(grad, lead + tuple(self._source.shape), np.float64)
+        engine.sync_producer(grad)
+        self._checked_device_weights().adjoint_dev(src_ptr, dtype_id, g_ptr, K, out_ptr, method_id)
+        engine.dev_sync()  # (as _regrid_device: complete when the call returns, whatever stream its consumer uses)
+        return out
+
+    def _checked_device_weights(self):
+        weights = self._ensure_device_weights()
+        rows = getattr(weights, "n", self._target.size)
+        if rows != self._target.size:
+            raise ValueError(f"the weights have {rows} rows, the target grid {self._target.size} cells")
+        return weights
 
     def _data_source_dims(self, data, dims):
         if isinstance(self._source, StructuredGrid2d):
@@ -476,7 +559,13 @@ class CentroidLocatorRegridder(BaseRegridder):
             w = self._weights
             if w is None:
                 raise ValueError("Weights have not been computed yet.")
-            self._device_weights = engine.DeviceCSR.from_triplet(w.row, w.col, w.data, w.n, w.m)
+            row, col, data = np.asarray(w.row), np.asarray(w.col), np.asarray(w.data)
+            if row.size and (np.diff(row) < 0).any():
+                # externally supplied, unsorted COO weights (the numpy forward scatters them as they are, ``_regrid``): the
+                # device matrix wants ascending rows; a stable sort keeps the order of a row's entries, so "the last wins"
+                order = np.argsort(row, kind="stable")
+                row, col, data = row[order], col[order], data[order]
+            self._device_weights = engine.DeviceCSR.from_triplet(row, col, data, w.n, w.m)
         return self._device_weights
 
     @classmethod
