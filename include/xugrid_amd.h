@@ -1091,6 +1091,67 @@ int xr_snapgrid_copy_dev(const xr_snapgrid *snapgrid, int what, void *out_dev);
 int xr_snapgrid_values_dev(const xr_snapgrid *snapgrid, const double *values_dev, int64_t K, double *out_dev);
 int xr_snapgrid_destroy(xr_snapgrid *snapgrid);
 
+/* ---- meshes from cell geometry: sorted unique rows, CF cell bounds, lattices, rings and lines; xr_geometry.hip, DESIGN
+ * section 24.  Every pointer argument whose name ends in _dev is device memory; inputs are only read.
+ *
+ * xr_unique_xy_dev: np.unique of xy_dev float64[n, 2] along axis 0 with return_index and return_inverse.  Two rows are one
+ * when both coordinates compare == as doubles (-0.0 == 0.0); the kept bits are those of the first such row in input order; the
+ * unique rows ascend by x, then by y, with < on doubles.  index[u] is the input position of the kept row, inverse[i] the
+ * sorted rank of row i's key.  Rows with a NaN or an infinity are counted: with any, the handle holds the count only and the
+ * caller words the error.  The key table of xr_merge_meshes_dev finds the first occurrences; they are sorted by a stable LSD
+ * radix sort, one byte per pass, over the order-preserving images of the coordinates; passes whose byte is equal in all
+ * keys are skipped.  XR_ERR_LIMIT: n >= 2^30.
+ * xr_unique_xy_info: sizes[5] = n, n_unique, rows with a non-finite coordinate, sort passes run, sort passes skipped.
+ * xr_unique_xy_copy_dev: what 0 the unique rows float64[n_unique, 2], 1 index int64[n_unique], 2 inverse int64[n]. */
+typedef struct xr_unique_xy xr_unique_xy;
+int xr_unique_xy_dev(const double *xy_dev, int64_t n, xr_unique_xy **out);
+int xr_unique_xy_info(const xr_unique_xy *unique, int64_t *sizes);
+int xr_unique_xy_copy_dev(const xr_unique_xy *unique, int what, void *out_dev);
+int xr_unique_xy_destroy(xr_unique_xy *unique);
+
+/* xr_mesh_from_bounds_dev: conversion.bounds2d_to_topology2d (conversion.py:297-354) on x_dev / y_dev float64[n_cell, 4], the
+ * four corners of every cell in any order.  Per cell: the corners sorted by x, then y; n_unique = corners that differ from
+ * their cyclic predecessor; valid = n_unique >= 3 and quad_area > 0 (the fan from the first sorted corner, |.| per triangle).
+ * index_out_dev uint8[n_cell] (bytes 0 / 1) = valid and all eight coordinates finite.  The cells of the index, in order, become the faces:
+ * their corners ordered by atan2 about the mean corner (a corner at its sorted predecessor's angle goes last, ties keep the
+ * sorted order), numbered by the rule of xr_unique_xy_dev; the last slot of a face with n_unique == 3 is -1.
+ * counts[4] = faces, cells that are not valid (NaN cells included: the reference's warning), sort passes run / skipped.
+ * The caller destroys the mesh with xr_mesh_destroy.  XR_ERR_LIMIT: n_cell >= 2^28 (the corner rows reach the limit of xr_unique_xy_dev). */
+int xr_mesh_from_bounds_dev(const double *x_dev, const double *y_dev, int64_t n_cell, xr_mesh **out, uint8_t *index_out_dev, int64_t *counts);
+
+/* xr_interval_breaks_dev: conversion.infer_interval_breaks (conversion.py:171-199) of coord_dev float64[rows, cols] along axis
+ * 0 (out_dev float64[rows + 1, cols]) or 1 (float64[rows, cols + 1]): first - half the first step, every element but the last
+ * + half its step, last + half the last step; a line of one element gives it twice.  problems[2] = 1 when some neighbour pair
+ * along the axis does not ascend / does not descend (a NaN does neither), else 0: the coordinate is monotonic when either is 0.
+ * xr_mesh_from_intervals_dev: the lattice of x_dev / y_dev float64[ny + 1, nx + 1] node coordinates as a mesh: node id = row *
+ * (nx + 1) + column, face id = row * nx + column, quads (lower left, lower right, upper right, upper left) where left and
+ * right swap when x[0, 1] < x[0, 0], lower and upper when y[1, 0] < y[0, 0]. */
+int xr_interval_breaks_dev(const double *coord_dev, int64_t rows, int64_t cols, int axis, double *out_dev, int64_t *problems);
+int xr_mesh_from_intervals_dev(const double *x_dev, const double *y_dev, int64_t ny, int64_t nx, xr_mesh **out);
+
+/* xr_mesh_from_rings_dev: conversion.polygons_to_faces (conversion.py:82-117) on closed rings: coords_dev float64[n_vertex, 2],
+ * ring_off_dev int64[n_ring + 1]; poly_off_dev int64[n_poly + 1] or NULL (n_poly 0).  Every ring loses its closing vertex, the
+ * nodes are the sorted unique vertices (xr_unique_xy_dev), face r is ring r's vertices in order, n_max_node the longest ring,
+ * -1 behind shorter ones; without rings an empty mesh of width 3.  problems[5] = rings of fewer than four vertices, rings
+ * whose last vertex is not == the first, offsets that do not ascend from 0 to n_vertex, polygons that do not hold exactly
+ * one ring (holes), vertices with a non-finite coordinate; with any, *out is NULL and the caller words the error.
+ * xr_mesh_ring_offsets_dev / xr_mesh_ring_coords_dev: the way back (conversion.faces_to_polygons): ring f is face f's nodes in
+ * order and its first node again (a face without a node: an empty ring).  The first writes ring_off_out_dev int64[n_face + 1], poly_off_out_dev int64[n_face + 1] = 0 .. n_face
+ * (one ring per polygon; NULL: not wanted) and *n_vertex, the second
+ * coords_out_dev float64[n_vertex, 2] for those offsets. */
+int xr_mesh_from_rings_dev(const double *coords_dev, int64_t n_vertex, const int64_t *ring_off_dev, int64_t n_ring, const int64_t *poly_off_dev,
+                           int64_t n_poly, xr_mesh **out, int64_t *problems);
+int xr_mesh_ring_offsets_dev(const xr_mesh *mesh, int64_t *ring_off_out_dev, int64_t *poly_off_out_dev, int64_t *n_vertex);
+int xr_mesh_ring_coords_dev(const xr_mesh *mesh, const int64_t *ring_off_dev, int64_t n_vertex, double *coords_out_dev);
+
+/* xr_lines_to_network_dev: conversion.linestrings_to_edges (conversion.py:70-79): coords_dev float64[n_vertex, 2],
+ * line_off_dev int64[n_line + 1].  The nodes are the sorted unique vertices (*nodes_out: rows 0 of xr_unique_xy_copy_dev), an
+ * edge joins every two consecutive vertices of one line, in order (a repeated vertex gives a self loop, a line of one vertex
+ * no edge): edges_out_dev int64[max(n_vertex - 1, 0), 2], of which the first counts[0] rows are written.  counts[1] = offsets
+ * that do not ascend from 0 to n_vertex (then *nodes_out is NULL), counts[2] = vertices with a non-finite coordinate. */
+int xr_lines_to_network_dev(const double *coords_dev, int64_t n_vertex, const int64_t *line_off_dev, int64_t n_line, xr_unique_xy **nodes_out,
+                            int64_t *edges_out_dev, int64_t *counts);
+
 /* ---- raw HBM helpers for hosts that do not bring their own allocator -------------------- */
 int xr_dev_alloc(int64_t bytes, void **ptr_out);
 int xr_dev_free(void *ptr);

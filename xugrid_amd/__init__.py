@@ -11,6 +11,7 @@ from ._lib import XugridAmdError  # noqa: F401
 from .burn import burn_vector_geometry, locate_polygon  # noqa: F401
 from .celltree import CellTree2d  # noqa: F401
 from .fill import laplace_interpolate  # noqa: F401
+from .geometry import unique_xy  # noqa: F401
 from . import connectivity  # noqa: F401
 from .graph import binary_dilation, binary_erosion, connected_components, reverse_cuthill_mckee  # noqa: F401
 from .partition import label_partitions, labels_to_indices, merge_partitions, partition_by_label  # noqa: F401

@@ -233,6 +233,17 @@ SIGNATURES = {
     "xr_snapgrid_copy_dev": (c_int, [vp, c_int, vp]),
     "xr_snapgrid_values_dev": (c_int, [vp, vp, c_i64, vp]),
     "xr_snapgrid_destroy": (c_int, [vp]),
+    "xr_unique_xy_dev": (c_int, [vp, c_i64, p_vp]),
+    "xr_unique_xy_info": (c_int, [vp, p_i64]),
+    "xr_unique_xy_copy_dev": (c_int, [vp, c_int, vp]),
+    "xr_unique_xy_destroy": (c_int, [vp]),
+    "xr_mesh_from_bounds_dev": (c_int, [vp, vp, c_i64, p_vp, vp, p_i64]),
+    "xr_interval_breaks_dev": (c_int, [vp, c_i64, c_i64, c_int, vp, p_i64]),
+    "xr_mesh_from_intervals_dev": (c_int, [vp, vp, c_i64, c_i64, p_vp]),
+    "xr_mesh_from_rings_dev": (c_int, [vp, c_i64, vp, c_i64, vp, c_i64, p_vp, p_i64]),
+    "xr_mesh_ring_offsets_dev": (c_int, [vp, vp, vp, p_i64]),
+    "xr_mesh_ring_coords_dev": (c_int, [vp, vp, c_i64, vp]),
+    "xr_lines_to_network_dev": (c_int, [vp, c_i64, vp, c_i64, p_vp, vp, p_i64]),
     "xr_dev_alloc": (c_int, [c_i64, p_vp]),
     "xr_dev_free": (c_int, [vp]),
     "xr_dev_upload": (c_int, [vp, vp, c_i64]),

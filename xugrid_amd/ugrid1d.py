@@ -32,6 +32,21 @@ class Ugrid1d:
         self.edge_node_connectivity = np.ascontiguousarray(edges)
         self.name = name
 
+    @staticmethod
+    def from_lines(lines, name="network1d"):
+        """Lines as coordinate arrays ``(coords (V, 2), line_offsets)`` -> network: ``conversion.linestrings_to_edges`` without
+        shapely, on the device.  An edge joins every two consecutive vertices of a line; the nodes are the sorted unique
+        vertices."""
+        from . import geometry
+
+        return geometry.from_lines(lines, name)
+
+    def to_lines(self):
+        """-> ``(coords (2 n_edge, 2), line_offsets)``: one two-vertex line per edge."""
+        from . import geometry
+
+        return geometry.to_lines(self)
+
     # ---- ugridbase.py:560-614, :955-959
     @property
     def n_node(self) -> int:

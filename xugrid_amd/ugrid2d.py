@@ -10,7 +10,7 @@ import numpy as np
 
 import ctypes
 
-from . import _lib, connectivity, engine, facet, fill, graph, sample, snap
+from . import _lib, connectivity, engine, facet, fill, geometry, graph, sample, snap
 from .celltree import CellTree2d
 from .engine import FloatDType, IntDType
 
@@ -760,8 +760,16 @@ class Ugrid2d:
         return Ugrid2d(node_x, node_y, FILL_VALUE, face_nodes, name=name)
 
     @staticmethod
-    def from_structured_bounds(x_bounds, y_bounds, name="mesh2d"):
-        """(nx, 2) and (ny, 2) cell bounds -> quad mesh; ugrid2d.py:1973-2034 (2-D bounds only)."""
+    def from_structured_bounds(x_bounds, y_bounds, name="mesh2d", return_index=False):
+        """(nx, 2) and (ny, 2) cell bounds -> quad mesh, or the (N, M, 4) corner arrays of a curvilinear grid (CF cell bounds,
+        host or device arrays) -> a device-resident mesh of its valid cells; ugrid2d.py:1973-2034.  The corners of a cell may
+        come in any order.  A cell with fewer than three distinct corners or no area is left out with a ``UserWarning`` that
+        counts them; a cell with a NaN or infinite corner is left out too.  ``return_index``: also which cells became faces --
+        ``slice(None, None)`` for 2-D bounds; for 3-D ones a bool ``(N * M,)`` array: numpy for host bounds, a torch tensor for torch
+        bounds, a ``DeviceArray`` of dtype bool for other device arrays.  The mesh is
+        built on the device (xugrid_amd/geometry.py)."""
+        if geometry._ndim(x_bounds) == 3:
+            return geometry.from_bounds(x_bounds, y_bounds, name, return_index)
         x_bounds = np.asarray(x_bounds, dtype=FloatDType)
         y_bounds = np.asarray(y_bounds, dtype=FloatDType)
         if x_bounds.ndim != 2 or y_bounds.ndim != 2:
@@ -770,7 +778,44 @@ class Ugrid2d:
         x = connectivity.bounds1d_to_vertices(x_bounds)
         y = connectivity.bounds1d_to_vertices(y_bounds)
         node_y, node_x = (a.ravel() for a in np.meshgrid(y, x, indexing="ij"))
-        return Ugrid2d._from_intervals_helper(node_x, node_y, nx, ny, name)
+        grid = Ugrid2d._from_intervals_helper(node_x, node_y, nx, ny, name)
+        return (grid, slice(None, None)) if return_index else grid
+
+    @staticmethod
+    def from_structured_intervals1d(x_intervals, y_intervals, name="mesh2d"):
+        """(M + 1,) and (N + 1,) interval values -> the rectilinear quad mesh, generated on the device; ugrid2d.py:1915-1938."""
+        return geometry.from_intervals1d(x_intervals, y_intervals, name)
+
+    @staticmethod
+    def from_structured_intervals2d(x_intervals, y_intervals, name="mesh2d"):
+        """(N + 1, M + 1) node coordinates of a curvilinear lattice (host or device arrays) -> a device-resident quad mesh,
+        numbered and oriented as ``_from_intervals_helper`` does; ugrid2d.py:1941-1971."""
+        return geometry.from_intervals2d(x_intervals, y_intervals, name)
+
+    @staticmethod
+    def from_structured(x, y, name="mesh2d"):
+        """Cell CENTRE coordinates -> mesh; ugrid2d.py:2036-2150 on arrays.  1-D ``x`` (M,) and ``y`` (N,): the rectilinear mesh
+        of the inferred breaks.  2-D ``x`` and ``y`` (N, M) of a rotated or curvilinear grid: breaks along axis 1, then axis 0
+        (``infer_interval_breaks``), then ``from_structured_intervals2d``.  A non-monotonic coordinate raises ``ValueError``."""
+        return geometry.from_structured(x, y, name)
+
+    @staticmethod
+    def from_polygons(polygons, name="mesh2d"):
+        """Polygons as coordinate arrays -> mesh: ``from_shapely`` (ugrid2d.py:1867-1892, ``conversion.polygons_to_faces``)
+        without shapely.  ``polygons``: ``(coords (V, 2), ring_offsets)`` or what ``polygonize`` returns.  Every ring loses its
+        closing vertex, the nodes are the sorted unique vertices, faces keep ring and vertex order.  Holes, open rings and rings
+        of fewer than four vertices raise ``ValueError``."""
+        return geometry.from_polygons(polygons, name)
+
+    def to_polygons(self):
+        """-> ``(coords, ring_offsets, polygon_offsets)``: every face as one closed ring (``conversion.faces_to_polygons``),
+        numpy for a host grid, ``DeviceArray`` for a device-resident one."""
+        return geometry.to_polygons(self)
+
+    def bounding_polygon(self):
+        """-> ``(coords, ring_offsets)`` of the grid's outline, holes included: of the polygons ``polygonize`` traces for a
+        constant field the one with the largest bounding box, the first among equals (ugrid2d.py:2192-2205)."""
+        return geometry.bounding_polygon(self)
 
     @staticmethod
     def from_structured_bounds_device(x_bounds, y_bounds, name="mesh2d"):
