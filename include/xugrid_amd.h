@@ -370,6 +370,36 @@ int xr_outer_info(const xr_outer *outer, int64_t *n, int64_t *m, int64_t *nnz);
 /* borrowed handle of the materialised product (owned by `outer`; do not destroy) */
 int xr_outer_csr(xr_outer *outer, const xr_csr **out);
 int xr_outer_destroy(xr_outer *outer);
+/* Layered grids: a 2-D grid plus top / bottom of every layer in every cell (float64, layer-major: value of layer l in cell
+ * c at [l * n_cell + c] with column stride 1; column stride 0: arrays of n_layer values, the same layering in every cell,
+ * not expanded).  From the 2-D weights `w2d` (rows = target cells j, entries (i, w) in the caller's ids and in the order
+ * xr_csr_download returns them, whatever order the handle stores) the 3-D matrix: one entry for every entry of w2d and
+ * every layer pair (lt, ls) with
+ *     dz = min(top_s[ls, i], top_t[lt, j]) - max(bottom_s[ls, i], bottom_t[lt, j]) > 0
+ * -- a NaN bound or top <= bottom: no such layer in that cell; layers that only touch: nothing; any layer order.  Row
+ * lt * n_target + j, column ls * n_source + i, so data is (..., n_layer, n_cell) on both sides.  A row keeps w2d's order of
+ * i, ls ascending within one i.  Weight w * dz; relative != 0: w * (dz / (top_s[ls, i] - bottom_s[ls, i])), the share of the
+ * source voxel's height -- single IEEE operations in that order.  The result is an independent matrix like any other
+ * (applies, adjoint, download); rows of more than 32 entries are listed for the cooperative reducers.  XR_ERR_LIMIT,
+ * before anything is launched, where n_layer_t * nnz(w2d), n_layer_t * n_target or n_layer_s * n_source leave the int32
+ * range; the number of entries is known behind the count pass and checked there.
+ * xr_csr_layered takes host arrays and uploads them; xr_csr_layered_dev takes device pointers. */
+int xr_csr_layered(const xr_csr *w2d, const double *top_s, const double *bottom_s, int64_t n_layer_s, int64_t col_stride_s,
+                   const double *top_t, const double *bottom_t, int64_t n_layer_t, int64_t col_stride_t, int relative,
+                   xr_csr **out);
+int xr_csr_layered_dev(const xr_csr *w2d, const double *top_s_dev, const double *bottom_s_dev, int64_t n_layer_s,
+                       int64_t col_stride_s, const double *top_t_dev, const double *bottom_t_dev, int64_t n_layer_t,
+                       int64_t col_stride_t, int relative, xr_csr **out);
+/* The vertical building block on its own, with the signature and the ids of the reference's overlap_1d_nd
+ * (xugrid/regrid/overlap_1d.py:162-245): source_bounds float64 (n, n_layer_s, 2) and target_bounds (m, n_layer_t, 2) hold
+ * (lower, upper) per column and layer, source_index / target_index int64 (o,) name the column pairs -- any o, every id
+ * checked (XR_ERR_INVALID).  Result: the triplets (source column * n_layer_s + ls, target column * n_layer_t + lt, dz) of
+ * the rule above in the order pair k, then lt, then ls.  *n_out = their number p; they are written (int64, int64,
+ * float64, device pointers) only when capacity >= p: call with capacity 0 for the size, then again. */
+int xr_overlap_1d_nd_dev(const double *source_bounds_dev, int64_t n, int64_t n_layer_s, const double *target_bounds_dev,
+                         int64_t m, int64_t n_layer_t, const int64_t *source_index_dev, const int64_t *target_index_dev,
+                         int64_t o, int64_t capacity, int64_t *source_out_dev, int64_t *target_out_dev,
+                         double *overlap_out_dev, int64_t *n_out);
 /* NetworkGridder weights (xugrid/regrid/gridder.py:66-73 through UnstructuredGrid2d.intersection_length,
  * xugrid/regrid/unstructured.py:203-215): replaces numba_celltree's
  *     celltree.intersect_edges(edge_coords) -> (edge_index, face_index, intersections[n, 2, 2]),

@@ -19,10 +19,14 @@ from .polygonize import polygonize  # noqa: F401
 from .regrid import (  # noqa: F401
     BarycentricInterpolator,
     CentroidLocatorRegridder,
+    LayeredGrid,
+    LayeredOverlapRegridder,
+    LayeredRelativeOverlapRegridder,
     NetworkGridder,
     OverlapRegridder,
     Raster,
     RelativeOverlapRegridder,
+    overlap_1d_nd,
 )
 from .snap import snap_nodes, snap_to_nodes  # noqa: F401
 from .snapgrid import create_snap_to_grid_dataframe, snap_to_grid  # noqa: F401

@@ -107,6 +107,9 @@ SIGNATURES = {
     "xr_outer_info": (c_int, [vp, vp, vp, vp]),
     "xr_outer_csr": (c_int, [vp, p_vp]),
     "xr_outer_destroy": (c_int, [vp]),
+    "xr_csr_layered": (c_int, [vp, vp, vp, c_i64, c_i64, vp, vp, c_i64, c_i64, c_int, p_vp]),
+    "xr_csr_layered_dev": (c_int, [vp, vp, vp, c_i64, c_i64, vp, vp, c_i64, c_i64, c_int, p_vp]),
+    "xr_overlap_1d_nd_dev": (c_int, [vp, c_i64, c_i64, vp, c_i64, c_i64, vp, vp, c_i64, c_i64, vp, vp, vp, p_i64]),
     "xr_apply_outer": (c_int, [vp, c_int, c_f64, vp, c_int, c_i64, vp]),
     "xr_apply_outer_dev": (c_int, [vp, c_int, c_f64, vp, c_int, c_i64, vp]),
     "xr_edge_length_csr": (c_int, [vp, vp, c_i64, p_vp]),

@@ -85,6 +85,14 @@ template <typename F> static void staged_chunks(int64_t K, int64_t n_src, size_t
 
 // xr_csr.hip
 void upload_narrow(const int64_t *host, int64_t n, int32_t *dev); // host int64 -> device int32 (sizes checked by the caller)
+// the matrix as the caller numbers it (what xr_csr_download copies out): the stored arrays, or copies the view owns
+struct CallerView {
+    const int32_t *indptr = nullptr, *indices = nullptr;
+    const double *data = nullptr;
+    DevBuf<int32_t> c_indptr, c_indices, c_columns;
+    DevBuf<double> c_data;
+};
+void caller_view(const xr_csr *csr, CallerView &view, bool want_columns = true);
 void ensure_tiled(const xr_csr *csr);                             // the row tiling, if keys are pending (exclusive scope)
 int prepare_for_apply(const xr_csr *csr, int64_t K);              // row tiling + apply plan in front of a shared-scope apply
 // xr_apply.hip

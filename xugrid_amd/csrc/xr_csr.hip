@@ -61,6 +61,32 @@ void upload_narrow(const int64_t *host, int64_t n, int32_t *dev) {
     XR_LAUNCH("narrow_i64", k_narrow_i64, dim3(div_up(n, 256)), dim3(256), 0, wide.get(), dev, n);
 }
 
+// The matrix in the CALLER's row and column ids whatever order it is stored in: rows stored in query order are put back
+// (stored row r is the caller's row row_order[r]) and renumbered columns are translated, into copies the view owns; a matrix
+// stored as the caller numbers it is viewed in place.  want_columns = false leaves the stored column ids.
+void caller_view(const xr_csr *csr, CallerView &v, bool want_columns) {
+    v.indptr = csr->indptr.get(), v.indices = csr->indices.get(), v.data = csr->data.get();
+    if (csr->has_row_order && csr->n > 0) {
+        DevBuf<int32_t> len((size_t)csr->n);
+        v.c_indptr.alloc((size_t)csr->n + 1);
+        v.c_indices.alloc((size_t)csr->nnz);
+        v.c_data.alloc((size_t)csr->nnz);
+        XR_LAUNCH("unpermute_len", k_unpermute_len, dim3(div_up(csr->n, 256)), dim3(256), 0, csr->indptr.get(),
+                  csr->row_order.get(), csr->n, len.get());
+        exclusive_scan_i32(len.get(), v.c_indptr.get(), csr->n);
+        XR_LAUNCH("unpermute_rows", k_unpermute_rows, dim3(div_up(csr->n * 64, 256)), dim3(256), 0, csr->indptr.get(),
+                  csr->indices.get(), csr->data.get(), csr->row_order.get(), csr->n, v.c_indptr.get(), v.c_indices.get(),
+                  v.c_data.get());
+        v.indptr = v.c_indptr.get(), v.indices = v.c_indices.get(), v.data = v.c_data.get();
+    }
+    if (want_columns && csr->has_col_perm && csr->nnz > 0) { // stored column ids -> the caller's
+        v.c_columns.alloc((size_t)csr->nnz);
+        XR_LAUNCH("col_ids", k_gather_i32, dim3(div_up(csr->nnz, 256)), dim3(256), 0, csr->col_of.get(), v.indices, csr->nnz,
+                  v.c_columns.get());
+        v.indices = v.c_columns.get();
+    }
+}
+
 static void set_long_rows(xr_csr *csr, const std::vector<int32_t> &longs) {
     csr->has_long = !longs.empty();
     if (!csr->has_long) return;
@@ -210,41 +236,16 @@ int xr_csr_info(const xr_csr *csr, int64_t *n, int64_t *m, int64_t *nnz) {
 int xr_csr_download(const xr_csr *csr, double *data, int64_t *indices, int64_t *indptr) {
     XR_API_BEGIN
     XR_REQUIRE(csr, XR_ERR_INVALID, "xr_csr_download: NULL csr");
-    const int32_t *d_indptr = csr->indptr.get(), *d_indices = csr->indices.get();
-    const double *d_data = csr->data.get();
-    DevBuf<int32_t> c_indptr, c_indices;
-    DevBuf<double> c_data;
-    if (csr->has_row_order && csr->n > 0) {
-        // rows are stored in query order: rebuild the caller's row order on the device
-        DevBuf<int32_t> len((size_t)csr->n);
-        c_indptr.alloc((size_t)csr->n + 1);
-        c_indices.alloc((size_t)csr->nnz);
-        c_data.alloc((size_t)csr->nnz);
-        XR_LAUNCH("unpermute_len", k_unpermute_len, dim3(div_up(csr->n, 256)), dim3(256), 0, csr->indptr.get(),
-                  csr->row_order.get(), csr->n, len.get());
-        exclusive_scan_i32(len.get(), c_indptr.get(), csr->n);
-        XR_LAUNCH("unpermute_rows", k_unpermute_rows, dim3(div_up(csr->n * 64, 256)), dim3(256), 0, csr->indptr.get(),
-                  csr->indices.get(), csr->data.get(), csr->row_order.get(), csr->n, c_indptr.get(), c_indices.get(),
-                  c_data.get());
-        d_indptr = c_indptr.get();
-        d_indices = c_indices.get();
-        d_data = c_data.get();
-    }
+    CallerView v;
+    caller_view(csr, v, indices != nullptr);
+    const int32_t *d_indptr = v.indptr, *d_indices = v.indices;
+    const double *d_data = v.data;
     if (data && csr->nnz > 0) {
         d2h(data, d_data, sizeof(double) * (size_t)csr->nnz);
     }
     DevBuf<int64_t> wide;
     if (indices || indptr) wide.alloc((size_t)std::max(csr->nnz, csr->n + 1));
-    if (indices) {
-        DevBuf<int32_t> caller_ids;
-        if (csr->has_col_perm && csr->nnz > 0) { // stored column ids -> the caller's
-            caller_ids.alloc((size_t)csr->nnz);
-            XR_LAUNCH("col_ids", k_gather_i32, dim3(div_up(csr->nnz, 256)), dim3(256), 0, csr->col_of.get(), d_indices,
-                      csr->nnz, caller_ids.get());
-            d_indices = caller_ids.get();
-        }
-        download_wide(d_indices, csr->nnz, indices, wide);
-    }
+    download_wide(d_indices, csr->nnz, indices, wide);
     download_wide(d_indptr, csr->n + 1, indptr, wide);
     stream_sync();
     XR_API_END

@@ -1359,6 +1359,40 @@ class DeviceCSR(Handle):
         check(_lib.load().xr_csr_transpose(self._h, ctypes.byref(handle)))
         return DeviceCSR(handle)
 
+    def layered(self, top_s, bottom_s, top_t, bottom_t, relative=False) -> "DeviceCSR":
+        """The 3-D matrix of these 2-D weights and two layerings (include/xugrid_amd.h: xr_csr_layered): row
+        ``lt * n + j``, column ``ls * m + i``, weight ``w_ji * dz`` for every layer pair with a vertical overlap ``dz > 0``
+        (``relative``: times ``dz / (top_s - bottom_s)`` instead).  top / bottom: float64 ``(n_layer, cells...)`` or
+        ``(n_layer,)`` (the same layering in every cell), all numpy, or device arrays (numpy ones among them are
+        uploaded)."""
+        arrays, sides = [], []
+        for name, value, cells in (("top_s", top_s, self.m), ("bottom_s", bottom_s, self.m), ("top_t", top_t, self.n),
+                                   ("bottom_t", bottom_t, self.n)):
+            info = device_array_info(value)
+            if info is None:
+                value = np.ascontiguousarray(value, dtype=np.float64)
+                shape = value.shape
+            else:
+                if info[2] != np.dtype(np.float64):
+                    raise TypeError(f"{name}: device arrays must be float64, received {info[2]}")
+                shape = tuple(info[1])
+            if len(shape) < 1 or (len(shape) > 1 and int(np.prod(shape[1:], dtype=np.int64)) != cells):
+                raise ValueError(f"{name}: shape (n_layer,) or (n_layer, {cells}) expected, received {tuple(shape)}")
+            if sides and len(sides) % 2 == 1 and (shape[0], 0 if len(shape) == 1 else 1) != sides[-1]:
+                raise ValueError(f"{name}: shape {tuple(shape)} differs from the shape of its top")
+            arrays.append(value)
+            sides.append((int(shape[0]), 0 if len(shape) == 1 else 1))
+        handle = ctypes.c_void_p()
+        if all(isinstance(a, np.ndarray) for a in arrays):
+            fn, (ts, bs, tt, bt) = _lib.load().xr_csr_layered, (_ptr(a) for a in arrays)
+        else:
+            keep = [a if device_array_info(a) is not None else DeviceArray.from_host(a) for a in arrays]
+            for a in keep:
+                sync_producer(a)
+            fn, (ts, bs, tt, bt) = _lib.load().xr_csr_layered_dev, (vp(device_array_info(a)[0]) for a in keep)
+        check(fn(self._h, ts, bs, *sides[0], tt, bt, *sides[2], 1 if relative else 0, ctypes.byref(handle)))
+        return DeviceCSR(handle)
+
     def drop_transpose(self):
         """Release the cached transposed weights (about 12 bytes per entry); the next ``adjoint`` rebuilds them."""
         check(_lib.load().xr_csr_drop_transpose(self._h))

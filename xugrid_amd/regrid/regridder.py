@@ -30,7 +30,7 @@ from .unstructured import UnstructuredGrid2d
 
 def setup_grid(obj, **kwargs):
     """regridder.py:72-80."""
-    if isinstance(obj, (UnstructuredGrid2d, StructuredGrid2d)):
+    if isinstance(obj, (UnstructuredGrid2d, StructuredGrid2d)) or getattr(obj, "layered", False):  # (regrid/layered.py)
         return obj
     if isinstance(obj, Ugrid2d) or (hasattr(obj, "grid") and isinstance(getattr(obj, "grid"), Ugrid2d)):
         return UnstructuredGrid2d(obj)
