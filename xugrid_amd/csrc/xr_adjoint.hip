@@ -116,60 +116,54 @@ __global__ void __launch_bounds__(256) k_tr_row_ids(const uint32_t *__restrict__
     if (q < nnz) out[q] = (int32_t)(tr_row[q] & TR_ROW_MASK);
 }
 
-static void drop_transposed(xr_csr *csr) {
-    csr->tr_ready = csr->tr_output_stored = false;
-    csr->tr_indptr.release(), csr->tr_row.release(), csr->tr_w.release(), csr->tr_long.release();
-    csr->tr_n_long = csr->tr_max_len = 0;
-}
-
 void ensure_transposed(const xr_csr *ccsr) {
     xr_csr *csr = const_cast<xr_csr *>(ccsr); // like the plan: a cache attached to the weights
-    if (csr->tr_ready && csr->tr_output_stored == csr->output_stored) return;
+    if (csr->tr.ready && csr->tr.output_stored == csr->stored.output_stored) return;
     XR_REQUIRE(exclusive_held(), XR_ERR_INVALID, "internal: transposed weights requested outside the exclusive scope");
-    drop_transposed(csr);
+    csr->tr.release();
     const int64_t n = csr->n, m = csr->m, nnz = csr->nnz;
-    const int32_t *col_of = csr->has_col_perm ? csr->col_of.get() : nullptr;
+    const int32_t *col_of = csr->cols.permuted ? csr->cols.col_of.get() : nullptr;
     DevBuf<int32_t> count((size_t)m + 1), cursor((size_t)m + 1), is_long((size_t)m + 1), pos((size_t)m + 1), stats(1);
     DevBuf<uint64_t> keys((size_t)nnz);
-    csr->tr_indptr.alloc((size_t)m + 1);
+    csr->tr.indptr.alloc((size_t)m + 1);
     fill_i32(count.get(), 0, m + 1);
     fill_i32(cursor.get(), 0, m + 1);
     fill_i32(stats.get(), 0, 1);
     if (nnz > 0) XR_LAUNCH("tr_count", k_tr_count, dim3(div_up(nnz, 256)), dim3(256), 0, csr->indices.get(), col_of, nnz, count.get());
-    if (m > 0) exclusive_scan_i32(count.get(), csr->tr_indptr.get(), m);
-    else fill_i32(csr->tr_indptr.get(), 0, 1);
+    if (m > 0) exclusive_scan_i32(count.get(), csr->tr.indptr.get(), m);
+    else fill_i32(csr->tr.indptr.get(), 0, 1);
     if (nnz > 0)
         XR_LAUNCH("tr_fill", k_tr_fill, dim3(div_up(n * 64, 256)), dim3(256), 0, csr->indptr.get(), csr->indices.get(),
-                  row_order_of(csr), col_of, n, csr->tr_indptr.get(), cursor.get(), keys.get());
+                  row_order_of(csr), col_of, n, csr->tr.indptr.get(), cursor.get(), keys.get());
     int32_t n_long = 0;
     if (m > 0) {
-        XR_LAUNCH("tr_sort_short", k_tr_sort_short, dim3(div_up(m, 256)), dim3(256), 0, csr->tr_indptr.get(), m, keys.get(),
+        XR_LAUNCH("tr_sort_short", k_tr_sort_short, dim3(div_up(m, 256)), dim3(256), 0, csr->tr.indptr.get(), m, keys.get(),
                   is_long.get(), stats.get());
         exclusive_scan_i32(is_long.get(), pos.get(), m);
         n_long = read_scalar(pos.get() + m);
-        csr->tr_max_len = read_scalar(stats.get());
+        csr->tr.max_len = read_scalar(stats.get());
     }
     if (n_long > 0) {
-        csr->tr_long.alloc((size_t)n_long);
+        csr->tr.long_cols.alloc((size_t)n_long);
         XR_LAUNCH("tr_long_ids", k_compact_ids<int32_t>, dim3(div_up(m, 256)), dim3(256), 0, is_long.get(), pos.get(), m,
-                  csr->tr_long.get());
+                  csr->tr.long_cols.get());
         XR_LAUNCH("tr_sort_long", k_tr_sort_long, dim3((unsigned)std::min<int64_t>(n_long, (int64_t)engine().num_cu * 32)),
-                  dim3(256), 0, csr->tr_indptr.get(), csr->tr_long.get(), n_long, keys.get());
+                  dim3(256), 0, csr->tr.indptr.get(), csr->tr.long_cols.get(), n_long, keys.get());
     }
-    csr->tr_row.alloc((size_t)nnz);
-    csr->tr_w.alloc((size_t)nnz);
+    csr->tr.row.alloc((size_t)nnz);
+    csr->tr.w.alloc((size_t)nnz);
     if (nnz > 0)
         XR_LAUNCH("tr_finish", k_tr_finish, dim3(div_up(nnz, 256)), dim3(256), 0, keys.get(), csr->data.get(), nnz,
-                  csr->tr_row.get(), csr->tr_w.get());
-    csr->tr_n_long = n_long;
-    csr->tr_output_stored = csr->output_stored;
-    csr->tr_ready = true;
+                  csr->tr.row.get(), csr->tr.w.get());
+    csr->tr.n_long = n_long;
+    csr->tr.output_stored = csr->stored.output_stored;
+    csr->tr.ready = true;
 }
 
 int prepare_for_adjoint(const xr_csr *csr, int method) {
     XR_API_BEGIN
     with_adjoint_reducer(method, [](auto) {}); // (a reducer without an adjoint builds nothing)
-    if (csr && !(csr->tr_ready && csr->tr_output_stored == csr->output_stored)) {
+    if (csr && !(csr->tr.ready && csr->tr.output_stored == csr->stored.output_stored)) {
         ensure_transposed(csr);
         stream_sync();
     }
@@ -411,41 +405,41 @@ static void launch_adjoint(const xr_csr *csr, const SRC *src, const SRC *src_sto
         r = scratch.get();
         const int32_t *row_order = row_order_of(csr);
         XR_LAUNCH("adjoint_rows", (k_adj_rows<METHOD, SRC>), dim3(div_up(T, AP_BLOCK), ytiles), dim3(AP_BLOCK), 0,
-                  csr->indptr.get(), csr->indices.get(), csr->data.get(), row_order, csr->has_long, T, S, src_stored, grad, K,
+                  csr->indptr.get(), csr->indices.get(), csr->data.get(), row_order, csr->longs.any, T, S, src_stored, grad, K,
                   scratch.get());
-        if (csr->has_long) {
+        if (csr->longs.any) {
             XR_LAUNCH("adjoint_rows_wave", (k_adj_rows_wave<METHOD, SRC>), dim3(cu * 16 / ylong, ylong), dim3(AP_BLOCK), 0,
-                      csr->indptr.get(), csr->indices.get(), csr->data.get(), row_order, csr->long_rows.get(),
-                      csr->n_long.get(), T, S, src_stored, grad, K, scratch.get());
-            if (!(csr->max_row_len >= 0 && csr->max_row_len <= APPLY_WAVE))
+                      csr->indptr.get(), csr->indices.get(), csr->data.get(), row_order, csr->longs.rows.get(),
+                      csr->longs.n_dev.get(), T, S, src_stored, grad, K, scratch.get());
+            if (!(csr->longs.max_row_len >= 0 && csr->longs.max_row_len <= APPLY_WAVE))
                 XR_LAUNCH("adjoint_rows_block", (k_adj_rows_block<METHOD, SRC>), dim3(cu * 8 / ylong, ylong), dim3(AP_BLOCK), 0,
-                          csr->indptr.get(), csr->indices.get(), csr->data.get(), row_order, csr->long_rows.get(),
-                          csr->n_long.get(), T, S, src_stored, grad, K, scratch.get());
+                          csr->indptr.get(), csr->indices.get(), csr->data.get(), row_order, csr->longs.rows.get(),
+                          csr->longs.n_dev.get(), T, S, src_stored, grad, K, scratch.get());
         }
     }
-    const bool has_long = csr->tr_n_long > 0;
+    const bool has_long = csr->tr.n_long > 0;
     XR_LAUNCH("adjoint_cols", (k_adj_cols<METHOD, SRC>), dim3(div_up(S, AP_BLOCK), ytiles), dim3(AP_BLOCK), 0,
-              csr->tr_indptr.get(), csr->tr_row.get(), csr->tr_w.get(), has_long, T, S, src, r, K, out);
+              csr->tr.indptr.get(), csr->tr.row.get(), csr->tr.w.get(), has_long, T, S, src, r, K, out);
     if (has_long) {
-        const int n_long = (int)csr->tr_n_long;
-        const bool any_huge = csr->tr_max_len > APPLY_WAVE;
+        const int n_long = (int)csr->tr.n_long;
+        const bool any_huge = csr->tr.max_len > APPLY_WAVE;
         const unsigned gx = (unsigned)std::min<int64_t>(div_up(n_long, AP_BLOCK / 64), cu * 16 / ylong);
-        XR_LAUNCH("adjoint_cols_wave", (k_adj_cols_wave<METHOD, SRC>), dim3(gx, ylong), dim3(AP_BLOCK), 0, csr->tr_indptr.get(),
-                  csr->tr_row.get(), csr->tr_w.get(), csr->tr_long.get(), n_long, any_huge, T, S, src, r, K, out);
+        XR_LAUNCH("adjoint_cols_wave", (k_adj_cols_wave<METHOD, SRC>), dim3(gx, ylong), dim3(AP_BLOCK), 0, csr->tr.indptr.get(),
+                  csr->tr.row.get(), csr->tr.w.get(), csr->tr.long_cols.get(), n_long, any_huge, T, S, src, r, K, out);
         if (any_huge)
             XR_LAUNCH("adjoint_cols_block", (k_adj_cols_block<METHOD, SRC>),
-                      dim3((unsigned)std::min<int64_t>(n_long, cu * 8 / ylong), ylong), dim3(AP_BLOCK), 0, csr->tr_indptr.get(),
-                      csr->tr_row.get(), csr->tr_w.get(), csr->tr_long.get(), n_long, T, S, src, r, K, out);
+                      dim3((unsigned)std::min<int64_t>(n_long, cu * 8 / ylong), ylong), dim3(AP_BLOCK), 0, csr->tr.indptr.get(),
+                      csr->tr.row.get(), csr->tr.w.get(), csr->tr.long_cols.get(), n_long, T, S, src, r, K, out);
     }
 }
 
 void csr_adjoint_dev(const xr_csr *csr, int method, const void *src_dev, int dtype, const double *grad_dev, int64_t K,
                      double *out_dev) {
     with_adjoint_reducer(method, [](auto) {}); // (the reducer is checked whatever the sizes are)
-    XR_REQUIRE(!(csr->has_col_perm && csr->source_permuted), XR_ERR_INVALID,
+    XR_REQUIRE(!(csr->cols.permuted && csr->cols.source_permuted), XR_ERR_INVALID,
                "the adjoint apply takes and returns source blocks in the caller's column order: call "
                "xr_csr_expect_permuted(csr, 0) first");
-    XR_REQUIRE(csr->tr_ready && csr->tr_output_stored == csr->output_stored, XR_ERR_INVALID,
+    XR_REQUIRE(csr->tr.ready && csr->tr.output_stored == csr->stored.output_stored, XR_ERR_INVALID,
                "internal: adjoint apply without transposed weights");
     if (K == 0 || csr->m == 0) return;
     with_source_type(src_dev ? dtype : XR_F64, [&](auto tag) {
@@ -476,20 +470,20 @@ int xr_csr_transpose(const xr_csr *csr, xr_csr **out) {
     t->indices.alloc((size_t)t->nnz);
     t->data.alloc((size_t)t->nnz);
     hipStream_t st = launch_stream();
-    XR_HIP(hipMemcpyAsync(t->indptr.get(), csr->tr_indptr.get(), sizeof(int32_t) * ((size_t)t->n + 1), hipMemcpyDeviceToDevice, st));
+    XR_HIP(hipMemcpyAsync(t->indptr.get(), csr->tr.indptr.get(), sizeof(int32_t) * ((size_t)t->n + 1), hipMemcpyDeviceToDevice, st));
     if (t->nnz > 0) {
-        XR_HIP(hipMemcpyAsync(t->data.get(), csr->tr_w.get(), sizeof(double) * (size_t)t->nnz, hipMemcpyDeviceToDevice, st));
-        XR_LAUNCH("tr_row_ids", k_tr_row_ids, dim3(div_up(t->nnz, 256)), dim3(256), 0, csr->tr_row.get(), t->nnz, t->indices.get());
+        XR_HIP(hipMemcpyAsync(t->data.get(), csr->tr.w.get(), sizeof(double) * (size_t)t->nnz, hipMemcpyDeviceToDevice, st));
+        XR_LAUNCH("tr_row_ids", k_tr_row_ids, dim3(div_up(t->nnz, 256)), dim3(256), 0, csr->tr.row.get(), t->nnz, t->indices.get());
     }
-    t->has_long = csr->tr_n_long > 0;
-    if (t->has_long) {
-        const int32_t count = (int32_t)csr->tr_n_long;
-        t->long_rows.alloc((size_t)count);
-        t->n_long.alloc(1);
-        XR_HIP(hipMemcpyAsync(t->long_rows.get(), csr->tr_long.get(), sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToDevice, st));
-        h2d(t->n_long.get(), &count, sizeof(int32_t));
+    t->longs.any = csr->tr.n_long > 0;
+    if (t->longs.any) {
+        const int32_t count = (int32_t)csr->tr.n_long;
+        t->longs.rows.alloc((size_t)count);
+        t->longs.n_dev.alloc(1);
+        XR_HIP(hipMemcpyAsync(t->longs.rows.get(), csr->tr.long_cols.get(), sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToDevice, st));
+        h2d(t->longs.n_dev.get(), &count, sizeof(int32_t));
     }
-    t->max_row_len = csr->tr_max_len;
+    t->longs.max_row_len = csr->tr.max_len;
     stream_sync();
     *out = t.release();
     XR_API_END
@@ -498,9 +492,9 @@ int xr_csr_transpose(const xr_csr *csr, xr_csr **out) {
 int xr_csr_drop_transpose(xr_csr *csr) {
     XR_API_BEGIN
     XR_REQUIRE(csr, XR_ERR_INVALID, "xr_csr_drop_transpose: NULL argument");
-    if (csr->tr_indptr.get()) { // (also a structure the row tiling has invalidated)
+    if (csr->tr.indptr.get()) { // (also a structure the row tiling has invalidated)
         release_point();
-        drop_transposed(csr);
+        csr->tr.release();
     }
     XR_API_END
 }

@@ -1,6 +1,9 @@
-// xr_apply.h -- what the units of the sparse apply share besides the reducers (xr_reduce.h): xr_apply.hip (the full apply),
-// xr_partial.hip (the partial states of the source-sharded apply), xr_csr.hip (the MatrixCSR handle) and xr_outer.hip (the
-// separable weights).  Constants, a few host helpers, and the functions one of these units defines for the others.
+// xr_apply.h -- what the units of the sparse apply share besides the reducers (xr_reduce.h): xr_apply.hip (the entry points
+// and the dispatch of the full apply) with its three pipelines -- xr_apply_stream.hip (the streamed reducers),
+// xr_apply_plan.hip (the many-variable plan), xr_apply_workspace.hip (mode and percentiles) --, xr_partial.hip (the partial
+// states of the source-sharded apply), xr_csr.hip (the MatrixCSR handle) and xr_outer.hip (the separable weights).
+// Constants, a few host helpers, and the functions one of these units defines for the others: plain functions that take the
+// reducer and dtype ids -- every unit dispatches to the kernels it owns itself, no template crosses a unit boundary.
 #pragma once
 #include "xr_objects.h"
 #include "xr_overlap_tail.h"
@@ -17,7 +20,7 @@ static constexpr int AP_BLOCK = 256;
 // the reference's sequential loop (agreement ~1e-15 relative instead of bit-exact).
 static constexpr int APPLY_LONG = XR_APPLY_LONG_ROW;
 static constexpr int APPLY_WAVE = XR_APPLY_WAVE_ROW;
-// ... by a group of 16 lanes up to APPLY_GROUP16 entries, by all 64 beyond (apply_row_group, xr_apply.hip; the row pass of
+// ... by a group of 16 lanes up to APPLY_GROUP16 entries, by all 64 beyond (apply_row_group, xr_apply_stream.hip; the row pass of
 // the adjoint walks the same way, xr_adjoint.hip)
 static constexpr int APPLY_GROUP16 = 512;
 
@@ -29,7 +32,7 @@ static constexpr int W1_CAP = 384; // entries per wave window: 64 rows x 4 entri
 static constexpr int PLAN_KT = 8; // source variables per pipeline stage (LDS: PLAN_KT * PLAN_UMAX doubles)
 
 static inline const int32_t *row_order_of(const xr_csr *csr) {
-    return (csr->has_row_order && !csr->output_stored) ? csr->row_order.get() : nullptr;
+    return (csr->stored.has_row_order && !csr->stored.output_stored) ? csr->stored.row_order.get() : nullptr;
 }
 
 // (with_source_type, the table of the source dtypes, is in xr_internal.h)
@@ -38,6 +41,8 @@ static size_t source_size(int dtype) {
     with_source_type(dtype, [&](auto tag) { size = sizeof(tag); });
     return size;
 }
+// ... and back: the dtype id of an element type, for a call into another unit
+template <typename SRC> constexpr int source_dtype = sizeof(SRC) == sizeof(double) ? XR_F64 : XR_F32;
 
 // the caller's source block into the stored column order: dst[k][j] = src[k][col_of[j]] (every source line is read once;
 // the columns of a line are spatial neighbours, so they are consumed within a short stretch of j: L2 hits)
@@ -53,13 +58,13 @@ k_permute_source(const SRC *__restrict__ src, const int32_t *__restrict__ col_of
 // -> the source block in the STORED column order (the caller's block itself unless the columns were renumbered)
 template <typename SRC>
 static const SRC *stored_source(const xr_csr *csr, const SRC *src, int64_t K, DevBuf<char> &permuted) {
-    if (!(csr->has_col_perm && !csr->source_permuted && K > 0 && csr->m > 0)) return src;
+    if (!(csr->cols.permuted && !csr->cols.source_permuted && K > 0 && csr->m > 0)) return src;
     permuted.alloc((size_t)K * (size_t)csr->m * sizeof(SRC));
     SRC *dst = reinterpret_cast<SRC *>(permuted.get());
     for (int64_t k0 = 0; k0 < K; k0 += 65535) {
         const int64_t kc = std::min<int64_t>(K - k0, 65535);
         dim3 grid(div_up(csr->m, 256), (unsigned)kc);
-        XR_LAUNCH("permute_source", k_permute_source<SRC>, grid, dim3(256), 0, src + k0 * csr->m, csr->col_of.get(), csr->m,
+        XR_LAUNCH("permute_source", k_permute_source<SRC>, grid, dim3(256), 0, src + k0 * csr->m, csr->cols.col_of.get(), csr->m,
                   dst + k0 * csr->m);
     }
     return dst;
@@ -95,8 +100,14 @@ struct CallerView {
 void caller_view(const xr_csr *csr, CallerView &view, bool want_columns = true);
 void ensure_tiled(const xr_csr *csr);                             // the row tiling, if keys are pending (exclusive scope)
 int prepare_for_apply(const xr_csr *csr, int64_t K);              // row tiling + apply plan in front of a shared-scope apply
-// xr_apply.hip
+// xr_apply_plan.hip
 void ensure_plan(const xr_csr *csr);                              // the apply plan of the many-variable kernels (exclusive scope)
+// the planned row blocks of a matrix whose plan is built ("apply_plan"; the unplanned blocks and the long rows: launch_stream)
+void apply_planned(const xr_csr *csr, int method, const void *src_dev, int dtype, int64_t K, double *out_dev);
+// xr_apply_stream.hip, xr_apply_workspace.hip: the two halves of apply_dispatch -- the streamed reducers (which place
+// apply_planned in their launch sequence) and mode / percentiles.  src_dev is in the STORED column order (stored_source)
+void apply_stream(const xr_csr *csr, int method, const void *src_dev, int dtype, int64_t K, double *out_dev, const ApplyContext *ctx);
+void apply_workspace(const xr_csr *csr, int method, double percentile, const void *src_dev, int dtype, int64_t K, double *out_dev);
 // the apply of a finished matrix on the calling thread's launch stream (xr_apply.hip) and its partial states for the
 // source-sharded apply (xr_partial.hip).  ctx: the apply is enqueued behind a weight build the host has not confirmed yet (K = 1,
 // overlap_tri) -- it obeys the build's gate and may take the build's tail into its launch (ApplyContext, xr_overlap_tail.h)

@@ -66,35 +66,35 @@ void upload_narrow(const int64_t *host, int64_t n, int32_t *dev) {
 // stored as the caller numbers it is viewed in place.  want_columns = false leaves the stored column ids.
 void caller_view(const xr_csr *csr, CallerView &v, bool want_columns) {
     v.indptr = csr->indptr.get(), v.indices = csr->indices.get(), v.data = csr->data.get();
-    if (csr->has_row_order && csr->n > 0) {
+    if (csr->stored.has_row_order && csr->n > 0) {
         DevBuf<int32_t> len((size_t)csr->n);
         v.c_indptr.alloc((size_t)csr->n + 1);
         v.c_indices.alloc((size_t)csr->nnz);
         v.c_data.alloc((size_t)csr->nnz);
         XR_LAUNCH("unpermute_len", k_unpermute_len, dim3(div_up(csr->n, 256)), dim3(256), 0, csr->indptr.get(),
-                  csr->row_order.get(), csr->n, len.get());
+                  csr->stored.row_order.get(), csr->n, len.get());
         exclusive_scan_i32(len.get(), v.c_indptr.get(), csr->n);
         XR_LAUNCH("unpermute_rows", k_unpermute_rows, dim3(div_up(csr->n * 64, 256)), dim3(256), 0, csr->indptr.get(),
-                  csr->indices.get(), csr->data.get(), csr->row_order.get(), csr->n, v.c_indptr.get(), v.c_indices.get(),
+                  csr->indices.get(), csr->data.get(), csr->stored.row_order.get(), csr->n, v.c_indptr.get(), v.c_indices.get(),
                   v.c_data.get());
         v.indptr = v.c_indptr.get(), v.indices = v.c_indices.get(), v.data = v.c_data.get();
     }
-    if (want_columns && csr->has_col_perm && csr->nnz > 0) { // stored column ids -> the caller's
+    if (want_columns && csr->cols.permuted && csr->nnz > 0) { // stored column ids -> the caller's
         v.c_columns.alloc((size_t)csr->nnz);
-        XR_LAUNCH("col_ids", k_gather_i32, dim3(div_up(csr->nnz, 256)), dim3(256), 0, csr->col_of.get(), v.indices, csr->nnz,
+        XR_LAUNCH("col_ids", k_gather_i32, dim3(div_up(csr->nnz, 256)), dim3(256), 0, csr->cols.col_of.get(), v.indices, csr->nnz,
                   v.c_columns.get());
         v.indices = v.c_columns.get();
     }
 }
 
+// the long rows as the host found them in the caller's arrays: the list and its count are uploaded, no kernel lists them
 static void set_long_rows(xr_csr *csr, const std::vector<int32_t> &longs) {
-    csr->has_long = !longs.empty();
-    if (!csr->has_long) return;
+    if (longs.empty()) return;
     const int32_t count = (int32_t)longs.size();
-    csr->long_rows.alloc(longs.size());
-    csr->n_long.alloc(1);
-    h2d(csr->long_rows.get(), longs.data(), sizeof(int32_t) * longs.size());
-    h2d(csr->n_long.get(), &count, sizeof(int32_t));
+    csr->longs.begin(longs.size());
+    h2d(csr->longs.rows.get(), longs.data(), sizeof(int32_t) * longs.size());
+    h2d(csr->longs.n_dev.get(), &count, sizeof(int32_t));
+    csr->longs.end(count);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -150,49 +150,44 @@ __global__ void k_tile_rows(const int32_t *__restrict__ indptr, const int32_t *_
 
 void ensure_tiled(const xr_csr *ccsr) {
     xr_csr *csr = const_cast<xr_csr *>(ccsr); // like the plan: a cache-friendly re-layout of the same matrix
-    if (!csr->has_tile_key) return;
+    if (!csr->tiling.pending) return;
     // (a re-layout of the matrix: only under the exclusive scope -- the apply entry points call prepare_for_apply first,
     // so that the concurrent, shared part of an apply finds this done)
     XR_REQUIRE(exclusive_held(), XR_ERR_INVALID, "internal: row tiling requested outside the exclusive scope");
-    csr->has_tile_key = false;
-    const int64_t n = csr->n, R = csr->tile_key_range;
+    csr->tiling.pending = false;
+    const int64_t n = csr->n, R = csr->tiling.key_range;
     if (n == 0 || R <= 1) {
-        csr->tile_key.release();
+        csr->tiling.release();
         return;
     }
-    hipStream_t st = launch_stream();
     DevBuf<int32_t> hist((size_t)R + 1), start((size_t)R + 1), members((size_t)n), perm((size_t)n), len((size_t)n);
     fill_i32(hist.get(), 0, R + 1);
-    XR_LAUNCH("bincount", k_bincount, dim3(div_up(n, 256)), dim3(256), 0, csr->tile_key.get(), n, hist.get());
+    XR_LAUNCH("bincount", k_bincount, dim3(div_up(n, 256)), dim3(256), 0, csr->tiling.key.get(), n, hist.get());
     exclusive_scan_i32(hist.get(), start.get(), R);
     fill_i32(hist.get(), 0, R + 1);
-    XR_LAUNCH("tile_scatter", k_tile_scatter, dim3(div_up(n, 256)), dim3(256), 0, csr->tile_key.get(), n, start.get(),
+    XR_LAUNCH("tile_scatter", k_tile_scatter, dim3(div_up(n, 256)), dim3(256), 0, csr->tiling.key.get(), n, start.get(),
               hist.get(), members.get());
-    XR_LAUNCH("tile_rank", k_tile_rank, dim3(div_up(n, 256)), dim3(256), 0, csr->tile_key.get(), start.get(),
+    XR_LAUNCH("tile_rank", k_tile_rank, dim3(div_up(n, 256)), dim3(256), 0, csr->tiling.key.get(), start.get(),
               members.get(), n, perm.get());
     XR_LAUNCH("tile_len", k_tile_len, dim3(div_up(n, 256)), dim3(256), 0, csr->indptr.get(), perm.get(), n, len.get());
-    DevBuf<int32_t> t_indptr((size_t)n + 1), t_indices((size_t)csr->nnz), t_row_order((size_t)n),
-        t_long((size_t)(csr->nnz / APPLY_LONG + 1)), t_nlong(1);
+    DevBuf<int32_t> t_indptr((size_t)n + 1), t_indices((size_t)csr->nnz), t_row_order((size_t)n);
     DevBuf<double> t_data((size_t)csr->nnz);
+    CsrLongRows t_longs; // (the rows keep their lengths; their stored positions are listed anew)
+    t_longs.max_row_len = csr->longs.max_row_len;
     exclusive_scan_i32(len.get(), t_indptr.get(), n);
-    XR_HIP(hipMemsetAsync(t_nlong.get(), 0, sizeof(int32_t), st));
+    t_longs.begin((size_t)(csr->nnz / APPLY_LONG + 1));
     XR_LAUNCH("tile_rows", k_tile_rows, dim3(div_up(n * 64, 256)), dim3(256), 0, csr->indptr.get(), csr->indices.get(),
-              csr->data.get(), csr->has_row_order ? csr->row_order.get() : (const int32_t *)nullptr, perm.get(), n,
-              t_indptr.get(), t_indices.get(), t_data.get(), t_row_order.get(), t_long.get(), t_nlong.get());
-    const int32_t nl = read_scalar(t_nlong.get());
+              csr->data.get(), csr->stored.has_row_order ? csr->stored.row_order.get() : (const int32_t *)nullptr, perm.get(), n,
+              t_indptr.get(), t_indices.get(), t_data.get(), t_row_order.get(), t_longs.rows.get(), t_longs.n_dev.get());
+    t_longs.end();
     csr->indptr = std::move(t_indptr);
     csr->indices = std::move(t_indices);
     csr->data = std::move(t_data);
-    csr->row_order = std::move(t_row_order);
-    csr->has_row_order = true;
-    csr->long_rows = std::move(t_long);
-    csr->n_long = std::move(t_nlong);
-    csr->has_long = nl > 0;
-    csr->plan_ready = false;
-    // transposed weights built while the matrix delivered in stored order hold stored row positions: stale from here on
-    // (built in the caller's ids they are untouched: ensure_transposed, xr_adjoint.hip)
-    if (csr->tr_output_stored) csr->tr_ready = false;
-    csr->tile_key.release();
+    csr->stored.row_order = std::move(t_row_order);
+    csr->stored.has_row_order = true;
+    csr->longs = std::move(t_longs);
+    csr->rows_regrouped();
+    csr->tiling.release();
 }
 
 // The row tiling of the many-variable apply is PART of the stored order.  It is normally deferred to the first apply with
@@ -200,7 +195,7 @@ void ensure_tiled(const xr_csr *ccsr) {
 // it settled right away, whatever K the coming applies have -- otherwise a later apply would regroup the rows under a
 // permutation the caller has already read, and every result after that would be silently mis-ordered.
 static void settle_row_layout(const xr_csr *csr) {
-    if (csr && csr->n > 0 && csr->has_tile_key) {
+    if (csr && csr->n > 0 && csr->tiling.pending) {
         ensure_tiled(csr);
         stream_sync();
     }
@@ -210,7 +205,7 @@ static void settle_row_layout(const xr_csr *csr) {
 // scope; the apply proper then only reads the matrix and runs under the shared scope next to other threads' applies.
 int prepare_for_apply(const xr_csr *csr, int64_t K) {
     XR_API_BEGIN
-    if (csr && csr->n > 0 && K >= PLAN_KT && option(OPT_APPLY_PLAN) != 0 && (csr->has_tile_key || !csr->plan_ready)) {
+    if (csr && csr->n > 0 && K >= PLAN_KT && option(OPT_APPLY_PLAN) != 0 && (csr->tiling.pending || !csr->plan.ready)) {
         ensure_tiled(csr);
         ensure_plan(csr);
         stream_sync();
@@ -326,28 +321,28 @@ int xr_csr_set_row_keys(xr_csr *csr, const int64_t *keys, int64_t key_range) {
                "xr_csr_set_row_keys: key_range must be in [1, 2^24]");
     // With the output in stored order the stored order is part of what the caller has been told (xr_csr_row_order): new
     // keys would regroup the rows under every result that is read through the old permutation.
-    XR_REQUIRE(!csr->output_stored, XR_ERR_INVALID,
+    XR_REQUIRE(!csr->stored.output_stored, XR_ERR_INVALID,
                "xr_csr_set_row_keys: the matrix delivers its output in stored order -- its row order is frozen; call "
                "xr_csr_output_stored_order(csr, 0) first, set the keys, switch it on again and re-read xr_csr_row_order");
     for (int64_t i = 0; i < csr->n; i++)
         XR_REQUIRE(keys[i] >= 0 && keys[i] < key_range, XR_ERR_INVALID, "xr_csr_set_row_keys: key %lld outside [0,%lld)",
                    (long long)keys[i], (long long)key_range);
     if (csr->n > 0) {
-        csr->tile_key.alloc((size_t)csr->n);
-        if (csr->has_row_order) {
+        csr->tiling.key.alloc((size_t)csr->n);
+        if (csr->stored.has_row_order) {
             // rows already stored in another order (built by xr_overlap, or tiled before): the keys are per CALLER row, the
             // regrouping works on stored rows -- key of stored row r = keys[row_order[r]]; the permutations compose
             DevBuf<int32_t> by_caller((size_t)csr->n);
             upload_narrow(keys, csr->n, by_caller.get());
             XR_LAUNCH("gather_keys", k_gather_i32, dim3(div_up(csr->n, 256)), dim3(256), 0, by_caller.get(),
-                      csr->row_order.get(), csr->n, csr->tile_key.get());
+                      csr->stored.row_order.get(), csr->n, csr->tiling.key.get());
         } else {
-            upload_narrow(keys, csr->n, csr->tile_key.get());
+            upload_narrow(keys, csr->n, csr->tiling.key.get());
         }
         stream_sync();
-        csr->plan_ready = false;
-        csr->tile_key_range = key_range;
-        csr->has_tile_key = key_range > 1;
+        csr->keys_changed();
+        csr->tiling.key_range = key_range;
+        csr->tiling.pending = key_range > 1;
     }
     XR_API_END
 }
@@ -357,7 +352,7 @@ int xr_csr_set_col_keys(xr_csr *csr, const int64_t *keys, int64_t key_range) {
     XR_REQUIRE(csr && (keys || csr->m == 0), XR_ERR_INVALID, "xr_csr_set_col_keys: NULL argument");
     XR_REQUIRE(key_range >= 1 && key_range <= ((int64_t)1 << 24), XR_ERR_INVALID,
                "xr_csr_set_col_keys: key_range must be in [1, 2^24]");
-    XR_REQUIRE(!csr->has_col_perm, XR_ERR_INVALID, "xr_csr_set_col_keys: the columns of this matrix are renumbered already");
+    XR_REQUIRE(!csr->cols.permuted, XR_ERR_INVALID, "xr_csr_set_col_keys: the columns of this matrix are renumbered already");
     for (int64_t i = 0; i < csr->m; i++)
         XR_REQUIRE(keys[i] >= 0 && keys[i] < key_range, XR_ERR_INVALID, "xr_csr_set_col_keys: key %lld outside [0,%lld)",
                    (long long)keys[i], (long long)key_range);
@@ -373,16 +368,16 @@ int xr_csr_set_col_keys(xr_csr *csr, const int64_t *keys, int64_t key_range) {
         fill_i32(hist.get(), 0, key_range + 1);
         XR_LAUNCH("tile_scatter", k_tile_scatter, dim3(div_up(m, 256)), dim3(256), 0, key.get(), m, start.get(), hist.get(),
                   members.get());
-        csr->col_of.alloc((size_t)m);
+        csr->cols.col_of.alloc((size_t)m);
         XR_LAUNCH("tile_rank", k_tile_rank, dim3(div_up(m, 256)), dim3(256), 0, key.get(), start.get(), members.get(), m,
-                  csr->col_of.get());
-        XR_LAUNCH("col_inverse", k_scatter_iota_i32, dim3(div_up(m, 256)), dim3(256), 0, csr->col_of.get(), m, rank.get());
+                  csr->cols.col_of.get());
+        XR_LAUNCH("col_inverse", k_scatter_iota_i32, dim3(div_up(m, 256)), dim3(256), 0, csr->cols.col_of.get(), m, rank.get());
         if (csr->nnz > 0)
             XR_LAUNCH("col_relabel", k_relabel_i32, dim3(div_up(csr->nnz, 256)), dim3(256), 0, rank.get(),
                       csr->indices.get(), csr->nnz);
         stream_sync();
-        csr->has_col_perm = true;
-        csr->plan_ready = false;
+        csr->cols.permuted = true;
+        csr->keys_changed();
     }
     XR_API_END
 }
@@ -390,9 +385,9 @@ int xr_csr_set_col_keys(xr_csr *csr, const int64_t *keys, int64_t key_range) {
 int xr_csr_col_order(const xr_csr *csr, int64_t *order_out) {
     XR_API_BEGIN
     XR_REQUIRE(csr && (order_out || csr->m == 0), XR_ERR_INVALID, "xr_csr_col_order: NULL argument");
-    if (csr->has_col_perm) {
+    if (csr->cols.permuted) {
         DevBuf<int64_t> wide((size_t)csr->m);
-        download_wide(csr->col_of.get(), csr->m, order_out, wide);
+        download_wide(csr->cols.col_of.get(), csr->m, order_out, wide);
         stream_sync();
     } else {
         for (int64_t i = 0; i < csr->m; i++) order_out[i] = i;
@@ -403,7 +398,7 @@ int xr_csr_col_order(const xr_csr *csr, int64_t *order_out) {
 int xr_csr_expect_permuted(xr_csr *csr, int permuted) {
     XR_API_BEGIN
     XR_REQUIRE(csr, XR_ERR_INVALID, "xr_csr_expect_permuted: NULL argument");
-    csr->source_permuted = permuted != 0;
+    csr->cols.source_permuted = permuted != 0;
     XR_API_END
 }
 
@@ -411,7 +406,7 @@ int xr_csr_output_stored_order(xr_csr *csr, int stored) {
     XR_API_BEGIN
     XR_REQUIRE(csr, XR_ERR_INVALID, "xr_csr_output_stored_order: NULL argument");
     if (stored) settle_row_layout(csr); // from here on the order is frozen (xr_csr_set_row_keys refuses)
-    csr->output_stored = stored != 0;
+    csr->stored.output_stored = stored != 0;
     XR_API_END
 }
 
@@ -420,9 +415,9 @@ int xr_csr_row_order(const xr_csr *csr, int64_t K_hint, int64_t *order_out) {
     (void)K_hint; // (kept in the signature; the layout is settled whatever K is)
     XR_REQUIRE(csr && (order_out || csr->n == 0), XR_ERR_INVALID, "xr_csr_row_order: NULL argument");
     settle_row_layout(csr);
-    if (csr->has_row_order) {
+    if (csr->stored.has_row_order) {
         DevBuf<int64_t> wide((size_t)csr->n);
-        download_wide(csr->row_order.get(), csr->n, order_out, wide);
+        download_wide(csr->stored.row_order.get(), csr->n, order_out, wide);
         stream_sync();
     } else {
         for (int64_t i = 0; i < csr->n; i++) order_out[i] = i;
@@ -434,12 +429,12 @@ int xr_csr_long_rows(const xr_csr *csr, int64_t capacity, int64_t *rows_out, int
     XR_API_BEGIN
     XR_REQUIRE(csr && n_out && (rows_out || capacity == 0) && capacity >= 0, XR_ERR_INVALID, "xr_csr_long_rows: invalid argument");
     stream_sync();
-    const int64_t n = csr->n_long.get() ? read_scalar(csr->n_long.get()) : 0;
+    const int64_t n = csr->longs.n_dev.get() ? read_scalar(csr->longs.n_dev.get()) : 0;
     *n_out = n;
     const int64_t take = n < capacity ? n : capacity;
     if (take > 0) {
         DevBuf<int64_t> wide((size_t)take);
-        download_wide(csr->long_rows.get(), take, rows_out, wide);
+        download_wide(csr->longs.rows.get(), take, rows_out, wide);
         stream_sync();
     }
     XR_API_END

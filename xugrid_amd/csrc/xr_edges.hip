@@ -842,19 +842,17 @@ static void edge_length_csr(xr_mesh *tree, const double *edge_xy_host, int64_t n
     }
     const int32_t P = (int32_t)csr->nnz;
     DevBuf<int32_t> sort_list((size_t)(P / ROW_SORT_SMALL + 1));
-    csr->long_rows.alloc((size_t)(P / XR_APPLY_LONG_ROW + 1));
-    csr->n_long.alloc(1);
-    XR_HIP(hipMemsetAsync(csr->n_long.get(), 0, sizeof(int32_t), st));
+    csr->longs.begin((size_t)(P / XR_APPLY_LONG_ROW + 1));
     XR_LAUNCH("edge_rows_sort", k_edge_rows_sort, dim3(div_up(F, 256)), dim3(256), 0, csr->indptr.get(), F,
-              csr->indices.get(), csr->data.get(), sort_list.get(), counters.get() + 1, csr->long_rows.get(),
-              csr->n_long.get());
+              csr->indices.get(), csr->data.get(), sort_list.get(), counters.get() + 1, csr->longs.rows.get(),
+              csr->longs.n_dev.get());
     // (the queued rows' kernel reads their number on the device: it is launched without the host knowing it -- one read-back at
     // the end, of the long-row count the apply wants, instead of two in front of this launch)
     DevBuf<int32_t> tmp_idx((size_t)P);
     DevBuf<double> tmp_val((size_t)P);
     XR_LAUNCH("edge_rows_sort_big", k_edge_rows_sort_big, dim3(engine().num_cu * 4), dim3(256), 0, csr->indptr.get(),
               csr->indices.get(), csr->data.get(), sort_list.get(), counters.get() + 1, tmp_idx.get(), tmp_val.get());
-    csr->has_long = read_scalar(csr->n_long.get()) > 0;
+    csr->longs.end();
     stream_sync();
 }
 

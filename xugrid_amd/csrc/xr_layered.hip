@@ -288,13 +288,12 @@ static xr_csr *csr_layered(const xr_csr *w2d, const Layers &s, const Layers &t, 
     // the rows of more than 32 entries, ascending (flags -> scan -> compaction, as the transposed weights list theirs)
     exclusive_scan_i32(is_long.get(), pos.get(), csr->n);
     const int32_t n_long = read_scalar(pos.get() + csr->n);
-    csr->has_long = n_long > 0;
-    if (n_long > 0) {
-        csr->long_rows.alloc((size_t)n_long);
-        csr->n_long.alloc(1);
+    if (n_long > 0) { // (counted by the scan: the kernel lists the rows, the count is uploaded)
+        csr->longs.begin((size_t)n_long);
         XR_LAUNCH("layered_long_ids", k_compact_ids<int32_t>, dim3(div_up(csr->n, 256)), dim3(256), 0, is_long.get(), pos.get(),
-                  csr->n, csr->long_rows.get());
-        h2d(csr->n_long.get(), &n_long, sizeof(int32_t));
+                  csr->n, csr->longs.rows.get());
+        h2d(csr->longs.n_dev.get(), &n_long, sizeof(int32_t));
+        csr->longs.end(n_long);
     }
     stream_sync();
     return csr.release();

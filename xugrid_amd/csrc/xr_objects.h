@@ -174,56 +174,135 @@ struct xr_mesh : xr::MeshRaw {
 static constexpr int XR_APPLY_LONG_ROW = 32;
 static constexpr int XR_APPLY_WAVE_ROW = 2048;
 
-// Device-resident MatrixCSR (xugrid/core/sparse.py:81-137), int32 structure + float64 data.
+// Device-resident MatrixCSR (xugrid/core/sparse.py:81-137), int32 structure + float64 data.  A matrix IS its three arrays;
+// everything else hangs off it in stages, one small struct per lifetime (as xr_mesh above), each listing its buffers once:
+//   stored   the order the rows are stored in, when it is not the caller's
+//   longs    the list of the long rows (the cooperative kernels of the applies)
+//   tiling   row keys waiting for the many-variable apply to regroup the stored rows
+//   cols     the renumbering of the columns
+//   plan     the apply plan of the many-variable kernels (lazily built cache)
+//   tr       the transposed weights of the adjoint apply (lazily built cache)
+// Which cache goes stale on which event: xr_csr::rows_regrouped(), xr_csr::keys_changed().
+namespace xr {
+// Rows may be STORED in a spatially coherent order instead of the caller's: stored row r is the
+// caller's row row_order[r] (weights built by xr_overlap: the query mesh's query order).  The
+// apply kernels scatter their outputs through it; xr_csr_download un-permutes.
+struct CsrStoredOrder {
+    DevBuf<int32_t> row_order; // [n]
+    bool has_row_order = false;
+    bool output_stored = false; // applies write row r of the STORED order to out[k, r] (xr_csr_output_stored_order)
+    void release() {
+        has_row_order = false;
+        row_order.release();
+    }
+};
+
+// stored rows with more than XR_APPLY_LONG_ROW entries (reduced by one wave or block each in the apply)
+struct CsrLongRows {
+    DevBuf<int32_t> rows;     // [<= n]
+    DevBuf<int32_t> n_dev;    // [1] device-side count (matrices of the fused build: TAIL_WORDS = 4 words, indexed by TailWord --
+                              // the count, the gate of an apply enqueued behind the build, n_big, p_regular; xr_overlap_tail.h)
+    int64_t max_row_len = -1; // entries of the longest row if the builder reported it (-1: unknown)
+    bool any = false;         // the list is not empty: the applies launch the long rows' kernels
+    // in front of the kernel that lists the rows: room for `capacity` of them and `words` control words, the count ([0]) zero
+    void begin(size_t capacity, int words = 1) {
+        rows.alloc(capacity);
+        n_dev.alloc((size_t)words);
+        XR_HIP(hipMemsetAsync(n_dev.get(), 0, sizeof(int32_t), launch_stream()));
+    }
+    // behind it: `count` rows were listed (negative: the caller does not know -- read from the device)
+    void end(int64_t count = -1) { any = (count >= 0 ? count : (int64_t)read_scalar(n_dev.get())) > 0; }
+    void release() {
+        any = false;
+        max_row_len = -1;
+        rows.release(), n_dev.release();
+    }
+};
+
+// Coarse Morton key per STORED row (tile of ~12 target extents).  Set by xr_overlap when the rows are kept
+// in the caller's order, or by xr_csr_set_row_keys; consumed once by the many-variable apply, which regroups
+// the stored rows into compact 2-D tiles (xr_csr.hip: ensure_tiled) and then drops the keys.
+struct CsrTiling {
+    DevBuf<int32_t> key;   // [n]
+    bool pending = false;
+    int64_t key_range = 0; // keys are in [0, key_range)
+    void release() {
+        pending = false;
+        key.release();
+    }
+};
+
+// Columns renumbered by a spatial key (xr_csr_set_col_keys): stored column j is the caller's column col_of[j].
+// The apply gathers the caller's source block into the stored order first unless the caller says it already is.
+struct CsrColumns {
+    DevBuf<int32_t> col_of; // [m]
+    bool permuted = false;
+    bool source_permuted = false;
+    void release() {
+        permuted = false;
+        col_of.release();
+    }
+};
+
+// "apply plan" for many source variables (built lazily, xr_apply_plan.hip: ensure_plan): per block of 256 stored
+// rows the sorted list of DISTINCT column ids and, per entry, its 16-bit position in that list
+struct CsrPlan {
+    bool ready = false;
+    bool merged = false;           // the lists are per GROUP of row blocks (k_plan_build<PLAN_GROUP>), not per block
+    DevBuf<int32_t> unplanned;     // blocks the plan could not take (handled by the direct kernel)
+    int n_unplanned = 0;
+    int lmax = 0;                  // entries of the largest planned block, rounded up to 256 (LDS stage of the apply)
+    DevBuf<int32_t> ucol;          // [n_blocks * PLAN_UMAX]
+    DevBuf<int32_t> nuniq;         // [n_blocks], -1 = block not planned (falls back to direct gathers)
+    DevBuf<uint16_t> loc;          // [nnz]
+    void release() {
+        ready = false;
+        unplanned.release(), ucol.release(), nuniq.release(), loc.release();
+    }
+};
+
+// the transposed weights of the adjoint apply (built lazily, xr_adjoint.hip: ensure_transposed), in the ids the applies
+// use -- caller's columns, output rows -- with a copy of every weight: per column the entries in ascending (row, storage
+// position).  Built in the caller's row ids, no re-layout of the stored matrix touches them; built in stored positions
+// (output_stored), the row tiling invalidates them (xr_csr::rows_regrouped) and the next adjoint rebuilds them
+struct CsrTransposed {
+    bool ready = false;
+    bool output_stored = false; // the row ids are stored positions (the matrix delivered in stored order when this was built)
+    DevBuf<int32_t> indptr;     // [m+1]
+    DevBuf<uint32_t> row;       // [nnz] row id; bit 31: the entry is the last of its row (what XR_SELECT copies)
+    DevBuf<double> w;           // [nnz]
+    DevBuf<int32_t> long_cols;  // [n_long] columns with more than XR_APPLY_LONG_ROW entries, ascending
+    int64_t n_long = 0, max_len = 0;
+    void release() {
+        ready = output_stored = false;
+        indptr.release(), row.release(), w.release(), long_cols.release();
+        n_long = max_len = 0;
+    }
+};
+} // namespace xr
+
 struct xr_csr {
     int64_t n = 0, m = 0, nnz = 0;
     xr::DevBuf<int32_t> indptr;    // [n+1]
     xr::DevBuf<int32_t> indices;   // [nnz]
     xr::DevBuf<double> data;       // [nnz]
-    // Rows may be STORED in a spatially coherent order instead of the caller's: stored row r is the
-    // caller's row row_order[r] (weights built by xr_overlap: the query mesh's query order).  The
-    // apply kernels scatter their outputs through it; xr_csr_download un-permutes.
-    xr::DevBuf<int32_t> row_order; // [n]
-    bool has_row_order = false;
-    // stored rows with more than XR_APPLY_LONG_ROW entries (reduced by one wave or block each in the apply)
-    xr::DevBuf<int32_t> long_rows; // [<= n]
-    xr::DevBuf<int32_t> n_long;    // [1] device-side count (matrices of the fused build: TAIL_WORDS = 4 words, indexed by TailWord --
-                                   // the count, the gate of an apply enqueued behind the build, n_big, p_regular; xr_overlap_tail.h)
-    int64_t max_row_len = -1;      // entries of the longest row if the builder reported it (-1: unknown)
-    bool has_long = false;
-    // Coarse Morton key per STORED row (tile of ~12 target extents).  Set by xr_overlap when the rows are kept
-    // in the caller's order, or by xr_csr_set_row_keys; consumed once by the many-variable apply, which regroups
-    // the stored rows into compact 2-D tiles (xr_csr.hip: ensure_tiled) and then drops the keys.
-    xr::DevBuf<int32_t> tile_key; // [n]
-    bool has_tile_key = false;
-    int64_t tile_key_range = 0;   // keys are in [0, tile_key_range)
-    // Columns renumbered by a spatial key (xr_csr_set_col_keys): stored column j is the caller's column col_of[j].
-    // The apply gathers the caller's source block into the stored order first unless the caller says it already is.
-    xr::DevBuf<int32_t> col_of; // [m]
-    bool has_col_perm = false;
-    bool source_permuted = false;
-    bool output_stored = false; // applies write row r of the STORED order to out[k, r] (xr_csr_output_stored_order)
-    // "apply plan" for many source variables (built lazily, xr_apply.hip: ensure_plan): per block of 256 stored
-    // rows the sorted list of DISTINCT column ids and, per entry, its 16-bit position in that list
-    bool plan_ready = false;
-    bool plan_merged = false;           // the lists are per GROUP of row blocks (k_plan_build_group), not per block
-    xr::DevBuf<int32_t> plan_unplanned; // blocks the plan could not take (handled by the direct kernel)
-    int plan_n_unplanned = 0;
-    int plan_lmax = 0;               // entries of the largest planned block, rounded up to 256 (LDS stage of the apply)
-    xr::DevBuf<int32_t> plan_ucol;   // [n_blocks * PLAN_UMAX]
-    xr::DevBuf<int32_t> plan_nuniq;  // [n_blocks], -1 = block not planned (falls back to direct gathers)
-    xr::DevBuf<uint16_t> plan_loc;   // [nnz]
-    // the transposed weights of the adjoint apply (built lazily, xr_adjoint.hip: ensure_transposed), in the ids the applies
-    // use -- caller's columns, output rows -- with a copy of every weight: per column the entries in ascending (row, storage
-    // position).  Built in the caller's row ids, no re-layout of the stored matrix touches them; built in stored positions
-    // (tr_output_stored), the row tiling invalidates them (ensure_tiled) and the next adjoint rebuilds them
-    bool tr_ready = false;
-    bool tr_output_stored = false;  // the row ids are stored positions (the matrix delivered in stored order when this was built)
-    xr::DevBuf<int32_t> tr_indptr;  // [m+1]
-    xr::DevBuf<uint32_t> tr_row;    // [nnz] row id; bit 31: the entry is the last of its row (what XR_SELECT copies)
-    xr::DevBuf<double> tr_w;        // [nnz]
-    xr::DevBuf<int32_t> tr_long;    // [tr_n_long] columns with more than XR_APPLY_LONG_ROW entries, ascending
-    int64_t tr_n_long = 0, tr_max_len = 0;
+    xr::CsrStoredOrder stored;
+    xr::CsrLongRows longs;
+    xr::CsrTiling tiling;
+    xr::CsrColumns cols;
+    xr::CsrPlan plan;
+    xr::CsrTransposed tr;
+
+    // The two events that make a lazily built cache stale.  (A stale cache keeps its buffers until it is rebuilt.)
+    // The stored rows were regrouped (ensure_tiled): the plan indexes stored rows; so does a transpose built in stored
+    // positions -- one built in the caller's ids is untouched.
+    void rows_regrouped() {
+        plan.ready = false;
+        if (tr.output_stored) tr.ready = false;
+    }
+    // The tiling keys or the column ids changed (xr_csr_set_row_keys, xr_csr_set_col_keys): the plan is rebuilt; the
+    // transpose is left as it is.
+    void keys_changed() { plan.ready = false; }
 };
 
 // Separable (rectilinear) weights kept as the two per-axis sparse matrices (xugrid/regrid/structured.py:503-601): the

@@ -229,11 +229,9 @@ static xr_csr *outer_materialise(const xr_outer *o) {
     csr->indptr.alloc((size_t)n + 1);
     csr->indices.alloc((size_t)nnz);
     csr->data.alloc((size_t)nnz);
-    csr->long_rows.alloc((size_t)(nnz / XR_APPLY_LONG_ROW + 1));
-    csr->n_long.alloc(1);
-    XR_HIP(hipMemsetAsync(csr->n_long.get(), 0, sizeof(int32_t), launch_stream()));
+    csr->longs.begin((size_t)(nnz / XR_APPLY_LONG_ROW + 1));
     XR_LAUNCH("outer_indptr", k_outer_indptr, dim3(div_up(n + 1, 256)), dim3(256), 0, o->ipy.get(), o->ipx.get(), o->nty,
-              o->ntx, o->Px, nnz, csr->indptr.get(), csr->long_rows.get(), csr->n_long.get());
+              o->ntx, o->Px, nnz, csr->indptr.get(), csr->longs.rows.get(), csr->longs.n_dev.get());
     if (nnz > 0) {
         const int64_t gx = std::min<int64_t>(div_up(o->max_cy * o->Px, 256), 1 << 16);
         const int64_t gy = std::min<int64_t>(o->nty, 32768);
@@ -241,8 +239,7 @@ static xr_csr *outer_materialise(const xr_outer *o) {
                   o->wy.get(), o->ipx.get(), o->sx.get(), o->wx.get(), o->tx.get(), o->nty, o->nsx, o->Px,
                   csr->indices.get(), csr->data.get());
     }
-    const int32_t nl = read_scalar(csr->n_long.get());
-    csr->has_long = nl > 0;
+    csr->longs.end();
     return csr.release();
 }
 

@@ -839,18 +839,18 @@ void launch_row_fill_long(int row_class, const xr_mesh *tree, const SearchLists 
 
 // Rows kept in the caller's (coherent, but typically strip-like) numbering get a coarse Morton key each: tiles of 12-24 mean
 // target extents, runs of TILE_RUN consecutive rows kept together.  A Morton-sorted query order is tiled already.
-// -> the key's parameters; csr->tile_key allocated, csr->has_tile_key / tile_key_range set
+// -> the key's parameters; csr->tiling.key allocated, csr->tiling.pending / key_range set
 static MortonParams tile_key_params(const xr_mesh *query, xr_csr *csr) {
     MortonParams tile{};
-    csr->has_tile_key = false;
+    csr->tiling.pending = false;
     if (!query->qo.identity) return tile;
     const int64_t T = query->n_face;
     // tile edge <= 12 mean extents (the side count is a power of two): about one block of 256 triangles per tile
     tile = morton_cover(query->stats.h, T, 12.0, 0, 12);
     tile.n_run = TILE_RUN;
-    csr->tile_key.alloc((size_t)T);
-    csr->tile_key_range = (int64_t)tile.n_side * tile.n_side;
-    csr->has_tile_key = tile.n_side > 1;
+    csr->tiling.key.alloc((size_t)T);
+    csr->tiling.key_range = (int64_t)tile.n_side * tile.n_side;
+    csr->tiling.pending = tile.n_side > 1;
     return tile;
 }
 

@@ -13,7 +13,7 @@
 //                             thousand (rows, entries) pairs into every block's first stored row and CSR base
 //   k_assemble                the block that owns 256 consecutive target faces counts its survivors per row in LDS, ranks
 //                             every survivor among its row and writes the final CSR at its base.  No row counters in
-//                             HBM.  (xr_csr::row_order maps stored rows to the caller's faces.)  Up to 8192 blocks every
+//                             HBM.  (xr_csr::stored.row_order maps stored rows to the caller's faces.)  Up to 8192 blocks every
 //                             block sums the counts of the blocks in front of it itself instead of k_assemble_scan
 //   big faces (hull slivers, > SLOTS hits; 0.1 % of the faces, but their block-per-face kernels are chains of dependent
 //   phases: 15 % of the step when run in line) on a SIDE STREAM, forked behind k_search: k_search_big -> k_clip_tri_queue on
@@ -533,7 +533,7 @@ static void attempt_allocate(FusedBuild &b, FusedAttempt &a, int64_t per_face, i
     XR_REQUIRE(a.cap < ((int64_t)1 << 31), XR_ERR_LIMIT, "nnz exceeds the int32 range");
     b.csr->indices.alloc((size_t)a.cap);
     b.csr->data.alloc((size_t)a.cap);
-    b.csr->long_rows.alloc((size_t)(a.cap / XR_APPLY_LONG_ROW + 1));
+    b.csr->longs.rows.alloc((size_t)(a.cap / XR_APPLY_LONG_ROW + 1));
     for (DevBuf<int32_t> *buf : {&a.big_tgt, &a.big_src, &a.big_sid, &a.big_indices}) buf->alloc((size_t)big_capacity);
     a.big_area.alloc((size_t)big_capacity);
     a.big_data.alloc((size_t)big_capacity);
@@ -574,7 +574,7 @@ static void enqueue_big_chain(const FusedBuild &b, const FusedAttempt &a) {
     // behind the clip is one launch shorter where it is the step's critical path, 0.506 -> 0.500 ms in an A/B)
     const LongRows big_rows{a.big_sid.get(), a.big_area.get(), b.big_indptr.get(), a.big_indices.get(), a.big_data.get(),
                             b.slot_face.get(), a.n_big_dev, 0, a.n_pending_dev, b.l.nnz_row.get(), b.big_indptr.get(), &a.fc->p_big,
-                            b.csr->long_rows.get(), a.fc, b.T};
+                            b.csr->longs.rows.get(), a.fc, b.T};
     SideForkScope fork;
     launch_row_fill_long(2, b.tree, b.l, b.tree_area, b.relative, big_rows);
     fork.end_launches();
@@ -600,7 +600,7 @@ static void enqueue_regular(const FusedBuild &b, const FusedAttempt &a) {
     XR_LAUNCH("assemble", k_assemble, dim3(grid), dim3(FB), 0, query->qo_bbox(), query->qo_fxy(), query->qo_len(), query->m,
               query->qo_perm(), b.T, b.cand_tgt.get(), b.l.cand_off.get(), b.l.cand_count.get(), b.l.block_seg.get(), b.l.is_big.get(),
               b.cand_area.get(), b.cand_sid.get(), b.tree_area, b.relative, b.tile, b.tile_key, a.fc, csr->indptr.get(),
-              csr->indices.get(), csr->data.get(), csr->row_order.get(), a.cap, b.remap,
+              csr->indices.get(), csr->data.get(), csr->stored.row_order.get(), a.cap, b.remap,
               b.scan_mode == 1 ? b.blk_base.get() : (const int32_t *)nullptr,
               b.scan_mode == 1 ? b.blk_base.get() + grid : (const int32_t *)nullptr,
               b.scan_mode == 2 ? b.blk_rows : (const int32_t *)nullptr, b.scan_mode == 2 ? b.blk_surv : (const int32_t *)nullptr);
@@ -620,7 +620,7 @@ static PlaceBig enqueue_tail(const FusedBuild &b, const FusedAttempt &a, bool ta
     xr_csr *csr = b.csr;
     const PlaceBig place{a.n_big_dev, b.slot_face.get(), b.big_indptr.get(), a.big_indices.get(), a.big_data.get(), b.T,
                          query->qo_perm(), query->qo_bbox(), query->qo_fxy(), query->qo_len(), query->m, b.tile, b.tile_key, a.fc,
-                         csr->indptr.get(), csr->indices.get(), csr->data.get(), csr->row_order.get(), a.cap, a.n_pending_dev};
+                         csr->indptr.get(), csr->indices.get(), csr->data.get(), csr->stored.row_order.get(), a.cap, a.n_pending_dev};
     if (!tail_fused) XR_LAUNCH("place_big", k_place_big, dim3(TAIL_PLACE_BLOCKS), dim3(256), 0, place);
     return place;
 }
@@ -631,12 +631,12 @@ static int32_t enqueue_publish_and_apply(const FusedBuild &b, const FusedAttempt
                                          EarlyApply *early) {
     host_stamp(5);
     const int32_t seq = mailbox_next_seq();
-    XR_LAUNCH("publish", k_publish_all, dim3(1), dim3(64), 0, a.ctl, a.fc, b.csr->n_long.get(), const_cast<int32_t *>(engine().mailbox),
+    XR_LAUNCH("publish", k_publish_all, dim3(1), dim3(64), 0, a.ctl, a.fc, b.csr->longs.n_dev.get(), const_cast<int32_t *>(engine().mailbox),
               seq, a.cap, a.big_capacity);
     if (a.ctl_cached) zero_scratch_done(1); // (the counters are zero again behind k_publish_all)
     if (early) {
-        const ApplyTail tail{place, b.csr->n_long.get()};
-        const ApplyContext ctx{b.csr->n_long.get() + TAIL_GATE, tail_fused ? &tail : nullptr};
+        const ApplyTail tail{place, b.csr->longs.n_dev.get()};
+        const ApplyContext ctx{b.csr->longs.n_dev.get() + TAIL_GATE, tail_fused ? &tail : nullptr};
         early->fn(b.csr, &ctx);
     }
     host_stamp(6);
@@ -654,11 +654,13 @@ static FusedMail read_back(int32_t seq) {
 
 bool overlap_tri(xr_mesh *tree, xr_mesh *query, const double *tree_area, bool relative, xr_csr *csr, const MortonParams &tile,
                  EarlyApply *early) {
-    FusedBuild b{tree, query, tree_area, relative, csr, tile, csr->has_tile_key ? csr->tile_key.get() : nullptr};
+    FusedBuild b{tree, query, tree_area, relative, csr, tile, csr->tiling.pending ? csr->tiling.key.get() : nullptr};
     const int64_t T = b.T;
-    csr->n_long.alloc(TAIL_WORDS); // (TailWord: the rows of more than XR_APPLY_LONG_ROW entries, the gate of an apply enqueued behind the build ...)
-    csr->row_order.alloc((size_t)T);
-    csr->has_row_order = true;
+    // (CsrLongRows::begin is not used on this timed path: the list is sized per attempt (attempt_allocate), the words once, and
+    // k_publish_all writes them -- no clear)
+    csr->longs.n_dev.alloc(TAIL_WORDS); // (TailWord: the rows of more than XR_APPLY_LONG_ROW entries, the gate of an apply enqueued behind the build ...)
+    csr->stored.row_order.alloc((size_t)T);
+    csr->stored.has_row_order = true;
     const bool tail_fused = early && early->takes_tail && option(OPT_TAIL_FUSED) != 0;
     const int64_t margin_opt = option(OPT_QUEUE_MARGIN); // test hook: a tiny margin forces the regrow path
     int64_t big_capacity = margin_opt > 0 ? margin_opt : ((int64_t)4 << 20);
@@ -683,7 +685,7 @@ bool overlap_tri(xr_mesh *tree, xr_mesh *query, const double *tree_area, bool re
         }
         switch (verdict) {
         case FUSED_GENERAL:
-            csr->has_row_order = false; // (the general pipeline stores the rows in query order)
+            csr->stored.has_row_order = false; // (the general pipeline stores the rows in query order)
             return false;
         case FUSED_GROW_BIG: // some big faces needed more room than the margin
             big_capacity = (int64_t)m.c_big + 1024;
@@ -697,8 +699,8 @@ bool overlap_tri(xr_mesh *tree, xr_mesh *query, const double *tree_area, bool re
         XR_REQUIRE(m.rows_regular == T - m.n_big, XR_ERR_INVALID, "xr_overlap: internal row count mismatch");
         tree->last_candidates = (int64_t)m.c_reg + m.c_big;
         csr->nnz = (int64_t)m.p_regular + m.p_big;
-        csr->has_long = m.n_apply_long > 0; // rows of more than XR_APPLY_LONG_ROW entries (none: the apply skips their kernels)
-        csr->max_row_len = m.n_apply_long > 0 ? m.max_row : XR_APPLY_LONG_ROW;
+        csr->longs.end(m.n_apply_long); // rows of more than XR_APPLY_LONG_ROW entries (none: the apply skips their kernels)
+        csr->longs.max_row_len = m.n_apply_long > 0 ? m.max_row : XR_APPLY_LONG_ROW;
         if (early) early->done = true; // (the apply enqueued in THIS attempt saw the final matrix)
         return true;
     }

@@ -241,7 +241,7 @@ static constexpr int ROW_LDS = 3072; // short-row candidate entries one block ca
 // block's candidate segment is contiguous, so the loads are coalesced -- then the block works
 // ENTRY-parallel: each thread takes entries, ranks a survivor among the survivors of its row
 // (adjacent in LDS) and writes it to its final CSR position.  Rows are stored in QUERY order
-// (row r belongs to the caller's face q_perm[r], xr_csr::row_order).
+// (row r belongs to the caller's face q_perm[r], xr_csr::stored.row_order).
 __global__ void __launch_bounds__(256)
 k_row_fill(const int32_t *__restrict__ cand_off, const int32_t *__restrict__ cand_count,
            const int2 *__restrict__ block_seg, const uint8_t *__restrict__ is_big,
@@ -391,7 +391,7 @@ void overlap_general(xr_mesh *tree, xr_mesh *query, const double *tree_area, boo
     XR_REQUIRE(capacity < ((int64_t)1 << 31), XR_ERR_LIMIT, "candidate pair queue exceeds the int32 range");
     DevBuf<int32_t> cand_tgt((size_t)capacity), cand_src((size_t)capacity);
     const PairQueue queue{cand_tgt.get(), cand_src.get(), word(GEN_QUEUE_CURSOR), capacity};
-    launch_search(tree, query, l, queue, word(GEN_N_BIG), tile, csr->has_tile_key ? csr->tile_key.get() : nullptr);
+    launch_search(tree, query, l, queue, word(GEN_N_BIG), tile, csr->tiling.pending ? csr->tiling.key.get() : nullptr);
     launch_search_big(tree, query, l, queue, word(GEN_N_BIG), word(GEN_N_PENDING));
     // queue length and number of big faces still to be filled -> host
     int32_t *mail = const_cast<int32_t *>(engine().mailbox);
@@ -447,22 +447,20 @@ void overlap_general(xr_mesh *tree, xr_mesh *query, const double *tree_area, boo
     csr->data.alloc((size_t)P);
     // rows are best processed in the query mesh's spatial order (apply kernels)
     if (query->qo_perm()) {
-        csr->row_order.alloc((size_t)T);
-        XR_HIP(hipMemcpyAsync(csr->row_order.get(), query->qo_perm(), sizeof(int32_t) * (size_t)T,
+        csr->stored.row_order.alloc((size_t)T);
+        XR_HIP(hipMemcpyAsync(csr->stored.row_order.get(), query->qo_perm(), sizeof(int32_t) * (size_t)T,
                               hipMemcpyDeviceToDevice, st));
-        csr->has_row_order = true;
+        csr->stored.has_row_order = true;
     }
     if (P > 0) {
         DevBuf<int32_t> long_rows((size_t)T);
-        csr->long_rows.alloc((size_t)(P / XR_APPLY_LONG_ROW + 1));
-        csr->n_long.alloc(1);
-        csr->has_long = true;
-        XR_HIP(hipMemsetAsync(csr->n_long.get(), 0, sizeof(int32_t), st));
+        csr->longs.begin((size_t)(P / XR_APPLY_LONG_ROW + 1));
+        csr->longs.end(1); // (not read back: the applies launch the long rows' kernels, which may find the list empty)
         const bool remap = REMAP_ROW_FILL;
         XR_LAUNCH("row_fill", k_row_fill, dim3(xcd_grid(div_up(T, 256), remap)), dim3(256), 0, l.cand_off.get(), l.cand_count.get(),
                   l.block_seg.get(), l.is_big.get(), cand_tgt.get(), cand_sid.get(), cand_area.get(), T, csr->indptr.get(), tree_area, relative,
-                  csr->indices.get(), csr->data.get(), long_rows.get(), word(GEN_N_LONG_ROWS), csr->long_rows.get(),
-                  csr->n_long.get(), remap);
+                  csr->indices.get(), csr->data.get(), long_rows.get(), word(GEN_N_LONG_ROWS), csr->longs.rows.get(),
+                  csr->longs.n_dev.get(), remap);
         launch_row_fill_long(0, tree, l, tree_area, relative,
                              LongRows{cand_sid.get(), cand_area.get(), csr->indptr.get(), csr->indices.get(), csr->data.get(),
                                       long_rows.get(), word(GEN_N_LONG_ROWS), -1});

@@ -1,5 +1,5 @@
 // xr_overlap_tail.h -- what the fused weight build (xr_overlap_fused.hip) and the K = 1 apply enqueued behind it
-// (xr_apply.hip: k_apply_tail1, xr_partial.hip) share: the control block's words, the verdict on an attempt -- ONE function,
+// (xr_apply_stream.hip: k_apply_tail1, xr_partial.hip) share: the control block's words, the verdict on an attempt -- ONE function,
 // evaluated by k_publish_all for the gate and by overlap_tri after its read-back --, the context an apply enqueued behind the
 // build is handed, and the placement of the big faces' rows behind the regular ones -- a launch of its own (k_place_big) or
 // the leading blocks of the apply's launch.
@@ -127,7 +127,7 @@ __device__ __forceinline__ void place_big_rows(const PlaceBig &p, int block, int
 // What the K = 1 apply's launch needs to take the place of k_place_big and to read the big rows from the big faces' own CSR.
 struct ApplyTail {
     PlaceBig place;
-    const int32_t *words; // what k_publish_all left in the matrix' own words (xr_csr::n_long), indexed by TailWord
+    const int32_t *words; // what k_publish_all left in the matrix' own words (xr_csr::longs.n_dev), indexed by TailWord
 };
 // What overlap_tri hands an apply it enqueues behind an attempt, before the host has read the attempt's sizes back
 // (csr_apply_dev, csr_partial_dev; callers with a finished matrix pass none).  The sizes of the matrix are then not known on
@@ -136,10 +136,10 @@ struct ApplyTail {
 struct ApplyContext {
     const int32_t *gate;   // the build's gate word (TAIL_GATE): every block of the apply leaves unless the attempt was final
     const ApplyTail *tail; // the apply's launch places the big rows itself (k_apply_tail1), or null
-    bool has_long = true;     // (in place of xr_csr::has_long / max_row_len: long rows possible, of any length)
+    bool has_long = true;     // (in place of xr_csr::longs.any / longs.max_row_len: long rows possible, of any length)
     int64_t max_row_len = -1;
 };
-// xr_csr::n_long of a matrix of the fused build, written by k_publish_all
+// xr_csr::longs.n_dev of a matrix of the fused build, written by k_publish_all
 enum TailWord : int { TAIL_N_LONG = 0, TAIL_GATE = 1, TAIL_N_BIG = 2, TAIL_P_REGULAR = 3, TAIL_WORDS = 4 };
 static constexpr int TAIL_PLACE_BLOCKS = 64; // leading blocks of the apply's launch that place the big rows (k_place_big's grid)
 

@@ -368,7 +368,7 @@ using namespace xr;
 // xr_overlap_partial_dev, then gated like the early apply: ctx)
 void xr::csr_partial_dev(const xr_csr *csr, int method, const void *source_dev, int source_dtype, int64_t K, double *out_dev,
                          int rows_layout, const ApplyContext *ctx) {
-    const bool has_long = ctx ? ctx->has_long : csr->has_long;
+    const bool has_long = ctx ? ctx->has_long : csr->longs.any;
     XR_REQUIRE(partial_components(method) > 0, XR_ERR_INVALID, "reducer %d does not decompose over source shards", method);
     with_source_type(source_dtype, [&](auto tag) {
         using SRC = decltype(tag);
@@ -399,7 +399,7 @@ void xr::csr_partial_dev(const xr_csr *csr, int method, const void *source_dev, 
             with_decomposable(method, [&](auto m) {
                 XR_LAUNCH("apply_partial", (k_apply_partial_w1<decltype(m)::value, SRC>), grid, dim3(AP_BLOCK), 0,
                           csr->indptr.get(), csr->indices.get(), csr->data.get(), row_order_of(csr), csr->n, csr->m, src,
-                          out_dev, rows_layout != 0, has_long, gate, csr->long_rows.get(), csr->n_long.get(),
+                          out_dev, rows_layout != 0, has_long, gate, csr->longs.rows.get(), csr->longs.n_dev.get(),
                           n_long_blocks);
             });
         } else { // K = 2 ... 7: one thread per (stored row, variable)
@@ -410,7 +410,7 @@ void xr::csr_partial_dev(const xr_csr *csr, int method, const void *source_dev, 
         if (has_long && !long_done) {
             dim3 lgrid(64, (unsigned)K);
             XR_LAUNCH("apply_partial_long", k_apply_partial_long<SRC>, lgrid, dim3(256), 0, method, csr->indptr.get(),
-                      csr->indices.get(), csr->data.get(), row_order_of(csr), csr->long_rows.get(), csr->n_long.get(),
+                      csr->indices.get(), csr->data.get(), row_order_of(csr), csr->longs.rows.get(), csr->longs.n_dev.get(),
                       csr->n, csr->m, src, K, out_dev, rows_layout != 0, gate);
         }
     });

@@ -1,5 +1,5 @@
 // xr_reduce.h -- the reducers of xugrid/regrid/reduce.py as the apply units share them: the streaming states `Red<METHOD>` with
-// their wave / block / group merges (xr_apply.hip, xr_outer.hip), the partial states of the shard-decomposable reducers
+// their wave / block / group merges (xr_apply_stream.hip, xr_outer.hip), the partial states of the shard-decomposable reducers
 // (xr_partial.hip; their component layout is part of include/xugrid_amd.h) and the tables that turn a run-time reducer id
 // into a template argument.  Two codings of the same reducers with different component layouts: they are not interchangeable.
 // No kernels and no launches here.
@@ -181,7 +181,7 @@ template <int METHOD> __device__ __forceinline__ void block_merge(Red<METHOD> &r
     r = t;
 }
 
-// ... by a group of G lanes (apply_row_group, xr_apply.hip)
+// ... by a group of G lanes (apply_row_group, xr_apply_stream.hip)
 template <int METHOD, int G> __device__ __forceinline__ void group_merge(Red<METHOD> &r) {
     const int lane = threadIdx.x & 63;
 #pragma unroll
